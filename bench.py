@@ -10,6 +10,8 @@ N > 1   : one process per GPU (torch.distributed.run), every rank decodes its ow
           checkpoint once and gathers the decoded waveforms at the end of every step.
 
 Prints ONE JSON line on rank 0.  Synthetic seeded weights and audio (no network for checkpoints/datasets).
+A plain run sets up, warms up, times --steps steps and prints the line; --full adds the roofline profiling and timeline
+passes, the two-batches-in-flight figure and the CPU baseline.  --dump-outputs DIR writes the last timed step's outputs.
 """
 import argparse
 import json
@@ -41,6 +43,23 @@ def fp8_label():
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one float32 <path>/<name>.npy per array.  An array larger than
+    its share of the 64 MB budget is written as a fixed seeded sample of its elements (the same indices on every run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {path}: {', '.join(arrays)}")
 
 
 def host_threads():
@@ -131,6 +150,8 @@ def bench_training(args, eng, mc, u, cc, sd_main, sd_cond, wav, T, rank, world, 
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, device=dev)
     assert bool(torch.isfinite(loss).all()), "non-finite loss"
     log(f"timed region: {elapsed:.3f} s for {args.steps} optimisation step(s), last loss {float(loss.cpu()[0]):.4f}")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss})
     n_par = sum(v.numel() for v in sd.values())
     fwd_flops, _ = eng.unet_step_cost(B, T // mc.hop_length)
     ach = 3.0 * fwd_flops * args.steps / elapsed / 1e12           # forward + dX + dW of every conv-shaped layer
@@ -226,8 +247,7 @@ def bench_c1(args, eng, cc, sd_cond, wav, T, rank, world, dev, result_fd):
     def step():
         cond = eng.get_cond(wav)
         out = eng.decode_latents(L.MODEL_COND, cond)
-        parallel.gather_results(out, world)
-        return out
+        return out, parallel.gather_results(out, world)
     for _ in range(max(1, args.warmup)):
         step()
     if torch.distributed.is_initialized():
@@ -235,12 +255,14 @@ def bench_c1(args, eng, cc, sd_cond, wav, T, rank, world, dev, result_fd):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        out = step()
+        out, outs = step()
     torch.cuda.synchronize(dev)
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, device=dev)
     assert bool(torch.isfinite(out).all()) and out.shape[-1] == T
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"wav": torch.cat(outs)})
     flops = seanet_flops(cc, T) * B
     ach = flops * args.steps / elapsed / 1e12
     result = {
@@ -302,7 +324,14 @@ def main():
                     help="batches decoded concurrently (default 1 = the metric's reading: one batch of the config's size at a time). "
                          "n > 1: n engines on n streams, every batch as ONE chain; steps are dealt round-robin and all K finish inside "
                          "the timed region (supplementary number, see DESIGN.md section 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline figure, each a run of its own: the roofline profiling and "
+                         "timeline passes, the two-batches-in-flight figure and the CPU baseline (--no-* switch them off one by one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_pipelined = True
     args.batch = args.batch or (13 if args.config == "c5" else (1 if args.config == "c1" else 32))
     args.dtype = args.dtype or ("fp8" if args.config == "c5" else ("f32" if args.config == "c4" else "bf16"))
     if args.config in ("c4", "c1"):
@@ -384,6 +413,7 @@ def main():
         return
 
     step_no = [0]
+    last_outs = [None]     # the last step's decoded waveforms of every rank (--dump-outputs)
 
     failures = []      # device-side failure flags (a bounded in-launch wait that gave up: [gn_wait] / [coop_lstm]) seen by the timed calls
 
@@ -402,11 +432,11 @@ def main():
         step_no[0] += 1
         if n_fl == 1:
             out = checked_decode(eng)
-            parallel.gather_results(out, world)      # RCCL all_gather of the decoded waveforms (no-op without a process group)
+            last_outs[0] = parallel.gather_results(out, world)      # RCCL all_gather of the decoded waveforms (no-op without a process group)
             return out
         with torch.cuda.stream(slot_streams[k]):
             out = checked_decode(engines[k])
-            parallel.gather_results(out, world)
+            last_outs[0] = parallel.gather_results(out, world)
         return out
 
     for i in range(max(args.warmup, n_fl if args.warmup else 0)):     # every engine captures its graphs before the timed region
@@ -433,6 +463,8 @@ def main():
     assert os.environ.get("LDC_CONV_DEBUG") or bool(torch.isfinite(out).all()), "non-finite output"   # (ablation runs compute garbage)
     log(f"timed region: {elapsed:.3f} s for {args.steps} step(s)")
     hs = [e_k.host_stats(reset=True) for e_k in engines]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"wav": torch.cat(last_outs[0])})
 
     audio_s = world * B * (T / 16000.0) * args.steps
     result = {

@@ -1,5 +1,5 @@
 """Aggregate an LDC_PROFILE_DUMP file (class flops bytes us per launch) by distinct (class, flops, bytes) shape.
-Usage: LDC_PROFILE_DUMP=/tmp/d.txt python bench.py --no-cpu-baseline; python tools/prof_shapes.py /tmp/d.txt"""
+Usage: LDC_PROFILE_DUMP=/tmp/d.txt python bench.py --full --no-cpu-baseline; python tools/prof_shapes.py /tmp/d.txt"""
 import collections
 import sys
 names = ("other", "conv", "gn_apply", "layernorm", "linattn", "attn_full", "elementwise")

@@ -10,7 +10,7 @@ if [[ $STAGE == all || $STAGE == test ]]; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
 fi
 if [[ $STAGE == all || $STAGE == bench ]]; then
-  timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; cat $O/bench.json
+  timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; cat $O/bench.json
 fi
 if [[ $STAGE == all || $STAGE == prof ]]; then
   rm -rf $O/prof_r02
@@ -29,6 +29,6 @@ if [[ $STAGE == all || $STAGE == pmc ]]; then
   cat $O/conv_traffic_r02.json
 fi
 if [[ $STAGE == all || $STAGE == shapes ]]; then
-  LDC_PROFILE_DUMP=/tmp/d.txt timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_shapes.json 2> $O/bench_shapes.err
+  LDC_PROFILE_DUMP=/tmp/d.txt timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_shapes.json 2> $O/bench_shapes.err
   python tools/prof_shapes.py /tmp/d.txt > $O/shapes_r02.txt 2>&1; head -60 $O/shapes_r02.txt
 fi

@@ -10,13 +10,13 @@ if [[ $STAGE == all || $STAGE == test ]]; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
 fi
 if [[ $STAGE == all || $STAGE == bench ]]; then
-  timeout 900 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; tail -2 $O/bench_c2.err
+  timeout 900 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; tail -2 $O/bench_c2.err
   for c in c3 c8 c5 c4; do
-    timeout 900 python bench.py --config $c --steps 3 --warmup 1 > $O/bench_$c.json 2> $O/bench_$c.err; tail -1 $O/bench_$c.err
+    timeout 900 python bench.py --full --config $c --steps 3 --warmup 1 > $O/bench_$c.json 2> $O/bench_$c.err; tail -1 $O/bench_$c.err
   done
   LDC_TRAIN_FP32_MFMA=1 timeout 600 python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c4_fp32_mfma.json 2> /dev/null
-  LDC_FP8_ACT=0 timeout 600 python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_c5_weights_only.json 2> /dev/null
-  timeout 600 python bench.py --dtype fp8 --steps 4 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_c2_fp8.json 2> /dev/null
+  LDC_FP8_ACT=0 timeout 600 python bench.py --full --config c5 --steps 3 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_c5_weights_only.json 2> /dev/null
+  timeout 600 python bench.py --full --dtype fp8 --steps 4 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_c2_fp8.json 2> /dev/null
   python - <<PY
 import json, glob
 for f in sorted(glob.glob("$O/bench_*.json")):
@@ -56,6 +56,6 @@ if [[ $STAGE == all || $STAGE == pmc ]]; then
   cat $O/conv_traffic.json $O/cal_traffic.json
 fi
 if [[ $STAGE == all || $STAGE == shapes ]]; then
-  LDC_PROFILE_DUMP=/tmp/d.txt timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_shapes.json 2> $O/bench_shapes.err
+  LDC_PROFILE_DUMP=/tmp/d.txt timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_shapes.json 2> $O/bench_shapes.err
   python tools/prof_shapes.py /tmp/d.txt > $O/layer_shapes.txt 2>&1; head -30 $O/layer_shapes.txt
 fi

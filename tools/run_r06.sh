@@ -15,9 +15,9 @@ test)
   ( time timeout 1500 python -m pytest tests -m gpu -q -x --durations=8 > $O/gputest.log 2>&1 ) 2> $O/gputest.time; tail -14 $O/gputest.log; cat $O/gputest.time
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log ;;
 benchq)   # quick c2 line, no CPU baseline
-  timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-pipelined > $O/benchq_c2.json 2> $O/benchq_c2.err; tail -2 $O/benchq_c2.err; cat $O/benchq_c2.json ;;
+  timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-pipelined > $O/benchq_c2.json 2> $O/benchq_c2.err; tail -2 $O/benchq_c2.err; cat $O/benchq_c2.json ;;
 bench)
-  timeout 900 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; tail -2 $O/bench_c2.err; cat $O/bench_c2.json ;;
+  timeout 900 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; tail -2 $O/bench_c2.err; cat $O/bench_c2.json ;;
 leantest)
   timeout 900 python -m pytest tests/test_gpu_bench_shape.py tests/test_gpu_parity.py -m gpu -q -x -k "lean_conv_kernel or conv_fast_every_tile_shape" > $O/leantest.log 2>&1; tail -5 $O/leantest.log ;;
 leanab)   # the lean kernel against conv_fast_kernel: hot microbenchmark with per-workgroup stamps, then the quick c2 line
@@ -74,11 +74,11 @@ pmc)   # PMC_TAG=_nosk LDC_OPTIONS=conv_splitk=0 bash tools/run_r06.sh pmc : the
 timed)
   timeout 600 python tools/timed_mode_stats.py > $O/timed_mode_kernel_stats.md 2> $O/timed_mode.err; head -12 $O/timed_mode_kernel_stats.md ;;
 configs)   # the other BASELINE configs (builder-run lines)
-  timeout 300 python bench.py --config c1 --steps 20 --warmup 3 > $O/bench_c1.json 2> $O/bench_c1.err; tail -1 $O/bench_c1.err
+  timeout 300 python bench.py --full --config c1 --steps 20 --warmup 3 > $O/bench_c1.json 2> $O/bench_c1.err; tail -1 $O/bench_c1.err
   for c in c3 c8 c5 c4; do
-    timeout 900 python bench.py --config $c --steps $([ $c = c4 ] && echo 6 || echo 3) --warmup $([ $c = c4 ] && echo 2 || echo 1) > $O/bench_$c.json 2> $O/bench_$c.err; tail -1 $O/bench_$c.err
+    timeout 900 python bench.py --full --config $c --steps $([ $c = c4 ] && echo 6 || echo 3) --warmup $([ $c = c4 ] && echo 2 || echo 1) > $O/bench_$c.json 2> $O/bench_$c.err; tail -1 $O/bench_$c.err
   done
-  timeout 600 python bench.py --dtype fp8 --steps 4 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_c2_fp8.json 2> /dev/null
+  timeout 600 python bench.py --full --dtype fp8 --steps 4 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_c2_fp8.json 2> /dev/null
   python - <<PY
 import json, glob
 for f in sorted(glob.glob("$O/bench_*.json")):

@@ -1,6 +1,6 @@
 cd /tmp; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 rm -rf $O/prof_serial
-LDC_SERIAL=1 timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof_serial -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-roofline > $O/prof_serial.log 2>&1
+LDC_SERIAL=1 timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof_serial -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-roofline > $O/prof_serial.log 2>&1
 python - <<'PY'
 import sqlite3,glob,os
 db=glob.glob(os.environ.get('GRAFT_REPO_ROOT','.')+'/gpurun_out/prof_serial/**/*.db',recursive=True)[0]
