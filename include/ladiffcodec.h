@@ -201,6 +201,24 @@ int ldc_output_normalise(ldc_ctx* ctx, float* wav_inout, int B, int T, int per_i
 int ldc_decode(ldc_ctx* ctx, const float* wav, int B, int T, int n_steps, const float* noise, int per_item,
                float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
 
+/* DDIM sampling: diffusion.ddim_sample (ddpm_loss.py:268-303) with clip_denoised, started at any t_start <= timesteps.
+ * times = reversed(torch.linspace(-1, t_start - 1, n_steps + 1).int()); per pair (t, t_next):
+ *   x0 = clamp(sqrt_recip_ac[t] img - sqrt_recipm1_ac[t] eps, -1, 1); img = x0 if t_next < 0, else
+ *   img = x0 sqrt(ac[t_next]) + c eps + sigma z,  sigma = eta sqrt((1 - a / a_next)(1 - a_next) / (1 - a)), c = sqrt(1 - a_next - sigma^2).
+ * sigma and c are computed on the host in float32; z is drawn only where sigma > 0.  Refused: n_steps outside [1, t_start],
+ * t_start outside [1, timesteps], eta outside [0, 1] or not finite.
+ * ldc_ddim_times: the reference's list of n_steps + 1 timesteps (the last is -1); host-only, needs no context or GPU. */
+int ldc_ddim_times(int t_start, int n_steps, int* times_out);
+/* t_start = timesteps with an N(0,1) start image is the reference's ddim_sample.  fill_start != 0: img is drawn ~N(0,1) on the
+ * device first; 0: img holds the start image.  noise [n_steps,B,C,L] (entry j at iteration j; the last is unused) or NULL.
+ * The steps replay captured graphs as ldc_denoise's do, keyed by (B, L, F) and the sampler kind: any n_steps and eta reuse them. */
+int ldc_ddim_sample(ldc_ctx* ctx, float* img_inout, const float* cond, const float* noise, int fill_start, int t_start,
+                    int n_steps, float eta, int B, int L, int F, void* stream);
+/* ldc_decode with DDIM sampling from t_start (the start image is the upsampled, max-normalised condition, as in ldc_decode's
+ * halfway sampling).  noise [n_steps,B,C,L] or NULL. */
+int ldc_decode_ddim(ldc_ctx* ctx, const float* wav, int B, int T, int t_start, int n_steps, float eta, const float* noise,
+                    int per_item, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+
 /* bit-stream layer: the on-wire format between ldc_rvq_encode and ldc_rvq_decode -- SURVEY.md section 8(f) row 3 ------------
  * Every batch item is an independent stream.  All results are bit-exact with the reference classes.  These calls need no
  * weights (any context of the device).

@@ -3,6 +3,7 @@
 //
 //   p_sample arithmetic  : reference srcs/losses/ddpm_loss.py:175-179 (x0 from eps), :237-238 (clamp),
 //                          :199-206 (posterior mean), :249-250 (noise unless t == 0)
+//   ddim_update          : ddpm_loss.py:268-303 (ddim_sample, clip_denoised); coefficients per iteration from the host
 //   max-abs scaling      : unet.py:401-403 (per item, +1e-20) and sample.py:129 (whole tensor, +1e-8)
 //   output normalisation : sample.py:133-134
 // All kernels here are HBM-bound: p_sample_update moves 4 fp32 reads/writes + 2 dtype accesses per
@@ -321,6 +322,98 @@ hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const fl
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// DDIM update (ddpm_loss.py ddim_sample with clip_denoised): the p_sample_update tiling, coefficients of iteration
+// j = st[1] from the host-written schedule table.  x0 uses eps as the UNet returned it (the reference does not
+// re-derive pred_noise from the clipped x0).
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* eps_cl, const float* noise,
+                                                          int64_t noise_step_stride, void* x_cl, int C, int L,
+                                                          StepTables tb, const DdimStep* sched, const int* st,
+                                                          uint64_t elem_base) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  float ev[4], xin[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int l = l0 + i, c = c0 + tx;
+    ev[ii] = (l < L && c < C) ? dld<T>(eps_cl, ((size_t)b * L + l) * C + c) : 0.f;
+    const int cc = c0 + i, ll = l0 + tx;
+    xin[ii] = (cc < C && ll < L) ? x[((size_t)b * C + cc) * L + ll] : 0.f;
+  }
+  const int j = st[1];
+  const uint64_t seed = ((uint64_t)(unsigned)st[3] << 32) | (uint64_t)(unsigned)st[2];
+  const DdimStep sp = sched[j];
+  const float recip = tb.sqrt_recip_alphas_cumprod[sp.t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[sp.t];
+  const bool draw = !sp.last && sp.sigma > 0.f;
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
+  __syncthreads();
+  float newv[4];
+  // one Philox block per thread at the global index of its first element, as in p_sample_update_kernel
+  float zz[4] = {0.f, 0.f, 0.f, 0.f};
+  if (draw && !noise) philox_normal4(seed, (unsigned)j, elem_base + ((size_t)b * C + c0 + ty) * L + l0 + tx, zz);
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int c = c0 + i, l = l0 + tx;
+    newv[ii] = 0.f;
+    if (c < C && l < L) {
+      const size_t idx = ((size_t)b * C + c) * L + l;
+      const float e = tile[tx][i];
+      float x0 = recip * xin[ii] - recipm1 * e;
+      x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+      float v = x0;
+      if (!sp.last) {
+        v = x0 * sp.sqrt_an + sp.c * e;
+        if (draw) v += sp.sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);
+      }
+      x[idx] = v;
+      newv[ii] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][l]
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int l = l0 + i, c = c0 + tx;
+    if (l < L && c < C) dst<T>(x_cl, ((size_t)b * L + l) * C + c, tile[tx][i]);
+  }
+}
+
+hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
+                              void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
+                              uint64_t elem_base, hipStream_t s) {
+  dim3 grid((L + 31) / 32, (C + 31) / 32, B);
+  if (dt == DT_F32)
+    hipLaunchKernelGGL(ddim_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L,
+                       tb, sched, st, elem_base);
+  else
+    hipLaunchKernelGGL(ddim_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C,
+                       L, tb, sched, st, elem_base);
+  return hipGetLastError();
+}
+
+// the DDIM schedule table written on the stream (kernel arguments carry the entries: no host buffer outlives the call)
+constexpr int kDdimChunk = 64;
+struct DdimChunk { DdimStep e[kDdimChunk]; };
+__global__ void ddim_table_write_kernel(DdimStep* dst, DdimChunk src, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = src.e[threadIdx.x];
+}
+hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src, int n, hipStream_t s) {
+  for (int i0 = 0; i0 < n; i0 += kDdimChunk) {
+    DdimChunk ch{};
+    const int m = std::min(kDdimChunk, n - i0);
+    for (int i = 0; i < m; ++i) ch.e[i] = src[i0 + i];
+    hipLaunchKernelGGL(ddim_table_write_kernel, dim3(1), dim3(kDdimChunk), 0, s, dst + i0, ch, m);
+  }
+  return hipGetLastError();
+}
+
 // tl (optional): device-side timeline of the timed (graph-replayed, multi-stream) mode: constant-rate clock (100 MHz,
 // s_memrealtime) at the begin and the end of every step of this batch part, slot = the step's iteration index
 __global__ void step_advance_kernel(int* st, unsigned long long* tl) {
@@ -337,10 +430,11 @@ __global__ void step_set_kernel(int* st, int t, int j, unsigned key_lo, unsigned
 // First kernel of a denoise step.  Workgroup 0 owns the part's step state: with `advance` it first moves on from the previous step
 // (t - 1, iteration + 1: until round 5 a one-thread launch of its own behind p_sample_update; the timeline's end stamp of that step
 // is taken here), counts the UNet-pass epoch up (st[4]: the XCD-team chains tag their tile flags with it, never cleared, never 0)
-// and copies the timestep's (scale | shift) row; every other workgroup clears the step's accumulator region (GroupNorm sums,
+// and copies the timestep's (scale | shift) row (DDIM: of the timestep the schedule table holds for iteration j); every other workgroup clears the step's accumulator region (GroupNorm sums,
 // split-K counters, k-max keys: until round 3 a memset node of its own): zero_n16 16-byte pieces starting at `zero`.
 __global__ __launch_bounds__(1024) void step_begin_kernel(const float* table, int stride, int* st, float* cur,
-                                                          unsigned long long* tl, uint4* zero, long long zero_n16, int advance) {
+                                                          unsigned long long* tl, uint4* zero, long long zero_n16, int advance,
+                                                          const DdimStep* ddim) {
   constexpr int nthr = 1024;
   if (blockIdx.x == 0) {
     __shared__ int sh_t;
@@ -354,6 +448,10 @@ __global__ __launch_bounds__(1024) void step_begin_kernel(const float* table, in
         j += 1;
         st[0] = t;
         st[1] = j;
+      }
+      if (ddim) {   // DDIM: the timestep of iteration j comes from the strided schedule
+        t = ddim[max(j, 0)].t;
+        st[0] = t;
       }
       if (tl) tl[2 * (j & 2047)] = now;
       st[4] = epoch + 1;
@@ -386,11 +484,11 @@ __global__ __launch_bounds__(1024) void step_begin_kernel(const float* table, in
   for (long long i = bi * nthr + threadIdx.x; i < zero_n16; i += nb * nthr) zero[i] = z;
 }
 hipError_t launch_step_begin(const float* table, int stride, int* st, float* cur, unsigned long long* tl, hipStream_t s,
-                             void* zero, size_t zero_bytes, int advance) {
+                             void* zero, size_t zero_bytes, int advance, const DdimStep* ddim) {
   const long long n16 = (long long)((zero_bytes + 15) / 16);
   const long long want = n16 > 0 ? 1 + (n16 + 4095) / 4096 : 1;
   hipLaunchKernelGGL(step_begin_kernel, dim3((unsigned)std::min<long long>(256, want)), dim3(1024), 0, s, table, stride, st, cur, tl,
-                     reinterpret_cast<uint4*>(zero), n16, advance);
+                     reinterpret_cast<uint4*>(zero), n16, advance, ddim);
   return hipGetLastError();
 }
 // one workgroup that holds its CU slot for `us` microseconds of the 100 MHz wall clock (bounded): the stream-overlap calibration of ldc_api.cpp

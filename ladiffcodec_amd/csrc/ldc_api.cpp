@@ -584,6 +584,7 @@ static int build_unet(ldc_ctx* c, std::string* missing) {
     float* d = nullptr;
     LDCCHK(c->wmem.upload(&d, t->data));
     dev[n] = d;
+    if (std::string(n) == "alphas_cumprod") c->alphas_cumprod = t->data;
   }
   c->sched.sqrt_recip_alphas_cumprod = dev["sqrt_recip_alphas_cumprod"];
   c->sched.sqrt_recipm1_alphas_cumprod = dev["sqrt_recipm1_alphas_cumprod"];
@@ -792,6 +793,7 @@ extern "C" int ldc_destroy(ldc_ctx* c) {
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->outnorm_ws) (void)hipFree(c->outnorm_ws);
   if (c->state_buf) (void)hipFree(c->state_buf);
+  if (c->ddim_table) (void)hipFree(c->ddim_table);
   if (c->step_state) (void)hipFree(c->step_state);
   if (c->dev_flag_host) (void)hipHostFree(c->dev_flag_host);
   if (c->tl_buf) (void)hipFree(c->tl_buf);
@@ -2107,15 +2109,22 @@ extern "C" int ldc_unet_debug_tap(ldc_ctx* c, const char* name, float* out, int6
 
 // one reverse-diffusion step of batch part k on stream s: select the timestep row, run the UNet, update the state,
 // advance this part's step counter.  Parts never interact, so each is a self-contained chain.
-static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* noise, int64_t noise_stride, hipStream_t s) {
+// ddim (null: DDPM p_sample): the device schedule table of a DDIM loop (step_begin takes t from it, ddim_update the coefficients)
+static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* noise, int64_t noise_stride, hipStream_t s,
+                     const DdimStep* ddim = nullptr) {
   Plan* pl = h.p[k];
   const size_t off = (size_t)h.b0[k] * c->unet.channels * pl->L;
   unsigned long long* tl = c->timeline ? c->tl_buf + (size_t)k * 2048 * 2 : nullptr;
   // (the step state moves on in the step's FIRST kernel: the callers start a loop from (t + 1, iteration - 1), set_steps)
-  HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, tl, s, pl->zero_ptr, pl->zero_bytes, c->merge_advance));
+  HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, tl, s, pl->zero_ptr, pl->zero_bytes, c->merge_advance,
+                           ddim));
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
-  HIPCHK(launch_p_sample_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
-                                c->unet.channels, pl->L, c->sched, pl->step_state, (uint64_t)off, s));
+  if (ddim)
+    HIPCHK(launch_ddim_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
+                              c->unet.channels, pl->L, c->sched, ddim, pl->step_state, (uint64_t)off, s));
+  else
+    HIPCHK(launch_p_sample_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
+                                  c->unet.channels, pl->L, c->sched, pl->step_state, (uint64_t)off, s));
   if (!c->merge_advance) HIPCHK(launch_step_advance(pl->step_state, tl, s));   // (LDC_STEP_ADVANCE_LAUNCH: the round-4 structure, for A/B runs)
   return LDC_OK;
 }
@@ -2149,13 +2158,14 @@ static int set_steps(ldc_ctx* c, const Halves& h, int t, int j, hipStream_t s) {
 }
 
 // one step of every part, eagerly: part 0 on s, the others on the auxiliary streams, joined at the end
-static int one_step(ldc_ctx* c, const Halves& h, float* x, const float* noise, int64_t noise_stride, hipStream_t s) {
+static int one_step(ldc_ctx* c, const Halves& h, float* x, const float* noise, int64_t noise_stride, hipStream_t s,
+                    const DdimStep* ddim = nullptr) {
   if (parts_parallel(c, h)) {
     LDCCHK(fork_parts(c, h, s));
-    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, k == 0 ? s : c->aux_stream[k]));
+    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, k == 0 ? s : c->aux_stream[k], ddim));
     LDCCHK(join_parts(c, h, s));
   } else {
-    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, s));
+    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, s, ddim));
   }
   return LDC_OK;
 }
@@ -2179,20 +2189,24 @@ extern "C" int ldc_p_sample(ldc_ctx* c, float* x, int t, const float* cond, cons
 
 // the denoise loop on prepared plans (cond already processed, x_cl already set)
 // left_forked (optional): the caller continues per part on the parts' streams; the per-part replay path then leaves them un-joined and says so
-static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const float* noise, int n_steps, hipStream_t s, bool* left_forked = nullptr) {
+// ddim (optional): n_steps DDIM iterations on the schedule already written to c->ddim_table (ddim == c->ddim_table); else DDPM
+// steps from t = n_steps - 1 down to 0
+static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const float* noise, int n_steps, hipStream_t s, bool* left_forked = nullptr,
+                        const DdimStep* ddim = nullptr) {
   if (left_forked) *left_forked = false;
   const int L = h.p[0]->L, F = h.p[0]->F;
   const int64_t stride = (int64_t)B * c->unet.channels * L;
-  LDCCHK(set_steps(c, h, n_steps - 1, 0, s));
+  LDCCHK(set_steps(c, h, n_steps - 1, 0, s));   // (DDIM: t is overwritten from the table in every step's first kernel)
   if (c->profile || c->serial_parts || n_steps < 3) {
     if (left_forked && h.n >= 2) LDCCHK(join_parts(c, h, s));   // (the caller's per-part work is on the auxiliary streams; these steps may all run on s)
-    for (int i = 0; i < n_steps; ++i) LDCCHK(one_step(c, h, x, noise, stride, s));
+    for (int i = 0; i < n_steps; ++i) LDCCHK(one_step(c, h, x, noise, stride, s, ddim));
     for (int k = 0; k < h.n; ++k) LDCCHK(stamp_loop_end(c, h, k, s));
     return LDC_OK;
   }
   StepGraph* sg = nullptr;
+  const int kind = ddim ? 1 : 0;   // a DDPM loop never replays a DDIM graph or the reverse; both stay cached side by side
   for (auto& g : c->graphs)
-    if (g.B == B && g.L == L && g.F == F) sg = &g;
+    if (g.B == B && g.L == L && g.F == F && g.ddim == kind) sg = &g;
   if (!sg) {
     // graphs of shapes whose plans are gone were dropped with them (evict_plan); additionally keep at most 16 alive
     if (c->graphs.size() >= 16) {
@@ -2205,7 +2219,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     }
     c->graphs.push_back(StepGraph());
     sg = &c->graphs.back();
-    sg->B = B; sg->L = L; sg->F = F;
+    sg->B = B; sg->L = L; sg->F = F; sg->ddim = kind;
   }
   sg->last_use = ++c->use_tick;
   const bool par = parts_parallel(c, h);
@@ -2216,14 +2230,18 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   // 10 / 25 steps 2 % / 16 % slower), 10 steps of a single chain (5 steps 2.8 % slower; 8 / 10 / 25 equal).  A remainder of
   // single-step replays is slow (13 or 17 steps per graph: 154 instead of 124 ms), so the defaults divide the usual 50.
   int k_want = c->graph_steps > 0 ? c->graph_steps : (h.n == 1 ? 10 : 5);
-  if (c->graph_steps == 0) {   // prefer a graph length that divides the step count (within the flat part of the measured range)
+  if (ddim) {
+    // DDIM: one graph length whatever the step count, so that every S and eta replays the same captured graphs (a DDIM decode has
+    // a few to a few tens of steps: 5 steps per graph, and single-step replays for the remainder)
+    k_want = c->graph_steps > 0 ? c->graph_steps : 5;
+  } else if (c->graph_steps == 0) {   // prefer a graph length that divides the step count (within the flat part of the measured range)
     const int lo = h.n == 1 ? 8 : 3, hi = h.n == 1 ? 25 : 7;
     int best = 0;
     for (int k = lo; k <= hi; ++k)
       if (n_steps % k == 0 && (best == 0 || std::abs(k - k_want) < std::abs(best - k_want))) best = k;
     if (best) k_want = best;
   }
-  const int K = std::min(k_want, std::max(1, n_steps - 1));
+  const int K = ddim ? k_want : std::min(k_want, std::max(1, n_steps - 1));
   int done = 0;
   if (!sg->any() || sg->noise != noise || sg->x != x || sg->stream != s || sg->n != h.n * 100 + K + ((par && c->part_graphs && (h.n == 2 || c->part_graphs >= 2)) ? 100000 : 0)) {
     if (sg->any()) {
@@ -2233,7 +2251,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
       sg->destroy();
     }
     // first step eagerly: loads code objects / sets function attributes outside of the capture
-    LDCCHK(one_step(c, h, x, noise, stride, s));
+    LDCCHK(one_step(c, h, x, noise, stride, s, ddim));
     done = 1;
     const bool per_part = par && c->part_graphs && (h.n == 2 || c->part_graphs >= 2);   // (LDC_PART_GRAPHS=2: also for three / four parts)   // (three parts on per-part graphs measured 45 % slower than the fork/join graph)
     if (per_part) {
@@ -2249,7 +2267,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
           hipGraph_t g = nullptr;
           HIPCHK(hipStreamBeginCapture(sk, hipStreamCaptureModeRelaxed));
           int r = LDC_OK;
-          for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, sk);
+          for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, sk, ddim);
           hipError_t e = hipStreamEndCapture(sk, &g);
           if (r != LDC_OK) { if (g) (void)hipGraphDestroy(g); return r; }
           if (e != hipSuccess) return fail(LDC_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
@@ -2271,7 +2289,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
       int r = LDC_OK;
       if (par) r = fork_parts(c, h, s);
       for (int k = 0; k < h.n && r == LDC_OK; ++k)
-        for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, (k == 0 || !par) ? s : c->aux_stream[k]);
+        for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, (k == 0 || !par) ? s : c->aux_stream[k], ddim);
       if (par && r == LDC_OK) r = join_parts(c, h, s);
       hipError_t e = hipStreamEndCapture(s, &g);
       if (r != LDC_OK) { if (g) (void)hipGraphDestroy(g); return r; }
@@ -2454,6 +2472,88 @@ extern "C" int ldc_infilling(ldc_ctx* c, float* img, float* infill_img, const fl
   return finish_stream(c, stream);
 }
 
+// ---- DDIM sampling (GaussianDiffusion1D.ddim_sample, ddpm_loss.py:268-303, with clip_denoised) from any t_start <= timesteps ----
+// times = reversed(torch.linspace(-1, t_start - 1, n_steps + 1).int()).  ATen's float32 linspace computes the first half forwards
+// from the start and the second half backwards from the end (step = (end - start) / (n - 1), all in float32); .int() truncates
+// toward zero.  Host-only: needs no context.
+extern "C" int ldc_ddim_times(int t_start, int n_steps, int* times_out) {
+#pragma clang fp contract(off)
+  if (!times_out) return fail(LDC_E_INVALID, "null output");
+  if (t_start < 1) return fail(LDC_E_INVALID, "t_start must be >= 1");
+  if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps must be in [1, t_start = %d] (more would repeat timesteps)", t_start);
+  const int n = n_steps + 1, half = n / 2;
+  const float a = -1.0f, b = (float)(t_start - 1);
+  const float step = (b - a) / (float)(n - 1);
+  for (int i = 0; i < n; ++i) {
+    const float v = i < half ? a + step * (float)i : b - step * (float)(n - 1 - i);
+    times_out[n - 1 - i] = (int)v;
+  }
+  return LDC_OK;
+}
+
+// the per-iteration coefficients into c->ddim_host; float32 in the reference's order of operations.  *draws: some sigma > 0
+static int ddim_schedule(ldc_ctx* c, int t_start, int n_steps, float eta, bool* draws) {
+  if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "eta must be a finite value in [0, 1]");
+  if (t_start < 1 || t_start > c->unet.timesteps) return fail(LDC_E_INVALID, "t_start must be in [1,%d]", c->unet.timesteps);
+  if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps must be in [1, t_start = %d] (more would repeat timesteps)", t_start);
+  if ((int)c->alphas_cumprod.size() != c->unet.timesteps) return fail(LDC_E_STATE, "no alphas_cumprod schedule loaded");
+  std::vector<int> times(n_steps + 1);
+  LDCCHK(ldc_ddim_times(t_start, n_steps, times.data()));
+  const std::vector<float>& ac = c->alphas_cumprod;
+  c->ddim_host.assign(n_steps, DdimStep{});
+  *draws = false;
+  for (int j = 0; j < n_steps; ++j) {
+    DdimStep& e = c->ddim_host[j];
+    const int t = times[j], tn = times[j + 1];
+    e.t = t;
+    e.last = tn < 0;
+    if (e.last) continue;
+    const float alpha = ac[t], alpha_next = ac[tn];
+    const float sigma = eta * std::sqrt((1.0f - alpha / alpha_next) * (1.0f - alpha_next) / (1.0f - alpha));
+    e.sigma = sigma;
+    e.c = std::sqrt(std::max(0.0f, 1.0f - alpha_next - sigma * sigma));   // (>= 0 for eta <= 1; the clamp only absorbs rounding)
+    e.sqrt_an = std::sqrt(alpha_next);
+    *draws = *draws || sigma > 0.0f;
+  }
+  return LDC_OK;
+}
+
+// c->ddim_host -> the context's device table, ordered on s behind everything queued there before (earlier calls' replays read it)
+static int ddim_upload(ldc_ctx* c, hipStream_t s) {
+  if (!c->ddim_table) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, (size_t)(c->unet.timesteps + 1) * sizeof(DdimStep)));
+    c->ddim_table = (DdimStep*)p;
+  }
+  HIPCHK(launch_ddim_table_write(c->ddim_table, c->ddim_host.data(), (int)c->ddim_host.size(), s));
+  return LDC_OK;
+}
+
+// DDIM over prepared arguments, as ldc_p_sample_loop: fill_start draws the N(0,1) start image on the device (Philox stream
+// 0xfffffffd); `noise` (optional, parity runs) [n_steps][B][C][L], entry j for iteration j (the last one is not read)
+extern "C" int ldc_ddim_sample(ldc_ctx* c, float* img, const float* cond, const float* noise, int fill_start, int t_start, int n_steps,
+                               float eta, int B, int L, int F, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  LDCCHK(check_unet_args(c, B, L, F));
+  bool draws = false;
+  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  hipStream_t s = pick_stream(c, stream);
+  LDCCHK(ddim_upload(c, s));
+  next_noise_key(c, (noise == nullptr && draws) || fill_start);
+  if (fill_start) HIPCHK(launch_random_fill(img, (int64_t)B * c->unet.channels * L, 0, c->cur_key, 0xfffffffdu, s));
+  Halves h;
+  LDCCHK(get_halves(c, B, L, F, s, &h));
+  LDCCHK(load_cond(c, h, cond, s));
+  const size_t nbytes = (size_t)B * c->unet.channels * L * 4;
+  LDCCHK(ensure_state(c, nbytes));
+  HIPCHK(hipMemcpyAsync(c->state_buf, img, nbytes, hipMemcpyDeviceToDevice, s));
+  LDCCHK(load_x(c, h, c->state_buf, s));
+  LDCCHK(denoise_loop(c, h, B, c->state_buf, noise, n_steps, s, nullptr, c->ddim_table));
+  HIPCHK(hipMemcpyAsync(img, c->state_buf, nbytes, hipMemcpyDeviceToDevice, s));
+  return finish_stream(c, stream);
+}
+
 static int ensure_outnorm(ldc_ctx* c, int B) {
   const size_t need = output_normalise_ws_bytes(B);
   if (need <= c->outnorm_ws_bytes) return LDC_OK;
@@ -2475,12 +2575,10 @@ extern "C" int ldc_output_normalise(ldc_ctx* c, float* wav, int B, int T, int pe
   return finish_stream(c, stream);
 }
 
-// synthesis() body for one resident batch (sample.py:94-134)
-extern "C" int ldc_decode(ldc_ctx* c, const float* wav, int B, int T, int n_steps, const float* noise, int per_item,
-                          float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
-  if (!wav || !wav_out || B <= 0 || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
-  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
+// synthesis() body for one resident batch (sample.py:94-134): ldc_decode (DDPM halfway sampling, ddim = false) and ldc_decode_ddim
+// (n_steps DDIM iterations on the schedule ddim_schedule left in c->ddim_host; draws: some of them add noise)
+static int decode_body(ldc_ctx* c, const float* wav, int B, int T, int n_steps, bool ddim, bool draws, const float* noise, int per_item,
+                       float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
   const Codec& cc = c->codec[LDC_MODEL_COND];
   const Codec& mc = c->codec[LDC_MODEL_MAIN];
   if (T % cc.hop || T % mc.hop) return fail(LDC_E_INVALID, "T must be a multiple of %d and %d (sample.py:87 trims to 640)", cc.hop, mc.hop);
@@ -2488,6 +2586,7 @@ extern "C" int ldc_decode(ldc_ctx* c, const float* wav, int B, int T, int n_step
   LDCCHK(check_unet_args(c, B, L, F));
   LDCCHK(ensure_outnorm(c, B));
   hipStream_t s = pick_stream(c, stream);
+  if (ddim) LDCCHK(ddim_upload(c, s));   // (in front of everything: the parts' streams fork from s behind it)
   Halves h;
   LDCCHK(get_halves(c, B, L, F, s, &h));
   // The codec front end (cond encoder -> RVQ -> upsampler -> start image) and back end (decoder) are chains of ~40 latency-bound
@@ -2544,9 +2643,10 @@ extern "C" int ldc_decode(ldc_ctx* c, const float* wav, int B, int T, int n_step
       // (the cooperative LSTMs), and one part's latency-bound back end then runs under the other's last denoise steps.
       // (c->ends_join / LDC_ENDS_JOIN: both joins as before, for A/B runs)
       if (split_ends && c->ends_join) { parts_open = false; LDCCHK(join_parts(c, h, s)); }
-      next_noise_key(c, noise == nullptr);
+      next_noise_key(c, noise == nullptr && draws);
       bool forked = false;
-      const int dr = denoise_loop(c, h, B, x, noise, n_steps, s, (split_ends && !c->ends_join) ? &forked : nullptr);
+      const int dr = denoise_loop(c, h, B, x, noise, n_steps, s, (split_ends && !c->ends_join) ? &forked : nullptr,
+                                  ddim ? c->ddim_table : nullptr);
       if (dr != LDC_OK) return bail(dr);
       if (split_ends && !forked) { parts_open = false; LDCCHK(fork_parts(c, h, s)); }   // (the loop joined, or never left s)
       parts_open = split_ends;
@@ -2578,6 +2678,25 @@ extern "C" int ldc_decode(ldc_ctx* c, const float* wav, int B, int T, int n_step
     return LDC_OK;
   }));
   return finish_stream(c, stream);
+}
+
+extern "C" int ldc_decode(ldc_ctx* c, const float* wav, int B, int T, int n_steps, const float* noise, int per_item,
+                          float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || B <= 0 || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
+  return decode_body(c, wav, B, T, n_steps, false, true, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
+// the decode with DDIM sampling from t_start (the DDIM counterpart of halfway_sampling: the start image is the upsampled,
+// max-normalised condition, as in ldc_decode); noise (optional) [n_steps][B][C][L]
+extern "C" int ldc_decode_ddim(ldc_ctx* c, const float* wav, int B, int T, int t_start, int n_steps, float eta, const float* noise,
+                               int per_item, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || B <= 0 || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  bool draws = false;
+  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  return decode_body(c, wav, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
 }
 
 

@@ -216,8 +216,9 @@ struct Halves {                // (the name dates from the two-way split; n part
 
 static constexpr int kKstOps = 256;   // stamp slots per step (one per op of the step list)
 
-struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update, step_advance}
+struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update, step_advance}
   int B = 0, L = 0, F = 0, n = 0;
+  int ddim = 0;      // sampler kind (part of the cache key): 1 = DDIM steps (the schedule table's address is captured, not its contents)
   const float* noise = nullptr;
   float* x = nullptr;
   hipStream_t stream = nullptr;
@@ -252,6 +253,9 @@ struct ldc_ctx {
   const float* sqrt_alphas_cumprod = nullptr;
   const float* sqrt_one_minus_alphas_cumprod = nullptr;
   const float* p2_loss_weight = nullptr;
+  std::vector<float> alphas_cumprod;   // host copy of the schedule buffer: the DDIM coefficients are computed on the host
+  DdimStep* ddim_table = nullptr;      // device [timesteps + 1]: allocated once, so captured DDIM graphs keep a valid address
+  std::vector<DdimStep> ddim_host;     // the last schedule written to it
   int* step_state = nullptr;    // device int[2]: t, j
   std::vector<std::unique_ptr<Plan>> plans;
   std::vector<StepGraph> graphs;

@@ -195,6 +195,23 @@ hipError_t launch_axpby(float* x, const float* y, float a, float b, int64_t n, h
 hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                                   void* x_cl, int B, int C, int L, StepTables tb, const int* st,
                                   uint64_t elem_base, hipStream_t s);
+// One iteration of DDIM sampling (reference ddpm_loss.py ddim_sample, clip_denoised): the host fills one entry per
+// iteration j (ldc_api.cpp: ddim_schedule) into a device table that the step state indexes.
+struct DdimStep {
+  int t;           // UNet timestep of iteration j
+  int last;        // time_next < 0: x <- x0
+  float sqrt_an;   // sqrt(alphas_cumprod[time_next])
+  float c;         // sqrt(1 - alpha_next - sigma^2)
+  float sigma;     // eta * sqrt((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)); noise is drawn only when > 0
+  float pad_[3];
+};
+// x0 = clamp(sqrt_recip_ac[t] x - sqrt_recipm1_ac[t] eps, -1, 1); x <- last ? x0 : x0 sqrt_an + c eps + sigma z.
+// Same layouts as launch_p_sample_update; t, coefficients and the draw of iteration j = st[1] from sched[j]
+// (noise tape entry j, or Philox (key, j, global element)).
+hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src_host, int n, hipStream_t s);   // dst[0..n) = src_host[0..n), stream-ordered
+hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
+                              void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
+                              uint64_t elem_base, hipStream_t s);
 // x /= (maxabs[b or 0] + eps) in place on a raw element stream (n_per_item elements per item)
 hipError_t launch_scale_by_maxabs(int dt, void* x, int B, int64_t n_per_item, const float* maxabs, int per_item,
                                   float eps, hipStream_t s);
@@ -208,8 +225,9 @@ hipError_t launch_step_advance(int* st, unsigned long long* tl, hipStream_t s); 
 // dependent load through the step counter
 // also zeroes [zero, zero + zero_bytes) (rounded up to 16 bytes: the caller pads the region): the step's accumulators
 // advance = 1: first move the step state on from the previous step (t - 1, iteration + 1), i.e. a loop starts from (t + 1, -1)
+// ddim (DDIM loops, else null): then t = ddim[j].t, the timestep of iteration j of the strided schedule
 hipError_t launch_step_begin(const float* table, int stride, int* st, float* cur, unsigned long long* tl, hipStream_t s,
-                             void* zero = nullptr, size_t zero_bytes = 0, int advance = 0);
+                             void* zero = nullptr, size_t zero_bytes = 0, int advance = 0, const DdimStep* ddim = nullptr);
 hipError_t launch_step_set(int* st, int t, int j, uint64_t noise_key, hipStream_t s);
 hipError_t launch_clock_sample(unsigned long long* out2, hipStream_t s);   // out2[0] = 100 MHz wall clock, out2[1] = s_memtime (shader cycles)
 hipError_t launch_spin_us(unsigned us, hipStream_t s);   // one workgroup busy for `us` microseconds (stream-overlap calibration)

@@ -300,6 +300,25 @@ class Engine:
         self._exit()
         return img, infill
 
+    def ddim_sample(self, cond, t_start: int, n_steps: int, eta: float = 0.0, img=None, noise=None, length: Optional[int] = None):
+        """DDIM sampling (diffusion.ddim_sample with clip_denoised) from `t_start`: n_steps strided iterations from `img` (or from a
+        device-drawn N(0,1) image).  noise [n_steps, B, C, L] injects the draws (parity runs)."""
+        cond = self._f32(cond)
+        B, _, F = cond.shape
+        if img is None:
+            Lx = int(length) if length is not None else F * int(np.prod(self.unet.upsampling_ratios or ()))
+            img = self.torch.empty(B, self.unet.inp_channels, Lx, device=cond.device, dtype=self.torch.float32)
+            fill = 1
+        else:
+            img = self._f32(img).clone()
+            fill = 0
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        L.check(self.lib.ldc_ddim_sample(self._ctx, img.data_ptr(), cond.data_ptr(), noise.data_ptr() if noise is not None else None,
+                                         fill, int(t_start), int(n_steps), float(eta), B, img.shape[2], F, s))
+        self._exit()
+        return img
+
     def output_normalise(self, wav, per_item: bool = False):
         wav = self._f32(wav).clone()
         B = wav.shape[0]
@@ -323,6 +342,27 @@ class Engine:
         p = lambda t: t.data_ptr() if t is not None else None
         L.check(self.lib.ldc_decode(self._ctx, wav.data_ptr(), B, T, int(n_steps), p(noise), int(per_item), out.data_ptr(),
                                     p(lat), p(cond), p(codes), s))
+        self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
+        return out
+
+    def decode_ddim(self, wav, t_start: int, n_steps: int, eta: float = 0.0, noise=None, per_item: bool = False,
+                    want_stages: bool = False):
+        """`decode` with DDIM sampling: n_steps iterations from t_start, starting at the upsampled, normalised condition."""
+        wav = self._f32(wav)
+        B, _, T = wav.shape
+        F, Lz = T // self.cond_codec.hop_length, T // self.main_codec.hop_length
+        out = self._empty(B, 1, T)
+        lat = self._empty(B, self.main_codec.rep_dims, Lz) if want_stages else None
+        cond = self._empty(B, self.main_codec.rep_dims, F) if want_stages else None
+        n_q = self.cond_codec.n_q_for_bandwidth(None)
+        codes = self._empty(n_q, B, F, dtype=self.torch.int64) if want_stages else None
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        L.check(self.lib.ldc_decode_ddim(self._ctx, wav.data_ptr(), B, T, int(t_start), int(n_steps), float(eta), p(noise),
+                                         int(per_item), out.data_ptr(), p(lat), p(cond), p(codes), s))
         self._exit()
         if want_stages:
             return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
@@ -461,6 +501,10 @@ class _Diffusion:
         self._eng = eng
         self.seq_length = None
         self.num_timesteps = eng.unet.timesteps
+        # ddpm_loss.py:125-132 (is_ddim_sampling is hard-coded False there; set it to sample with DDIM)
+        self.sampling_timesteps = eng.unet.timesteps
+        self.ddim_sampling_eta = 0.0
+        self.is_ddim_sampling = False
 
     def p_sample(self, x, t: int, condition=None, noise=None):
         return self._eng.p_sample(x, t, condition, noise), None
@@ -478,10 +522,19 @@ class _Diffusion:
         """ddpm_loss.py:253-266; `img`/`noise` inject the start image and the per-step draws (parity runs)."""
         return self._eng.p_sample_loop(condition, img=img, noise=noise, length=shape[2])
 
+    def ddim_sample(self, shape, condition=None, clip_denoised=True, img=None, noise=None):
+        """ddpm_loss.py:268-303: sampling_timesteps DDIM iterations from num_timesteps with eta = ddim_sampling_eta;
+        `img`/`noise` inject the start image and the [S, B, C, L] draws (parity runs)."""
+        if not clip_denoised:
+            raise NotImplementedError("ddim_sample runs with clip_denoised=True only")
+        return self._eng.ddim_sample(condition, int(self.num_timesteps), int(self.sampling_timesteps), float(self.ddim_sampling_eta),
+                                     img=img, noise=noise, length=shape[2])
+
     def sample(self, batch_size=16, condition=None):
-        """ddpm_loss.py:305-309 (DDIM sampling is not on the hot path: is_ddim_sampling is False at 1000 steps)."""
+        """ddpm_loss.py:305-309: p_sample_loop, or ddim_sample when is_ddim_sampling is set."""
         assert self.seq_length is not None, "set diffusion.seq_length as the reference's constructor does"
-        return self.p_sample_loop((batch_size, self._eng.unet.inp_channels, self.seq_length), condition)
+        fn = self.ddim_sample if self.is_ddim_sampling else self.p_sample_loop
+        return fn((batch_size, self._eng.unet.inp_channels, self.seq_length), condition)
 
     def infilling(self, infill_img, condition, midway_t=None, noise=None, offset=0, lam=0.8, img=None, noises=None):
         """ddpm_loss.py:331-367 (`noise` and `offset` are accepted and unused, as in the reference); `img`/`noises`

@@ -214,7 +214,35 @@ def output_path(wav_file: str, input_dir: str, output_dir: str) -> str:
     return os.path.join(output_dir, f"{save_path}.wav")
 
 
-def synthesis(inp_args) -> List[str]:
+class DdpmSampler:
+    """The reference's decode: halfway sampling, `n_steps` ancestral steps (Engine.decode).  `draws`: noise tensors per call."""
+
+    def __init__(self, n_steps: int):
+        self.n_steps = self.draws = int(n_steps)
+
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        if want_stages:
+            return eng.decode(batch, self.n_steps, noise=noise, per_item=per_item, want_stages=True)
+        return eng.decode(batch, self.n_steps, noise=noise, per_item=per_item)
+
+
+class DdimSampler:
+    """DDIM decode (Engine.decode_ddim): `n_steps` strided iterations from `t_start` with `eta`."""
+
+    def __init__(self, t_start: int, n_steps: int, eta: float = 0.0):
+        self.t_start, self.n_steps, self.eta = int(t_start), int(n_steps), float(eta)
+        self.draws = self.n_steps
+
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        return eng.decode_ddim(batch, self.t_start, self.n_steps, self.eta, noise=noise, per_item=per_item, want_stages=want_stages)
+
+
+def _sampler(inp_args, sampler):
+    return sampler if sampler is not None else DdpmSampler(inp_args.midway_t)
+
+
+def synthesis(inp_args, sampler=None) -> List[str]:
+    """`sampler`: DdpmSampler (default, --midway_t steps) or DdimSampler."""
     import torch
     from scipy.io import wavfile
 
@@ -248,7 +276,7 @@ def synthesis(inp_args) -> List[str]:
         eng.load_state_dict(L.MODEL_COND, sd_cond)       # load_model(model, path, strict=True)
         eng.finalize(strict=True)
         engines.append(eng)
-    written = decode_files(engines if n_eng > 1 else engines[0], files, inp_args, rank, world, local_rank)
+    written = decode_files(engines if n_eng > 1 else engines[0], files, inp_args, rank, world, local_rank, sampler=sampler)
     for eng in engines:
         eng.close()
     return written
@@ -269,12 +297,15 @@ def apply_device_fallback(eng, err) -> bool:
     return True
 
 
-def decode_with_retry(eng, batch, n_steps: int, noise, per_item: bool):
+def decode_with_retry(eng, batch, n_steps: int, noise, per_item: bool, sampler=None):
     """One engine call; a batch hit by a device-side failure (or by the report of an earlier call's) is decoded again after
-    the matching fallback (apply_device_fallback), twice at most: the LSTM and the GroupNorm exchange can each give up once."""
+    the matching fallback (apply_device_fallback), twice at most: the LSTM and the GroupNorm exchange can each give up once.
+    `sampler` (optional) replaces the DDPM decode of n_steps."""
     from . import lib as L
     for attempt in range(3):
         try:
+            if sampler is not None:
+                return sampler(eng, batch, noise, per_item)
             return eng.decode(batch, n_steps, noise=noise, per_item=per_item)
         except L.LdcError as e:
             if attempt == 2 or not apply_device_fallback(eng, e):
@@ -326,13 +357,14 @@ def plan_chunks(n_samples: int, chunk: int, quantum: int = _CHUNK_QUANTUM) -> Li
     return out
 
 
-def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: int, local_rank: int) -> List[str]:
+def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: int, local_rank: int, sampler=None) -> List[str]:
     """Long-form mode: every chunk of every recording of this rank is one batch item (equal-length chunks share engine calls
     across recordings); the chunks' latents go through the decoder, the raw waveforms are joined per recording and the
     reference's output normalisation (sample.py:133-134) runs once over the whole recording."""
     import torch
     from scipy.io import wavfile
     from . import lib as L, parallel
+    sampler = _sampler(inp_args, sampler)
     quantum = chunk_quantum(getattr(inp_args, "enc_ratios", [8, 4]))
     chunk = max(quantum, int(round(inp_args.chunk_sec * 16000)) // quantum * quantum)
     mine = parallel.shard_utterances([sh[1] for sh in wavs.shapes], rank, world)
@@ -352,8 +384,8 @@ def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: i
             # test seam (see decode_files): keys are (file index, chunk number)
             provider = getattr(inp_args, "noise_provider", None)
             hop = int(np.prod(getattr(inp_args, "enc_ratios", [8])))
-            noise = provider([(i, k) for i, k, _ in part], inp_args.midway_t, ln // hop).to(dev) if provider is not None else None
-            stages = eng.decode(batch.to(dev), inp_args.midway_t, noise=noise, per_item=True, want_stages=True)
+            noise = provider([(i, k) for i, k, _ in part], sampler.draws, ln // hop).to(dev) if provider is not None else None
+            stages = sampler(eng, batch.to(dev), noise, True, want_stages=True)
             wav_raw = eng.decode_latents(L.MODEL_MAIN, stages["latents"])          # un-normalised decoder output
             for j, (i, k, _) in enumerate(part):
                 raw[i][k] = wav_raw[j:j + 1]
@@ -371,12 +403,14 @@ def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: i
     return written
 
 
-def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_rank: int) -> List[str]:
-    """`eng`: one engine, or a list of engines (one batch in flight per engine, each on its own stream)."""
+def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_rank: int, sampler=None) -> List[str]:
+    """`eng`: one engine, or a list of engines (one batch in flight per engine, each on its own stream); `sampler`: as synthesis."""
     import torch
     from scipy.io import wavfile
     engines = list(eng) if isinstance(eng, (list, tuple)) else [eng]
     eng = engines[0]
+    sampler = _sampler(inp_args, sampler)
+    steps = sampler.draws
     wavs = LazyWavs(files, eng)                     # headers only: (channels, samples at 16 kHz); data is loaded per shard
     keep = [i for i, sh in enumerate(wavs.shapes) if sh[1] // 640 * 640 > 0]                  # sample.py:87-88
     files, wavs = [files[i] for i in keep], wavs.subset(keep)
@@ -388,7 +422,7 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
         short_i = [i for i, m in enumerate(is_long) if not m]
         long_f, long_w = [files[i] for i in long_i], wavs.subset(long_i)
         files, wavs = [files[i] for i in short_i], wavs.subset(short_i)
-        written_long = decode_long_files(eng, long_f, long_w, inp_args, rank, world, local_rank) if long_f else []
+        written_long = decode_long_files(eng, long_f, long_w, inp_args, rank, world, local_rank, sampler=sampler) if long_f else []
     else:
         written_long = []
     lengths = [sh[1] for sh in wavs.shapes]
@@ -410,11 +444,11 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
             # (that report -- LDC_E_HIP with the failure's tag -- may well arrive in the redo itself: decode_with_retry applies the
             # matching fallback and decodes again; without a report the cooperative LSTM is the one that poisons silently)
             eng_k, batch_k, per_item_k, noise_k = redo
-            out = decode_with_retry(eng_k, batch_k.to(dev), inp_args.midway_t, noise_k, per_item_k).cpu()
+            out = decode_with_retry(eng_k, batch_k.to(dev), steps, noise_k, per_item_k, sampler).cpu()
             if not bool(torch.isfinite(out).all()):
                 eng_k.set_option("lstm_stream", 1)
                 eng_k.set_option("fuse_gn_epi", 0)
-                out = decode_with_retry(eng_k, batch_k.to(dev), inp_args.midway_t, noise_k, per_item_k).cpu()
+                out = decode_with_retry(eng_k, batch_k.to(dev), steps, noise_k, per_item_k, sampler).cpu()
             if not bool(torch.isfinite(out).all()):
                 raise RuntimeError(f"non-finite audio decoded for {[files[i] for i in idxs]}")
         out = out.numpy()
@@ -436,12 +470,12 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
             retire(pending.pop(0))             # the batch this engine decoded last: its output is read before the slot is reused
         # test seam: a callable (file indices, steps, latent length) -> noise [steps, B, 128, L] replaces the device-drawn noise
         provider = getattr(inp_args, "noise_provider", None)
-        noise = provider(idxs, inp_args.midway_t, n // hop).to(dev) if provider is not None else None
+        noise = provider(idxs, steps, n // hop).to(dev) if provider is not None else None
         if streams[slot] is not None:
             with torch.cuda.stream(streams[slot]):
-                out = decode_with_retry(engines[slot], batch.to(dev, non_blocking=True), inp_args.midway_t, noise, not joint)
+                out = decode_with_retry(engines[slot], batch.to(dev, non_blocking=True), steps, noise, not joint, sampler)
         else:
-            out = decode_with_retry(engines[slot], batch.to(dev), inp_args.midway_t, noise, not joint)
+            out = decode_with_retry(engines[slot], batch.to(dev), steps, noise, not joint, sampler)
         pending.append((out, idxs, joint, streams[slot], (engines[slot], batch, not joint, noise)))
     while pending:
         retire(pending.pop(0))
