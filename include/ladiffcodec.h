@@ -156,7 +156,7 @@ int ldc_seanet_decode(ldc_ctx* ctx, int which, const float* z, int B, int L, flo
  * n_q = number of codebooks used.  codes_out [n_q,B,F] int64 (may be NULL), quantized_out [B,D,F]. */
 int ldc_rvq_encode(ldc_ctx* ctx, const float* z, int B, int F, int n_q, int64_t* codes_out, float* quantized_out,
                    void* stream);
-/* quantizer.decode(codes) (core_vq.py:356-362) */
+/* quantizer.decode(codes) (core_vq.py:356-362); a code outside [0, bins) is refused ("[bad_code]", see ldc_decode_codes) */
 int ldc_rvq_decode(ldc_ctx* ctx, const int64_t* codes, int B, int F, int n_q, float* quantized_out, void* stream);
 /* model_for_cond.get_cond(wav) (model.py:223-231) = encode + rvq, fused on one stream.
  * codes_out may be NULL.  bandwidth <= 0 means the configured cond_bandwidth. */
@@ -218,6 +218,25 @@ int ldc_ddim_sample(ldc_ctx* ctx, float* img_inout, const float* cond, const flo
  * halfway sampling).  noise [n_steps,B,C,L] or NULL. */
 int ldc_decode_ddim(ldc_ctx* ctx, const float* wav, int B, int T, int t_start, int n_steps, float eta, const float* noise,
                     int per_item, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+
+/* The decode of ldc_decode / ldc_decode_ddim started from RVQ codes instead of a waveform (the receiver side):
+ * quantizer.decode(codes) -> upsample, /= max|.| -> sampling -> decoder -> output normalisation.
+ * Exactly one of codes ([n_q,B,F] int64, device) / packed ([B][packed_stride] bytes, device, `bits` per code in
+ * compress.py's push order: for t: for k, LSB first, as ldc_pack_codes writes them) is non-NULL.  wav_out [B,1,F*320];
+ * cond_out [B,D,F] (the dequantised condition), latents_out [B,D,F*320/hop]; optional stage outputs may be NULL.
+ * For the codes get_cond returns, the condition is bit-identical to the waveform decode's, and so is everything after it.
+ * Refused (LDC_E_INVALID, before any GPU work): both sources or neither, n_q outside [1, n_q_layers], an F whose T = F*320
+ * ldc_decode would refuse, bits outside [ceil(log2(bins)), 16], packed_stride < ldc_packed_bytes(n_q, F, bits), and the
+ * n_steps / t_start / eta refusals of ldc_decode / ldc_decode_ddim.  A code VALUE outside [0, bins) is found on the device:
+ * its condition row is NaN (never an out-of-bounds read) and the call -- or, with a non-NULL stream, the next call on the
+ * context -- fails with LDC_E_INVALID and "[bad_code]" in ldc_last_error(), naming a codebook, item and frame.
+ * ldc_rvq_decode validates its codes the same way. */
+int ldc_decode_codes(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits,
+                     int n_q, int B, int F, int n_steps, const float* noise, int per_item,
+                     float* wav_out, float* latents_out, float* cond_out, void* stream);
+int ldc_decode_codes_ddim(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits,
+                          int n_q, int B, int F, int t_start, int n_steps, float eta, const float* noise, int per_item,
+                          float* wav_out, float* latents_out, float* cond_out, void* stream);
 
 /* bit-stream layer: the on-wire format between ldc_rvq_encode and ldc_rvq_decode -- SURVEY.md section 8(f) row 3 ------------
  * Every batch item is an independent stream.  All results are bit-exact with the reference classes.  These calls need no

@@ -46,6 +46,67 @@ def read_ecdc_header(fo: tp.IO[bytes]):
     return json.loads(_read_exactly(fo, meta_size).decode("utf-8"))
 
 
+MODEL_NAME = "ladiffcodec_16khz"      # the container's `m`
+
+
+def packed_bytes(n_q: int, F: int, bits: int = 10) -> int:
+    """ldc_packed_bytes on the host: BitPacker bytes of n_q * F codes of `bits` bits."""
+    return (int(n_q) * int(F) * int(bits) + 7) // 8
+
+
+def ecdc_meta(audio_length: int, n_q: int, model_name: str = MODEL_NAME, hop_length: int = 320, channels: int = 1) -> dict:
+    """Header fields as compress.py:47-71 writes them (lm: plain packing); a multi-channel container adds `ch`."""
+    meta = {"m": model_name, "al": int(audio_length), "nc": int(n_q), "lm": False, "hop": int(hop_length)}
+    if channels > 1:
+        meta["ch"] = int(channels)
+    return meta
+
+
+def ecdc_container(payloads: tp.Sequence[bytes], audio_length: int, n_q: int, model_name: str = MODEL_NAME,
+                   hop_length: int = 320) -> bytes:
+    """One container: header + the packed payloads of its channels back to back (one channel: the reference's layout)."""
+    fo = io.BytesIO()
+    write_ecdc_header(fo, ecdc_meta(audio_length, n_q, model_name, hop_length, len(payloads)))
+    for p in payloads:
+        fo.write(p)
+    return fo.getvalue()
+
+
+def parse_ecdc(blob: bytes, name: str, n_q_layers: int, bits: int = 10, model_name: str = MODEL_NAME, hop_length: int = 320):
+    """Validate a plainly packed container on the host -> (meta, payload rows uint8 [ch, packed_bytes], F).  Every refusal is a
+    ValueError naming `name`: bad magic / version, another model, an LM-coded (`lm: true`) or arithmetic-coded (`ac`) payload,
+    nc outside [1, n_q_layers], another hop, a payload that is not exactly ch x packed_bytes(nc, F, bits) long."""
+    import numpy as np
+    fo = io.BytesIO(blob)
+    try:
+        meta = read_ecdc_header(fo)
+    except (ValueError, EOFError, struct.error, UnicodeDecodeError) as e:
+        raise ValueError(f"{name}: {e}") from None
+    if not isinstance(meta, dict):
+        raise ValueError(f"{name}: header metadata is not an object")
+    if meta.get("m") != model_name:
+        raise ValueError(f"{name}: model {meta.get('m')!r}, expected {model_name!r}")
+    if meta.get("lm", False) is not False:
+        raise ValueError(f"{name}: payload is coded with a language model (lm: true): not decodable here")
+    if "ac" in meta:
+        raise ValueError(f"{name}: payload is arithmetic-coded (ac: {meta['ac']!r}): not decodable here")
+    nc, al, hop, ch = meta.get("nc"), meta.get("al"), meta.get("hop", 320), meta.get("ch", 1)
+    if not all(isinstance(v, int) and not isinstance(v, bool) for v in (nc, al, hop, ch)):
+        raise ValueError(f"{name}: nc / al / hop / ch must be integers")
+    if not 1 <= nc <= n_q_layers:
+        raise ValueError(f"{name}: nc {nc} outside [1, {n_q_layers}]")
+    if hop != hop_length:
+        raise ValueError(f"{name}: hop {hop}, expected {hop_length}")
+    if al < 1 or ch < 1:
+        raise ValueError(f"{name}: al {al} / ch {ch} must be positive")
+    F = -(-al // hop)
+    nb = packed_bytes(nc, F, bits)
+    payload = fo.read()
+    if len(payload) != ch * nb:
+        raise ValueError(f"{name}: payload of {len(payload)} bytes, expected {ch} x {nb}")
+    return meta, np.frombuffer(payload, np.uint8).reshape(ch, nb), F
+
+
 class Bitstream:
     """GPU bit packer / range coder bound to an Engine's context and stream."""
 
@@ -163,7 +224,7 @@ class Bitstream:
         out = []
         for b in range(B):
             fo = io.BytesIO()
-            meta = {"m": model_name, "al": int(audio_length), "nc": int(n_q), "lm": False, "hop": int(hop_length)}
+            meta = ecdc_meta(audio_length, n_q, model_name, hop_length)
             if static_cdf is not None:
                 meta["ac"] = "static"
             write_ecdc_header(fo, meta)

@@ -1,0 +1,74 @@
+"""`python -m ladiffcodec_amd.compress` -- the sender: every `**/*.wav` under `--input_dir` becomes an ECDC container of its RVQ codes.
+
+Flags: those of `srcs.sample` (the checkpoints included: a context is built with both models, so `--model_path` is needed here
+too).  Every file is read at 16 kHz and trimmed to a multiple of 640 samples (sample.py:87); files of equal length are encoded
+in batches of `--batch_size` (sample.plan_batches), the codes computed at `--cond_bandwidth` (Engine.get_cond) and packed at
+10 bits per code on the GPU (Bitstream.pack_codes).  `<output_dir><rel>.ecdc` holds the reference container
+(compress.py:28-84 with use_lm False: keys m, al = trimmed length, nc, lm, hop) and the payload; a file of C > 1 channels
+becomes one container with the extra key `ch: C` and its C payloads back to back.  `python -m ladiffcodec_amd.decompress`
+turns the containers back into audio.
+"""
+from __future__ import annotations
+
+import glob
+import os
+from typing import List
+
+from .sample import build_parser
+
+BITS = 10      # log2(bins): compress.py's BitPacker width
+
+
+def compress_files(eng, files: List[str], inp_args, rank: int = 0, world: int = 1) -> List[str]:
+    """Encode and write this rank's files; -> the container paths written."""
+    from .bitstream import Bitstream, ecdc_container
+    from .sample import LazyWavs, output_path, plan_batches
+
+    bs = Bitstream(eng)
+    wavs = LazyWavs(files, eng)
+    keep = [i for i, sh in enumerate(wavs.shapes) if sh[1] // 640 * 640 > 0]                  # sample.py:87-88
+    files, wavs = [files[i] for i in keep], wavs.subset(keep)
+    lengths, channels = [sh[1] for sh in wavs.shapes], [sh[0] for sh in wavs.shapes]
+    dev = eng.device
+    written = []
+    for idxs, joint in plan_batches(lengths, channels, rank, world, inp_args.batch_size):
+        n = lengths[idxs[0]] // 640 * 640
+        batch = wavs.batch(idxs, joint, n).to(dev)
+        _, codes = eng.get_cond(batch, bandwidth=float(inp_args.cond_bandwidth), return_codes=True)
+        rows = bs.pack_codes(codes, BITS).cpu().numpy()                                          # [B, packed bytes]
+        n_q = int(codes.shape[0])
+        groups = [(idxs[0], [r.tobytes() for r in rows])] if joint else [(i, [rows[k].tobytes()]) for k, i in enumerate(idxs)]
+        for i, payloads in groups:
+            path = output_path(files[i], inp_args.input_dir, inp_args.output_dir, ".wav", ".ecdc")
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            with open(path, "wb") as fo:
+                fo.write(ecdc_container(payloads, n, n_q))
+            written.append(path)
+        for i in idxs:
+            wavs.drop(i)
+    return written
+
+
+def compress(inp_args) -> List[str]:
+    from . import parallel
+    from .sample import _unsupported, build_engines
+
+    _unsupported(inp_args)
+    rank, local_rank, world = parallel.init_process_group("nccl")
+    files = sorted(glob.glob(os.path.join(inp_args.input_dir, "**/*.wav"), recursive=True))
+    inp_args.in_flight = 1                      # one engine: the encode has nothing to keep in flight
+    (eng,) = build_engines(inp_args, files, rank, world, local_rank)
+    try:
+        return compress_files(eng, files, inp_args, rank, world)
+    finally:
+        eng.close()
+
+
+def main(argv=None):
+    p = build_parser()
+    p.description = "compress wav files to ECDC containers of their RVQ codes"
+    return compress(p.parse_args(argv))
+
+
+if __name__ == "__main__":
+    main()

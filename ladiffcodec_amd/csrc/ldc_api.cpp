@@ -1241,7 +1241,7 @@ extern "C" int ldc_rvq_decode(ldc_ctx* c, const int64_t* codes, int B, int F, in
   LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
     float* qr = (float*)ar.alloc((size_t)B * F * D * 4);
     if (!dry) {
-      HIPCHK(launch_rvq_decode(codes, B * F, D, cd.codebooks, cd.bins, n_q, qr, s));
+      HIPCHK(launch_rvq_dequant(codes, nullptr, 0, 0, n_q, B, 0, B, F, cd.codebooks, cd.bins, D, qr, c->dev_flag_dev, s));
       HIPCHK(launch_from_cl(DT_F32, qr, quantized_out, B, D, F, nullptr, 0, 0.f, s));
     }
     return LDC_OK;
@@ -2577,7 +2577,16 @@ extern "C" int ldc_output_normalise(ldc_ctx* c, float* wav, int B, int T, int pe
 
 // synthesis() body for one resident batch (sample.py:94-134): ldc_decode (DDPM halfway sampling, ddim = false) and ldc_decode_ddim
 // (n_steps DDIM iterations on the schedule ddim_schedule left in c->ddim_host; draws: some of them add noise)
-static int decode_body(ldc_ctx* c, const float* wav, int B, int T, int n_steps, bool ddim, bool draws, const float* noise, int per_item,
+// the front end's source: a waveform [B,1,T] (cond encoder -> RVQ) or RVQ codes (dequantisation only; one of codes / packed)
+struct FrontSrc {
+  const float* wav = nullptr;
+  const int64_t* codes = nullptr;
+  const uint8_t* packed = nullptr;
+  int64_t packed_stride = 0;
+  int bits = 0, n_q = 0;
+};
+
+static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_steps, bool ddim, bool draws, const float* noise, int per_item,
                        float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
   const Codec& cc = c->codec[LDC_MODEL_COND];
   const Codec& mc = c->codec[LDC_MODEL_MAIN];
@@ -2614,7 +2623,15 @@ static int decode_body(ldc_ctx* c, const float* wav, int B, int T, int n_steps, 
       const int b0 = split_ends ? h.b0[k] : 0, Bk = split_ends ? h.p[k]->B : B;
       float* qr = nullptr;
       int Fq = 0;
-      LDCCHK(get_cond_rows(c, wav + (size_t)b0 * T, Bk, T, 0.f, ar, dry, sk, &qr, &Fq, codes_out, n_front));
+      if (src.wav) {
+        LDCCHK(get_cond_rows(c, src.wav + (size_t)b0 * T, Bk, T, 0.f, ar, dry, sk, &qr, &Fq, codes_out, n_front));
+      } else {
+        qr = (float*)ar.alloc((size_t)Bk * F * D * 4);
+        Fq = F;
+        if (!dry)
+          HIPCHK(launch_rvq_dequant(src.codes, src.packed, src.packed_stride, src.bits, src.n_q, B, b0, Bk, F, cc.codebooks, cc.bins, D, qr,
+                                    c->dev_flag_dev, sk));
+      }
       if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
       // start image: upsample, /= max|.|+1e-8 (sample.py:125-129)
       void* up = nullptr;
@@ -2685,7 +2702,9 @@ extern "C" int ldc_decode(ldc_ctx* c, const float* wav, int B, int T, int n_step
   LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
   if (!wav || !wav_out || B <= 0 || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
   if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
-  return decode_body(c, wav, B, T, n_steps, false, true, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_body(c, src, B, T, n_steps, false, true, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
 }
 
 // the decode with DDIM sampling from t_start (the DDIM counterpart of halfway_sampling: the start image is the upsampled,
@@ -2696,7 +2715,70 @@ extern "C" int ldc_decode_ddim(ldc_ctx* c, const float* wav, int B, int T, int t
   if (!wav || !wav_out || B <= 0 || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
   bool draws = false;
   LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
-  return decode_body(c, wav, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_body(c, src, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
+// the receiver side: ldc_decode / ldc_decode_ddim from RVQ codes.  The context-free refusals come first (a NULL context sees them
+// too); then those that need the codec; bad code VALUES are found on the device (LDC_E_INVALID "[bad_code]", see check_dev_flag).
+static int codes_args(const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B, int F,
+                      const float* wav_out) {
+  if ((codes == nullptr) == (packed == nullptr)) return fail(LDC_E_INVALID, "exactly one of codes / packed must be given");
+  if (!wav_out || B <= 0 || F <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (n_q < 1) return fail(LDC_E_INVALID, "n_q must be >= 1");
+  if (packed && (bits < 1 || bits > 16)) return fail(LDC_E_INVALID, "bits must be in [1,16]");
+  if (packed && packed_stride < ldc_packed_bytes(n_q, F, bits))
+    return fail(LDC_E_INVALID, "packed_stride %lld < %lld packed bytes per item", (long long)packed_stride, (long long)ldc_packed_bytes(n_q, F, bits));
+  return LDC_OK;
+}
+
+static int codes_src(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int F, FrontSrc* src,
+                     int* T) {
+  const Codec& cd = c->codec[LDC_MODEL_COND];
+  if (n_q > cd.n_q_layers) return fail(LDC_E_INVALID, "n_q must be in [1,%d]", cd.n_q_layers);
+  if (packed) {
+    int need = 0;
+    while ((1ll << need) < cd.bins) ++need;
+    if (bits < need) return fail(LDC_E_INVALID, "bits must be in [%d,16] for %d bins", need, cd.bins);
+  }
+  if ((int64_t)F * cd.hop > INT32_MAX) return fail(LDC_E_INVALID, "F too large");
+  *T = F * cd.hop;
+  src->codes = codes;
+  src->packed = packed;
+  src->packed_stride = packed_stride;
+  src->bits = bits;
+  src->n_q = n_q;
+  return LDC_OK;
+}
+
+extern "C" int ldc_decode_codes(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                                int F, int n_steps, const float* noise, int per_item, float* wav_out, float* latents_out, float* cond_out,
+                                void* stream) {
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, B, F, wav_out));
+  if (n_steps < 1) return fail(LDC_E_INVALID, "n_steps must be >= 1");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, F, &src, &T));
+  return decode_body(c, src, B, T, n_steps, false, true, noise, per_item, wav_out, latents_out, cond_out, nullptr, stream);
+}
+
+extern "C" int ldc_decode_codes_ddim(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
+                                     int B, int F, int t_start, int n_steps, float eta, const float* noise, int per_item, float* wav_out,
+                                     float* latents_out, float* cond_out, void* stream) {
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, B, F, wav_out));
+  if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "eta must be a finite value in [0, 1]");
+  if (t_start < 1) return fail(LDC_E_INVALID, "t_start must be >= 1");
+  if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps must be in [1, t_start = %d] (more would repeat timesteps)", t_start);
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, F, &src, &T));
+  bool draws = false;
+  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  return decode_body(c, src, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, nullptr, stream);
 }
 
 

@@ -332,7 +332,8 @@ struct ldc_ctx {
   int plan_count_cap = 24;                                     // LDC_PLAN_CACHE_N
   // device-drawn noise: every sampler call that draws advances the epoch, so no two calls share a realisation
   uint64_t noise_epoch = 0, cur_key = 0;
-  // asynchronous device-side failure flag (cooperative LSTM timeout), host-mapped
+  // asynchronous device-side failure flag, host-mapped: word 0 = 1 cooperative LSTM timeout, 2 fused GroupNorm wait timeout,
+  // LDC_DEV_BAD_CODE an out-of-range RVQ code (its position in words 2..3)
   unsigned* dev_flag_host = nullptr;
   unsigned* dev_flag_dev = nullptr;
   int enc_final_act = ACT_NONE;
@@ -368,6 +369,11 @@ inline int check_dev_flag(ldc_ctx* c) {
   const unsigned v = c->dev_flag_host ? *reinterpret_cast<volatile unsigned*>(c->dev_flag_host) : 0u;
   if (v) {
     *reinterpret_cast<volatile unsigned*>(c->dev_flag_host) = 0u;
+    if (v == LDC_DEV_BAD_CODE) {   // outside input, not a device failure: LDC_E_INVALID, and no fallback keys on it
+      const uint64_t w = *reinterpret_cast<volatile uint64_t*>(c->dev_flag_host + 2);
+      return fail(LDC_E_INVALID, "[bad_code] an RVQ code is outside [0, %d) (e.g. codebook %d, item %d, frame %d); the rows of such "
+                                 "codes are NaN", c->codec[LDC_MODEL_COND].bins, (int)(w >> 56), (int)((w >> 32) & 0xffffff), (int)(uint32_t)w);
+    }
     // the bracketed tag is what callers key their fallback on (sample.py: decode_with_retry)
     if (v == 2)
       return fail(LDC_E_HIP, "device-side failure [gn_wait]: the in-launch GroupNorm exchange of a fused conv timed out (its tiles were "

@@ -277,8 +277,12 @@ hipError_t launch_lstm_coop(int dt, const void* pre, const float* w_rm, void* ou
 // codes [n_q][B*F] int64 (nullable), quantized_cl [B*F][D] fp32.
 hipError_t launch_rvq(const float* z_rows, int rows, int D, const float* codebooks, const float* cb_sqnorm, int bins,
                       int n_q, int64_t* codes, float* quantized_rows, hipStream_t s, int variant = 1);   // variant 0: the round-1 kernel (same codes, bit for bit)
-hipError_t launch_rvq_decode(const int64_t* codes, int rows, int D, const float* codebooks, int bins, int n_q,
-                             float* quantized_rows, hipStream_t s);
+// Dequantisation: rows [Bk*F][D] of items b0 .. b0+Bk-1 from exactly one of codes [n_q][B_total][F] int64 / packed [B][packed_stride]
+// (BitPacker payload, `bits` <= 16 per code, compress.py's push order).  A code outside [0, bins) gives a NaN row and raises *flag
+// = LDC_DEV_BAD_CODE (flag: the context's host-mapped words; (codebook << 56 | item << 32 | frame) of one bad code in words 2..3).
+constexpr unsigned LDC_DEV_BAD_CODE = 3u;
+hipError_t launch_rvq_dequant(const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B_total, int b0,
+                              int Bk, int F, const float* codebooks, int bins, int D, float* quantized_rows, unsigned* flag, hipStream_t s);
 hipError_t launch_sqnorm_rows(const float* x, int rows, int D, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------

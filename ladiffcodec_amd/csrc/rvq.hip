@@ -314,15 +314,65 @@ __global__ __launch_bounds__(256) void rvq_tiled_kernel(const float* __restrict_
   }
 }
 
-__global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* codes, int rows, int D, const float* cb, int bins,
-                                                         int n_q, float* qout) {
-  const size_t total = (size_t)rows * D;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const size_t r = i / D;
-    const int c = (int)(i % D);
-    float acc = 0.f;
-    for (int q = 0; q < n_q; ++q) acc += cb[((size_t)q * bins + codes[(size_t)q * rows + r]) * D + c];
-    qout[i] = acc;
+// Dequantisation (the receiver's front end): condition rows [Bk*F][D] from RVQ codes, one wave64 per frame row.  Lane k < n_q
+// fetches the row's stage-k code once (int64 [n_q][B_total][F] at items b0.., or the BitPacker payload [B][stride]: symbol
+// t * n_q + k, `bits` LSB first, as unpack_codes_kernel reads it); the stages then reach every lane as wave-uniform scalars and the
+// chosen codebook rows stream in coalesced (D % 128 == 0: one float2 per lane, 512 contiguous bytes per wave).  The sum runs in
+// stage order from 0.f, as rvq_tiled_kernel's qout and the reference (core_vq.py:338-340): the rows are bit-identical to the encode
+// side's.  A code outside [0, bins) is never used as an index: its row is NaN and the host-mapped flag word takes LDC_DEV_BAD_CODE,
+// with (codebook, item, frame) of one such code in words 2..3.
+template <bool PACKED, bool VEC2>
+__global__ __launch_bounds__(256) void rvq_dequant_kernel(const int64_t* __restrict__ codes, const uint8_t* __restrict__ packed,
+                                                          int64_t stride, int bits, int n_q, int B_total, int b0, int rows, int F,
+                                                          const float* __restrict__ cb, int bins, int D, float* __restrict__ qout,
+                                                          unsigned* flag) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;   // (wave-uniform)
+  const int b = b0 + r / F, t = r % F;
+  int64_t code = 0;
+  if (lane < n_q) {
+    if (PACKED) {
+      const int64_t bit0 = ((int64_t)t * n_q + lane) * bits, j0 = bit0 >> 3, nbytes = ((int64_t)n_q * F * bits + 7) / 8;
+      const uint8_t* row = packed + (size_t)b * stride;
+      uint32_t acc = 0;
+#pragma unroll
+      for (int q = 0; q < 3; ++q)   // bits <= 16: a symbol spans at most three bytes
+        if (j0 + q < nbytes) acc |= (uint32_t)row[j0 + q] << (8 * q);
+      code = (int64_t)((acc >> (bit0 & 7)) & ((1u << bits) - 1u));
+    } else {
+      code = codes[((size_t)lane * B_total + b) * F + t];
+    }
+  }
+  const bool bad_lane = lane < n_q && (code < 0 || code >= bins);
+  const uint64_t bad = __ballot(bad_lane);
+  float* out = qout + (size_t)r * D;
+  if (bad) {
+    for (int c = lane; c < D; c += 64) out[c] = __builtin_nanf("");
+    if (bad_lane && lane == __builtin_ctzll(bad)) {
+      *reinterpret_cast<volatile uint64_t*>(flag + 2) = ((uint64_t)lane << 56) | ((uint64_t)(b & 0xffffff) << 32) | (uint32_t)t;
+      *reinterpret_cast<volatile unsigned*>(flag) = LDC_DEV_BAD_CODE;
+    }
+    return;
+  }
+  const int idx = (int)code;
+  if (VEC2) {
+    for (int c = 2 * lane; c < D; c += 128) {
+      float2 acc = make_float2(0.f, 0.f);
+      for (int q = 0; q < n_q; ++q) {
+        const int j = __builtin_amdgcn_readlane(idx, q);
+        const float2 e = *reinterpret_cast<const float2*>(cb + ((size_t)q * bins + j) * D + c);
+        acc.x += e.x;
+        acc.y += e.y;
+      }
+      *reinterpret_cast<float2*>(out + c) = acc;
+    }
+  } else {
+    for (int c = lane; c < D; c += 64) {
+      float acc = 0.f;
+      for (int q = 0; q < n_q; ++q) acc += cb[((size_t)q * bins + __builtin_amdgcn_readlane(idx, q)) * D + c];
+      out[c] = acc;
+    }
   }
 }
 
@@ -368,10 +418,21 @@ hipError_t launch_rvq(const float* z_rows, int rows, int D, const float* codeboo
   return hipGetLastError();
 }
 
-hipError_t launch_rvq_decode(const int64_t* codes, int rows, int D, const float* codebooks, int bins, int n_q,
-                             float* quantized_rows, hipStream_t s) {
-  int blocks = (int)std::min<size_t>(((size_t)rows * D + 255) / 256, 2048);
-  hipLaunchKernelGGL(rvq_decode_kernel, dim3(blocks), dim3(256), 0, s, codes, rows, D, codebooks, bins, n_q, quantized_rows);
+hipError_t launch_rvq_dequant(const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B_total, int b0,
+                              int Bk, int F, const float* codebooks, int bins, int D, float* quantized_rows, unsigned* flag, hipStream_t s) {
+  if ((codes == nullptr) == (packed == nullptr) || !flag || n_q < 1 || n_q > 64 || Bk < 1 || F < 1 || D < 1 || b0 < 0) return hipErrorInvalidValue;
+  if (packed && (bits < 1 || bits > 16)) return hipErrorInvalidValue;
+  if (codes && b0 + Bk > B_total) return hipErrorInvalidValue;
+  const int rows = Bk * F;
+  const dim3 grid((rows + 3) / 4), block(256);
+  const bool v2 = D % 128 == 0;
+  if (packed) {
+    if (v2) hipLaunchKernelGGL((rvq_dequant_kernel<true, true>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
+    else hipLaunchKernelGGL((rvq_dequant_kernel<true, false>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
+  } else {
+    if (v2) hipLaunchKernelGGL((rvq_dequant_kernel<false, true>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
+    else hipLaunchKernelGGL((rvq_dequant_kernel<false, false>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
+  }
   return hipGetLastError();
 }
 

@@ -1,0 +1,135 @@
+"""`python -m ladiffcodec_amd.decompress` -- the receiver: every `**/*.ecdc` under `--input_dir` becomes `<output_dir><rel>.wav`.
+
+Flags: those of `srcs.sample` plus `--ddim_steps` (0: the DDPM halfway sampling of `--midway_t` steps, the default) and
+`--ddim_eta`, checked as `sample_ddim` checks them.  Every container is validated on the host first (magic, version, `m`,
+`lm` false, no `ac`, nc <= the codebooks of the model, hop 320, payload exactly ch x packed bytes); a file that fails stops the
+run before anything is decoded, with an error naming it.  The payload rows go to the GPU as they are and the decode starts
+from them (Engine.decode_codes): the cond encoder does not run.  Batching, per-item / joint normalisation, `--in_flight`,
+`--seed`, rank sharding and `--chunk_sec` are those of `srcs.sample` (sample.decode_files over a container source); a long
+mono stream under `--chunk_sec` is cut at frame counts that are multiples of chunk_quantum / 320, its chunks decoded as batch
+items and their raw decoder outputs joined and normalised over the whole recording.  The codes of such a recording come from
+a whole-file encode, so that output is not `srcs.sample --chunk_sec` of the waveform.
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import os
+from typing import Dict, List, Tuple
+
+import numpy as np
+
+from .sample import CodesBatch, build_parser as _base_parser
+
+BITS = 10
+
+_FLAGS = [
+    ("--ddim_steps", dict(type=int, default=0, help="DDIM iterations from --midway_t (at most --midway_t); 0 = DDPM halfway sampling")),
+    ("--ddim_eta", dict(type=float, default=0.0, help="DDIM eta in [0, 1]")),
+]
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = _base_parser()
+    p.description = "decompress ECDC containers of RVQ codes to wav files"
+    for flag, kw in _FLAGS:
+        p.add_argument(flag, **kw)
+    return p
+
+
+def sampler_from_args(a):
+    from .sample import CodesSampler, DdpmSampler
+    from .sample_ddim import sampler_from_args as ddim_sampler
+    return CodesSampler(ddim_sampler(a) if a.ddim_steps > 0 else DdpmSampler(a.midway_t))
+
+
+def unpack_rows(rows: np.ndarray, n_q: int, F: int, bits: int = BITS) -> np.ndarray:
+    """BitUnpacker on the host: payload rows [B, >= packed bytes] -> codes [n_q, B, F] int64 (push order for t: for k)."""
+    B = rows.shape[0]
+    b = np.unpackbits(np.ascontiguousarray(rows), axis=1, bitorder="little")[:, :n_q * F * bits].reshape(B, F, n_q, bits)
+    vals = (b.astype(np.int64) << np.arange(bits, dtype=np.int64)).sum(-1)
+    return np.ascontiguousarray(vals.transpose(2, 0, 1))
+
+
+class EcdcSource:
+    """decode_files' batch source over validated containers: shapes (channels, al); batches of payload rows (CodesBatch)."""
+
+    in_ext = ".ecdc"
+
+    def __init__(self, files: List[str], n_q_layers: int):
+        from .bitstream import parse_ecdc
+        self.files = files
+        self.parsed = []
+        for f in files:
+            with open(f, "rb") as fo:
+                self.parsed.append(parse_ecdc(fo.read(), f, n_q_layers, BITS))
+        self.shapes = [(rows.shape[0], int(meta["al"])) for meta, rows, _ in self.parsed]
+        self._codes: Dict[int, np.ndarray] = {}
+
+    def subset(self, idx: List[int]) -> "EcdcSource":
+        out = EcdcSource.__new__(EcdcSource)
+        out.files = [self.files[i] for i in idx]
+        out.parsed = [self.parsed[i] for i in idx]
+        out.shapes = [self.shapes[i] for i in idx]
+        out._codes = {}
+        return out
+
+    def __len__(self):
+        return len(self.files)
+
+    def n_q(self, i: int) -> int:
+        return int(self.parsed[i][0]["nc"])
+
+    def batch(self, idxs: List[int], joint: bool, n: int) -> CodesBatch:
+        """payload rows [B, packed bytes] of the files' first n // 320 frames (their full length: al is trimmed by compress)"""
+        import torch
+        rows = self.parsed[idxs[0]][1] if joint else np.stack([self.parsed[i][1][0] for i in idxs])
+        n_q = {self.n_q(i) for i in idxs}
+        if len(n_q) != 1:
+            raise ValueError(f"one batch mixes numbers of codebooks {sorted(n_q)}")
+        return CodesBatch(packed=torch.from_numpy(np.array(rows)), n_q=n_q.pop(), F=n // 320, bits=BITS)
+
+    def chunk_batch(self, part: List[Tuple[int, int, int]], ln: int) -> CodesBatch:
+        """codes [n_q, len(part), ln // 320] of chunks (file, order, start sample) of mono streams"""
+        import torch
+        out = []
+        for i, _, st in part:
+            if i not in self._codes:
+                meta, rows, F = self.parsed[i]
+                self._codes[i] = unpack_rows(rows, self.n_q(i), F)
+            out.append(self._codes[i][:, 0, st // 320:(st + ln) // 320])
+        return CodesBatch(codes=torch.from_numpy(np.ascontiguousarray(np.stack(out, axis=1))))
+
+
+def decompress(inp_args) -> List[str]:
+    from . import parallel
+    from .sample import _unsupported, build_engines, decode_files
+    from .spec import CodecConfig
+
+    _unsupported(inp_args)
+    sampler = sampler_from_args(inp_args)
+    # the codebooks the cond quantizer is built with (as build_engines builds it: ratios [8,5,4,2] at --cond_bandwidth)
+    n_q_layers = CodecConfig(enc_ratios=(8, 5, 4, 2), quantization=True, bandwidth=inp_args.cond_bandwidth).n_q_layers
+    files = sorted(glob.glob(os.path.join(inp_args.input_dir, "**/*.ecdc"), recursive=True))
+    source = EcdcSource(files, n_q_layers)          # every header is checked before anything is decoded
+    rank, local_rank, world = parallel.init_process_group("nccl")
+    engines = build_engines(inp_args, files, rank, world, local_rank)
+    written = []
+    try:
+        # a batch shares its number of codebooks: one pass per nc (a run written by one compress call has one)
+        for nc in sorted({source.n_q(i) for i in range(len(files))}):
+            idx = [i for i in range(len(files)) if source.n_q(i) == nc]
+            written += decode_files(engines if len(engines) > 1 else engines[0], [files[i] for i in idx], inp_args, rank, world,
+                                    local_rank, sampler=sampler, source=source.subset(idx))
+    finally:
+        for eng in engines:
+            eng.close()
+    return written
+
+
+def main(argv=None):
+    return decompress(build_parser().parse_args(argv))
+
+
+if __name__ == "__main__":
+    main()

@@ -368,6 +368,63 @@ class Engine:
             return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
         return out
 
+    def _codes_args(self, codes, packed, bits, n_q, F):
+        """-> (codes ptr, packed ptr, packed stride, n_q, B, F, kept tensors) for ldc_decode_codes*"""
+        t = self.torch
+        if (codes is None) == (packed is None):
+            raise ValueError("exactly one of codes / packed")
+        if codes is not None:
+            codes = codes.to(self.device, t.int64).contiguous()
+            n_q, B, F = codes.shape
+            return codes.data_ptr(), None, 0, n_q, B, F, codes
+        if n_q is None or F is None:
+            raise ValueError("a packed payload needs n_q and F")
+        packed = packed.to(self.device, t.uint8)
+        if packed.dim() != 2 or packed.stride(1) != 1:
+            packed = packed.reshape(packed.shape[0], -1).contiguous()
+        return None, packed.data_ptr(), packed.stride(0), int(n_q), packed.shape[0], int(F), packed
+
+    def _codes_outputs(self, B, F, want_stages):
+        T = F * self.cond_codec.hop_length
+        out = self._empty(B, 1, T)
+        lat = self._empty(B, self.main_codec.rep_dims, T // self.main_codec.hop_length) if want_stages else None
+        cond = self._empty(B, self.main_codec.rep_dims, F) if want_stages else None
+        return out, lat, cond
+
+    def decode_codes(self, codes=None, packed=None, bits: int = 10, n_steps: Optional[int] = None, noise=None, per_item: bool = False,
+                     want_stages: bool = False, n_q: Optional[int] = None, F: Optional[int] = None):
+        """`decode` started from RVQ codes (the receiver side): codes [n_q, B, F] int64, or packed [B, >= packed bytes] uint8 (the
+        BitPacker payload of `bits` per code; n_q and F passed in).  want_stages: {"wav", "latents", "cond"}."""
+        if n_steps is None:
+            raise ValueError("n_steps is required")
+        cp, pp, stride, n_q, B, F, keep = self._codes_args(codes, packed, bits, n_q, F)
+        out, lat, cond = self._codes_outputs(B, F, want_stages)
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        L.check(self.lib.ldc_decode_codes(self._ctx, cp, pp, stride, int(bits), n_q, B, F, int(n_steps), p(noise), int(per_item),
+                                          out.data_ptr(), p(lat), p(cond), s))
+        self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond}
+        return out
+
+    def decode_codes_ddim(self, codes=None, packed=None, bits: int = 10, t_start: int = 100, n_steps: int = 10, eta: float = 0.0,
+                          noise=None, per_item: bool = False, want_stages: bool = False, n_q: Optional[int] = None,
+                          F: Optional[int] = None):
+        """`decode_ddim` started from RVQ codes; the code arguments as decode_codes."""
+        cp, pp, stride, n_q, B, F, keep = self._codes_args(codes, packed, bits, n_q, F)
+        out, lat, cond = self._codes_outputs(B, F, want_stages)
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        L.check(self.lib.ldc_decode_codes_ddim(self._ctx, cp, pp, stride, int(bits), n_q, B, F, int(t_start), int(n_steps), float(eta),
+                                               p(noise), int(per_item), out.data_ptr(), p(lat), p(cond), s))
+        self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond}
+        return out
+
     # ---- accounting ------------------------------------------------------------------------------
     def unet_step_cost(self, B: int, Lz: int):
         fl, by = C.c_double(), C.c_double()

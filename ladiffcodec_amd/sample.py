@@ -178,7 +178,12 @@ def resample_out_len(n: int, sr_in: int, sr_out: int) -> int:
 class LazyWavs:
     """The run's recordings at 16 kHz, loaded (and resampled on the GPU) on first use: a rank touches only the files of its own
     shard (through round 2 every rank read and resampled the whole corpus before sharding it: world-times redundant I/O and
-    O(corpus) host memory per rank).  `shapes[i]` = (channels, samples) from the header."""
+    O(corpus) host memory per rank).  `shapes[i]` = (channels, samples) from the header.
+
+    The batch source of decode_files: `batch` / `chunk_batch` build what the sampler decodes (here a waveform tensor; the
+    decompress CLI's source hands out code batches), `in_ext` is the input extension output_path replaces."""
+
+    in_ext = ".wav"
 
     def __init__(self, files: List[str], eng):
         self.files, self.eng = files, eng
@@ -206,12 +211,25 @@ class LazyWavs:
     def drop(self, i: int) -> None:
         self._cache.pop(i, None)
 
+    def batch(self, idxs: List[int], joint: bool, n: int):
+        """[channels, 1, n] of one file (joint, as sample.py:85) or [len(idxs), 1, n] of mono files."""
+        import torch
+        if joint:
+            return torch.from_numpy(np.ascontiguousarray(self[idxs[0]][:, None, :n]))
+        return torch.from_numpy(np.stack([self[i][0, :n] for i in idxs])[:, None, :])
 
-def output_path(wav_file: str, input_dir: str, output_dir: str) -> str:
-    """sample.py:75-81,136: save_path = output_dir + wav_file[len(input_dir):][:-4]; file = save_path + '.wav'."""
-    local_path = wav_file[len(input_dir):][:-4]
+    def chunk_batch(self, part: List[Tuple[int, int, int]], ln: int):
+        """[len(part), 1, ln]: chunk (file, order, start) of mono recordings."""
+        import torch
+        return torch.from_numpy(np.stack([self[i][0, st:st + ln] for i, _, st in part])[:, None, :])
+
+
+def output_path(wav_file: str, input_dir: str, output_dir: str, in_ext: str = ".wav", out_ext: str = ".wav") -> str:
+    """sample.py:75-81,136: save_path = output_dir + wav_file[len(input_dir):][:-4]; file = save_path + '.wav'.
+    (in_ext / out_ext: the compress / decompress CLIs name their files the same way, .wav <-> .ecdc)"""
+    local_path = wav_file[len(input_dir):][:-len(in_ext)]
     save_path = output_dir + local_path
-    return os.path.join(output_dir, f"{save_path}.wav")
+    return os.path.join(output_dir, f"{save_path}{out_ext}")
 
 
 class DdpmSampler:
@@ -237,21 +255,60 @@ class DdimSampler:
         return eng.decode_ddim(batch, self.t_start, self.n_steps, self.eta, noise=noise, per_item=per_item, want_stages=want_stages)
 
 
+class CodesBatch:
+    """A batch of RVQ codes for CodesSampler: packed [B, >= packed bytes] uint8 (the container payload rows, `bits` per code) or
+    codes [n_q, B, F] int64.  `.to(device)` as a tensor batch, so decode_with_retry and the in-flight retire path take it as is."""
+
+    def __init__(self, packed=None, codes=None, n_q: int = 0, F: int = 0, bits: int = 10):
+        self.packed, self.codes, self.bits = packed, codes, int(bits)
+        self.n_q = int(codes.shape[0]) if codes is not None else int(n_q)
+        self.F = int(codes.shape[2]) if codes is not None else int(F)
+
+    def to(self, device, non_blocking: bool = False):
+        mv = lambda t: t.to(device, non_blocking=non_blocking) if t is not None else None
+        return CodesBatch(mv(self.packed), mv(self.codes), self.n_q, self.F, self.bits)
+
+
+class CodesSampler:
+    """The decode of `inner` (DdpmSampler / DdimSampler) started from a CodesBatch: Engine.decode_codes / decode_codes_ddim."""
+
+    def __init__(self, inner):
+        self.inner = inner
+        self.n_steps = self.draws = inner.draws
+
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        kw = dict(codes=batch.codes, packed=batch.packed, bits=batch.bits, n_q=batch.n_q, F=batch.F, noise=noise, per_item=per_item,
+                  want_stages=want_stages)
+        if isinstance(self.inner, DdimSampler):
+            return eng.decode_codes_ddim(t_start=self.inner.t_start, n_steps=self.inner.n_steps, eta=self.inner.eta, **kw)
+        return eng.decode_codes(n_steps=self.inner.n_steps, **kw)
+
+
 def _sampler(inp_args, sampler):
     return sampler if sampler is not None else DdpmSampler(inp_args.midway_t)
 
 
 def synthesis(inp_args, sampler=None) -> List[str]:
     """`sampler`: DdpmSampler (default, --midway_t steps) or DdimSampler."""
-    import torch
-    from scipy.io import wavfile
-
-    from . import checkpoint, lib as L, parallel
-    from .model import Engine
-    from .spec import CodecConfig, UnetConfig
+    from . import parallel
 
     _unsupported(inp_args)
     rank, local_rank, world = parallel.init_process_group("nccl")
+    files = sorted(glob.glob(os.path.join(inp_args.input_dir, "**/*.wav"), recursive=True))
+    engines = build_engines(inp_args, files, rank, world, local_rank)
+    written = decode_files(engines if len(engines) > 1 else engines[0], files, inp_args, rank, world, local_rank, sampler=sampler)
+    for eng in engines:
+        eng.close()
+    return written
+
+
+def build_engines(inp_args, files: List[str], rank: int, world: int, local_rank: int):
+    """The run's engines (both models loaded from --model_path / --model_for_cond): --in_flight of them when the rank has several
+    batches, else one."""
+    from . import checkpoint, lib as L
+    from .model import Engine
+    from .spec import CodecConfig, UnetConfig
+
     main_codec = CodecConfig(rep_dims=inp_args.rep_dims, n_filters=inp_args.n_filters,
                              n_residual_layers=inp_args.n_residual_layers, lstm=inp_args.lstm,
                              enc_ratios=tuple(inp_args.enc_ratios), quantization=False,
@@ -262,7 +319,6 @@ def synthesis(inp_args, sampler=None) -> List[str]:
                              final_activation=inp_args.final_activation)   # quirk Q1: ratios are always [8,5,4,2]
     unet = UnetConfig(dim=inp_args.diff_dims, inp_channels=inp_args.rep_dims, upsampling_ratios=tuple(inp_args.upsampling_ratios),
                       unet_scale_cond=inp_args.unet_scale_cond, unet_scale_x=inp_args.unet_scale_x)
-    files = sorted(glob.glob(os.path.join(inp_args.input_dir, "**/*.wav"), recursive=True))
     n_eng = max(1, int(getattr(inp_args, "in_flight", 1)))
     if len(files) <= inp_args.batch_size * world:        # a single batch per rank: nothing to pipeline
         n_eng = 1
@@ -276,10 +332,7 @@ def synthesis(inp_args, sampler=None) -> List[str]:
         eng.load_state_dict(L.MODEL_COND, sd_cond)       # load_model(model, path, strict=True)
         eng.finalize(strict=True)
         engines.append(eng)
-    written = decode_files(engines if n_eng > 1 else engines[0], files, inp_args, rank, world, local_rank, sampler=sampler)
-    for eng in engines:
-        eng.close()
-    return written
+    return engines
 
 
 def apply_device_fallback(eng, err) -> bool:
@@ -380,7 +433,7 @@ def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: i
     for ln, items in sorted(pieces.items(), reverse=True):
         for s in range(0, len(items), inp_args.batch_size):
             part = items[s:s + inp_args.batch_size]
-            batch = torch.from_numpy(np.stack([wavs[i][0, st:st + ln] for i, _, st in part])[:, None, :])
+            batch = wavs.chunk_batch(part, ln)
             # test seam (see decode_files): keys are (file index, chunk number)
             provider = getattr(inp_args, "noise_provider", None)
             hop = int(np.prod(getattr(inp_args, "enc_ratios", [8])))
@@ -396,22 +449,23 @@ def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: i
         whole = eng.output_normalise(torch.cat(raw[i], dim=-1), per_item=False)
         if not bool(torch.isfinite(whole).all()):
             raise RuntimeError(f"non-finite audio decoded for {files[i]}")
-        path = output_path(files[i], inp_args.input_dir, inp_args.output_dir)
+        path = output_path(files[i], inp_args.input_dir, inp_args.output_dir, wavs.in_ext)
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         wavfile.write(path, 16000, np.ascontiguousarray(whole.cpu().numpy()[0, 0]))
         written.append(path)
     return written
 
 
-def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_rank: int, sampler=None) -> List[str]:
-    """`eng`: one engine, or a list of engines (one batch in flight per engine, each on its own stream); `sampler`: as synthesis."""
+def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_rank: int, sampler=None, source=None) -> List[str]:
+    """`eng`: one engine, or a list of engines (one batch in flight per engine, each on its own stream); `sampler`: as synthesis;
+    `source`: the batch source over `files` (default LazyWavs; see there)."""
     import torch
     from scipy.io import wavfile
     engines = list(eng) if isinstance(eng, (list, tuple)) else [eng]
     eng = engines[0]
     sampler = _sampler(inp_args, sampler)
     steps = sampler.draws
-    wavs = LazyWavs(files, eng)                     # headers only: (channels, samples at 16 kHz); data is loaded per shard
+    wavs = source if source is not None else LazyWavs(files, eng)   # headers only: (channels, samples at 16 kHz); data is loaded per shard
     keep = [i for i, sh in enumerate(wavs.shapes) if sh[1] // 640 * 640 > 0]                  # sample.py:87-88
     files, wavs = [files[i] for i in keep], wavs.subset(keep)
     chunk_sec = float(getattr(inp_args, "chunk_sec", 0.0) or 0.0)
@@ -453,7 +507,7 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
                 raise RuntimeError(f"non-finite audio decoded for {[files[i] for i in idxs]}")
         out = out.numpy()
         for k, i in enumerate(idxs):
-            path = output_path(files[i], inp_args.input_dir, inp_args.output_dir)
+            path = output_path(files[i], inp_args.input_dir, inp_args.output_dir, wavs.in_ext)
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             data = out[:, 0, :].T if joint else out[k, 0]                                     # [T, channels] | [T]
             wavfile.write(path, 16000, np.ascontiguousarray(data))
@@ -461,10 +515,7 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
 
     for j, (idxs, joint) in enumerate(plan_batches(lengths, channels, rank, world, inp_args.batch_size)):
         n = lengths[idxs[0]] // 640 * 640
-        if joint:
-            batch = torch.from_numpy(np.ascontiguousarray(wavs[idxs[0]][:, None, :n]))      # [channels, 1, T], as sample.py:85
-        else:
-            batch = torch.from_numpy(np.stack([wavs[i][0, :n] for i in idxs])[:, None, :])
+        batch = wavs.batch(idxs, joint, n)
         slot = j % len(engines)
         if len(pending) >= len(engines):
             retire(pending.pop(0))             # the batch this engine decoded last: its output is read before the slot is reused
