@@ -389,9 +389,25 @@ int ldc_profile_enable(ldc_ctx* ctx, int on);
  * (n_words 32-bit words; NULL: unmasked). */
 int ldc_xcc_census(ldc_ctx* ctx, const uint32_t* mask, int n_words, int wgs, int* hist16);
 
-/* Test hook: raises the context's device-side failure flag exactly as a kernel whose bounded spin gave up would (code 1: the
- * cooperative LSTM's hidden-state exchange, 2: the in-launch GroupNorm exchange of a fused conv).  The next call on the context
- * reports LDC_E_HIP with "device-side failure [coop_lstm]" / "[gn_wait]" in ldc_last_error and clears the flag. */
+/* Test hook: one attention core (4 heads x 32) on caller data, in the context's UNet dtype.  qkv: [B, 384, L] fp32 on the device
+ * (q | k | v, head-major), converted to channels-last rows as ldc_unet_forward converts its inputs; then exactly the launches a
+ * plan makes.  kind 0: LinearAttention core with its own column-maximum pass; 1: the same with the maxima prepared in the
+ * workspace as to_qkv's fused epilogue leaves them; 2: context + fused tail (to_out 1x1 conv, LayerNorm, + residual; bf16 contexts,
+ * C in {256, 512, 1024}; w_out [C, 128], b_out [C], gain [C] in host memory, resid [B, C, L] fp32 on the device); 3: the
+ * bottleneck's softmax attention core.  out: [B, 128, L] fp32 on the device ([B, C, L] for kind 2).  The arguments of kind 2 are
+ * ignored otherwise.  Synchronous (waits for its stream); reports a device-side failure of its own launches. */
+int ldc_debug_attn_core(ldc_ctx* ctx, int kind, const float* qkv, int B, int L, const float* w_out, const float* b_out,
+                        const float* gain, const float* resid, int C, float* out, void* stream);
+/* Test hook: Residual(PreNorm(LinearAttention)) of level "down<i>" / "up<i>", or Residual(PreNorm(Attention)) of "mid", of the
+ * loaded UNet on x [B, C, L] fp32 (device) -> out [B, C, L].  The launches come from the plan builder itself, so every option
+ * (fold_ctx, fuse_attn_tail, fuse_kmax, fold_ln, conv_lean) routes as in a decode.  Synchronous; honours the device-side failure
+ * flag (LDC_E_HIP, "device-side failure [ctx_range]" when the context fold met k values outside its valid range). */
+int ldc_debug_attention_block(ldc_ctx* ctx, const char* name, const float* x, int B, int L, float* out, void* stream);
+
+/* Test hook: raises the context's device-side failure flag exactly as a kernel that gave up would (code 1: the
+ * cooperative LSTM's hidden-state exchange, 2: the in-launch GroupNorm exchange of a fused conv, 4: the LinearAttention context
+ * fold outside its valid k range).  The next call on the context reports LDC_E_HIP with "device-side failure [coop_lstm]" /
+ * "[gn_wait]" / "[ctx_range]" in ldc_last_error and clears the flag. */
 int ldc_debug_raise_failure(ldc_ctx* ctx, int code);
 /* Test hook: number of device-wide synchronisations (hipDeviceSynchronize) this library has issued in this process.  Steady-state
  * stage calls issue none: the count does not move across warm ldc_decode calls. */

@@ -360,7 +360,7 @@ __device__ __forceinline__ float reduce16_over32(const float (&v)[16], int lane)
 template <int C>   // output channels; 32 positions per workgroup
 __global__ __launch_bounds__(256) void linattn_tail_mfma_kernel(const unsigned short* qkv, const float* ws, size_t ws_stride, float scale,
                                                                 const unsigned short* wo, int n_pad, const float* bias, const float* gain,
-                                                                const unsigned short* resid, unsigned short* out, int L) {
+                                                                const unsigned short* resid, unsigned short* out, int L, unsigned* fail_flag) {
   constexpr int D = 32, HD = 128, R = 32, CPW = C / 4, NT = CPW / 32;
   constexpr int AP = HD + 8;                  // sA pitch (bf16 elements): 272 B rows
   constexpr int TP = CPW * 4 + 16;            // transpose pitch (bytes, fp32 values)
@@ -395,18 +395,22 @@ __global__ __launch_bounds__(256) void linattn_tail_mfma_kernel(const unsigned s
       else qq[sx] = make_uint4(0, 0, 0, 0);
     }
     uint4 af[2];
+    bool ks_bad = false;   // a column sum outside [kLinattnKsumMin, kLinattnKsumMax) or NaN (ldc_kernels.h)
 #pragma unroll
     for (int sx = 0; sx < 2; ++sx) {
       unsigned wv[4];
 #pragma unroll
       for (int m = 0; m < 8; m += 2) {
         const int d0 = 16 * sx + 8 * g + m;
-        const float c0 = wsb[2 * HD + (size_t)h * D * D + d0 * D + i32] * (scale / wsb[HD + h * D + d0]);
-        const float c1 = wsb[2 * HD + (size_t)h * D * D + (d0 + 1) * D + i32] * (scale / wsb[HD + h * D + d0 + 1]);
+        const float ks0 = wsb[HD + h * D + d0], ks1 = wsb[HD + h * D + d0 + 1];
+        ks_bad |= !(ks0 >= kLinattnKsumMin && ks0 < kLinattnKsumMax) | !(ks1 >= kLinattnKsumMin && ks1 < kLinattnKsumMax);
+        const float c0 = wsb[2 * HD + (size_t)h * D * D + d0 * D + i32] * (scale / ks0);
+        const float c1 = wsb[2 * HD + (size_t)h * D * D + (d0 + 1) * D + i32] * (scale / ks1);
         wv[m >> 1] = (unsigned)af2bf(c0) | ((unsigned)af2bf(c1) << 16);
       }
       af[sx] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
     }
+    if (ks_bad && fail_flag) __hip_atomic_store(fail_flag, kDevFailCtxRange, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     float x[16];
     float mx = -INFINITY;
 #pragma unroll
@@ -537,7 +541,7 @@ __global__ __launch_bounds__(256) void linattn_tail_mfma_kernel(const unsigned s
 
 template <int C>
 static hipError_t launch_tail_cfg(const void* qkv, const float* ws, size_t wss, float scale, const void* wo, int n_pad, const float* bias,
-                                  const float* gain, const void* resid, void* out, int B, int L, hipStream_t s) {
+                                  const float* gain, const void* resid, void* out, int B, int L, unsigned* fail_flag, hipStream_t s) {
   constexpr int R = 32, CPW = C / 4;
   const size_t lds = (size_t)R * (128 + 8) * 2 + (size_t)5 * R * 4 + (size_t)4 * R * (CPW * 4 + 16);
   auto kern = linattn_tail_mfma_kernel<C>;
@@ -549,7 +553,7 @@ static hipError_t launch_tail_cfg(const void* qkv, const float* ws, size_t wss, 
   }
   hipLaunchKernelGGL(kern, dim3((L + R - 1) / R, B), dim3(256), lds, s, reinterpret_cast<const unsigned short*>(qkv), ws, wss, scale,
                      reinterpret_cast<const unsigned short*>(wo), n_pad, bias, gain, reinterpret_cast<const unsigned short*>(resid),
-                     reinterpret_cast<unsigned short*>(out), L);
+                     reinterpret_cast<unsigned short*>(out), L, fail_flag);
   return hipGetLastError();
 }
 
@@ -565,18 +569,35 @@ hipError_t launch_linattn_ctx(int dt, const void* qkv, float* ws, int B, int L, 
   return hipGetLastError();
 }
 
-// out = LayerNorm_C(to_out(linear-attention output)) * gain + resid, from the qkv rows and the finished context in `ws`
+// out = LayerNorm_C(to_out(linear-attention output)) * gain + resid, from the qkv rows and the finished context in `ws`.
+// fail_flag (may be null): the context's host-mapped failure word, raised to kDevFailCtxRange when a column sum of `ws` is outside
+// [kLinattnKsumMin, kLinattnKsumMax) -- only the context fold's unshifted exponentials can leave such a sum (a shifted column sums to
+// a value in [1, L])
 hipError_t launch_linattn_tail(int dt, const void* qkv, const float* ws, const void* wo_packed, int n_pad, const float* bias, const float* gain,
-                               const void* resid, void* out, int B, int L, int heads, int dim_head, int C, hipStream_t s) {
+                               const void* resid, void* out, int B, int L, int heads, int dim_head, int C, unsigned* fail_flag, hipStream_t s) {
   if (!linattn_tail_supported(dt, heads, dim_head, C) || !bias || !gain || !resid) return hipErrorInvalidValue;
   const size_t wss = linattn_ws_per_item(heads, dim_head);
   const float scale = 1.0f / sqrtf((float)dim_head);
-  if (C == 256) return launch_tail_cfg<256>(qkv, ws, wss, scale, wo_packed, n_pad, bias, gain, resid, out, B, L, s);
-  if (C == 512) return launch_tail_cfg<512>(qkv, ws, wss, scale, wo_packed, n_pad, bias, gain, resid, out, B, L, s);
-  return launch_tail_cfg<1024>(qkv, ws, wss, scale, wo_packed, n_pad, bias, gain, resid, out, B, L, s);
+  if (C == 256) return launch_tail_cfg<256>(qkv, ws, wss, scale, wo_packed, n_pad, bias, gain, resid, out, B, L, fail_flag, s);
+  if (C == 512) return launch_tail_cfg<512>(qkv, ws, wss, scale, wo_packed, n_pad, bias, gain, resid, out, B, L, fail_flag, s);
+  return launch_tail_cfg<1024>(qkv, ws, wss, scale, wo_packed, n_pad, bias, gain, resid, out, B, L, fail_flag, s);
 }
 
 size_t linattn_ws_floats_per_item(int heads, int dim_head) { return linattn_ws_per_item(heads, dim_head); }
+
+// the k column maxima as keys in a cleared `ws`: what a to_qkv conv with the fused column max leaves for launch_linattn(kmax_fused)
+// and launch_linattn_ctx, computed from the stored qkv rows (ldc_debug_attn_core)
+hipError_t launch_linattn_kmax(int dt, const void* qkv, float* ws, int B, int L, int heads, int dim_head, hipStream_t s) {
+  const int HD = heads * dim_head;
+  if (dim_head != 32 || HD > 256 || 256 % HD) return hipErrorInvalidValue;
+  const size_t wss = linattn_ws_per_item(heads, dim_head);
+  hipError_t e = hipMemsetAsync(ws, 0, (size_t)B * wss * sizeof(float), s);
+  if (e != hipSuccess) return e;
+  const int rpb = 128;
+  if (dt == DT_F32) hipLaunchKernelGGL(linattn_kmax_kernel<float>, dim3((L + rpb - 1) / rpb, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss);
+  else hipLaunchKernelGGL(linattn_kmax_kernel<__bf16>, dim3((L + rpb - 1) / rpb, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss);
+  return hipGetLastError();
+}
 
 // kmax_fused: the caller zeroed `ws` before the qkv conv and that conv's epilogue already produced the column
 // maxima (conv_device.h epilogue_colmax)

@@ -443,9 +443,14 @@ __device__ __forceinline__ void lean_epilogue_gn(const KA& a, f32x16 (&acc)[TM][
 
 
 // LinearAttention context inside to_qkv (srcs/modules/unet.py:208-216: k = softmax_n(k), context[d][e] = sum_n k[d][n] v[e][n]).  The tile holds
-// k_h (columns 0-31: the waves with wn = 0) and v_h (32-63: wn = 1) of ONE head for BM positions.  softmax over positions is shift-invariant,
-// so no maximum is needed: p = exp(min(k, 60)) (fp32 and bf16 share the exponent range; 1 200 positions x e^60 is 1e29), rounded to bf16
-// once; the same rounded values feed the column sums.  P^T and V^T go to LDS ([column][position], as attention.hip: linattn_ctx_mfma_kernel
+// k_h (columns 0-31: the waves with wn = 0) and v_h (32-63: wn = 1) of ONE head for BM positions.  softmax over positions is shift-invariant
+// while nothing clamps or underflows, so inside that range no maximum is needed: p = exp(min(k, kLinattnKClamp)), rounded to bf16 once; the same
+// rounded values feed the column sums.  VALID RANGE (ldc_kernels.h: kLinattnKClamp, kLinattnKsumMin, kLinattnKsumMax): every column's sum of
+// exp(k) in [2^-100, 1e26), which implies every k < 60.  Outside it the result would be silently wrong (entries above the clamp flattened to
+// one weight; a column far below zero underflowing to 0 / 0).  Nothing is tested here: a clamped entry alone lifts its column's sum to e^60 >
+// 1e26, so the tail that consumes the sums (attention.hip: linattn_tail_mfma_kernel) sees either fault in the sum it divides by and raises
+// the context's failure word: the call fails with "device-side failure [ctx_range]" and fold_ctx 0 is the fallback.
+// P^T and V^T go to LDS ([column][position], as attention.hip: linattn_ctx_mfma_kernel
 // stages them), wave 0 multiplies them on the MFMA and adds the 32 x 32 partial context and the 32 partial sums to the item's workspace with
 // fp32 atomics -- what the context launch did, without its launch, without the column-max pass in front of it and without k and v ever
 // being written (two thirds of to_qkv's output).  A tile that straddles items makes one pass per item with the other items' positions zeroed.
@@ -469,7 +474,7 @@ __device__ __forceinline__ void lean_epilogue_qkv_ctx(const KA& a, f32x16 (&acc)
         const int m = m0 + rl;
         const bool in = m >= lo && m < hi;
         if (wn == 0) {
-          const unsigned short pb = in ? hw_bf16(__expf(fminf(acc[i][0][r], 60.0f))) : (unsigned short)0;
+          const unsigned short pb = in ? hw_bf16(__expf(fminf(acc[i][0][r], kLinattnKClamp))) : (unsigned short)0;
           ps += __uint_as_float((unsigned)pb << 16);
           spT[i32 * P + rl] = pb;
         } else {

@@ -910,9 +910,10 @@ extern "C" int ldc_set_option(ldc_ctx* c, const char* name, int value) {
 // option changes, profiling / tuning reads)
 extern "C" long long ldc_debug_sync_count(void) { return g_device_syncs; }
 
-// debug hook: raise the device-side failure flag as a kernel that gave up would (1 = cooperative LSTM, 2 = fused GroupNorm wait)
+// debug hook: raise the device-side failure flag as a kernel that gave up would (1 = cooperative LSTM, 2 = fused GroupNorm wait,
+// 4 = LinearAttention context fold outside its valid k range; 3 is the RVQ bad-code report, which has no hook)
 extern "C" int ldc_debug_raise_failure(ldc_ctx* c, int code) {
-  if (!c || !c->dev_flag_host || (code != 1 && code != 2)) return fail(LDC_E_INVALID, "bad arguments");
+  if (!c || !c->dev_flag_host || (code != 1 && code != 2 && code != (int)kDevFailCtxRange)) return fail(LDC_E_INVALID, "bad arguments");
   *reinterpret_cast<volatile unsigned*>(c->dev_flag_host) = (unsigned)code;
   return LDC_OK;
 }
@@ -1630,8 +1631,9 @@ struct PlanBuilder {
         }
         const int dim = a.dim;
         info = "tail_c" + std::to_string(dim) + "_L" + std::to_string(L) + "_B" + std::to_string(B);
+        unsigned* flag = c->dev_flag_dev;
         add([=](hipStream_t s) {
-          return launch_linattn_tail(dt, qkv, ws, ap->out.w, ap->out.n_pad, ap->out.bias, ap->out_g, x, out, Bn, L, H, Dh, dim, s);
+          return launch_linattn_tail(dt, qkv, ws, ap->out.w, ap->out.n_pad, ap->out.bias, ap->out_g, x, out, Bn, L, H, Dh, dim, flag, s);
         }, false, 2.0 * rows * hid * dim, LDC_CLASS_LINATTN, (1.0 * hid + 2.0 * dim) * rows * es);
         return out;
       }
@@ -2105,6 +2107,70 @@ extern "C" int ldc_unet_debug_tap(ldc_ctx* c, const char* name, float* out, int6
     HIPCHK(launch_from_cl(c->dt, tp.p, out + (size_t)h.b0[k] * tp.C * tp.L, h.p[k]->B, tp.C, tp.L, nullptr, 0, 0.f, s));
   }
   return finish_stream(c, stream);
+}
+
+// Residual(PreNorm(LinearAttention | Attention)) of one block of the loaded UNet on caller data (tests).  The launches come from
+// PlanBuilder::attention() itself, on a private plan that is never cached: every option (fold_ctx, fuse_attn_tail, fuse_kmax, fold_ln,
+// conv_lean) routes as it does in a decode -- the PreNorm folded into to_qkv, the context fold, the tail.  What differs from a decode:
+// no ResnetBlock in front, so a folded PreNorm computes its row statistics itself (as ldc_ln_fold_compare's out[0]) and an unfolded one
+// is its own launch; the batch is one part.  Synchronous: the call waits for its stream and reports a device-side failure of its own
+// launches.  Allocates and frees its workspace (hipFree waits for the device): not for the decode path.
+extern "C" int ldc_debug_attention_block(ldc_ctx* c, const char* name, const float* x, int B, int L, float* out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!name || !x || !out || B <= 0 || L <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  const UnetW& u = c->unet;
+  const LinAttnW* a = nullptr;
+  bool linear = true;
+  const std::string n = name;
+  auto level = [&](const char* pre, const std::vector<LevelW>& lv) {
+    const size_t pl = strlen(pre);
+    if (n.compare(0, pl, pre) != 0 || n.size() == pl || n.find_first_not_of("0123456789", pl) != std::string::npos) return;
+    const size_t i = (size_t)atoi(n.c_str() + pl);
+    if (i < lv.size()) a = &lv[i].attn;
+  };
+  if (n == "mid") { a = &u.mid_attn; linear = false; }
+  else { level("down", u.downs); level("up", u.ups); }
+  if (!a) return fail(LDC_E_INVALID, "unknown attention block '%s' (down0..down%zu, mid, up0..up%zu)", name, u.downs.size() - 1, u.ups.size() - 1);
+  hipStream_t s = pick_stream(c, stream);
+  const int dt = c->dt, C = a->dim;
+  const size_t es = dt_size(dt);
+  const size_t lin_bytes = (size_t)B * linattn_ws_floats_per_item(u.heads, u.dim_head) * 4;
+  const int sk_tiles_cap = 1024;
+  Plan pl;
+  pl.B = B; pl.L = L;
+  void *x_cl = nullptr, *y_cl = nullptr, *zero = nullptr;
+  auto build = [&](Arena& ar) {
+    pl.step_ops.clear(); pl.step_is_conv.clear(); pl.step_where.clear(); pl.step_flops.clear(); pl.step_class.clear(); pl.step_bytes.clear(); pl.step_info.clear();
+    pl.sk_need_max = 0; pl.part_need = 0;
+    PlanBuilder pb{c, &pl, &ar, B, es};
+    zero = ar.alloc((size_t)sk_tiles_cap * 4 + lin_bytes);   // split-K arrival counters | LinearAttention workspace: what a step clears
+    pb.sk_count = reinterpret_cast<unsigned*>(zero);
+    pb.sk_count_cap = sk_tiles_cap;
+    pb.linattn_ws = reinterpret_cast<float*>(pb.sk_count + sk_tiles_cap);
+    pb.sk_part_cap = pl.sk_floats;
+    pb.sk_part = (float*)ar.alloc((size_t)std::max<long long>(pb.sk_part_cap, 4) * 4);
+    x_cl = pb.act(B * L, C);
+    y_cl = pb.attention(*a, x_cl, L, linear);
+  };
+  for (int pass = 0; pass < 2; ++pass) {   // split-K workspace from the convs' own dry runs, as get_plan sizes it
+    Arena dry;
+    build(dry);
+    pl.sk_floats = std::max(pl.sk_floats, pl.sk_need_max);
+  }
+  Arena measure;
+  build(measure);
+  DevMem keep;
+  void* base = nullptr;
+  LDCCHK(keep.alloc(&base, measure.off + 4096));
+  Arena real;
+  real.base = (char*)base; real.cap = measure.off + 4096;
+  build(real);
+  HIPCHK(hipMemsetAsync(zero, 0, (size_t)sk_tiles_cap * 4 + lin_bytes, s));
+  HIPCHK(launch_to_cl(dt, x, x_cl, B, C, L, nullptr, 0, 0.f, s));
+  LDCCHK(run_ops(c, &pl, pl.step_ops, true, s));
+  HIPCHK(launch_from_cl(dt, y_cl, out, B, C, L, nullptr, 0, 0.f, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return check_dev_flag(c);
 }
 
 // one reverse-diffusion step of batch part k on stream s: select the timestep row, run the UNet, update the state,

@@ -623,6 +623,63 @@ extern "C" int ldc_conv_compare(ldc_ctx* c, int dtype, int B, int L, int cin1, i
   return LDC_OK;
 }
 
+// One attention core (4 heads x 32) on caller data, in the context's UNet dtype: qkv [B][384][L] fp32 on the device is converted to
+// channels-last rows as ldc_unet_forward converts its inputs, then exactly the launches the plan makes for `kind`:
+//   0  launch_linattn, column maxima by its own pass          -> out [B][128][L]
+//   1  launch_linattn with the maxima already in the workspace (prepared from the given qkv, as to_qkv's fused epilogue leaves them)
+//   2  launch_linattn_ctx + launch_linattn_tail: to_out (w_out [C][128], b_out [C], host), LayerNorm gain [C] (host), + resid
+//      ([B][C][L] fp32, device)                               -> out [B][C][L]   (bf16 context, C in {256, 512, 1024})
+//   3  launch_attn_full                                       -> out [B][128][L]
+// Synchronous: waits for its stream and reports a device-side failure of its own launches.
+extern "C" int ldc_debug_attn_core(ldc_ctx* c, int kind, const float* qkv, int B, int L, const float* w_out, const float* b_out,
+                                   const float* gain, const float* resid, int C, float* out, void* stream) {
+  if (!c || !qkv || !out || B < 1 || L < 1 || kind < 0 || kind > 3) return fail(LDC_E_INVALID, "bad arguments");
+  HIPCHK(hipSetDevice(c->device));
+  const int dt = c->dt, H = 4, D = 32, HD = H * D;
+  const size_t es = dt_size(dt), wss = linattn_ws_floats_per_item(H, D);
+  if (kind == 2 && (!w_out || !b_out || !gain || !resid || !linattn_tail_supported(dt, H, D, C)))
+    return fail(LDC_E_INVALID, "the fused tail needs a bf16 context, C in {256, 512, 1024}, and to_out weight, bias, gain and residual");
+  hipStream_t s = pick_stream(c, stream);
+  const int Co = kind == 2 ? C : HD;
+  DevMem keep;
+  void *q_cl = nullptr, *o_cl = nullptr, *ws = nullptr, *r_cl = nullptr;
+  LDCCHK(keep.alloc(&q_cl, (size_t)B * L * 3 * HD * es));
+  LDCCHK(keep.alloc(&o_cl, (size_t)B * L * Co * es));
+  LDCCHK(keep.alloc(&ws, (size_t)B * wss * 4));
+  ConvLayer to_out;
+  float* d_gain = nullptr;
+  if (kind == 2) {
+    const bool saved_w8 = c->w8;
+    c->w8 = false;
+    std::swap(keep.ptrs, c->wmem.ptrs);
+    ConvSpec sp;
+    sp.dt = dt; sp.cin1 = HD; sp.cout = C; sp.k = 1;
+    int rc = make_conv(c, sp, w_out, b_out, &to_out);
+    if (rc == LDC_OK) rc = c->wmem.upload(&d_gain, std::vector<float>(gain, gain + C));
+    std::swap(keep.ptrs, c->wmem.ptrs);
+    c->w8 = saved_w8;
+    LDCCHK(rc);
+    LDCCHK(keep.alloc(&r_cl, (size_t)B * L * C * es));
+    HIPCHK(launch_to_cl(dt, resid, r_cl, B, C, L, nullptr, 0, 0.f, s));
+  }
+  HIPCHK(launch_to_cl(dt, qkv, q_cl, B, 3 * HD, L, nullptr, 0, 0.f, s));
+  if (kind == 0) {
+    HIPCHK(launch_linattn(dt, q_cl, o_cl, (float*)ws, B, L, H, D, false, s));
+  } else if (kind == 1) {
+    HIPCHK(launch_linattn_kmax(dt, q_cl, (float*)ws, B, L, H, D, s));
+    HIPCHK(launch_linattn(dt, q_cl, o_cl, (float*)ws, B, L, H, D, true, s));
+  } else if (kind == 2) {
+    HIPCHK(launch_linattn_kmax(dt, q_cl, (float*)ws, B, L, H, D, s));
+    HIPCHK(launch_linattn_ctx(dt, q_cl, (float*)ws, B, L, H, D, s));
+    HIPCHK(launch_linattn_tail(dt, q_cl, (const float*)ws, to_out.w, to_out.n_pad, to_out.bias, d_gain, r_cl, o_cl, B, L, H, D, C, c->dev_flag_dev, s));
+  } else {
+    HIPCHK(launch_attn_full(dt, q_cl, o_cl, B, L, H, D, s));
+  }
+  HIPCHK(launch_from_cl(dt, o_cl, out, B, Co, L, nullptr, 0, 0.f, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return check_dev_flag(c);
+}
+
 // Self-check of the fp8 x fp8 conv (conv_fast_fp8.hip): operands drawn ON the e4m3 grid, so the bf16-activation x fp8-weight
 // kernel (same quantised weights, expanded to bf16 in registers, bf16 MFMA) computes exactly the same products; the two results
 // may differ by the fp32 summation order only (one bf16 ulp of the output at most).  Reports max |diff| and max |output|.

@@ -333,7 +333,7 @@ struct ldc_ctx {
   // device-drawn noise: every sampler call that draws advances the epoch, so no two calls share a realisation
   uint64_t noise_epoch = 0, cur_key = 0;
   // asynchronous device-side failure flag, host-mapped: word 0 = 1 cooperative LSTM timeout, 2 fused GroupNorm wait timeout,
-  // LDC_DEV_BAD_CODE an out-of-range RVQ code (its position in words 2..3)
+  // 4 (kDevFailCtxRange) LinearAttention context fold outside its valid k range, 3 (LDC_DEV_BAD_CODE) an out-of-range RVQ code (its position in words 2..3)
   unsigned* dev_flag_host = nullptr;
   unsigned* dev_flag_dev = nullptr;
   int enc_final_act = ACT_NONE;
@@ -379,6 +379,11 @@ inline int check_dev_flag(ldc_ctx* c) {
       return fail(LDC_E_HIP, "device-side failure [gn_wait]: the in-launch GroupNorm exchange of a fused conv timed out (its tiles were "
                              "not all resident in time: is the GPU shared with another process?); the outputs of that call are NaN; "
                              "ldc_set_option(ctx, \"fuse_gn_epi\", 0) restores the separate conv + gn_apply launches");
+    if (v == kDevFailCtxRange)
+      return fail(LDC_E_HIP, "device-side failure [ctx_range]: the LinearAttention context folded into to_qkv met k values outside the range "
+                             "its unshifted exponentials are valid for (a column whose sum of exp(k) is below 2^-100 or reaches 1e26: a k of 60 or more); the "
+                             "outputs of that call are wrong; ldc_set_option(ctx, \"fold_ctx\", 0) restores the column maximum and the "
+                             "context launch, which shift by it");
     c->lstm_xcd = 0;   // (if it was the XCD-local form that gave up, the retry takes the placement-independent kernel)
     return fail(LDC_E_HIP, "device-side failure [coop_lstm]: cooperative LSTM: the hidden-state exchange timed out (its workgroups were "
                            "not co-resident: is the GPU shared with another process?); the outputs of that call are NaN; "

@@ -86,7 +86,10 @@ struct ConvCall {
   int colmax_lo = 0, colmax_hi = 0, colmax_stride = 0;
   // LinearAttention context inside to_qkv (round 6, lean kernel, bf16): the layer's output columns are ordered q | (k_h v_h) x heads, the
   // q tiles are stored, a (k_h | v_h) tile accumulates exp(k)^T v and the column sums of exp(k) into the item's workspace
-  // (qkv_ctx_ws + item * qkv_ctx_stride floats: kmax keys [HD] (unused) | ksum [HD] | ctx [H][D][D], zeroed every step) and stores nothing
+  // (qkv_ctx_ws + item * qkv_ctx_stride floats: kmax keys [HD] (unused) | ksum [HD] | ctx [H][D][D], zeroed every step) and stores nothing.
+  // The exponentials are NOT shifted by a column maximum: valid while every column's sum of exp(k) is in [kLinattnKsumMin, kLinattnKsumMax)
+  // = [2^-100, 1e26), hence every k < 60; outside that range the tail that consumes the workspace raises the context's failure word to
+  // kDevFailCtxRange ("[ctx_range]", fallback fold_ctx 0), never a silently wrong result (see kLinattnKClamp below)
   float* qkv_ctx_ws = nullptr;
   int qkv_ctx_stride = 0;
   float* sk_part = nullptr;   // optional split-K workspace (fp32 partial tiles) and arrival counters (pre-zeroed)
@@ -103,7 +106,7 @@ struct ConvCall {
   const float* gn_beta = nullptr;
   const float* gn_ss = nullptr;     // [2 n] scale | shift of the current timestep, or null
   int gn_out = 0;                   // bit 2: tanh after the residual add
-  unsigned* fail_flag = nullptr;    // host-mapped word raised when the bounded in-launch wait gives up
+  unsigned* fail_flag = nullptr;    // host-mapped word raised when the bounded in-launch wait gives up (2); the LinearAttention tail raises it to 4 when the context fold left its valid range
   float* rowstat_out = nullptr;        // fused apply with residual: per-row (sum, sumsq) partials of the output per 32-column block, [rows][n / 32][2]
   const float* ln_rowstat = nullptr;   // LayerNorm-folded conv (ConvLayer::ln_s): those partials of its input, or null (it reads its rows once more)
   unsigned long long* kst = nullptr;   // timed-mode stamps of this launch (ConvKArgs::kst), pipelined kernel only
@@ -162,7 +165,18 @@ size_t linattn_ws_floats_per_item(int heads, int dim_head);
 bool linattn_tail_supported(int dt, int heads, int dim_head, int C);
 hipError_t launch_linattn_ctx(int dt, const void* qkv, float* ctx_ws, int B, int L, int heads, int dim_head, hipStream_t s);
 hipError_t launch_linattn_tail(int dt, const void* qkv, const float* ctx_ws, const void* wo_packed, int n_pad, const float* bias, const float* gain,
-                               const void* resid, void* out, int B, int L, int heads, int dim_head, int C, hipStream_t s);
+                               const void* resid, void* out, int B, int L, int heads, int dim_head, int C, unsigned* fail_flag, hipStream_t s);
+hipError_t launch_linattn_kmax(int dt, const void* qkv, float* ctx_ws, int B, int L, int heads, int dim_head, hipStream_t s);
+// The context fold (ConvCall::qkv_ctx_ws) takes exp(min(k, kLinattnKClamp)) without a shift.  It agrees with the shifted kernels while
+// every column's sum of exp(k) lies in [kLinattnKsumMin, kLinattnKsumMax): above the floor every term within 2^-24 of the column's largest
+// is a normal number in fp32 and bf16 (a column maximum above about -69 - ln L); below the ceiling no entry was clamped (one clamped entry
+// contributes e^60 = 1.14e26, 1.137e26 after its rounding to bf16) and 1 200 positions cannot overflow.  The tail tests the sum it divides by
+// and raises the context's failure word to kDevFailCtxRange outside that range (also for Inf / NaN): the call fails with "device-side
+// failure [ctx_range]" and option fold_ctx 0 -- column max, then shifted exponentials -- is the fallback.
+constexpr float kLinattnKClamp = 60.0f;
+constexpr float kLinattnKsumMin = 7.888609052210118e-31f;   // 2^-100
+constexpr float kLinattnKsumMax = 1.0e26f;
+constexpr unsigned kDevFailCtxRange = 4u;   // (3 is LDC_DEV_BAD_CODE)
 hipError_t launch_attn_full(int dt, const void* qkv, void* out, int B, int L, int heads, int dim_head, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------

@@ -77,7 +77,8 @@ class Engine:
         L.check(self.lib.ldc_set_option(self._ctx, name.encode(), int(value)))
 
     def debug_raise_failure(self, code: int) -> None:
-        """test hook: raise the device-side failure flag (1 = cooperative LSTM gave up, 2 = fused GroupNorm wait gave up)"""
+        """test hook: raise the device-side failure flag (1 = cooperative LSTM gave up, 2 = fused GroupNorm wait gave up,
+        4 = LinearAttention context fold outside its valid k range)"""
         L.check(self.lib.ldc_debug_raise_failure(self._ctx, int(code)))
 
     def host_stats(self, reset: bool = True):
@@ -238,6 +239,44 @@ class Engine:
         s = self._enter()
         L.check(self.lib.ldc_unet_debug_tap(self._ctx, name.encode(), out.data_ptr(), out.numel(), s))
         self._exit()
+        return out
+
+    ATTN_CORE_KINDS = {"linattn": 0, "linattn_kmax_fused": 1, "linattn_ctx_tail": 2, "attn_full": 3}
+
+    def debug_attn_core(self, kind: str, qkv, to_out=None):
+        """ldc_debug_attn_core: one attention core (4 heads x 32) on qkv [B, 384, L] in the engine's UNet dtype.  kind: one of
+        ATTN_CORE_KINDS; 'linattn_ctx_tail' takes to_out = (weight [C, 128], bias [C], gain [C], residual [B, C, L]) and returns
+        [B, C, L], the others return [B, 128, L]."""
+        qkv = self._f32(qkv)
+        B, _, Lx = qkv.shape
+        k = self.ATTN_CORE_KINDS[kind]
+        w = b = g = r = None
+        Cc = 0
+        if k == 2:
+            w, b, g = (np.ascontiguousarray(np.asarray(t, dtype=np.float32)) for t in to_out[:3])
+            r = self._f32(to_out[3])
+            Cc = int(w.shape[0])
+        out = self._empty(B, Cc if k == 2 else 128, Lx)
+        hp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_debug_attn_core(self._ctx, k, qkv.data_ptr(), B, Lx, hp(w), hp(b), hp(g),
+                                                 r.data_ptr() if r is not None else None, Cc, out.data_ptr(), s))
+        finally:
+            self._exit()
+        return out
+
+    def debug_attention_block(self, name: str, x):
+        """ldc_debug_attention_block: the attention block 'down<i>' / 'up<i>' / 'mid' of the loaded UNet on x [B, C, L], routed by
+        the plan builder under the engine's current options."""
+        x = self._f32(x)
+        B, _, Lx = x.shape
+        out = self.torch.empty_like(x)
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_debug_attention_block(self._ctx, name.encode(), x.data_ptr(), B, Lx, out.data_ptr(), s))
+        finally:
+            self._exit()
         return out
 
     def p_sample(self, x, t: int, cond, noise=None):

@@ -339,12 +339,15 @@ def apply_device_fallback(eng, err) -> bool:
     """A kernel whose bounded in-launch wait gave up poisons its output with NaN and raises the context's device-side failure
     flag; the call that sees the flag fails with LDC_E_HIP and a tagged message (ldc_api.cpp: check_dev_flag).  Switch the engine
     to the form that needs no co-residency: "[coop_lstm]" -> the streamed LSTM kernel, "[gn_wait]" -> separate conv + gn_apply
-    launches.  Returns False for any other error."""
+    launches.  "[ctx_range]" is raised the same way by the LinearAttention context fold when a k is outside the range its unshifted
+    exponentials are valid for -> fold_ctx 0 (column maximum + context launch).  Returns False for any other error."""
     from . import lib as L
     if getattr(err, "code", None) != L.E_HIP or "device-side failure" not in str(err):
         return False
     if "[gn_wait]" in str(err):
         eng.set_option("fuse_gn_epi", 0)
+    elif "[ctx_range]" in str(err):
+        eng.set_option("fold_ctx", 0)
     else:
         eng.set_option("lstm_stream", 1)
     return True

@@ -297,7 +297,7 @@ def test_error_behaviour():
     bad.close()
 
 
-@pytest.mark.parametrize("code,tag,option", [(1, "[coop_lstm]", "lstm_stream"), (2, "[gn_wait]", "fuse_gn_epi")])
+@pytest.mark.parametrize("code,tag,option", [(1, "[coop_lstm]", "lstm_stream"), (2, "[gn_wait]", "fuse_gn_epi"), (4, "[ctx_range]", "fold_ctx")])
 def test_device_side_failure_fallback(code, tag, option):
     """A kernel whose bounded in-launch wait gave up raises the host-mapped flag; the next call fails with LDC_E_HIP and a
     tagged message, and the CLI's decode_with_retry applies the matching fallback and decodes the batch again (ADVICE r3:

@@ -166,6 +166,54 @@ def test_conv_upsample_activation_attention_against_autograd():
         assert rel(TR.activation(e, x.detach(), kind, dy=dy).cpu().numpy(), x.grad.numpy()) < 1e-5
 
 
+@pytest.mark.parametrize("N", [75, 300])
+def test_bottleneck_attention_forward_backward_against_fp64_autograd(N):
+    """TR.Attention (train.hip: attn_*_kernel) at the bottleneck's width, C = 1024: N = 75 is the bench shape, N = 300 takes more than
+    one pass of the 256-thread row loops.  Reference: oracle.ldc_oracle.full_attention in float64 under torch autograd."""
+    from oracle import ldc_oracle as O
+    e = engine("r84", "f32")
+    gen = torch.Generator().manual_seed(100 + N)
+    C, B = 1024, 2
+    p = {"norm.g": 1.0 + 0.2 * torch.randn(1, C, 1, generator=gen), "to_qkv.weight": torch.randn(384, C, 1, generator=gen) / C ** 0.5 * 2.0,
+         "to_out.weight": torch.randn(C, 128, 1, generator=gen) / 128 ** 0.5, "to_out.bias": 0.1 * torch.randn(C, generator=gen)}
+    x = torch.randn(B, C, N, generator=gen)
+    dy = torch.randn(B, C, N, generator=gen)
+    sd = {"a.fn." + ("norm.g" if k == "norm.g" else "fn." + k): v.double().requires_grad_() for k, v in p.items()}
+    xr = x.double().requires_grad_()
+    y = O.full_attention(sd, "a", xr, 4, 32)
+    y.backward(dy.double())
+    att = TR.Attention(e, p)
+    assert rel(att.forward(x).cpu().numpy(), y.detach().numpy()) < TOL
+    grads = att.backward(dy)
+    assert rel(grads["dx"].cpu().numpy(), xr.grad.numpy()) < TOL
+    for k in p:
+        ref = sd["a.fn." + ("norm.g" if k == "norm.g" else "fn." + k)].grad.numpy()
+        assert rel(grads[k].cpu().numpy().reshape(ref.shape), ref) < TOL, k
+
+
+@pytest.mark.parametrize("r,Lx", [(5, 120), (2, 600)])
+def test_conv_transpose_forward_backward_against_fp64_autograd(r, Lx):
+    """TR.ConvTranspose1d, the condition upsampler's SConvTranspose1d(128, 128, 2r, r), at its own width and lengths against
+    oracle.ldc_oracle.sconvtr1d in float64 under torch autograd."""
+    from oracle import ldc_oracle as O
+    e = engine("r84", "f32")
+    gen = torch.Generator().manual_seed(200 + r)
+    C, B = 128, 2
+    x = torch.randn(B, C, Lx, generator=gen)
+    w = torch.randn(C, C, 2 * r, generator=gen) / (2 * C) ** 0.5
+    b = 0.1 * torch.randn(C, generator=gen)
+    xr, wr, br = (t.double().requires_grad_() for t in (x, w, b))
+    y = O.sconvtr1d(xr, wr, br, r, causal=False)
+    assert y.shape == (B, C, Lx * r)
+    dy = torch.randn(y.shape, generator=gen)
+    y.backward(dy.double())
+    ct = TR.ConvTranspose1d(e, w, b, r)
+    assert rel(ct.forward(x).cpu().numpy(), y.detach().numpy()) < TOL
+    gr = ct.backward(dy)
+    assert rel(gr["dx"].cpu().numpy(), xr.grad.numpy()) < TOL and rel(gr["dw"].cpu().numpy(), wr.grad.numpy()) < TOL
+    assert rel(gr["db"].cpu().numpy(), br.grad.numpy()) < TOL
+
+
 def test_assembled_unet_forward_backward_reference_vectors():
     """Unet1D.forward / backward over the reference's own state dict (two levels, dim 16): output, input gradients and the
     gradient of every one of the 160 parameters against the reference's autograd (tests/golden/train_unet.npz); then one Adam
