@@ -219,6 +219,23 @@ int ldc_ddim_sample(ldc_ctx* ctx, float* img_inout, const float* cond, const flo
 int ldc_decode_ddim(ldc_ctx* ctx, const float* wav, int B, int T, int t_start, int n_steps, float eta, const float* noise,
                     int per_item, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
 
+/* ldc_decode / ldc_decode_ddim on a batch of items of different lengths: wav [B,1,Tmax], lengths_host[B] samples per item
+ * (host memory).  Every item is decoded as if alone (per-item normalisation).  t_start == 0: halfway DDPM sampling of
+ * n_steps (eta ignored); t_start > 0: DDIM as ldc_decode_ddim.  noise [n_steps,B,C,Lmax] or NULL; item b consumes
+ * noise[:, b, :, :L_b].  Outputs are zero beyond an item's length; what the padding of wav and noise holds is never read
+ * into a valid value.  Every length and Tmax must be a positive multiple of lcm(cond hop, main hop * 2^halvings) samples
+ * (2560 for enc_ratios 8 4, 640 for 8) and no length may exceed Tmax: LDC_E_INVALID otherwise, before any GPU work; the
+ * fp8 engine refuses ragged calls the same way.  The lengths live in device memory, so the step graph captured for
+ * (B, Tmax) is replayed for every set of lengths. */
+int ldc_decode_ragged(ldc_ctx* ctx, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps,
+                      float eta, const float* noise, float* wav_out, float* latents_out, float* cond_out,
+                      int64_t* codes_out, void* stream);
+/* Unet1D.forward with per-item latent lengths (test hook and building block): x [B,C,Lmax], cond [B,C,Fmax];
+ * latent_lens_host[B] in latent frames, multiples of lcm(prod(upsampling_ratios), 2^halvings).  eps_out is zero beyond
+ * an item's length. */
+int ldc_unet_forward_ragged(ldc_ctx* ctx, const float* x, int t, const float* cond, const int32_t* latent_lens_host,
+                            int B, int Lmax, int Fmax, float* eps_out, void* stream);
+
 /* The decode of ldc_decode / ldc_decode_ddim started from RVQ codes instead of a waveform (the receiver side):
  * quantizer.decode(codes) -> upsample, /= max|.| -> sampling -> decoder -> output normalisation.
  * Exactly one of codes ([n_q,B,F] int64, device) / packed ([B][packed_stride] bytes, device, `bits` per code in

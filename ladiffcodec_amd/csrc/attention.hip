@@ -49,10 +49,12 @@ __host__ __device__ inline size_t linattn_ws_per_item(int H, int D) { return (si
 // ---- pass 1: column max of k over positions ----
 template <typename T>
 __global__ __launch_bounds__(256) void linattn_kmax_kernel(const void* qkv, float* ws, int L, int HD, int rows_per_block,
-                                                           size_t ws_stride) {
+                                                           size_t ws_stride, const int* lens, int shift) {
   __shared__ float red[256];
   const int b = blockIdx.y;
-  const int r0 = blockIdx.x * rows_per_block, r1 = min(L, r0 + rows_per_block);
+  const int Lv = valid_rows(lens, shift, b, L);   // ragged batch: the softmax over positions runs over the item's valid rows
+  const int r0 = blockIdx.x * rows_per_block, r1 = min(Lv, r0 + rows_per_block);
+  if (r0 >= r1) return;
   const int col = threadIdx.x % HD, ph = threadIdx.x / HD, nph = 256 / HD;
   float m = -INFINITY;
   for (int r = r0 + ph; r < r1; r += nph) m = fmaxf(m, ld1<T>(qkv, ((size_t)(b * L + r)) * (3 * HD) + HD + col));
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(256) void linattn_kmax_kernel(const void* qkv, floa
 // ---- pass 2: unnormalised context and column sums over a chunk of rows, atomically merged ----
 template <typename T, int D>
 __global__ __launch_bounds__(256) void linattn_ctx_kernel(const void* qkv, float* ws, int L, int H, int rows_per_block,
-                                                          size_t ws_stride) {
+                                                          size_t ws_stride, const int* lens, int shift) {
   constexpr int TR = 64;
   __shared__ float sp[TR][D + 1];
   __shared__ float sv[TR][D];
@@ -75,7 +77,8 @@ __global__ __launch_bounds__(256) void linattn_ctx_kernel(const void* qkv, float
   const int HD = H * D;
   const int b = blockIdx.y / H, h = blockIdx.y % H;
   float* wsb = ws + (size_t)b * ws_stride;
-  const int r0 = blockIdx.x * rows_per_block, r1 = min(L, r0 + rows_per_block);
+  const int r0 = blockIdx.x * rows_per_block, r1 = min(valid_rows(lens, shift, b, L), r0 + rows_per_block);
+  if (r0 >= r1) return;   // (a chunk of padding rows: nothing to add)
   const int tid = threadIdx.x;
   if (tid < D) skmax[tid] = fkey_inv(reinterpret_cast<const unsigned*>(wsb)[h * D + tid]);
   __syncthreads();
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(256) void linattn_ctx_kernel(const void* qkv, float
 // ---- pass 3: out[n, h*D+e] = sum_d (ctx[d][e]/ksum[d]) * softmax_d(q[n,h,:])[d] * scale ----
 template <typename T, int D>
 __global__ __launch_bounds__(256) void linattn_out_kernel(const void* qkv, void* out, const float* ws, int L, int H,
-                                                          size_t ws_stride, float scale) {
+                                                          size_t ws_stride, float scale, const int* lens, int shift) {
   constexpr int HS = D * D + 8;   // padded head stride: the 4 heads of a wave hit different banks
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* sctx = reinterpret_cast<float*>(smem_raw);   // [H][HS]
@@ -130,6 +133,12 @@ __global__ __launch_bounds__(256) void linattn_out_kernel(const void* qkv, void*
   const int h = threadIdx.x % H;
   const int r = blockIdx.x * rows_per_block + threadIdx.x / H;
   if (r >= L) return;
+  if (r >= valid_rows(lens, shift, b, L)) {   // a padding row of a ragged batch: zeros, its q is not read
+    const size_t ob = ((size_t)(b * L + r)) * HD + h * D;
+#pragma unroll
+    for (int e = 0; e < D; ++e) st1<T>(out, ob + e, 0.f);
+    return;
+  }
   const size_t base = ((size_t)(b * L + r)) * (3 * HD) + h * D;
   float q[D];
   float m = -INFINITY;
@@ -176,7 +185,7 @@ __device__ __forceinline__ lf32x16 mfma_bf16(const uint4& a, const uint4& b, lf3
 }
 
 template <int R>   // rows per workgroup
-__global__ __launch_bounds__(256) void linattn_ctx_mfma_kernel(const unsigned short* qkv, float* ws, int L, size_t ws_stride) {
+__global__ __launch_bounds__(256) void linattn_ctx_mfma_kernel(const unsigned short* qkv, float* ws, int Lfull, size_t ws_stride, const int* lens, int shift) {
   constexpr int H = 4, D = 32, HD = 128, P = R + 8;
   __shared__ __attribute__((aligned(16))) unsigned short spT[HD][P];
   __shared__ __attribute__((aligned(16))) unsigned short svT[HD][P];
@@ -184,13 +193,15 @@ __global__ __launch_bounds__(256) void linattn_ctx_mfma_kernel(const unsigned sh
   const int b = blockIdx.y, tid = threadIdx.x;
   float* wsb = ws + (size_t)b * ws_stride;
   const int r0 = blockIdx.x * R;
+  const int L = valid_rows(lens, shift, b, Lfull);   // rows that contribute (ragged batch: the item's valid rows); Lfull is the row pitch
+  if (r0 >= L) return;
   constexpr int NP = R / 16;   // 16-byte pieces per thread and operand
   uint4 kk[NP], vv[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int id = tid + 256 * i, row = id >> 4, c16 = id & 15;
     if (r0 + row < L) {
-      const unsigned short* base = qkv + ((size_t)b * L + r0 + row) * (3 * HD) + 8 * c16;
+      const unsigned short* base = qkv + ((size_t)b * Lfull + r0 + row) * (3 * HD) + 8 * c16;
       kk[i] = *reinterpret_cast<const uint4*>(base + HD);
       vv[i] = *reinterpret_cast<const uint4*>(base + 2 * HD);
     } else {
@@ -246,11 +257,12 @@ __global__ __launch_bounds__(256) void linattn_ctx_mfma_kernel(const unsigned sh
 
 template <int TILES>   // 32-row tiles per workgroup
 __global__ __launch_bounds__(256) void linattn_out_mfma_kernel(const unsigned short* qkv, unsigned short* out, const float* ws,
-                                                               int L, size_t ws_stride, float scale) {
+                                                               int L, size_t ws_stride, float scale, const int* lens, int shift) {
   constexpr int D = 32, HD = 128;
   const int b = blockIdx.y, tid = threadIdx.x;
   const int h = tid >> 6, lane = tid & 63, i32 = lane & 31, g = lane >> 5;
   const int r0 = blockIdx.x * (32 * TILES);
+  const int Lv = valid_rows(lens, shift, b, L);   // ragged batch: rows [Lv, L) are padding, read as zero and written as zero
   // q row pieces first (independent of the context)
   uint4 qq[TILES][2];
 #pragma unroll
@@ -258,7 +270,7 @@ __global__ __launch_bounds__(256) void linattn_out_mfma_kernel(const unsigned sh
     const int n = r0 + 32 * t + i32;
 #pragma unroll
     for (int sx = 0; sx < 2; ++sx) {
-      if (n < L) qq[t][sx] = *reinterpret_cast<const uint4*>(qkv + ((size_t)b * L + n) * (3 * HD) + h * D + 16 * sx + 8 * g);
+      if (n < Lv) qq[t][sx] = *reinterpret_cast<const uint4*>(qkv + ((size_t)b * L + n) * (3 * HD) + h * D + 16 * sx + 8 * g);
       else qq[t][sx] = make_uint4(0, 0, 0, 0);
     }
   }
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(256) void linattn_out_mfma_kernel(const unsigned sh
       for (int rr = 0; rr < 4; ++rr) {
         const unsigned lo = (unsigned)af2bf(acc[4 * rr]) | ((unsigned)af2bf(acc[4 * rr + 1]) << 16);
         const unsigned hi = (unsigned)af2bf(acc[4 * rr + 2]) | ((unsigned)af2bf(acc[4 * rr + 3]) << 16);
-        *reinterpret_cast<uint2*>(orow + 8 * rr + 4 * g) = make_uint2(lo, hi);
+        *reinterpret_cast<uint2*>(orow + 8 * rr + 4 * g) = n < Lv ? make_uint2(lo, hi) : make_uint2(0u, 0u);
       }
     }
   }
@@ -565,7 +577,8 @@ bool linattn_tail_supported(int dt, int heads, int dim_head, int C) {
 hipError_t launch_linattn_ctx(int dt, const void* qkv, float* ws, int B, int L, int heads, int dim_head, hipStream_t s) {
   if (dt != DT_BF16 || heads != 4 || dim_head != 32) return hipErrorInvalidValue;
   const size_t wss = linattn_ws_per_item(heads, dim_head);
-  hipLaunchKernelGGL(linattn_ctx_mfma_kernel<64>, dim3((L + 63) / 64, B), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(qkv), ws, L, wss);
+  hipLaunchKernelGGL(linattn_ctx_mfma_kernel<64>, dim3((L + 63) / 64, B), dim3(256), 0, s, reinterpret_cast<const unsigned short*>(qkv), ws, L, wss,
+                     static_cast<const int*>(nullptr), 0);
   return hipGetLastError();
 }
 
@@ -587,26 +600,27 @@ size_t linattn_ws_floats_per_item(int heads, int dim_head) { return linattn_ws_p
 
 // the k column maxima as keys in a cleared `ws`: what a to_qkv conv with the fused column max leaves for launch_linattn(kmax_fused)
 // and launch_linattn_ctx, computed from the stored qkv rows (ldc_debug_attn_core)
-hipError_t launch_linattn_kmax(int dt, const void* qkv, float* ws, int B, int L, int heads, int dim_head, hipStream_t s) {
+hipError_t launch_linattn_kmax(int dt, const void* qkv, float* ws, int B, int L, int heads, int dim_head, hipStream_t s, const int* lens, int shift) {
   const int HD = heads * dim_head;
   if (dim_head != 32 || HD > 256 || 256 % HD) return hipErrorInvalidValue;
   const size_t wss = linattn_ws_per_item(heads, dim_head);
   hipError_t e = hipMemsetAsync(ws, 0, (size_t)B * wss * sizeof(float), s);
   if (e != hipSuccess) return e;
   const int rpb = 128;
-  if (dt == DT_F32) hipLaunchKernelGGL(linattn_kmax_kernel<float>, dim3((L + rpb - 1) / rpb, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss);
-  else hipLaunchKernelGGL(linattn_kmax_kernel<__bf16>, dim3((L + rpb - 1) / rpb, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss);
+  if (dt == DT_F32) hipLaunchKernelGGL(linattn_kmax_kernel<float>, dim3((L + rpb - 1) / rpb, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss, lens, shift);
+  else hipLaunchKernelGGL(linattn_kmax_kernel<__bf16>, dim3((L + rpb - 1) / rpb, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss, lens, shift);
   return hipGetLastError();
 }
 
 // kmax_fused: the caller zeroed `ws` before the qkv conv and that conv's epilogue already produced the column
 // maxima (conv_device.h epilogue_colmax)
 hipError_t launch_linattn(int dt, const void* qkv, void* out, float* ws, int B, int L, int heads, int dim_head,
-                          bool kmax_fused, hipStream_t s) {
+                          bool kmax_fused, hipStream_t s, const int* lens, int shift, bool ws_zeroed) {
+  if (lens && kmax_fused) return hipErrorInvalidValue;   // a conv's fused column maximum runs over every row of the item
   if (dim_head != 32 || heads * dim_head > 256 || 256 % (heads * dim_head) || 256 % heads) return hipErrorInvalidValue;
   const int HD = heads * dim_head;
   const size_t wss = linattn_ws_per_item(heads, dim_head);
-  if (!kmax_fused) {
+  if (!kmax_fused && !ws_zeroed) {
     hipError_t e = hipMemsetAsync(ws, 0, (size_t)B * wss * sizeof(float), s);
     if (e != hipSuccess) return e;
   }
@@ -616,21 +630,21 @@ hipError_t launch_linattn(int dt, const void* qkv, void* out, float* ws, int B, 
   const size_t lds_out = (size_t)heads * (dim_head * dim_head + 8) * sizeof(float);
   const int rows_out = 256 / heads;
   if (dt == DT_BF16 && heads == 4) {
-    if (!kmax_fused) hipLaunchKernelGGL(linattn_kmax_kernel<__bf16>, dim3(chunks, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss);
+    if (!kmax_fused) hipLaunchKernelGGL(linattn_kmax_kernel<__bf16>, dim3(chunks, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss, lens, shift);
     hipLaunchKernelGGL(linattn_ctx_mfma_kernel<64>, dim3((L + 63) / 64, B), dim3(256), 0, s,
-                       reinterpret_cast<const unsigned short*>(qkv), ws, L, wss);
+                       reinterpret_cast<const unsigned short*>(qkv), ws, L, wss, lens, shift);
     hipLaunchKernelGGL(linattn_out_mfma_kernel<2>, dim3((L + 63) / 64, B), dim3(256), 0, s,
-                       reinterpret_cast<const unsigned short*>(qkv), reinterpret_cast<unsigned short*>(out), ws, L, wss, scale);
+                       reinterpret_cast<const unsigned short*>(qkv), reinterpret_cast<unsigned short*>(out), ws, L, wss, scale, lens, shift);
   } else if (dt == DT_F32) {
-    if (!kmax_fused) hipLaunchKernelGGL(linattn_kmax_kernel<float>, dim3(chunks, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss);
-    hipLaunchKernelGGL((linattn_ctx_kernel<float, 32>), dim3(chunks, B * heads), dim3(256), 0, s, qkv, ws, L, heads, rpb, wss);
+    if (!kmax_fused) hipLaunchKernelGGL(linattn_kmax_kernel<float>, dim3(chunks, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss, lens, shift);
+    hipLaunchKernelGGL((linattn_ctx_kernel<float, 32>), dim3(chunks, B * heads), dim3(256), 0, s, qkv, ws, L, heads, rpb, wss, lens, shift);
     hipLaunchKernelGGL((linattn_out_kernel<float, 32>), dim3((L + rows_out - 1) / rows_out, B), dim3(256), lds_out, s, qkv,
-                       out, ws, L, heads, wss, scale);
+                       out, ws, L, heads, wss, scale, lens, shift);
   } else {
-    if (!kmax_fused) hipLaunchKernelGGL(linattn_kmax_kernel<__bf16>, dim3(chunks, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss);
-    hipLaunchKernelGGL((linattn_ctx_kernel<__bf16, 32>), dim3(chunks, B * heads), dim3(256), 0, s, qkv, ws, L, heads, rpb, wss);
+    if (!kmax_fused) hipLaunchKernelGGL(linattn_kmax_kernel<__bf16>, dim3(chunks, B), dim3(256), 0, s, qkv, ws, L, HD, rpb, wss, lens, shift);
+    hipLaunchKernelGGL((linattn_ctx_kernel<__bf16, 32>), dim3(chunks, B * heads), dim3(256), 0, s, qkv, ws, L, heads, rpb, wss, lens, shift);
     hipLaunchKernelGGL((linattn_out_kernel<__bf16, 32>), dim3((L + rows_out - 1) / rows_out, B), dim3(256), lds_out, s,
-                       qkv, out, ws, L, heads, wss, scale);
+                       qkv, out, ws, L, heads, wss, scale, lens, shift);
   }
   return hipGetLastError();
 }
@@ -645,7 +659,7 @@ hipError_t launch_linattn(int dt, const void* qkv, void* out, float* ws, int B, 
 // Keys/values pass through LDS in chunks of CH positions, so the sequence length is unbounded (a 35 s utterance
 // has n = 1094 at the bottleneck; the reference's softmax attention has no limit either).
 template <typename T, int D>
-__global__ __launch_bounds__(256) void attn_full_kernel(const void* qkv, void* out, int L, int H, float scale, int CH) {
+__global__ __launch_bounds__(256) void attn_full_kernel(const void* qkv, void* out, int L, int H, float scale, int CH, const int* lens, int shift) {
   constexpr int P = D + 4;   // padded row: the 4 lanes of a query read 4 different keys without bank conflicts
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* sk = reinterpret_cast<float*>(smem_raw);   // [CH][P]
@@ -654,14 +668,15 @@ __global__ __launch_bounds__(256) void attn_full_kernel(const void* qkv, void* o
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int part = threadIdx.x & 3;
   const int i = blockIdx.y * 64 + (threadIdx.x >> 2);
-  const int iq = min(i, L - 1);
+  const int Lv = valid_rows(lens, shift, b, L);   // ragged batch: keys [0, Lv); query rows [Lv, L) write zero (uniform over the workgroup)
+  const int iq = min(i, Lv - 1);
   float q[D], acc[D];
   const size_t qb = ((size_t)(b * L + iq)) * (3 * HD) + h * D;
 #pragma unroll
   for (int d = 0; d < D; ++d) { q[d] = ld1<T>(qkv, qb + d) * scale; acc[d] = 0.f; }
   float m = -INFINITY, l = 0.f;
-  for (int k0 = 0; k0 < L; k0 += CH) {
-    const int nk = min(CH, L - k0);
+  for (int k0 = 0; k0 < Lv; k0 += CH) {
+    const int nk = min(CH, Lv - k0);
     if (k0) __syncthreads();   // everyone is done with the previous chunk
     for (int idx = threadIdx.x; idx < nk * (D / 8); idx += 256) {
       const int r = idx / (D / 8), c8 = idx % (D / 8);
@@ -712,11 +727,11 @@ __global__ __launch_bounds__(256) void attn_full_kernel(const void* qkv, void* o
     const size_t ob = ((size_t)(b * L + i)) * HD + h * D;
 #pragma unroll
     for (int d = 0; d < D; ++d)
-      if ((d >> 3) == part) st1<T>(out, ob + d, acc[d] * inv);
+      if ((d >> 3) == part) st1<T>(out, ob + d, i < Lv ? acc[d] * inv : 0.f);
   }
 }
 
-hipError_t launch_attn_full(int dt, const void* qkv, void* out, int B, int L, int heads, int dim_head, hipStream_t s) {
+hipError_t launch_attn_full(int dt, const void* qkv, void* out, int B, int L, int heads, int dim_head, hipStream_t s, const int* lens, int shift) {
   if (dim_head != 32) return hipErrorInvalidValue;
   const int CH = std::min(L, 256);
   const size_t lds = (size_t)2 * CH * (dim_head + 4) * sizeof(float);
@@ -729,9 +744,9 @@ hipError_t launch_attn_full(int dt, const void* qkv, void* out, int B, int L, in
   }
   dim3 grid(B * heads, (L + 63) / 64);
   if (dt == DT_F32)
-    hipLaunchKernelGGL((attn_full_kernel<float, 32>), grid, dim3(256), lds, s, qkv, out, L, heads, scale, CH);
+    hipLaunchKernelGGL((attn_full_kernel<float, 32>), grid, dim3(256), lds, s, qkv, out, L, heads, scale, CH, lens, shift);
   else
-    hipLaunchKernelGGL((attn_full_kernel<__bf16, 32>), grid, dim3(256), lds, s, qkv, out, L, heads, scale, CH);
+    hipLaunchKernelGGL((attn_full_kernel<__bf16, 32>), grid, dim3(256), lds, s, qkv, out, L, heads, scale, CH, lens, shift);
   return hipGetLastError();
 }
 

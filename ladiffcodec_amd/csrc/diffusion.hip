@@ -219,9 +219,10 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, unsigned step, uin
 template <typename T>
 __global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const void* eps_cl, const float* noise,
                                                               int64_t noise_step_stride, void* x_cl, int C, int L,
-                                                              StepTables tb, const int* st, uint64_t elem_base) {
+                                                              StepTables tb, const int* st, uint64_t elem_base, const int* lens) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int Lv = valid_rows(lens, 0, b, L);   // ragged batch: positions [Lv, L) are padding -- x stays zero there, their noise is not read
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   // the tensor loads do not depend on the step: issue them before the (dependent) step-counter -> schedule-table chain
   // eps tile: read channels-last (coalesced over c), hand over transposed
@@ -259,10 +260,11 @@ __global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const vo
       float x0 = recip * xv - recipm1 * e;
       x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
       float v = c1 * x0 + c2 * xv;
-      if (t > 0) {
+      if (t > 0 && l < Lv) {
         const float z = noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii];
         v += sigma * z;
       }
+      v = l < Lv ? v : 0.f;
       x[idx] = v;
       newv[ii] = v;
     }
@@ -311,14 +313,14 @@ hipError_t launch_axpby(float* x, const float* y, float a, float b, int64_t n, h
 
 hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                                   void* x_cl, int B, int C, int L, StepTables tb, const int* st,
-                                  uint64_t elem_base, hipStream_t s) {
+                                  uint64_t elem_base, hipStream_t s, const int* lens) {
   dim3 grid((L + 31) / 32, (C + 31) / 32, B);
   if (dt == DT_F32)
     hipLaunchKernelGGL(p_sample_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L,
-                       tb, st, elem_base);
+                       tb, st, elem_base, lens);
   else
     hipLaunchKernelGGL(p_sample_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C,
-                       L, tb, st, elem_base);
+                       L, tb, st, elem_base, lens);
   return hipGetLastError();
 }
 
@@ -331,9 +333,10 @@ template <typename T>
 __global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* eps_cl, const float* noise,
                                                           int64_t noise_step_stride, void* x_cl, int C, int L,
                                                           StepTables tb, const DdimStep* sched, const int* st,
-                                                          uint64_t elem_base) {
+                                                          uint64_t elem_base, const int* lens) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int Lv = valid_rows(lens, 0, b, L);   // as p_sample_update_kernel
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   float ev[4], xin[4];
 #pragma unroll
@@ -369,8 +372,9 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* 
       float v = x0;
       if (!sp.last) {
         v = x0 * sp.sqrt_an + sp.c * e;
-        if (draw) v += sp.sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);
+        if (draw && l < Lv) v += sp.sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);
       }
+      v = l < Lv ? v : 0.f;
       x[idx] = v;
       newv[ii] = v;
     }
@@ -387,14 +391,14 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* 
 
 hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                               void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
-                              uint64_t elem_base, hipStream_t s) {
+                              uint64_t elem_base, hipStream_t s, const int* lens) {
   dim3 grid((L + 31) / 32, (C + 31) / 32, B);
   if (dt == DT_F32)
     hipLaunchKernelGGL(ddim_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L,
-                       tb, sched, st, elem_base);
+                       tb, sched, st, elem_base, lens);
   else
     hipLaunchKernelGGL(ddim_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C,
-                       L, tb, sched, st, elem_base);
+                       L, tb, sched, st, elem_base, lens);
   return hipGetLastError();
 }
 
@@ -525,11 +529,12 @@ hipError_t launch_step_set(int* st, int t, int j, uint64_t noise_key, hipStream_
 size_t output_normalise_ws_bytes(int B) { return (size_t)B * (2 * sizeof(double) + sizeof(float)) + 16; }
 
 __global__ __launch_bounds__(256) void outnorm_reduce_kernel(const float* x, int64_t n_per_item, int per_item,
-                                                             double* sums, float* maxabs) {
+                                                             double* sums, float* maxabs, const int* lens, int lens_unit) {
   const int b = blockIdx.y;
+  const int64_t n_valid = lens ? min(n_per_item, (int64_t)lens[b] * lens_unit) : n_per_item;   // ragged batch: the item's own samples
   double s = 0.0, ss = 0.0;
   float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_per_item; i += (int64_t)gridDim.x * 256) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_valid; i += (int64_t)gridDim.x * 256) {
     const float v = x[(size_t)b * n_per_item + i];
     s += v; ss += (double)v * v; m = fmaxf(m, fabsf(v));
   }
@@ -550,10 +555,11 @@ __global__ __launch_bounds__(256) void outnorm_reduce_kernel(const float* x, int
 }
 
 __global__ __launch_bounds__(256) void outnorm_apply_kernel(float* x, int64_t n_per_item, int per_item, int B,
-                                                            const double* sums, const float* maxabs) {
+                                                            const double* sums, const float* maxabs, const int* lens, int lens_unit) {
   const int b = blockIdx.y;
   const int slot = per_item ? b : 0;
-  const double n = per_item ? (double)n_per_item : (double)n_per_item * B;
+  const int64_t n_valid = lens ? min(n_per_item, (int64_t)lens[b] * lens_unit) : n_per_item;
+  const double n = per_item ? (double)n_valid : (double)n_per_item * B;
   const double mean = sums[2 * slot] / n;
   double var = (sums[2 * slot + 1] - n * mean * mean) / (n - 1.0);
   if (var < 0.0) var = 0.0;
@@ -561,19 +567,70 @@ __global__ __launch_bounds__(256) void outnorm_apply_kernel(float* x, int64_t n_
   const float mx = maxabs[slot] / sd + 1e-8f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_per_item; i += (int64_t)gridDim.x * 256) {
     const size_t idx = (size_t)b * n_per_item + i;
-    x[idx] = (x[idx] / sd) / mx;
+    x[idx] = i < n_valid ? (x[idx] / sd) / mx : 0.f;
   }
 }
 
-hipError_t launch_output_normalise(float* x, int B, int64_t n_per_item, int per_item, void* ws, hipStream_t s) {
+hipError_t launch_output_normalise(float* x, int B, int64_t n_per_item, int per_item, void* ws, hipStream_t s, const int* lens, int lens_unit) {
+  if (lens && !per_item) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(ws, 0, output_normalise_ws_bytes(B), s);
   if (e != hipSuccess) return e;
   double* sums = reinterpret_cast<double*>(ws);
   float* maxabs = reinterpret_cast<float*>(sums + 2 * B);
   int bx = (int)std::min<int64_t>((n_per_item + 255) / 256, 64);
   if (bx < 1) bx = 1;
-  hipLaunchKernelGGL(outnorm_reduce_kernel, dim3(bx, B), dim3(256), 0, s, x, n_per_item, per_item, sums, maxabs);
-  hipLaunchKernelGGL(outnorm_apply_kernel, dim3(bx, B), dim3(256), 0, s, x, n_per_item, per_item, B, sums, maxabs);
+  hipLaunchKernelGGL(outnorm_reduce_kernel, dim3(bx, B), dim3(256), 0, s, x, n_per_item, per_item, sums, maxabs, lens, lens_unit);
+  hipLaunchKernelGGL(outnorm_apply_kernel, dim3(bx, B), dim3(256), 0, s, x, n_per_item, per_item, B, sums, maxabs, lens, lens_unit);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ragged batches: the padding rows of x [B][L][C] (rows l >= lens[b] >> shift) written as zero.  An item's padding is one contiguous
+// byte range behind its valid rows, so the kernel only stores (16-byte pieces; nothing of the padding is read): grid (chunks, B).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mask_rows_kernel(uint4* x, int L, long long row16, const int* lens, int shift) {
+  const int b = blockIdx.y;
+  const int Lv = valid_rows(lens, shift, b, L);
+  const long long lo = ((long long)b * L + Lv) * row16, hi = ((long long)b + 1) * L * row16;
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  for (long long i = lo + (long long)blockIdx.x * 256 + threadIdx.x; i < hi; i += (long long)gridDim.x * 256) x[i] = z;
+}
+hipError_t launch_mask_rows(int dt, void* x, int B, int L, int C, const int* lens, int shift, hipStream_t s) {
+  const size_t row_bytes = (size_t)C * dt_size(dt);
+  if (!lens || row_bytes % 16 || (reinterpret_cast<uintptr_t>(x) & 15)) return hipErrorInvalidValue;
+  const long long row16 = (long long)(row_bytes / 16);
+  const int bx = (int)std::max<long long>(1, std::min<long long>(((long long)L * row16 + 255) / 256, 64));
+  hipLaunchKernelGGL(mask_rows_kernel, dim3(bx, B), dim3(256), 0, s, reinterpret_cast<uint4*>(x), L, row16, lens, shift);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void mask_codes_kernel(int64_t* codes, int n_q, int B, int F, const int* flens) {
+  const int64_t n = (int64_t)n_q * B * F;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int f = (int)(i % F), b = (int)((i / F) % B);
+    if (f >= flens[b]) codes[i] = 0;
+  }
+}
+hipError_t launch_mask_codes(int64_t* codes, int n_q, int B, int F, const int* flens, hipStream_t s) {
+  const int64_t n = (int64_t)n_q * B * F;
+  hipLaunchKernelGGL(mask_codes_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1024))), dim3(256), 0, s, codes, n_q,
+                     B, F, flens);
+  return hipGetLastError();
+}
+
+// the lengths of a ragged batch written on the stream, as launch_ddim_table_write writes its table
+constexpr int kLensChunk = 64;
+struct LensChunk { int v[kLensChunk]; };
+__global__ void lens_write_kernel(int* dst, LensChunk src, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = src.v[threadIdx.x];
+}
+hipError_t launch_lens_write(int* dst, const int* src, int n, hipStream_t s) {
+  for (int i0 = 0; i0 < n; i0 += kLensChunk) {
+    LensChunk ch{};
+    const int m = std::min(kLensChunk, n - i0);
+    for (int i = 0; i < m; ++i) ch.v[i] = src[i0 + i];
+    hipLaunchKernelGGL(lens_write_kernel, dim3(1), dim3(kLensChunk), 0, s, dst + i0, ch, m);
+  }
   return hipGetLastError();
 }
 

@@ -1284,8 +1284,9 @@ extern "C" int ldc_get_cond(ldc_ctx* c, const float* wav, int B, int T, float ba
 // ------------------------------------------------------------------------------------------------
 // cond upsampler (fp32): rows [B*F][C] -> rows [B*L][C]
 // ------------------------------------------------------------------------------------------------
+// flens (ragged batches): condition frames per item; every layer's output is cut to the item's length (see build_plan)
 static int upsample_rows(ldc_ctx* c, const void* rows_in, int B, int F, Arena& ar, bool dry, hipStream_t s, void** out,
-                         int* L_out) {
+                         int* L_out, const int* flens = nullptr) {
   const UnetW& u = c->unet;
   const void* x = rows_in;
   int L = F;
@@ -1295,6 +1296,7 @@ static int upsample_rows(ldc_ctx* c, const void* rows_in, int B, int F, Arena& a
     void* y = ar.alloc((size_t)B * cc.L_final * ly.tr_cout * 4);
     cc.y = y;
     if (!dry) HIPCHK(launch_conv(ly, cc, s));
+    if (!dry && flens) HIPCHK(launch_mask_rows(DT_F32, y, B, F, cc.L_final / F * ly.tr_cout, flens, 0, s));
     x = y;
     L = cc.L_final;
   }
@@ -1358,6 +1360,22 @@ struct PlanBuilder {
   void* act(int rows, int C) {
     pl->act_bytes += (double)rows * C * es;
     return ar->alloc((size_t)rows * C * es);
+  }
+  // ragged plan: the device lengths and the level of a tensor of L rows per item (a level's lengths are lens[b] >> level)
+  const int* lens() const { return pl->ragged ? pl->lens : nullptr; }
+  int level(int L) const {
+    int sh = 0;
+    while ((L << sh) < pl->L) ++sh;
+    return sh;
+  }
+  // the padding rows of y [B*L][C] written as zero: behind every plain conv whose output another conv reads (its bias and the taps that
+  // reach back over the item's edge leave values there)
+  void mask(void* y, int L, int C) {
+    if (!pl->ragged) return;
+    const int dt = c->dt, Bn = B, sh = level(L);
+    const int* ln = pl->lens;
+    info = "mask_rows_c" + std::to_string(C) + "_L" + std::to_string(L);
+    add([=](hipStream_t s) { return launch_mask_rows(dt, y, Bn, L, C, ln, sh, s); }, false, 0, LDC_CLASS_ELEMENTWISE, 0);
   }
   int where = 0;   // stream selector for the ops being added (0 main, 1 side)
   void mark(int kind) {   // 2 = fork (side waits for main), 3 = join (main waits for side)
@@ -1485,18 +1503,20 @@ struct PlanBuilder {
     const float* cur_ss = pl->cur_ss;
     // fp8-weight context: block1's output feeds block2's conv alone, so it is produced in fp8 and that conv runs fp8 x fp8
     const bool f8 = c->w8 && c->fp8_act && r.c2_f8.w != nullptr;
+    const int* ln = lens();   // ragged plan: conv -> gn_stats -> gn_apply, statistics over the valid rows, padding rows written as zero
+    const int sh = ln ? level(L) : 0;
     void* b = f8 ? ar->alloc((size_t)rows * r.cout) : act(rows, r.cout);
     void* out = (out_mode & 1) ? ar->alloc((size_t)rows * r.cout) : act(rows, r.cout);
     float* st1 = next_stats();
     float* st2 = next_stats();
     const int cpg = r.cout / g;
-    const bool fuse_stats = c->fuse_gn_stats && cpg >= 4 && (cpg & (cpg - 1)) == 0;
+    const bool fuse_stats = !ln && c->fuse_gn_stats && cpg >= 4 && (cpg & (cpg - 1)) == 0;   // (a conv's own sums run over every row)
     const bool rowstat_wanted = want_rowstat;
     want_rowstat = false;
     last_rowstat = nullptr;
     // GroupNorm apply inside the conv epilogue (in-launch per-item wait): the tile height must not exceed twice an item's rows
     // (a tile then straddles at most three items), and the output must be in the UNet dtype (fp8 outputs keep gn_apply)
-    const bool epi_ok = c->fuse_gn_epi && cpg % 32 == 0 && r.cout % 32 == 0 && L >= c->gn_epi_min_l;
+    const bool epi_ok = !ln && c->fuse_gn_epi && cpg % 32 == 0 && r.cout % 32 == 0 && L >= c->gn_epi_min_l;
     bool epi1 = false, epi2 = false;
     GnEpi ge1, ge2;
     if (epi_ok) {
@@ -1555,14 +1575,14 @@ struct PlanBuilder {
     } else {
       if (folded) y2_next = rr;
       conv(c1, x1, x2, a, nullptr, L, L, fuse_stats ? st1 : nullptr);
-      if (!fuse_stats) add([=](hipStream_t s) { return launch_gn_stats(dt, a, Bn, L, rp->cout, g, st1, s); });
+      if (!fuse_stats) add([=](hipStream_t s) { return launch_gn_stats(dt, a, Bn, L, rp->cout, g, st1, s, ln, sh); });
       add([=](hipStream_t s) {
         return launch_gn_apply(dt, a, b, nullptr, Bn, L, rp->cout, g, st1, rp->g1, rp->b1, cur_ss + rp->ss_off,
-                               0, nullptr, ACT_SILU, s, nullptr, nullptr, f8 ? 1 : 0);
+                               0, nullptr, ACT_SILU, s, nullptr, nullptr, f8 ? 1 : 0, ln, sh);
       }, false, 0, LDC_CLASS_GN_APPLY, (f8 ? 1.5 : 2.0) * Bn * L * rp->cout * es);
     }
     void* xn = nullptr;
-    if (ln_g && xn_out && c->fuse_ln && gn_apply_ln_fusable(r.cout)) {
+    if (ln_g && xn_out && c->fuse_ln && !ln && gn_apply_ln_fusable(r.cout)) {
       xn = xn_fp8 ? ar->alloc((size_t)rows * r.cout) : act(rows, r.cout);
       *xn_out = xn;
     }
@@ -1579,11 +1599,11 @@ struct PlanBuilder {
       return out;
     }
     conv(f8 ? r.c2_f8 : r.c2, b, nullptr, d, nullptr, L, L, fuse_stats ? st2 : nullptr);
-    if (!fuse_stats) add([=](hipStream_t s) { return launch_gn_stats(dt, d, Bn, L, rp->cout, g, st2, s); });
+    if (!fuse_stats) add([=](hipStream_t s) { return launch_gn_stats(dt, d, Bn, L, rp->cout, g, st2, s, ln, sh); });
     if (r.has_res && !folded) mark(3);
     const int out8_ln = ((xn && xn_fp8) ? 2 : 0) | (gn_apply_fp8_ok(r.cout) ? out_mode : 0);
     add([=](hipStream_t s) {
-      return launch_gn_apply(dt, d, out, res, Bn, L, rp->cout, g, st2, rp->g2, rp->b2, nullptr, 0, nullptr, ACT_SILU, s, xn, ln_g, out8_ln);
+      return launch_gn_apply(dt, d, out, res, Bn, L, rp->cout, g, st2, rp->g2, rp->b2, nullptr, 0, nullptr, ACT_SILU, s, xn, ln_g, out8_ln, ln, sh);
     }, false, 0, LDC_CLASS_GN_APPLY, (xn ? 4.0 : 3.0) * Bn * L * rp->cout * es);
     return out;
   }
@@ -1591,7 +1611,7 @@ struct PlanBuilder {
   // the attention block's PreNorm can ride inside to_qkv: the folded layer exists, runs on the pipelined kernel, and the ResnetBlock
   // in front fuses its GroupNorm apply (else its gn_apply launch writes the LayerNorm output on the way at no extra launch)
   bool ln_foldable(const LinAttnW& a, int L) {
-    if (!c->fold_ln || !c->fuse_gn_epi || c->w8 || !a.qkv_ln.w || L < c->gn_epi_min_l) return false;
+    if (pl->ragged || !c->fold_ln || !c->fuse_gn_epi || c->w8 || !a.qkv_ln.w || L < c->gn_epi_min_l) return false;
     int t[4];
     conv_bm(a.qkv_ln, L, L, false, t);
     return t[0] > 0;
@@ -1610,15 +1630,18 @@ struct PlanBuilder {
     void* o = act(rows, hid);
     void* out = act(rows, a.dim);
     const LinAttnW* ap = &a;
+    const int* ln = lens();
+    const int sh = ln ? level(L) : 0;
     // one workspace per LinearAttention layer when the k column-max is fused: all of them are zeroed by the
     // step's single memset (they sit behind the GroupNorm statistics)
-    float* ws = (linear && c->fuse_kmax) ? linattn_ws + (size_t)(linattn_used++) * B * linattn_ws_floats_per_item(H, Dh) : linattn_ws;
+    // (a ragged plan too: its workspaces are cleared with the step's accumulators, so that its step graphs hold kernel nodes only)
+    float* ws = (linear && (c->fuse_kmax || ln)) ? linattn_ws + (size_t)(linattn_used++) * B * linattn_ws_floats_per_item(H, Dh) : linattn_ws;
     if (!xn_pre && !lnf)
-      add([=](hipStream_t s) { return launch_ln_rows(dt, x, xn, nullptr, ap->norm_g, rows, ap->dim, s, f8 ? 1 : 0); }, false, 0, LDC_CLASS_LAYERNORM,
+      add([=](hipStream_t s) { return launch_ln_rows(dt, x, xn, nullptr, ap->norm_g, rows, ap->dim, s, f8 ? 1 : 0, ln, sh, L); }, false, 0, LDC_CLASS_LAYERNORM,
           2.0 * rows * a.dim * es);
     if (linear) {
       const size_t wss = linattn_ws_floats_per_item(H, Dh);
-      if (c->fuse_kmax && c->fuse_attn_tail && !a.out.w8 && linattn_tail_supported(dt, H, Dh, a.dim)) {
+      if (!ln && c->fuse_kmax && c->fuse_attn_tail && !a.out.w8 && linattn_tail_supported(dt, H, Dh, a.dim)) {
         // three launches: qkv conv (+ k column max) -> context -> tail (out, to_out conv, LayerNorm, + x); round 6: TWO where to_qkv
         // accumulates the context itself (lean kernel, bf16, folded PreNorm: ConvCall::qkv_ctx_ws)
         ln_rowstat_next = rowstat;
@@ -1637,7 +1660,7 @@ struct PlanBuilder {
         }, false, 2.0 * rows * hid * dim, LDC_CLASS_LINATTN, (1.0 * hid + 2.0 * dim) * rows * es);
         return out;
       }
-      if (c->fuse_kmax) {
+      if (c->fuse_kmax && !ln) {
         ln_rowstat_next = rowstat;
         conv(qkv_ly, xn, nullptr, qkv, nullptr, L, L, nullptr, reinterpret_cast<unsigned*>(ws), hid, 2 * hid, (int)wss);
         add([=](hipStream_t s) { return launch_linattn(dt, qkv, o, ws, Bn, L, H, Dh, true, s); }, false, 0, LDC_CLASS_LINATTN,
@@ -1645,18 +1668,19 @@ struct PlanBuilder {
       } else {
         ln_rowstat_next = rowstat;
         conv(qkv_ly, xn, nullptr, qkv, nullptr, L, L);
-        add([=](hipStream_t s) { return launch_linattn(dt, qkv, o, ws, Bn, L, H, Dh, false, s); }, false, 0, LDC_CLASS_LINATTN,
+        add([=](hipStream_t s) { return launch_linattn(dt, qkv, o, ws, Bn, L, H, Dh, false, s, ln, sh, ln != nullptr); }, false, 0, LDC_CLASS_LINATTN,
             5.0 * rows * hid * es);
       }
       void* t = act(rows, a.dim);
       conv(a.out, o, nullptr, t, nullptr, L, L);
-      add([=](hipStream_t s) { return launch_ln_rows(dt, t, out, x, ap->out_g, rows, ap->dim, s); }, false, 0, LDC_CLASS_LAYERNORM,
+      add([=](hipStream_t s) { return launch_ln_rows(dt, t, out, x, ap->out_g, rows, ap->dim, s, 0, ln, sh, L); }, false, 0, LDC_CLASS_LAYERNORM,
           3.0 * rows * a.dim * es);
     } else {
       ln_rowstat_next = rowstat;
       conv(qkv_ly, xn, nullptr, qkv, nullptr, L, L);
-      add([=](hipStream_t s) { return launch_attn_full(dt, qkv, o, Bn, L, H, Dh, s); }, false, 0, LDC_CLASS_ATTN_FULL, 4.0 * rows * hid * es);
+      add([=](hipStream_t s) { return launch_attn_full(dt, qkv, o, Bn, L, H, Dh, s, ln, sh); }, false, 0, LDC_CLASS_ATTN_FULL, 4.0 * rows * hid * es);
       conv(a.out, o, nullptr, out, x, L, L);   // + x in the epilogue
+      mask(out, L, a.dim);                     // (to_out's bias)
     }
     return out;
   }
@@ -1674,7 +1698,8 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
   pl->zero_once.clear();
   const int n_gn = 2 * (int)(2 * u.downs.size() + 2 + 2 * u.ups.size() + 1);
   const size_t gn_bytes = (size_t)n_gn * B * u.groups * kGnPad * 4;
-  const size_t n_lin = c->fuse_kmax ? u.downs.size() + u.ups.size() : 1;
+  const bool lin_zeroed = c->fuse_kmax || pl->ragged;   // one LinearAttention workspace per layer, inside the region the step's first kernel clears
+  const size_t n_lin = lin_zeroed ? u.downs.size() + u.ups.size() : 1;
   const size_t lin_bytes = n_lin * B * linattn_ws_floats_per_item(u.heads, u.dim_head) * 4;
   const int sk_tiles_cap = 1024;
   const size_t part_bytes = (pl->part_bytes + 63) / 64 * 64;   // granule regions of the fused GroupNorm applies (sized by the dry planning pass)
@@ -1687,8 +1712,8 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
   pb.sk_count_cap = sk_tiles_cap;
   pb.linattn_ws = pb.stats_pool + (gn_bytes + sk_count_bytes) / 4;
   // the region the step's ONE memset clears: GroupNorm sums, split-K counters, fused k-max keys, scale_x maxima
-  float* sx_max = pb.linattn_ws + (c->fuse_kmax ? lin_bytes / 4 : 0);
-  const size_t stats_bytes = gn_bytes + sk_count_bytes + (c->fuse_kmax ? lin_bytes : 0) + sx_bytes;
+  float* sx_max = pb.linattn_ws + (lin_zeroed ? lin_bytes / 4 : 0);
+  const size_t stats_bytes = gn_bytes + sk_count_bytes + (lin_zeroed ? lin_bytes : 0) + sx_bytes;
   pb.sk_part_cap = pl->sk_floats;   // sized from the convs' own needs by a dry planning pass (get_plan)
   pb.sk_part = (float*)ar.alloc((size_t)std::max<long long>(pb.sk_part_cap, 4) * 4);
   pl->maxabs = (float*)ar.alloc((size_t)B * 4);
@@ -1699,12 +1724,23 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
   pl->x_cl = ar.alloc((size_t)B * L * Cx * es);
   pl->eps_cl = ar.alloc((size_t)B * L * Cx * es);
   pl->cond_cl = ar.alloc((size_t)B * L * Cc * es);
+  if (pl->ragged) {
+    if (c->w8) return fail(LDC_E_INVALID, "ragged batches are not available on the fp8 engine (its fused forms have no length-aware variant): use dtype bf16 or f32");
+    pl->lens = (int*)ar.alloc((size_t)B * 4);
+    pl->flens = (int*)ar.alloc((size_t)B * 4);
+  } else {
+    pl->lens = pl->flens = nullptr;
+  }
   // ---- process_cond (unet.py:407-420): fp32 upsampler, per-item max-abs, cast to the UNet dtype ----
   void* cond_in = ar.alloc((size_t)B * F * Cc * 4);
   pl->cond_in_cl = cond_in;
   {
     const void* x = cond_in;
     int Lc = F;
+    const int Bn0 = B;
+    const int *rl = pl->ragged ? pl->lens : nullptr, *rf = pl->ragged ? pl->flens : nullptr;
+    // ragged: the upsampler sees zeros behind an item's last frame (whatever the caller's padding holds) ...
+    if (rf) pl->cond_ops.push_back([=](hipStream_t s) { return launch_mask_rows(DT_F32, cond_in, Bn0, F, Cc, rf, 0, s); });
     for (const ConvLayer& ly : u.upsamplers) {
       ConvCall cc;
       cc.B = B; cc.L_in = Lc; cc.L_rows = Lc + 1; cc.L_final = Lc * ly.tr_stride; cc.y_ld = ly.tr_cout; cc.x1 = x; cc.tune = &c->tune;
@@ -1712,9 +1748,18 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
       cc.y = y;
       const ConvLayer* lp = &ly;
       pl->cond_ops.push_back([lp, cc](hipStream_t s) { return launch_conv(*lp, cc, s); });
+      // ... and EVERY layer's output is cut to the item's length: the upsampler's transposed convs are not causal (their trim is
+      // symmetric), so what a layer leaves behind an item's end (its bias) would reach back into the item through the next layer.
+      // An item's rows of a layer's output are F_b rows of (positions per frame x channels) values.  The per-item maximum below then
+      // runs over the item's own frames, and the condition is zero in the padding
+      if (rf) {
+        const int row = cc.L_final / F * ly.tr_cout;
+        pl->cond_ops.push_back([=](hipStream_t s) { return launch_mask_rows(DT_F32, y, Bn0, F, row, rf, 0, s); });
+      }
       x = y;
       Lc = cc.L_final;
     }
+    (void)rl;
     if (Lc != L) return fail(LDC_E_INVALID, "upsampled condition length %d != latent length %d (F=%d, upsampling product %d)", Lc, L, F, upsample_factor(c));
     float* mx = pl->maxabs;
     void* cond_cl = pl->cond_cl;
@@ -1765,6 +1810,7 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
   } else {
     pb.conv(u.init, in_cond, in_x, x0, nullptr, L, L);
   }
+  pb.mask(x0, L, u.dim);
   pl->taps["init"] = {x0, u.dim, L};
   const void* x = x0;
   int Lc = L;
@@ -1780,6 +1826,7 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
     if (lv.kind == 0) Ln = (Lc + 2 - 4) / 2 + 1;
     void* y = pb.act(B * Ln, lv.cout);
     pb.conv(lv.resample, x, nullptr, y, nullptr, Lc, Ln);
+    pb.mask(y, Ln, lv.cout);
     x = y; Lc = Ln;
     pl->taps["down" + std::to_string(i)] = {y, lv.cout, Lc};
   }
@@ -1803,6 +1850,7 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
     const int Ln = lv.kind == 1 ? 2 * Lc : Lc;
     void* y = pb.act(B * Ln, lv.cout);
     pb.conv(lv.resample, x, nullptr, y, nullptr, Lc, Ln);
+    pb.mask(y, Ln, lv.cout);
     x = y; Lc = Ln;
     pl->taps["up" + std::to_string(i)] = {y, lv.cout, Lc};
   }
@@ -1848,14 +1896,15 @@ static void evict_plan(ldc_ctx* c, size_t idx) {
   c->plans.erase(c->plans.begin() + idx);
 }
 
-static int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out) {
+static int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false) {
   for (auto& p : c->plans)
-    if (p->B == B && p->L == L && p->F == F && p->slot == slot) {
+    if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged) {
       p->last_use = ++c->use_tick;
       *out = p.get();
       return LDC_OK;
     }
   std::unique_ptr<Plan> pl(new Plan());
+  pl->ragged = ragged;
   {   // pass 1: what do the convs of this plan need as split-K workspace?
     Arena dry;
     LDCCHK(build_plan(c, pl.get(), dry, B, L, F));
@@ -1963,7 +2012,7 @@ static int calibrate_part_streams(ldc_ctx* c, hipStream_t s) {
   return LDC_OK;
 }
 
-static int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h) {
+static int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool ragged = false) {
   *h = Halves();
   c->call_tick = c->use_tick;   // plans touched from here on belong to the call being served (not evictable)
   // Independent chains the batch is decoded as (utterances never interact inside the UNet).  A chain is a
@@ -1975,7 +2024,7 @@ static int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h)
   for (int k = 0; k < h->n; ++k) {
     const int lo = (int)((long long)B * k / h->n), hi = (int)((long long)B * (k + 1) / h->n);
     h->b0[k] = lo;
-    LDCCHK(get_plan(c, hi - lo, L, F, k, s, &h->p[k]));
+    LDCCHK(get_plan(c, hi - lo, L, F, k, s, &h->p[k], ragged));
   }
   c->last_halves = *h;
   return LDC_OK;
@@ -2089,6 +2138,69 @@ extern "C" int ldc_unet_forward(ldc_ctx* c, const float* x, int t, const float* 
   return finish_stream(c, stream);
 }
 
+// ---- ragged batches: items of different lengths in one [B, Lmax] layout ----
+// halvings of the UNet's down path: a latent length must survive them
+static int unet_halvings(const ldc_ctx* c) {
+  int n = 0;
+  for (const LevelW& lv : c->unet.downs) n += lv.kind == 0;
+  return n;
+}
+static long long lcm_ll(long long a, long long b) {
+  long long x = a, y = b;
+  while (y) { const long long t = x % y; x = y; y = t; }
+  return a / x * b;
+}
+// latent frames an item's length must be a multiple of: whole condition frames and the halvings
+static int ragged_latent_quantum(const ldc_ctx* c) { return (int)lcm_ll(upsample_factor(c), 1ll << unet_halvings(c)); }
+// every length of a ragged call, before any GPU work: `unit` is what the lengths count (latent frames or samples)
+static int check_ragged_lengths(const int32_t* lens, int B, int maxlen, long long quantum, const char* unit) {
+  if (!lens) return fail(LDC_E_INVALID, "null lengths");
+  if (maxlen <= 0 || maxlen % quantum) return fail(LDC_E_INVALID, "the padded length %d is not a positive multiple of %lld %s", maxlen, quantum, unit);
+  for (int b = 0; b < B; ++b)
+    if (lens[b] <= 0 || lens[b] > maxlen || lens[b] % quantum)
+      return fail(LDC_E_INVALID, "length %d of item %d must be a multiple of %lld %s in (0, %d]", (int)lens[b], b, quantum, unit, maxlen);
+  return LDC_OK;
+}
+// the parts' own slices of the lengths into their plans, ordered on s (every part's stream forks from s behind it)
+static int write_plan_lens(ldc_ctx* c, const Halves& h, const std::vector<int>& lat, hipStream_t s) {
+  const int up = upsample_factor(c);
+  for (int k = 0; k < h.n; ++k) {
+    Plan* pl = h.p[k];
+    std::vector<int> fr(pl->B);
+    for (int b = 0; b < pl->B; ++b) fr[b] = lat[h.b0[k] + b] / up;
+    HIPCHK(launch_lens_write(pl->lens, lat.data() + h.b0[k], pl->B, s));
+    HIPCHK(launch_lens_write(pl->flens, fr.data(), pl->B, s));
+  }
+  return LDC_OK;
+}
+
+extern "C" int ldc_unet_forward_ragged(ldc_ctx* c, const float* x, int t, const float* cond, const int32_t* latent_lens_host, int B, int Lmax,
+                                       int Fmax, float* eps_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!x || !cond || !eps_out) return fail(LDC_E_INVALID, "null tensor");
+  if (t < 0 || t >= c->unet.timesteps) return fail(LDC_E_INVALID, "t out of range");
+  LDCCHK(check_unet_args(c, B, Lmax, Fmax));
+  LDCCHK(check_ragged_lengths(latent_lens_host, B, Lmax, ragged_latent_quantum(c), "latent frames"));
+  if (c->w8) return fail(LDC_E_INVALID, "ragged batches are not available on the fp8 engine (its fused forms have no length-aware variant): use dtype bf16 or f32");
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(get_halves(c, B, Lmax, Fmax, s, &h, true));
+  LDCCHK(write_plan_lens(c, h, std::vector<int>(latent_lens_host, latent_lens_host + B), s));
+  LDCCHK(load_cond(c, h, cond, s));
+  LDCCHK(load_x(c, h, x, s));
+  for (int k = 0; k < h.n; ++k) {
+    Plan* pl = h.p[k];
+    HIPCHK(launch_mask_rows(c->dt, pl->x_cl, pl->B, Lmax, c->unet.channels, pl->lens, 0, s));   // (whatever the caller's padding holds)
+    HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
+    HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
+    LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+    HIPCHK(launch_mask_rows(c->dt, pl->eps_cl, pl->B, Lmax, c->unet.channels, pl->lens, 0, s));   // (final_conv's bias)
+    HIPCHK(launch_from_cl(c->dt, pl->eps_cl, eps_out + (size_t)h.b0[k] * c->unet.channels * Lmax, pl->B, c->unet.channels, Lmax, nullptr,
+                          0, 0.f, s));
+  }
+  return finish_stream(c, stream);
+}
+
 extern "C" int ldc_unet_debug_tap(ldc_ctx* c, const char* name, float* out, int64_t capacity, void* stream) {
   LDCCHK(check_ready(c, LDC_MODEL_MAIN));
   if (!name || !out) return fail(LDC_E_INVALID, "null argument");
@@ -2187,10 +2299,10 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
   if (ddim)
     HIPCHK(launch_ddim_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
-                              c->unet.channels, pl->L, c->sched, ddim, pl->step_state, (uint64_t)off, s));
+                              c->unet.channels, pl->L, c->sched, ddim, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr));
   else
     HIPCHK(launch_p_sample_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
-                                  c->unet.channels, pl->L, c->sched, pl->step_state, (uint64_t)off, s));
+                                  c->unet.channels, pl->L, c->sched, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr));
   if (!c->merge_advance) HIPCHK(launch_step_advance(pl->step_state, tl, s));   // (LDC_STEP_ADVANCE_LAUNCH: the round-4 structure, for A/B runs)
   return LDC_OK;
 }
@@ -2270,9 +2382,10 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     return LDC_OK;
   }
   StepGraph* sg = nullptr;
+  const int rag = h.p[0]->ragged ? 1 : 0;   // the steps of ragged plans are graphs of their own, replayed for any set of lengths
   const int kind = ddim ? 1 : 0;   // a DDPM loop never replays a DDIM graph or the reverse; both stay cached side by side
   for (auto& g : c->graphs)
-    if (g.B == B && g.L == L && g.F == F && g.ddim == kind) sg = &g;
+    if (g.B == B && g.L == L && g.F == F && g.ddim == kind && g.ragged == rag) sg = &g;
   if (!sg) {
     // graphs of shapes whose plans are gone were dropped with them (evict_plan); additionally keep at most 16 alive
     if (c->graphs.size() >= 16) {
@@ -2285,7 +2398,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     }
     c->graphs.push_back(StepGraph());
     sg = &c->graphs.back();
-    sg->B = B; sg->L = L; sg->F = F; sg->ddim = kind;
+    sg->B = B; sg->L = L; sg->F = F; sg->ddim = kind; sg->ragged = rag;
   }
   sg->last_use = ++c->use_tick;
   const bool par = parts_parallel(c, h);
@@ -2652,8 +2765,9 @@ struct FrontSrc {
   int bits = 0, n_q = 0;
 };
 
+// rag (ldc_decode_ragged): the items' own lengths in samples (host, validated); T is then the padded length
 static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_steps, bool ddim, bool draws, const float* noise, int per_item,
-                       float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+                       float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream, const int32_t* rag = nullptr) {
   const Codec& cc = c->codec[LDC_MODEL_COND];
   const Codec& mc = c->codec[LDC_MODEL_MAIN];
   if (T % cc.hop || T % mc.hop) return fail(LDC_E_INVALID, "T must be a multiple of %d and %d (sample.py:87 trims to 640)", cc.hop, mc.hop);
@@ -2663,7 +2777,12 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
   hipStream_t s = pick_stream(c, stream);
   if (ddim) LDCCHK(ddim_upload(c, s));   // (in front of everything: the parts' streams fork from s behind it)
   Halves h;
-  LDCCHK(get_halves(c, B, L, F, s, &h));
+  LDCCHK(get_halves(c, B, L, F, s, &h, rag != nullptr));
+  std::vector<int> rag_lat, rag_fr;   // ragged: latent / condition frames per item
+  if (rag) {
+    for (int b = 0; b < B; ++b) { rag_lat.push_back(rag[b] / mc.hop); rag_fr.push_back(rag[b] / cc.hop); }
+    LDCCHK(write_plan_lens(c, h, rag_lat, s));
+  }
   // The codec front end (cond encoder -> RVQ -> upsampler -> start image) and back end (decoder) are chains of ~40 latency-bound
   // launches each (fp32 convs on a fraction of the CUs, LSTM recurrences): with per-utterance normalisation nothing couples the
   // items, so every batch part runs its own front / back end on its own stream, like its denoise steps, and the parts' chains fill
@@ -2673,6 +2792,23 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
   LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
     float* x = latents_out ? latents_out : (float*)ar.alloc((size_t)B * D * L * 4);
     float* mx = (float*)ar.alloc((size_t)B * 4);
+    // ragged: the whole batch's lengths for the codec ends (a part reads its slice), and a copy of the waveform whose padding is zero.
+    // Encoder and decoder are causal (left reflect padding, forward LSTM, transposed convs trimmed on the right), so an item's first
+    // F_b frames / T_b samples in the padded layout are what it gives alone; everything behind them is cut off below.
+    int *lens_all = nullptr, *flens_all = nullptr;
+    const float* wav_in = src.wav;
+    if (rag) {
+      lens_all = (int*)ar.alloc((size_t)B * 4);
+      flens_all = (int*)ar.alloc((size_t)B * 4);
+      float* wm = (float*)ar.alloc((size_t)B * T * 4);
+      if (!dry) {
+        HIPCHK(launch_lens_write(lens_all, rag_lat.data(), B, s));
+        HIPCHK(launch_lens_write(flens_all, rag_fr.data(), B, s));
+        HIPCHK(hipMemcpyAsync(wm, src.wav, (size_t)B * T * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(launch_mask_rows(DT_F32, wm, B, L, mc.hop, lens_all, 0, s));
+      }
+      wav_in = wm;
+    }
     if (!dry && split_ends) LDCCHK(fork_parts(c, h, s));
     const int n_front = split_ends ? h.n : 1;
     // From here to the final join the parts' streams carry work that only join_parts orders against the caller's stream (and against the
@@ -2690,7 +2826,29 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
       float* qr = nullptr;
       int Fq = 0;
       if (src.wav) {
-        LDCCHK(get_cond_rows(c, src.wav + (size_t)b0 * T, Bk, T, 0.f, ar, dry, sk, &qr, &Fq, codes_out, n_front));
+        LDCCHK(get_cond_rows(c, wav_in + (size_t)b0 * T, Bk, T, 0.f, ar, dry, sk, &qr, &Fq, codes_out, n_front));
+        // ragged: an item with no more frames than the encoder's last conv pads on the left (k - 1 = 6) is NOT a prefix of its padded
+        // self -- the reference's reflect padding falls back to zeros plus a shorter reflection when the input is that short
+        // (conv.py:81-98) -- so such an item is encoded once more on its own and its rows and codes replace the batch's
+        if (rag) {
+          const int short_max = cc.enc.empty() ? 0 : cc.enc.back().k - 1;
+          const int n_q = n_q_for_bandwidth(c, 0.f);
+          for (int b = b0; b < b0 + Bk; ++b) {
+            if (rag_fr[b] > short_max) continue;
+            float* q1 = nullptr;
+            int F1 = 0;
+            int64_t* codes1 = codes_out ? (int64_t*)ar.alloc((size_t)n_q * rag_fr[b] * 8) : nullptr;
+            LDCCHK(get_cond_rows(c, wav_in + (size_t)b * T, 1, rag[b], 0.f, ar, dry, sk, &q1, &F1, codes1, n_front));
+            if (dry) continue;
+            HIPCHK(hipMemcpyAsync(qr + (size_t)(b - b0) * F * D, q1, (size_t)F1 * D * 4, hipMemcpyDeviceToDevice, sk));
+            if (codes_out)
+              HIPCHK(hipMemcpy2DAsync(codes_out + (size_t)b * F, (size_t)B * F * 8, codes1, (size_t)F1 * 8, (size_t)F1 * 8, n_q, hipMemcpyDeviceToDevice, sk));
+          }
+        }
+        if (rag && !dry) {   // codes and condition behind an item's last frame are 0 (RVQ is per frame)
+          if (codes_out) HIPCHK(launch_mask_codes(codes_out, n_q_for_bandwidth(c, 0.f), Bk, F, flens_all + b0, sk));
+          HIPCHK(launch_mask_rows(DT_F32, qr, Bk, F, D, flens_all + b0, 0, sk));
+        }
       } else {
         qr = (float*)ar.alloc((size_t)Bk * F * D * 4);
         Fq = F;
@@ -2702,7 +2860,7 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
       // start image: upsample, /= max|.|+1e-8 (sample.py:125-129)
       void* up = nullptr;
       int Lu = 0;
-      LDCCHK(upsample_rows(c, qr, Bk, F, ar, dry, sk, &up, &Lu));
+      LDCCHK(upsample_rows(c, qr, Bk, F, ar, dry, sk, &up, &Lu, rag ? flens_all + b0 : nullptr));   // ragged: the start image is zero in the padding, its maximum the item's own
       if (dry) continue;
       if (cond_out) HIPCHK(launch_from_cl(DT_F32, qr, cond_out + (size_t)b0 * D * F, Bk, D, F, nullptr, 0, 0.f, sk));
       HIPCHK(hipMemsetAsync(mx + b0, 0, (size_t)Bk * 4, sk));
@@ -2756,7 +2914,8 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
     { const int br = back_end(); if (br != LDC_OK) return bail(br); }
     if (!dry) {
       if (split_ends) { parts_open = false; LDCCHK(join_parts(c, h, s)); }
-      HIPCHK(launch_output_normalise(wav_out, B, Lo_all, per_item ? 1 : 0, c->outnorm_ws, s));
+      if (rag && Lo_all != T) return fail(LDC_E_INVALID, "internal: decoder produced %d samples, expected %d", Lo_all, T);
+      HIPCHK(launch_output_normalise(wav_out, B, Lo_all, per_item ? 1 : 0, c->outnorm_ws, s, lens_all, mc.hop));
     }
     return LDC_OK;
   }));
@@ -2784,6 +2943,23 @@ extern "C" int ldc_decode_ddim(ldc_ctx* c, const float* wav, int B, int T, int t
   FrontSrc src;
   src.wav = wav;
   return decode_body(c, src, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
+// ldc_decode / ldc_decode_ddim on a batch of items of different lengths (right-padded to Tmax): one call, every item as if alone
+extern "C" int ldc_decode_ragged(ldc_ctx* c, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps, float eta,
+                                 const float* noise, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || B <= 0 || Tmax <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (t_start < 0) return fail(LDC_E_INVALID, "t_start must be >= 0 (0: DDPM halfway sampling)");
+  const long long quantum = lcm_ll(c->codec[LDC_MODEL_COND].hop, (long long)c->codec[LDC_MODEL_MAIN].hop << unet_halvings(c));
+  LDCCHK(check_ragged_lengths(lengths_host, B, Tmax, quantum, "samples"));
+  if (c->w8) return fail(LDC_E_INVALID, "ragged batches are not available on the fp8 engine (its fused forms have no length-aware variant): use dtype bf16 or f32");
+  bool draws = true;
+  if (t_start > 0) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  else if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_body(c, src, B, Tmax, n_steps, t_start > 0, draws, noise, 1, wav_out, latents_out, cond_out, codes_out, stream, lengths_host);
 }
 
 // the receiver side: ldc_decode / ldc_decode_ddim from RVQ codes.  The context-free refusals come first (a NULL context sees them

@@ -173,6 +173,13 @@ struct UnetW {
 
 struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells the two halves of a batch apart
   int B = 0, L = 0, F = 0, slot = 0;
+  // Ragged plan (ldc_decode_ragged / ldc_unet_forward_ragged): L and F are the batch's LONGEST item, lens / flens the B items' own latent /
+  // condition frames in device memory (written before every call, read by the kernels: one captured graph serves every set of lengths).
+  // Built from the unfused launch forms only, with the invariant that every tensor a conv reads is exactly zero at rows >= the item's
+  // length; set before build_plan
+  bool ragged = false;
+  int* lens = nullptr;          // [B] latent frames at level 0 (a level's lengths are lens[b] >> level)
+  int* flens = nullptr;         // [B] condition frames
   uint64_t last_use = 0;        // LRU tick (ldc_ctx::use_tick)
   long long sk_floats = 0;      // split-K workspace this plan's convs need (sized by a dry run of the launchers)
   long long sk_need_max = 0;
@@ -218,6 +225,7 @@ static constexpr int kKstOps = 256;   // stamp slots per step (one per op of the
 
 struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update, step_advance}
   int B = 0, L = 0, F = 0, n = 0;
+  int ragged = 0;    // (part of the cache key) the steps of ragged plans
   int ddim = 0;      // sampler kind (part of the cache key): 1 = DDIM steps (the schedule table's address is captured, not its contents)
   const float* noise = nullptr;
   float* x = nullptr;

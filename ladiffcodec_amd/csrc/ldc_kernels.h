@@ -137,7 +137,11 @@ int conv_pick_bn(int n);
 // ------------------------------------------------------------------------------------------------
 // GroupNorm statistics of x [B][L][C]: stats[b][g] = (sum, sumsq) accumulated with fp32 atomics into a
 // pre-zeroed buffer.
-hipError_t launch_gn_stats(int dt, const void* x, int B, int L, int C, int groups, float* stats, hipStream_t s);
+// Ragged batches (every launcher below that takes `lens`): a device array of B lengths in rows of level 0; an item's valid rows at this
+// tensor's level are lens[b] >> shift, the rows behind them are padding -- left out of every reduction, written as exact zeros, always
+// by a select (a NaN in a padding row never reaches a valid one).  lens == null: every row is valid (the equal-length plans).
+hipError_t launch_gn_stats(int dt, const void* x, int B, int L, int C, int groups, float* stats, hipStream_t s, const int* lens = nullptr,
+                           int shift = 0);
 // y = act( GN(x)*(scale+1)+shift ) (+ residual).  scale_shift: fp32 [2*C] (scale then shift) selected
 // by *t_ptr from a table with row stride ss_stride, or null.  eps 1e-5.
 // out8 bit 0: y is written as OCP fp8 e4m3 ([rows][C] bytes, saturating) instead of dt; bit 1: the same for y_ln; bit 2: y = tanh(y)
@@ -145,12 +149,15 @@ hipError_t launch_gn_stats(int dt, const void* x, int B, int L, int C, int group
 // conv path: a tensor whose only consumer is a conv is produced in the conv's input type.)
 hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual, int B, int L, int C, int groups,
                            const float* stats, const float* gamma, const float* beta, const float* ss_table,
-                           int ss_stride, const int* t_ptr, int act, hipStream_t s, void* y_ln = nullptr, const float* ln_g = nullptr, int out8 = 0);
+                           int ss_stride, const int* t_ptr, int act, hipStream_t s, void* y_ln = nullptr, const float* ln_g = nullptr, int out8 = 0,
+                           const int* lens = nullptr, int shift = 0);
 // y_ln != null: also write channel-LayerNorm(y) * ln_g (needs gn_apply_ln_fusable(C) and ACT_SILU)
 bool gn_apply_ln_fusable(int C);
 // channel LayerNorm (gain only, biased var, eps 1e-5) per row; y = LN(x)*g (+ residual)
 hipError_t launch_ln_rows(int dt, const void* x, void* y, const void* residual, const float* g, int rows, int C,
-                          hipStream_t s, int out8 = 0);
+                          hipStream_t s, int out8 = 0, const int* lens = nullptr, int shift = 0, int L = 0);   // lens: rows = B * L
+// x [B][L][C]: rows l >= lens[b] >> shift of every item are written as zero (stores only: the padding is never read)
+hipError_t launch_mask_rows(int dt, void* x, int B, int L, int C, const int* lens, int shift, hipStream_t s);
 // elementwise tanh in place / out of place
 hipError_t launch_act(int dt, const void* x, void* y, int64_t n, int act, hipStream_t s, int out8 = 0);
 
@@ -159,14 +166,16 @@ hipError_t launch_act(int dt, const void* x, void* y, int64_t n, int act, hipStr
 // ------------------------------------------------------------------------------------------------
 // qkv [B*L][3*H*D] (q | k | v, head-major).  ctx_ws: fp32 [B][H][D][D].
 hipError_t launch_linattn(int dt, const void* qkv, void* out, float* ctx_ws, int B, int L, int heads, int dim_head,
-                          bool kmax_fused, hipStream_t s);
+                          bool kmax_fused, hipStream_t s, const int* lens = nullptr, int shift = 0, bool ws_zeroed = false);
+// lens: needs !kmax_fused (its own column-max pass).  ws_zeroed: the caller cleared `ws` (no memset here: the column-max pass still runs)
 size_t linattn_ws_floats_per_item(int heads, int dim_head);
 // LinearAttention in three launches (bf16 engine): qkv conv (+ k column max) -> context -> tail (out + to_out conv + LayerNorm + residual)
 bool linattn_tail_supported(int dt, int heads, int dim_head, int C);
 hipError_t launch_linattn_ctx(int dt, const void* qkv, float* ctx_ws, int B, int L, int heads, int dim_head, hipStream_t s);
 hipError_t launch_linattn_tail(int dt, const void* qkv, const float* ctx_ws, const void* wo_packed, int n_pad, const float* bias, const float* gain,
                                const void* resid, void* out, int B, int L, int heads, int dim_head, int C, unsigned* fail_flag, hipStream_t s);
-hipError_t launch_linattn_kmax(int dt, const void* qkv, float* ctx_ws, int B, int L, int heads, int dim_head, hipStream_t s);
+hipError_t launch_linattn_kmax(int dt, const void* qkv, float* ctx_ws, int B, int L, int heads, int dim_head, hipStream_t s,
+                               const int* lens = nullptr, int shift = 0);
 // The context fold (ConvCall::qkv_ctx_ws) takes exp(min(k, kLinattnKClamp)) without a shift.  It agrees with the shifted kernels while
 // every column's sum of exp(k) lies in [kLinattnKsumMin, kLinattnKsumMax): above the floor every term within 2^-24 of the column's largest
 // is a normal number in fp32 and bf16 (a column maximum above about -69 - ln L); below the ceiling no entry was clamped (one clamped entry
@@ -177,7 +186,8 @@ constexpr float kLinattnKClamp = 60.0f;
 constexpr float kLinattnKsumMin = 7.888609052210118e-31f;   // 2^-100
 constexpr float kLinattnKsumMax = 1.0e26f;
 constexpr unsigned kDevFailCtxRange = 4u;   // (3 is LDC_DEV_BAD_CODE)
-hipError_t launch_attn_full(int dt, const void* qkv, void* out, int B, int L, int heads, int dim_head, hipStream_t s);
+hipError_t launch_attn_full(int dt, const void* qkv, void* out, int B, int L, int heads, int dim_head, hipStream_t s, const int* lens = nullptr,
+                            int shift = 0);
 
 // ------------------------------------------------------------------------------------------------
 // diffusion.hip
@@ -208,7 +218,7 @@ hipError_t launch_random_fill(float* x, int64_t n, int uniform, uint64_t seed, u
 hipError_t launch_axpby(float* x, const float* y, float a, float b, int64_t n, hipStream_t s);
 hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                                   void* x_cl, int B, int C, int L, StepTables tb, const int* st,
-                                  uint64_t elem_base, hipStream_t s);
+                                  uint64_t elem_base, hipStream_t s, const int* lens = nullptr);   // lens [B] (positions): x and x_cl stay zero behind them
 // One iteration of DDIM sampling (reference ddpm_loss.py ddim_sample, clip_denoised): the host fills one entry per
 // iteration j (ldc_api.cpp: ddim_schedule) into a device table that the step state indexes.
 struct DdimStep {
@@ -225,7 +235,7 @@ struct DdimStep {
 hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src_host, int n, hipStream_t s);   // dst[0..n) = src_host[0..n), stream-ordered
 hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                               void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
-                              uint64_t elem_base, hipStream_t s);
+                              uint64_t elem_base, hipStream_t s, const int* lens = nullptr);
 // x /= (maxabs[b or 0] + eps) in place on a raw element stream (n_per_item elements per item)
 hipError_t launch_scale_by_maxabs(int dt, void* x, int B, int64_t n_per_item, const float* maxabs, int per_item,
                                   float eps, hipStream_t s);
@@ -246,7 +256,13 @@ hipError_t launch_step_set(int* st, int t, int j, uint64_t noise_key, hipStream_
 hipError_t launch_clock_sample(unsigned long long* out2, hipStream_t s);   // out2[0] = 100 MHz wall clock, out2[1] = s_memtime (shader cycles)
 hipError_t launch_spin_us(unsigned us, hipStream_t s);   // one workgroup busy for `us` microseconds (stream-overlap calibration)
 // output normalisation (sample.py:133-134); ws: double [B][2] + float [B] zeroed by the launcher
-hipError_t launch_output_normalise(float* x, int B, int64_t n_per_item, int per_item, void* ws, hipStream_t s);
+// lens (needs per_item): item b has lens[b] * lens_unit samples; statistics over those, the tail is written as zero
+hipError_t launch_output_normalise(float* x, int B, int64_t n_per_item, int per_item, void* ws, hipStream_t s, const int* lens = nullptr,
+                                   int lens_unit = 1);
+// dst[0..n) = src_host[0..n), stream-ordered (the values travel as kernel arguments: no host buffer outlives the call)
+hipError_t launch_lens_write(int* dst, const int* src_host, int n, hipStream_t s);
+// RVQ codes [n_q][B][F] int64 of a ragged batch: frames f >= flens[b] are written as 0
+hipError_t launch_mask_codes(int64_t* codes, int n_q, int B, int F, const int* flens, hipStream_t s);
 size_t output_normalise_ws_bytes(int B);
 
 // ------------------------------------------------------------------------------------------------

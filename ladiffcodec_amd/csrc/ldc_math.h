@@ -32,4 +32,9 @@ __device__ __forceinline__ float fast_tanh(float v) {
   return copysignf(t, v);
 }
 
+// Ragged batches ([B][Lmax][C] with a length per item): rows an item really has at the level whose lengths are
+// lens[b] >> shift; lens == null: every row (the equal-length plans).  Rows beyond it are the item's padding: reductions skip them
+// and outputs are written as zero there, always by a select, so that nothing a padding row holds (NaN, Inf) reaches a valid one.
+__device__ __forceinline__ int valid_rows(const int* lens, int shift, int b, int L) { return lens ? min(L, lens[b] >> shift) : L; }
+
 }  // namespace ldc

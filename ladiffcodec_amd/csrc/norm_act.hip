@@ -93,10 +93,12 @@ __device__ __forceinline__ void store8_fp8(void* y, size_t off, const float* o) 
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const void* x, int L, int C, int groups, int rows_per_block,
-                                                       float* stats) {
+                                                       float* stats, const int* lens, int shift) {
   __shared__ float red[2][64];   // up to 64 groups
   const int b = blockIdx.y;
-  const int r0 = blockIdx.x * rows_per_block, r1 = min(L, r0 + rows_per_block);
+  const int Lv = valid_rows(lens, shift, b, L);   // ragged batch: sums over the item's valid rows only
+  const int r0 = blockIdx.x * rows_per_block, r1 = min(Lv, r0 + rows_per_block);
+  if (r0 >= r1) return;
   const int vec_per_row = C / 8;
   const int tid = threadIdx.x;
   if (tid < 64) { red[0][tid] = 0.f; red[1][tid] = 0.f; }
@@ -136,16 +138,16 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const void* x, int L, int
   }
 }
 
-hipError_t launch_gn_stats(int dt, const void* x, int B, int L, int C, int groups, float* stats, hipStream_t s) {
+hipError_t launch_gn_stats(int dt, const void* x, int B, int L, int C, int groups, float* stats, hipStream_t s, const int* lens, int shift) {
   if (groups > 64 || C % 8 || C % groups) return hipErrorInvalidValue;
   // ~64 KB of data per block
   int rows_per_block = (int)std::max<size_t>(1, (64 * 1024) / ((size_t)C * dt_size(dt)));
   // keep the 256-thread flat walk aligned so that a thread stays in one vec column when possible
   dim3 grid((L + rows_per_block - 1) / rows_per_block, B);
   if (dt == DT_F32)
-    hipLaunchKernelGGL(gn_stats_kernel<float>, grid, dim3(256), 0, s, x, L, C, groups, rows_per_block, stats);
+    hipLaunchKernelGGL(gn_stats_kernel<float>, grid, dim3(256), 0, s, x, L, C, groups, rows_per_block, stats, lens, shift);
   else
-    hipLaunchKernelGGL(gn_stats_kernel<__bf16>, grid, dim3(256), 0, s, x, L, C, groups, rows_per_block, stats);
+    hipLaunchKernelGGL(gn_stats_kernel<__bf16>, grid, dim3(256), 0, s, x, L, C, groups, rows_per_block, stats, lens, shift);
   return hipGetLastError();
 }
 
@@ -156,17 +158,18 @@ template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const void* x, void* y, const void* residual, int B, int L, int C,
                                                        int groups, const float* stats, const float* gamma,
                                                        const float* beta, const float* ss_table, int ss_stride,
-                                                       const int* t_ptr, int act) {
+                                                       const int* t_ptr, int act, const int* lens, int shift) {
   const int vec_per_row = C / 8;
   const size_t total = (size_t)B * L * vec_per_row;
   const int cpg = C / groups;
-  const float inv_n = 1.0f / ((float)L * (float)cpg);
   const float* ss = nullptr;
   if (ss_table) ss = ss_table + (size_t)(t_ptr ? *t_ptr : 0) * ss_stride;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
     const size_t row = idx / vec_per_row;
     const int v = (int)(idx - row * vec_per_row);
     const int b = (int)(row / L);
+    const int Lv = valid_rows(lens, shift, b, L);
+    const float inv_n = 1.0f / ((float)Lv * (float)cpg);
     float f[8], o[8];
     Vec8<T>::load(x, row * C + v * 8, f);
 #pragma unroll
@@ -187,6 +190,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const void* x, void* y, c
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] += r[i];
     }
+    if ((int)(row - (size_t)b * L) >= Lv) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = 0.f;
+    }
     Vec8<T>::store(y, row * C + v * 8, o);
   }
 }
@@ -202,7 +209,7 @@ __global__ __launch_bounds__(256) void gn_apply_cols_kernel(const void* x, void*
                                                             int groups, int rows_per_block, const float* stats,
                                                             const float* gamma, const float* beta, const float* ss_table,
                                                             int ss_stride, const int* t_ptr, int act, int dbg,
-                                                            void* y_ln, const float* ln_g, int out8) {
+                                                            void* y_ln, const float* ln_g, int out8, const int* lens, int shift) {
   __shared__ __attribute__((aligned(16))) float s_a[2048];
   __shared__ __attribute__((aligned(16))) float s_b[2048];
   __shared__ float s_red[LN ? 2 * 4 * 8 : 1];   // [sum | sumsq][wave][q]
@@ -224,7 +231,8 @@ __global__ __launch_bounds__(256) void gn_apply_cols_kernel(const void* x, void*
   }
   // 2. per-channel affine of this item, once per workgroup
   const int cpg = C / groups;
-  const float inv_n = 1.0f / ((float)L * (float)cpg);
+  const int Lv = valid_rows(lens, shift, b, L);   // (the statistics were summed over Lv rows)
+  const float inv_n = 1.0f / ((float)Lv * (float)cpg);
   const float* ss = nullptr;
   if (ss_table) ss = ss_table + (size_t)(t_ptr ? *t_ptr : 0) * ss_stride;
   for (int c = threadIdx.x; c < C; c += 256) {
@@ -271,6 +279,10 @@ __global__ __launch_bounds__(256) void gn_apply_cols_kernel(const void* x, void*
       if (out8 & 4) {   // tanh of the block's output (unet.py:467: the final ResnetBlock feeds torch.tanh alone)
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = act_f(o[i], ACT_TANH);
+      }
+      if (r >= Lv) {   // a padding row of a ragged batch
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = 0.f;
       }
       if (out8 & 1) store8_fp8(y, ((size_t)b * L + r) * C + v * 8, o);
       else if (dbg & 8) Vec8<T>::store_nt(y, ((size_t)b * L + r) * C + v * 8, o);
@@ -336,7 +348,7 @@ __global__ __launch_bounds__(256) void gn_apply_cols_kernel(const void* x, void*
         const float rstd = rsqrtf(lsum[q] + 1e-5f);
         float o[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (f[q][i] - mean[q]) * rstd * g8[i];
+        for (int i = 0; i < 8; ++i) o[i] = r < Lv ? (f[q][i] - mean[q]) * rstd * g8[i] : 0.f;
         if (out8 & 2) store8_fp8(y_ln, ((size_t)b * L + r) * C + v * 8, o);
         else Vec8<T>::store(y_ln, ((size_t)b * L + r) * C + v * 8, o);
       }
@@ -360,17 +372,17 @@ static int gn_pick_u(int B, int L, int vpr) {
 template <typename T, int ACT, bool LN, int VPR>
 static void gn_launch_u(int U, dim3 grid, hipStream_t s, const void* x, void* y, const void* residual, int L, int C, int groups, int rpb,
                         const float* stats, const float* gamma, const float* beta, const float* ss_table, int ss_stride,
-                        const int* t_ptr, int act, int dbg, void* y_ln, const float* ln_g, int out8) {
+                        const int* t_ptr, int act, int dbg, void* y_ln, const float* ln_g, int out8, const int* lens, int shift) {
 #define LDC_GN_GO(UU)                                                                                                     \
   hipLaunchKernelGGL((gn_apply_cols_kernel<T, ACT, LN, VPR, UU>), grid, dim3(256), 0, s, x, y, residual, L, C, groups, rpb, \
-                     stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8)
+                     stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8, lens, shift)
   if (U == 8) LDC_GN_GO(8); else if (U == 4) LDC_GN_GO(4); else if (U == 2) LDC_GN_GO(2); else LDC_GN_GO(1);
 #undef LDC_GN_GO
 }
 
 hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual, int B, int L, int C, int groups,
                            const float* stats, const float* gamma, const float* beta, const float* ss_table,
-                           int ss_stride, const int* t_ptr, int act, hipStream_t s, void* y_ln, const float* ln_g, int out8) {
+                           int ss_stride, const int* t_ptr, int act, hipStream_t s, void* y_ln, const float* ln_g, int out8, const int* lens, int shift) {
   const int vpr = C / 8;
   if (y_ln && (!gn_apply_ln_fusable(C) || act != ACT_SILU)) return hipErrorInvalidValue;
   if (C % 8 == 0 && vpr <= 256 && 256 % vpr == 0 && C <= 2048) {
@@ -378,7 +390,7 @@ hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual,
     const int rpb = (256 / vpr) * U;   // one U-row trip per thread
     const int dbg = 0;
     dim3 grid((L + rpb - 1) / rpb, B);
-#define LDC_GN_ARGS grid, s, x, y, residual, L, C, groups, rpb, stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8
+#define LDC_GN_ARGS grid, s, x, y, residual, L, C, groups, rpb, stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8, lens, shift
     if (y_ln) {
       if (dt == DT_F32) {
         if (vpr == 32) gn_launch_u<float, ACT_SILU, true, 32>(U, LDC_GN_ARGS);
@@ -402,10 +414,10 @@ hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual,
   if (blocks < 1) blocks = 1;
   if (dt == DT_F32)
     hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(blocks), dim3(256), 0, s, x, y, residual, B, L, C, groups, stats,
-                       gamma, beta, ss_table, ss_stride, t_ptr, act);
+                       gamma, beta, ss_table, ss_stride, t_ptr, act, lens, shift);
   else
     hipLaunchKernelGGL(gn_apply_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, x, y, residual, B, L, C, groups, stats,
-                       gamma, beta, ss_table, ss_stride, t_ptr, act);
+                       gamma, beta, ss_table, ss_stride, t_ptr, act, lens, shift);
   return hipGetLastError();
 }
 
@@ -414,12 +426,13 @@ hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual,
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void ln_rows_kernel(const void* x, void* y, const void* residual, const float* g,
-                                                      int rows, int C) {
+                                                      int rows, int C, const int* lens, int shift, int L) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * 256) >> 6;
   const int vec_per_row = C / 8;
   for (int row = wave; row < rows; row += nwaves) {
+    const bool live = !lens || row % L < (lens[row / L] >> shift);   // ragged batch (rows = B * L): padding rows are written as zero
     float s = 0.f;
     // pass 1: mean
     for (int v = lane; v < vec_per_row; v += 64) {
@@ -453,6 +466,10 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const void* x, void* y, co
 #pragma unroll
         for (int i = 0; i < 8; ++i) o8[i] += r[i];
       }
+      if (!live) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o8[i] = 0.f;
+      }
       Vec8<T>::store(y, (size_t)row * C + v * 8, o8);
     }
   }
@@ -461,10 +478,11 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const void* x, void* y, co
 // Row held in registers (C <= 512 * NV): one global read, two-pass statistics on the registers, one write.
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void ln_rows_reg_kernel(const void* x, void* y, const void* residual, const float* g,
-                                                          int rows, int C, int out8) {
+                                                          int rows, int C, int out8, const int* lens, int shift, int L) {
   const int lane = threadIdx.x & 63;
   const int row = (blockIdx.x * 256 + threadIdx.x) >> 6;
   if (row >= rows) return;
+  const bool live = !lens || row % L < (lens[row / L] >> shift);   // ragged batch (rows = B * L): padding rows are written as zero
   const int vec_per_row = C / 8;
   float f[NV][8], r[NV][8];
   float s = 0.f;
@@ -503,6 +521,10 @@ __global__ __launch_bounds__(256) void ln_rows_reg_kernel(const void* x, void* y
 #pragma unroll
         for (int i = 0; i < 8; ++i) o8[i] += r[k][i];
       }
+      if (!live) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o8[i] = 0.f;
+      }
       if (out8) store8_fp8(y, (size_t)row * C + v * 8, o8);
       else Vec8<T>::store(y, (size_t)row * C + v * 8, o8);
     }
@@ -510,25 +532,25 @@ __global__ __launch_bounds__(256) void ln_rows_reg_kernel(const void* x, void* y
 }
 
 hipError_t launch_ln_rows(int dt, const void* x, void* y, const void* residual, const float* g, int rows, int C,
-                          hipStream_t s, int out8) {
-  if (C % 8 || (out8 && C > 1024)) return hipErrorInvalidValue;
+                          hipStream_t s, int out8, const int* lens, int shift, int L) {
+  if (C % 8 || (out8 && C > 1024) || (lens && (L <= 0 || rows % L))) return hipErrorInvalidValue;
   if (C <= 1024) {
     const int nb = (rows + 3) / 4;
     if (dt == DT_F32) {
-      if (C <= 512) hipLaunchKernelGGL((ln_rows_reg_kernel<float, 1>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8);
-      else hipLaunchKernelGGL((ln_rows_reg_kernel<float, 2>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8);
+      if (C <= 512) hipLaunchKernelGGL((ln_rows_reg_kernel<float, 1>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8, lens, shift, L);
+      else hipLaunchKernelGGL((ln_rows_reg_kernel<float, 2>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8, lens, shift, L);
     } else {
-      if (C <= 512) hipLaunchKernelGGL((ln_rows_reg_kernel<__bf16, 1>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8);
-      else hipLaunchKernelGGL((ln_rows_reg_kernel<__bf16, 2>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8);
+      if (C <= 512) hipLaunchKernelGGL((ln_rows_reg_kernel<__bf16, 1>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8, lens, shift, L);
+      else hipLaunchKernelGGL((ln_rows_reg_kernel<__bf16, 2>), dim3(nb), dim3(256), 0, s, x, y, residual, g, rows, C, out8, lens, shift, L);
     }
     return hipGetLastError();
   }
   int blocks = std::min((rows + 3) / 4, 256 * 8);
   if (blocks < 1) blocks = 1;
   if (dt == DT_F32)
-    hipLaunchKernelGGL(ln_rows_kernel<float>, dim3(blocks), dim3(256), 0, s, x, y, residual, g, rows, C);
+    hipLaunchKernelGGL(ln_rows_kernel<float>, dim3(blocks), dim3(256), 0, s, x, y, residual, g, rows, C, lens, shift, L);
   else
-    hipLaunchKernelGGL(ln_rows_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, x, y, residual, g, rows, C);
+    hipLaunchKernelGGL(ln_rows_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, x, y, residual, g, rows, C, lens, shift, L);
   return hipGetLastError();
 }
 

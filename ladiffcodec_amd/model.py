@@ -407,6 +407,52 @@ class Engine:
             return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
         return out
 
+    @staticmethod
+    def _lengths(lengths, B: int):
+        arr = (C.c_int32 * B)(*[int(v) for v in lengths])
+        if len(lengths) != B:
+            raise ValueError(f"{len(lengths)} lengths for a batch of {B}")
+        return arr
+
+    def decode_ragged(self, wav, lengths, n_steps: int, t_start: int = 0, eta: float = 0.0, noise=None, want_stages: bool = False):
+        """`decode` (t_start 0) / `decode_ddim` (t_start > 0) of items of different lengths in one call: wav [B, 1, Tmax] right-padded,
+        lengths[b] samples of item b (multiples of the chunk quantum, sample.chunk_quantum).  Every item comes out as if decoded
+        alone (per-item normalisation); item b consumes noise[:, b, :, :L_b]; outputs are zero beyond an item's length."""
+        wav = self._f32(wav)
+        B, _, T = wav.shape
+        F, Lz = T // self.cond_codec.hop_length, T // self.main_codec.hop_length
+        lens = self._lengths(list(lengths), B)
+        out = self._empty(B, 1, T)
+        lat = self._empty(B, self.main_codec.rep_dims, Lz) if want_stages else None
+        cond = self._empty(B, self.main_codec.rep_dims, F) if want_stages else None
+        n_q = self.cond_codec.n_q_for_bandwidth(None)
+        codes = self._empty(n_q, B, F, dtype=self.torch.int64) if want_stages else None
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        try:
+            L.check(self.lib.ldc_decode_ragged(self._ctx, wav.data_ptr(), lens, B, T, int(t_start), int(n_steps), float(eta), p(noise),
+                                               out.data_ptr(), p(lat), p(cond), p(codes), s))
+        finally:
+            self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
+        return out
+
+    def unet_forward_ragged(self, x, t: int, cond, latent_lens):
+        """`unet_forward` with per-item latent lengths: x [B, C, Lmax], cond [B, C, Fmax]; eps is zero beyond an item's length."""
+        x, cond = self._f32(x), self._f32(cond)
+        B, Cx, Lx = x.shape
+        lens = self._lengths(list(latent_lens), B)
+        eps = self._empty(B, Cx, Lx)
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_unet_forward_ragged(self._ctx, x.data_ptr(), int(t), cond.data_ptr(), lens, B, Lx, cond.shape[2],
+                                                     eps.data_ptr(), s))
+        finally:
+            self._exit()
+        return eps
+
     def _codes_args(self, codes, packed, bits, n_q, F):
         """-> (codes ptr, packed ptr, packed stride, n_q, B, F, kept tensors) for ldc_decode_codes*"""
         t = self.torch

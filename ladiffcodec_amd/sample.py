@@ -9,6 +9,8 @@ Same flags, defaults and output naming as the reference.  What differs, by desig
   * `midway_t` (a literal 100 at sample.py:69) is a flag, `--midway_t`, default 100;
   * `--seed` (default 0) seeds the device noise stream (rank r uses seed + r); every decode call draws fresh noise,
     as torch.randn_like does in the reference (ddpm_loss.py:249);
+  * `--ragged` batches mono files of DIFFERENT lengths (plan_ragged_batches, Engine.decode_ragged): every file is still decoded
+    as if alone, but trimmed to the chunk quantum (2560 samples for `--enc_ratios 8 4`) instead of the reference's 640;
   * under `torch.distributed.run` the FILE list is sharded over the ranks (one process per GPU; all channels of a
     file stay on one rank, every output file has exactly one writer).
 Flags that are inert in the reference stay accepted and inert (`--sampling_timesteps`,
@@ -77,6 +79,13 @@ _EXTRA: List[Tuple[str, dict]] = [
     ("--chunk_sec", dict(type=float, default=0.0, help="long-form mode (BASELINE config 5): mono recordings longer than this are "
                                                         "decoded as chunks of this length batched together, the chunks' raw decoder "
                                                         "outputs are joined and normalised over the whole recording; 0 = whole files")),
+    # (both absent from the namespace unless given -- argparse.SUPPRESS -- so a run without them carries exactly the arguments it carried
+    # before they existed; ragged_options() reads them with their defaults: off, 0.25)
+    ("--ragged", dict(dest="ragged", action="store_true", default=argparse.SUPPRESS,
+                      help="batch mono files of DIFFERENT lengths (Engine.decode_ragged: every file decoded as if alone); files are "
+                           "trimmed to the chunk quantum (2560 samples for --enc_ratios 8 4, coarser than the reference's 640)")),
+    ("--ragged_waste", dict(type=float, default=argparse.SUPPRESS, help="--ragged: a batch is closed before its padded size B * Tmax "
+                                                                        "exceeds (1 + this) x the samples it really holds (default 0.25)")),
 ]
 
 
@@ -85,6 +94,11 @@ def build_parser() -> argparse.ArgumentParser:
     for flag, kw in _FLAGS + _EXTRA:
         p.add_argument(flag, **kw)
     return p
+
+
+def ragged_options(a) -> Tuple[bool, float]:
+    """(--ragged, --ragged_waste) of a parsed namespace, with their defaults: off, 0.25."""
+    return bool(getattr(a, "ragged", False)), float(getattr(a, "ragged_waste", 0.25))
 
 
 def _unsupported(a) -> None:
@@ -218,6 +232,14 @@ class LazyWavs:
             return torch.from_numpy(np.ascontiguousarray(self[idxs[0]][:, None, :n]))
         return torch.from_numpy(np.stack([self[i][0, :n] for i in idxs])[:, None, :])
 
+    def padded_batch(self, idxs: List[int], lens: List[int]):
+        """[len(idxs), 1, max(lens)]: the first lens[k] samples of mono file idxs[k], zero-padded on the right (a ragged batch)."""
+        import torch
+        out = np.zeros((len(idxs), 1, max(lens)), np.float32)
+        for k, (i, n) in enumerate(zip(idxs, lens)):
+            out[k, 0, :n] = self[i][0, :n]
+        return torch.from_numpy(out)
+
     def chunk_batch(self, part: List[Tuple[int, int, int]], ln: int):
         """[len(part), 1, ln]: chunk (file, order, start) of mono recordings."""
         import torch
@@ -232,6 +254,18 @@ def output_path(wav_file: str, input_dir: str, output_dir: str, in_ext: str = ".
     return os.path.join(output_dir, f"{save_path}{out_ext}")
 
 
+class RaggedBatch:
+    """Mono files of different lengths as one engine call: wav [B, 1, Tmax] right-padded with zeros, lengths[b] samples of item b
+    (multiples of the chunk quantum).  `.to(device)` as a tensor batch (see CodesBatch); the samplers route it to
+    Engine.decode_ragged, whose outputs are zero behind an item's length."""
+
+    def __init__(self, wav, lengths):
+        self.wav, self.lengths = wav, [int(n) for n in lengths]
+
+    def to(self, device, non_blocking: bool = False):
+        return RaggedBatch(self.wav.to(device, non_blocking=non_blocking), self.lengths)
+
+
 class DdpmSampler:
     """The reference's decode: halfway sampling, `n_steps` ancestral steps (Engine.decode).  `draws`: noise tensors per call."""
 
@@ -239,6 +273,8 @@ class DdpmSampler:
         self.n_steps = self.draws = int(n_steps)
 
     def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        if isinstance(batch, RaggedBatch):
+            return eng.decode_ragged(batch.wav, batch.lengths, self.n_steps, noise=noise, want_stages=want_stages)
         if want_stages:
             return eng.decode(batch, self.n_steps, noise=noise, per_item=per_item, want_stages=True)
         return eng.decode(batch, self.n_steps, noise=noise, per_item=per_item)
@@ -252,6 +288,9 @@ class DdimSampler:
         self.draws = self.n_steps
 
     def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        if isinstance(batch, RaggedBatch):
+            return eng.decode_ragged(batch.wav, batch.lengths, self.n_steps, t_start=self.t_start, eta=self.eta, noise=noise,
+                                     want_stages=want_stages)
         return eng.decode_ddim(batch, self.t_start, self.n_steps, self.eta, noise=noise, per_item=per_item, want_stages=want_stages)
 
 
@@ -388,6 +427,44 @@ def plan_batches(lengths: List[int], channels: List[int], rank: int, world: int,
     return work
 
 
+def plan_ragged_batches(lengths: List[int], channels: List[int], rank: int, world: int, batch_size: int, waste: float,
+                        quantum: int) -> List[Tuple[List[int], bool]]:
+    """plan_batches for --ragged: the rank's mono files, trimmed to whole quanta and sorted by that length (longest first), are packed
+    greedily into batches of at most batch_size files; a batch is closed before its padded size B * Tmax would exceed (1 + waste) x
+    the samples it holds.  Multi-channel files keep their joint single-file batches; mono files shorter than one quantum (nothing of
+    them survives the trim) keep plan_batches' equal-length batches and the reference's 640-sample trim."""
+    from . import parallel
+    mine = parallel.shard_utterances(lengths, rank, world)
+    work: List[Tuple[List[int], bool]] = []
+    short: Dict[int, List[int]] = {}
+    mono: List[Tuple[int, int]] = []
+    for i in mine:
+        if channels[i] > 1:
+            work.append(([i], True))
+        elif lengths[i] // quantum == 0:
+            short.setdefault(lengths[i] // 640 * 640, []).append(i)
+        else:
+            mono.append((lengths[i] // quantum * quantum, i))
+    mono.sort(key=lambda t: (-t[0], t[1]))
+    cur: List[int] = []
+    tmax = held = 0
+    for n, i in mono:
+        if cur and (len(cur) == batch_size or (len(cur) + 1) * tmax > (1.0 + waste) * (held + n)):
+            work.append((cur, False))
+            cur = []
+        if not cur:
+            tmax = held = 0
+        cur.append(i)
+        tmax = max(tmax, n)
+        held += n
+    if cur:
+        work.append((cur, False))
+    for _, idxs in sorted(short.items(), reverse=True):
+        for s in range(0, len(idxs), batch_size):
+            work.append((idxs[s:s + batch_size], False))
+    return work
+
+
 _CHUNK_QUANTUM = 2560     # default quantum (enc_ratios 8 4): see chunk_quantum
 
 
@@ -487,11 +564,13 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
     written = []
     dev = torch.device("cuda", local_rank)
     streams = [torch.cuda.Stream(device=dev) for _ in engines] if len(engines) > 1 else [None]
-    pending: List[tuple] = []                 # (output tensor on the device, file indices, joint, stream, redo), oldest first
+    pending: List[tuple] = []                 # (output tensor on the device, file indices, joint, stream, redo, lengths | None), oldest first
+    ragged, ragged_waste = ragged_options(inp_args)
+    quantum = chunk_quantum(getattr(inp_args, "enc_ratios", [8, 4]))
     hop = int(np.prod(getattr(inp_args, "enc_ratios", [8])))   # samples per latent frame of the main codec (noise seam only)
 
     def retire(item):
-        out, idxs, joint, stream, redo = item
+        out, idxs, joint, stream, redo, lens = item
         if stream is not None:
             stream.synchronize()               # the producer stream, not the current one: waits for that engine's batch only
         out = out.cpu()
@@ -513,12 +592,24 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
             path = output_path(files[i], inp_args.input_dir, inp_args.output_dir, wavs.in_ext)
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             data = out[:, 0, :].T if joint else out[k, 0]                                     # [T, channels] | [T]
+            if lens is not None:
+                data = data[:lens[k]]                                                          # ragged batch: the item's own samples
             wavfile.write(path, 16000, np.ascontiguousarray(data))
             written.append(path)
 
-    for j, (idxs, joint) in enumerate(plan_batches(lengths, channels, rank, world, inp_args.batch_size)):
-        n = lengths[idxs[0]] // 640 * 640
-        batch = wavs.batch(idxs, joint, n)
+    if ragged:
+        work = plan_ragged_batches(lengths, channels, rank, world, inp_args.batch_size, ragged_waste, quantum)
+    else:
+        work = plan_batches(lengths, channels, rank, world, inp_args.batch_size)
+    for j, (idxs, joint) in enumerate(work):
+        lens = None
+        if ragged and not joint and lengths[idxs[0]] >= quantum:     # (plan_ragged_batches keeps sub-quantum files apart)
+            lens = [lengths[i] // quantum * quantum for i in idxs]
+            n = max(lens)
+            batch = RaggedBatch(wavs.padded_batch(idxs, lens), lens)
+        else:
+            n = lengths[idxs[0]] // 640 * 640
+            batch = wavs.batch(idxs, joint, n)
         slot = j % len(engines)
         if len(pending) >= len(engines):
             retire(pending.pop(0))             # the batch this engine decoded last: its output is read before the slot is reused
@@ -530,7 +621,7 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
                 out = decode_with_retry(engines[slot], batch.to(dev, non_blocking=True), steps, noise, not joint, sampler)
         else:
             out = decode_with_retry(engines[slot], batch.to(dev), steps, noise, not joint, sampler)
-        pending.append((out, idxs, joint, streams[slot], (engines[slot], batch, not joint, noise)))
+        pending.append((out, idxs, joint, streams[slot], (engines[slot], batch, not joint, noise), lens))
     while pending:
         retire(pending.pop(0))
     return written_long + written
