@@ -382,7 +382,9 @@ int ldc_train_adam_step_dev(ldc_ctx* ctx, float* param, const float* grad, float
 
 /* L1 primitives (reference srcs/modules/conv.py, lstm.py), exposed for the parity tests ---------- */
 /* SConv1d.forward (conv.py:217-232), reflect padding.  w [Cout,Cin,k] (already weight-norm folded),
- * all HOST float32; x/y DEVICE [B,Cin,L] / [B,Cout,Lout].  pre_elu applies ELU to the input. */
+ * all HOST float32; x/y DEVICE [B,Cin,L] / [B,Cout,Lout].  pre_elu applies ELU to the input.
+ * This hook is stricter than the encode / decode path: it refuses L <= pad_left (LDC_E_INVALID), while sea_conv (and
+ * ldc_debug_sea_conv, which runs through it) computes such inputs as the reference's pad1d does. */
 int ldc_sconv1d(ldc_ctx* ctx, const float* x, int B, int Cin, int L, const float* w_host, const float* b_host,
                 int Cout, int k, int stride, int dilation, int causal, int pre_elu, float* y, void* stream);
 /* SConvTranspose1d.forward (conv.py:252-274), w [Cin,Cout,k] host. */
@@ -420,6 +422,23 @@ int ldc_debug_attn_core(ldc_ctx* ctx, int kind, const float* qkv, int B, int L, 
  * (fold_ctx, fuse_attn_tail, fuse_kmax, fold_ln, conv_lean) routes as in a decode.  Synchronous; honours the device-side failure
  * flag (LDC_E_HIP, "device-side failure [ctx_range]" when the context fold met k values outside its valid range). */
 int ldc_debug_attention_block(ldc_ctx* ctx, const char* name, const float* x, int B, int L, float* out, void* stream);
+
+/* Test hook: one SEANet conv on caller-supplied host weights (already weight-norm folded) through the conv path an encode / decode
+ * takes (sea_conv: its ConvCall, its split-K workspace under option "sea_splitk").  Plain (transposed = 0; w [Cout, Cin, k], reflect padding
+ * as SConv1d.forward) or transposed (w [Cin, Cout, k], k == 2*stride, as SConvTranspose1d.forward); pre_elu applies ELU to the input;
+ * residual: NULL or [B, Cout, Lout] fp32 on the device, added in the epilogue (plain only).  Cin == 1 (plain) takes the encoder's first
+ * layer's kernels on x [B, 1, L]: causal, stride 1, dilation 1, no ELU, no residual, L > k - 1 (LDC_E_INVALID otherwise).  x / y on the
+ * device, [B, Cin, L] / [B, Cout, Lout].  route (int[8], host): [0] = 1 Cin = 1 rows kernel, 2 Cin = 1 generic kernel, 3 pipelined
+ * conv kernel, 4 generic conv kernel; for 4, [1..7] = WM, WN, TM, TN of its tile configuration, split-K factor, taps per LDS group,
+ * N tile.  Synchronous. */
+int ldc_debug_sea_conv(ldc_ctx* ctx, const float* x, int B, int Cin, int L, const float* w_host, const float* b_host, int Cout, int k,
+                       int stride, int dilation, int causal, int transposed, int pre_elu, const float* residual, float* y, int* route,
+                       void* stream);
+/* Test hook: op `index` of the encoder (decoder = 0) or decoder (1) of the loaded codec `which` (LDC_MODEL_MAIN / LDC_MODEL_COND) alone, on
+ * x [B, C_in, L] fp32 (device) -> out [B, C_out, L_out].  info (int[4], host) = kind (0 Cin = 1 conv, 1 conv, 2 transposed conv,
+ * 3 resblock, 4 LSTM), C_in, C_out, L_out; out == NULL: info only, nothing runs.  Synchronous. */
+int ldc_debug_sea_op(ldc_ctx* ctx, int which, int decoder, int index, const float* x, int B, int L, float* out, int64_t capacity_elems,
+                     int* info, void* stream);
 
 /* Test hook: raises the context's device-side failure flag exactly as a kernel that gave up would (code 1: the
  * cooperative LSTM's hidden-state exchange, 2: the in-launch GroupNorm exchange of a fused conv, 4: the LinearAttention context

@@ -49,6 +49,7 @@ struct ConvKArgs {
   int win_rows;        // generic kernel: LDS window capacity (rows); the zero row lives at index win_rows
   int tg;              // taps staged per weight slab
   int reflect_back, reflect_fwd;
+  int reflect_len;     // reflect padding mirrors about reflect_len - 1: L_in << ups, or the larger pad + 1 where the input is no longer than that (conv_kargs)
   float* gn_sum;       // fused GroupNorm statistics target [B][gn_groups][kGnPad] (pre-zeroed; [0] sum, [1] sum of squares) or null
   int gn_groups, gn_cpg;
   unsigned* colmax;    // fused column max over positions (LinearAttention k softmax): ordered-uint keys, pre-zeroed
@@ -171,9 +172,9 @@ template <typename KA>
 __device__ __forceinline__ int gather_row(const KA& a, int b, int l, int toff) {
   int u = l * a.stride + toff - a.pad_left;
   const int leff = a.L_in << a.ups;
-  if (a.pad_mode == PAD_REFLECT) {
+  if (a.pad_mode == PAD_REFLECT) {   // an input no longer than its larger pad is zero-extended to reflect_len first (the reference's pad1d, conv.py:81-98)
     if (u < 0) u = -u;
-    if (u >= leff) u = 2 * (leff - 1) - u;
+    if (u >= a.reflect_len) u = 2 * (a.reflect_len - 1) - u;
   }
   if (u < 0 || u >= leff) return -1;
   return b * a.L_in + (u >> a.ups);

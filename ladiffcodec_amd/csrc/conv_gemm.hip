@@ -483,6 +483,9 @@ static hipError_t conv_kargs(const ConvLayer& ly, const ConvCall& c, ConvKArgs& 
     const int over = (c.L_rows - 1) * ly.stride + (ly.taps - 1) * ly.dil - ly.pad_left - (c.L_in - 1);
     a.reflect_back = std::max(0, over);
   }
+  // The reference's pad1d zero-extends an input no longer than its larger pad to that pad + 1 before it reflects (conv.py:81-98): the
+  // mirror then stands at that length, and what it reaches behind the real rows is zero (gather_row)
+  a.reflect_len = std::max(c.L_in << ly.ups, std::max(a.reflect_fwd, a.reflect_back) + 1);
   // rows of input a 128-row tile can touch (per extra 128 rows of tile: + 128*stride >> ups)
   int span = ((BM - 1) * ly.stride + (ly.taps - 1) * ly.dil);
   span = (span >> ly.ups) + 1 + ly.ups + a.reflect_back + a.reflect_fwd;
@@ -529,6 +532,7 @@ hipError_t launch_conv(const ConvLayer& ly, const ConvCall& c, hipStream_t s) {
   if (!(c.tune && c.tune->force_generic) && conv_fast_eligible(ly)) {
     bool launched = false;
     hipError_t e = launch_conv_fast(ly, a, M, span, s, &launched);
+    if (launched && c.route_out) c.route_out[0] = CONV_ROUTE_PIPELINED;
     if (e != hipSuccess || launched) return e;
   }
   if (c.sk_need) return hipSuccess;   // dry run: the generic kernel never splits K
@@ -545,10 +549,16 @@ hipError_t launch_conv(const ConvLayer& ly, const ConvCall& c, hipStream_t s) {
   a.tg = std::max(1, std::min(ly.taps, (40 * 1024) / (bn * kPitch)));
   const size_t lds = (size_t)(a.win_rows + 1) * kPitch + (size_t)a.tg * bn * kPitch;
   if (lds > 160 * 1024) return hipErrorInvalidValue;
+  auto report = [&](int wm, int wn, int tm, int tn) {
+    if (!c.route_out) return;
+    const int r[8] = {CONV_ROUTE_GENERIC, wm, wn, tm, tn, a.ksplit, a.tg, bn};
+    std::copy(r, r + 8, c.route_out);
+  };
   if (small) {
     const int ks = generic_splitk(ly, c, M);
+    if (ks > 1) a.ksplit = ks;
+    report(2, 2, 1, 1);
     if (ks > 1) {
-      a.ksplit = ks;
       hipError_t e = ly.dt == DT_F32 ? launch_cfg<float, 2, 2, 1, 1>(a, M, lds, s) : launch_cfg<__bf16, 2, 2, 1, 1>(a, M, lds, s);
       if (e != hipSuccess) return e;
       const long n4 = (long)M * (a.n_pad / 4);
@@ -558,6 +568,9 @@ hipError_t launch_conv(const ConvLayer& ly, const ConvCall& c, hipStream_t s) {
     }
     return ly.dt == DT_F32 ? launch_cfg<float, 2, 2, 1, 1>(a, M, lds, s) : launch_cfg<__bf16, 2, 2, 1, 1>(a, M, lds, s);
   }
+  if (bn == 128) report(2, 2, 2, 2);
+  else if (bn == 64) report(2, 2, 2, 1);
+  else report(4, 1, 1, 1);
   if (ly.dt == DT_F32) {
     if (bn == 128) return launch_cfg<float, 2, 2, 2, 2>(a, M, lds, s);
     if (bn == 64) return launch_cfg<float, 2, 2, 2, 1>(a, M, lds, s);

@@ -1006,10 +1006,9 @@ int conv_out_len(const ConvLayer& ly, int L) {
 }
 
 
-static int sea_conv(SeaRun& R, const ConvLayer& ly, const void* x, const void* residual, int L_in, void** y, int* L_out,
-                    int cout) {
+int sea_conv(SeaRun& R, const ConvLayer& ly, const void* x, const void* residual, int L_in, void** y, int* L_out, int cout) {
   ConvCall cc;
-  cc.B = R.B; cc.L_in = L_in; cc.x1 = x; cc.residual = residual; cc.tune = &R.c->tune;
+  cc.B = R.B; cc.L_in = L_in; cc.x1 = x; cc.residual = residual; cc.tune = &R.c->tune; cc.route_out = R.route;
   if (ly.tr_stride) {
     cc.L_rows = L_in + 1;
     cc.L_final = L_in * ly.tr_stride;
@@ -1042,7 +1041,7 @@ int run_seanet(SeaRun& R, const std::vector<SeaOp>& ops, const void* x_in, int L
     int Ln = L;
     switch (op.kind) {
       case SeaOp::CONV_CIN1: {
-        if (L <= op.k - 1) return fail(LDC_E_INVALID, "input shorter than the first conv's receptive field");
+        if (L <= op.k - 1) return fail(LDC_E_INVALID, "input no longer than the first conv's reflect padding is not supported (L=%d pad=%d)", L, op.k - 1);
         y = R.ar->alloc((size_t)R.B * L * op.cout * 4);
         if (!R.dry) HIPCHK(launch_conv_cin1(DT_F32, (const float*)x, y, op.w1, op.b1, R.B, L, op.cout, op.k, R.s));
         C = op.cout;

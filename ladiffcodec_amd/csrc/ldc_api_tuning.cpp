@@ -130,6 +130,127 @@ extern "C" int ldc_slstm(ldc_ctx* c, const float* x, int B, int H, int T, const 
   return LDC_OK;   // tmpc.wmem frees the temporaries
 }
 
+// One SEANet conv on caller-supplied host weights through sea_conv() itself: the ConvCall, the split-K workspace (option "sea_splitk")
+// and the arena are the ones an encode / decode makes, so everything launch_conv decides from them -- tile configuration, split-K factor,
+// taps per LDS group, window -- is decided as there.  Cin == 1 takes the encoder's first layer's route, launch_conv_cin1 on [B][L].
+// route[0] = CONV_ROUTE_* (1 cin1_rows, 2 cin1_generic, 3 pipelined, 4 generic); generic: route[1..7] = WM, WN, TM, TN, ksplit, tg, N tile.
+extern "C" int ldc_debug_sea_conv(ldc_ctx* c, const float* x, int B, int Cin, int L, const float* w_host, const float* b_host, int Cout,
+                                  int k, int stride, int dilation, int causal, int transposed, int pre_elu, const float* residual,
+                                  float* y, int* route, void* stream) {
+  if (!c || !x || !w_host || !y || !route) return fail(LDC_E_INVALID, "null argument");
+  if (B <= 0 || Cin <= 0 || L <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || dilation <= 0) return fail(LDC_E_INVALID, "bad sizes");
+  if (transposed && (k != 2 * stride || dilation != 1)) return fail(LDC_E_INVALID, "only kernel_size == 2*stride transposed convs exist on the decode path");
+  if (transposed && residual) return fail(LDC_E_INVALID, "the residual epilogue belongs to plain convs");
+  for (int i = 0; i < 8; ++i) route[i] = 0;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = pick_stream(c, stream);
+  DevMem keep;
+  if (Cin == 1 && !transposed) {
+    if (!causal) return fail(LDC_E_INVALID, "the Cin = 1 conv is causal only");
+    if (stride != 1 || dilation != 1 || pre_elu || residual) return fail(LDC_E_INVALID, "the Cin = 1 conv has stride 1, dilation 1, no ELU and no residual");
+    if (L <= k - 1) return fail(LDC_E_INVALID, "input no longer than the Cin = 1 conv's reflect padding is not supported (L=%d pad=%d)", L, k - 1);
+    float *dw = nullptr, *db = nullptr;
+    LDCCHK(keep.upload(&dw, std::vector<float>(w_host, w_host + (size_t)Cout * k)));
+    if (b_host) LDCCHK(keep.upload(&db, std::vector<float>(b_host, b_host + Cout)));
+    void* yc = nullptr;
+    LDCCHK(keep.alloc(&yc, (size_t)B * L * Cout * 4));
+    HIPCHK(launch_conv_cin1(DT_F32, x, yc, dw, db, B, L, Cout, k, s, &route[0]));
+    HIPCHK(launch_from_cl(DT_F32, yc, y, B, Cout, L, nullptr, 0, 0.f, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return LDC_OK;
+  }
+  const int cp = round_up(Cin, 16);
+  ConvLayer ly;
+  int rc;
+  std::swap(keep.ptrs, c->wmem.ptrs);   // make_conv allocates from c->wmem; give it a temporary pool
+  if (transposed) {
+    std::vector<float> wp((size_t)cp * Cout * k, 0.f);
+    memcpy(wp.data(), w_host, (size_t)Cin * Cout * k * 4);
+    const int padding_total = k - stride;
+    rc = make_convtr(c, DT_F32, cp, Cout, stride, causal ? 0 : padding_total - padding_total / 2, pre_elu ? ACT_ELU : ACT_NONE, wp.data(), b_host, &ly);
+  } else {
+    std::vector<float> wp((size_t)Cout * cp * k, 0.f);
+    for (int o = 0; o < Cout; ++o)
+      for (int i = 0; i < Cin; ++i)
+        for (int t = 0; t < k; ++t) wp[((size_t)o * cp + i) * k + t] = w_host[((size_t)o * Cin + i) * k + t];
+    ConvSpec sp;
+    sp.dt = DT_F32; sp.cin1 = cp; sp.cout = Cout; sp.k = k; sp.stride = stride; sp.dil = dilation;
+    const int padding_total = (k - 1) * dilation - (stride - 1);
+    if (padding_total < 0) { std::swap(keep.ptrs, c->wmem.ptrs); return fail(LDC_E_INVALID, "stride exceeds the receptive field"); }
+    sp.pad_left = causal ? padding_total : padding_total - padding_total / 2;
+    sp.pad_mode = PAD_REFLECT; sp.pre_act = pre_elu ? ACT_ELU : ACT_NONE;
+    rc = make_conv(c, sp, wp.data(), b_host, &ly);
+  }
+  std::swap(keep.ptrs, c->wmem.ptrs);   // `keep` now owns the temporaries and frees them on return
+  LDCCHK(rc);
+  const int Lout = transposed ? L * stride : conv_out_len(ly, L);
+  void* tmp = nullptr;
+  if (cp != Cin) LDCCHK(keep.alloc(&tmp, (size_t)B * L * Cin * 4));
+  int ret = with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
+    SeaRun R{c, &ar, s, dry, B};
+    R.route = route;
+    void* xc = ar.alloc((size_t)B * L * cp * 4);
+    void* rcl = residual ? ar.alloc((size_t)B * Lout * Cout * 4) : nullptr;
+    if (!dry) {
+      if (cp == Cin) {
+        HIPCHK(launch_to_cl(DT_F32, x, xc, B, Cin, L, nullptr, 0, 0.f, s));
+      } else {   // [B][Cin][L] -> rows [B*L][cp]: transpose into the first Cin columns
+        HIPCHK(hipMemsetAsync(xc, 0, (size_t)B * L * cp * 4, s));
+        HIPCHK(launch_to_cl(DT_F32, x, tmp, B, Cin, L, nullptr, 0, 0.f, s));
+        HIPCHK(hipMemcpy2DAsync(xc, (size_t)cp * 4, tmp, (size_t)Cin * 4, (size_t)Cin * 4, (size_t)B * L, hipMemcpyDeviceToDevice, s));
+      }
+      if (residual) HIPCHK(launch_to_cl(DT_F32, residual, rcl, B, Cout, Lout, nullptr, 0, 0.f, s));
+    }
+    void* yc = nullptr;
+    int Lo = 0;
+    LDCCHK(sea_conv(R, ly, xc, rcl, L, &yc, &Lo, Cout));
+    if (Lo != Lout) return fail(LDC_E_INVALID, "internal: conv produced %d positions, expected %d", Lo, Lout);
+    if (!dry) HIPCHK(launch_from_cl(DT_F32, yc, y, B, Cout, Lout, nullptr, 0, 0.f, s));
+    return LDC_OK;
+  });
+  hipError_t e = hipStreamSynchronize(s);   // the temporaries are freed on return
+  if (ret != LDC_OK) return ret;
+  if (e != hipSuccess) return fail(LDC_E_HIP, "sync failed: %s", hipGetErrorString(e));
+  return LDC_OK;
+}
+
+// Op `index` of the encoder (decoder = 0) or decoder (1) of a loaded codec through run_seanet on x [B][C_in][L] fp32 (device).
+// info[0..3] = SeaOp kind (0 cin1 conv, 1 conv, 2 transposed conv, 3 resblock, 4 LSTM), C_in, C_out, L_out; out == NULL: info only.
+extern "C" int ldc_debug_sea_op(ldc_ctx* c, int which, int decoder, int index, const float* x, int B, int L, float* out,
+                                int64_t capacity_elems, int* info, void* stream) {
+  LDCCHK(check_ready(c, which));
+  if (!info || B <= 0 || L <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  const std::vector<SeaOp>& all = decoder ? c->codec[which].dec : c->codec[which].enc;
+  if (index < 0 || index >= (int)all.size()) return fail(LDC_E_INVALID, "op index %d outside [0, %d)", index, (int)all.size());
+  const std::vector<SeaOp> ops{all[(size_t)index]};
+  const int Cin = ops[0].cin;
+  hipStream_t s = pick_stream(c, stream);
+  info[0] = (int)ops[0].kind; info[1] = Cin; info[2] = 0; info[3] = 0;
+  if (out && !x) return fail(LDC_E_INVALID, "null input");
+  auto body = [&](Arena& ar, bool dry) -> int {
+    SeaRun R{c, &ar, s, dry, B};
+    void* xc = ar.alloc((size_t)B * L * Cin * 4);
+    if (!dry) HIPCHK(launch_to_cl(DT_F32, x, xc, B, Cin, L, nullptr, 0, 0.f, s));
+    void* o = nullptr;
+    int Lo = 0, C = 0;
+    LDCCHK(run_seanet(R, ops, xc, L, &o, &Lo, &C));
+    info[2] = C; info[3] = Lo;
+    if (!out) return LDC_OK;
+    if ((int64_t)B * C * Lo > capacity_elems) return fail(LDC_E_INVALID, "output needs %lld elements, capacity %lld", (long long)B * C * Lo, (long long)capacity_elems);
+    if (!dry) HIPCHK(launch_from_cl(DT_F32, o, out, B, C, Lo, nullptr, 0, 0.f, s));
+    return LDC_OK;
+  };
+  if (!out) {   // info only: the measuring pass alone
+    Arena measure;
+    return body(measure, true);
+  }
+  int ret = with_scratch(c, s, body);
+  hipError_t e = hipStreamSynchronize(s);
+  if (ret != LDC_OK) return ret;
+  if (e != hipSuccess) return fail(LDC_E_HIP, "sync failed: %s", hipGetErrorString(e));
+  return check_dev_flag(c);
+}
+
 // ------------------------------------------------------------------------------------------------
 // accounting / profiling
 // ------------------------------------------------------------------------------------------------

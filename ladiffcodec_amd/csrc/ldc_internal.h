@@ -450,6 +450,7 @@ struct SeaRun {   // measures or runs a SEANet stack
   int B;
   int side = -1;   // 0 / 1: aux_stream[2 + side] and lstm_ev[side] may carry the second stage of the two-layer LSTM pipeline (run_seanet)
   int teams = 1;   // batch parts whose codec ends may be in flight together: the XCD-local LSTM wants room for twice that many teams on its XCD
+  int* route = nullptr;   // test hook (ldc_debug_sea_conv): ConvCall::route_out of the convs this run launches
 };
 
 // ldc_api.cpp
@@ -460,6 +461,7 @@ int build_lstm(ldc_ctx* c, WeightReader& wr, const std::string& p, int H, int la
 void drop_plans(ldc_ctx* c);
 int ensure_scratch(ldc_ctx* c, size_t bytes, hipStream_t s);
 int conv_out_len(const ConvLayer& ly, int L);
+int sea_conv(SeaRun& R, const ConvLayer& ly, const void* x, const void* residual, int L_in, void** y, int* L_out, int cout);
 int run_seanet(SeaRun& R, const std::vector<SeaOp>& ops, const void* x_in, int L, void** out, int* L_out, int* C_out);
 int check_ready(ldc_ctx* c, int which, bool need_cond_codec = false);
 int check_unet_args(ldc_ctx* c, int B, int L, int F);

@@ -114,9 +114,12 @@ struct ConvCall {
   int kst_stride = 0;
   const ConvTune* tune = nullptr;   // null: defaults
   long long* sk_need = nullptr;     // dry run: no launch, *sk_need = split-K workspace floats this call would use
+  int* route_out = nullptr;         // test hook: int[8] = route (CONV_ROUTE_*), then for the generic kernel WM, WN, TM, TN, split-K factor, taps per LDS group tg, N tile
   int* bm_out = nullptr;            // dry run (with sk_need): int[4] = rows per tile of the pipelined kernel (0 when the generic kernel would run), wave rows WM, split-K factor, columns per tile
 };
 
+// which kernel a conv call ran on (ConvCall::route_out[0] / launch_conv_cin1's route_out)
+enum { CONV_ROUTE_NONE = 0, CONV_ROUTE_CIN1_ROWS = 1, CONV_ROUTE_CIN1_GENERIC = 2, CONV_ROUTE_PIPELINED = 3, CONV_ROUTE_GENERIC = 4 };
 hipError_t launch_conv(const ConvLayer& ly, const ConvCall& c, hipStream_t s);
 long long conv_generic_splitk_floats(const ConvLayer& ly, const ConvCall& c);   // workspace floats a generic_split call of this shape uses (0: it would not split)
 size_t conv_packed_weight_bytes(const ConvLayer& ly);
@@ -270,7 +273,7 @@ size_t output_normalise_ws_bytes(int B);
 // ------------------------------------------------------------------------------------------------
 // First SEANet conv: Cin = 1, causal reflect pad.  x [B][L] fp32 -> y [B][L][Cout] dt.  w [Cout][k] fp32.
 hipError_t launch_conv_cin1(int dt, const float* x, void* y, const float* w, const float* bias, int B, int L, int Cout,
-                            int k, hipStream_t s);
+                            int k, hipStream_t s, int* route_out = nullptr);   // route_out (test hook): *route_out = CONV_ROUTE_CIN1_*
 // LSTM recurrence over T for one layer.  pre [B][T][4H] dt_pre (input GEMM + both biases), w_hh [4H][H]
 // fp32, out [B][T][H]; if skip != null: out = h + skip (SLSTM skip, lstm.py:25-26).
 // a stretch of time steps of one LSTM layer on the register kernel: rows are item * bs + t * ts (in rows of 4H / H values), the

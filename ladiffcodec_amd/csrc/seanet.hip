@@ -100,15 +100,17 @@ __global__ __launch_bounds__(256) void conv_cin1_rows_kernel(const float* x, voi
 }
 
 hipError_t launch_conv_cin1(int dt, const float* x, void* y, const float* w, const float* bias, int B, int L, int Cout,
-                            int k, hipStream_t s) {
+                            int k, hipStream_t s, int* route_out) {
   if (L <= k - 1) return hipErrorInvalidValue;
   if (Cout % 4 == 0 && Cout <= 1024 && 256 % (Cout / 4) == 0 && k <= 8) {
+    if (route_out) *route_out = CONV_ROUTE_CIN1_ROWS;
     const int rpb = 8 * (1024 / Cout);
     dim3 grid((L + rpb - 1) / rpb, B);
     if (dt == DT_F32) hipLaunchKernelGGL(conv_cin1_rows_kernel<float>, grid, dim3(256), 0, s, x, y, w, bias, L, Cout, k, rpb);
     else hipLaunchKernelGGL(conv_cin1_rows_kernel<__bf16>, grid, dim3(256), 0, s, x, y, w, bias, L, Cout, k, rpb);
     return hipGetLastError();
   }
+  if (route_out) *route_out = CONV_ROUTE_CIN1_GENERIC;
   const size_t lds = (size_t)(Cout * k + Cout) * sizeof(float);
   int bx = (int)std::min<size_t>(((size_t)L * Cout + 255) / 256, 512);
   if (dt == DT_F32)

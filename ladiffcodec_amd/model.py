@@ -279,6 +279,59 @@ class Engine:
             self._exit()
         return out
 
+    SEA_ROUTES = {1: "cin1_rows", 2: "cin1_generic", 3: "pipelined", 4: "generic"}
+    SEA_OP_KINDS = ("conv_cin1", "conv", "convtr", "res", "lstm")
+
+    def debug_sea_conv(self, x, w, b, stride=1, dilation=1, causal=True, transposed=False, pre_elu=False, residual=None):
+        """ldc_debug_sea_conv: one SEANet conv (plain: w [Cout, Cin, k]; transposed: w [Cin, Cout, k], k = 2 * stride) on x [B, Cin, L]
+        through the conv path of an encode / decode.  Returns (y [B, Cout, Lout], route): route = {"route": one of SEA_ROUTES' names}
+        and, for the generic kernel, "tile" (WM, WN, TM, TN), "ksplit", "tg" and "bn"."""
+        x = self._f32(x)
+        w = np.ascontiguousarray(w, np.float32)
+        b = np.ascontiguousarray(b, np.float32) if b is not None else None
+        B, Cin, Lx = x.shape
+        if transposed:
+            _, Cout, k = w.shape
+            Lout = Lx * stride
+        else:
+            Cout, _, k = w.shape
+            Lout = -(-Lx // stride)
+        r = self._f32(residual) if residual is not None else None
+        y = self._empty(B, Cout, Lout)
+        route = (C.c_int * 8)()
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_debug_sea_conv(self._ctx, x.data_ptr(), B, Cin, Lx, w.ctypes.data_as(C.c_void_p),
+                                                b.ctypes.data_as(C.c_void_p) if b is not None else None, Cout, k, stride, dilation,
+                                                int(causal), int(transposed), int(pre_elu), r.data_ptr() if r is not None else None,
+                                                y.data_ptr(), route, s))
+        finally:
+            self._exit()
+        rep = {"route": self.SEA_ROUTES.get(route[0], "none")}
+        if route[0] == 4:
+            rep.update(tile=tuple(route[1:5]), ksplit=route[5], tg=route[6], bn=route[7])
+        return y, rep
+
+    def debug_sea_op_info(self, which: int, decoder: bool, index: int, B: int, Lx: int):
+        """(kind, C_in, C_out, L_out) of op `index` of the loaded codec's encoder / decoder for an input of Lx positions."""
+        info = (C.c_int * 4)()
+        L.check(self.lib.ldc_debug_sea_op(self._ctx, which, int(decoder), index, None, B, Lx, None, 0, info, None))
+        return self.SEA_OP_KINDS[info[0]], info[1], info[2], info[3]
+
+    def debug_sea_op(self, which: int, decoder: bool, index: int, x):
+        """ldc_debug_sea_op: op `index` of the encoder / decoder of the loaded codec `which` alone on x [B, C_in, L]."""
+        x = self._f32(x)
+        B, _, Lx = x.shape
+        _, _, Co, Lo = self.debug_sea_op_info(which, decoder, index, B, Lx)
+        out = self._empty(B, Co, Lo)
+        info = (C.c_int * 4)()
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_debug_sea_op(self._ctx, which, int(decoder), index, x.data_ptr(), B, Lx, out.data_ptr(), out.numel(), info, s))
+        finally:
+            self._exit()
+        return out
+
     def p_sample(self, x, t: int, cond, noise=None):
         x = self._f32(x).clone()
         cond = self._f32(cond)
