@@ -162,6 +162,13 @@ int ldc_rvq_decode(ldc_ctx* ctx, const int64_t* codes, int B, int F, int n_q, fl
  * codes_out may be NULL.  bandwidth <= 0 means the configured cond_bandwidth. */
 int ldc_get_cond(ldc_ctx* ctx, const float* wav, int B, int T, float bandwidth, float* cond_out, int64_t* codes_out,
                  void* stream);
+/* ldc_get_cond on a right-padded batch (the sender side of a mixed-length batch): wav [B,1,Tmax], lengths_host[B] samples per item
+ * (host memory), positive multiples of the cond hop (320), none above Tmax, Tmax itself such a multiple: LDC_E_INVALID otherwise,
+ * before any GPU work.  Every item's codes and condition rows are those of ldc_get_cond on the item alone (items of at most
+ * 6 frames, where the encoder's reflect padding changes form, are encoded on their own inside the call); codes_out [n_q,B,Fmax]
+ * and cond_out [B,D,Fmax] are zero behind lengths_host[b] / 320 frames.  What the padding of wav holds is never read into a value. */
+int ldc_get_cond_ragged(ldc_ctx* ctx, const float* wav, const int32_t* lengths_host, int B, int Tmax, float bandwidth,
+                        float* cond_out, int64_t* codes_out, void* stream);
 /* for layer in diff_model.upsampling_layers: img = layer(img)   (sample.py:125-128, unet.py:372-377)
  * normalise: 0 = raw; 1 = img /= max|img|+1e-8 over the whole tensor (sample.py:129);
  *            2 = the same per batch item (a batch of independent utterances). cond [B,C,F] -> [B,C,L] */
@@ -254,6 +261,21 @@ int ldc_decode_codes(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, 
 int ldc_decode_codes_ddim(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits,
                           int n_q, int B, int F, int t_start, int n_steps, float eta, const float* noise, int per_item,
                           float* wav_out, float* latents_out, float* cond_out, void* stream);
+/* ldc_decode_codes / ldc_decode_codes_ddim with the length semantics of ldc_decode_ragged (the receiver of containers of
+ * different lengths): frames_host[B] (host memory) condition frames of item b are its own.  codes [n_q,B,Fmax] or packed
+ * [B][packed_stride]: the codes behind an item's frames are neither read nor validated, and a packed item's stream is
+ * ldc_packed_bytes(n_q, frames_host[b], bits) bytes long -- nothing behind that byte of its row is read, so payloads of unequal
+ * containers go in as they are.  Within an item's frames the condition rows are bit-identical to ldc_rvq_decode of the item alone
+ * and a code outside [0, bins) is refused as in ldc_decode_codes ("[bad_code]" names its codebook, item and frame); rows behind
+ * them are zero.  t_start == 0: halfway DDPM sampling of n_steps; t_start > 0: DDIM.  Per-item normalisation; wav_out
+ * [B,1,Fmax*320], latents_out, cond_out are zero beyond an item's length; noise as in ldc_decode_ragged.
+ * Refused (LDC_E_INVALID, before any GPU work): what ldc_decode_codes refuses; a frames_host[b] that is not a positive multiple
+ * of the ragged quantum / 320 (8 frames for enc_ratios 8 4, 2 for 8) or exceeds Fmax; packed_stride below the packed bytes of
+ * the longest item; the fp8 engine.  The step graph captured for (B, Fmax) is the one ldc_decode_ragged replays at
+ * (B, Fmax * 320): it serves every set of lengths. */
+int ldc_decode_codes_ragged(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
+                            int B, int Fmax, const int32_t* frames_host, int t_start, int n_steps, float eta, const float* noise,
+                            float* wav_out, float* latents_out, float* cond_out, void* stream);
 
 /* bit-stream layer: the on-wire format between ldc_rvq_encode and ldc_rvq_decode -- SURVEY.md section 8(f) row 3 ------------
  * Every batch item is an independent stream.  All results are bit-exact with the reference classes.  These calls need no
@@ -277,6 +299,15 @@ int ldc_ac_encode(ldc_ctx* ctx, const int32_t* symbols, const int32_t* cdf, int 
 /* ArithmeticDecoder.pull x S (ac.py:218-260).  status_out[b]: 0 ok, 1 stream exhausted (pull returned None), 2 search failed. */
 int ldc_ac_decode(ldc_ctx* ctx, const uint8_t* in, int64_t in_stride, const int64_t* nbytes, const int32_t* cdf, int B, int S, int card,
                   int n_static, int total_range_bits, int32_t* symbols_out, int32_t* status_out, void* stream);
+/* The two calls above with a symbol count per stream: n_sym [B] int32 (device), 0 <= n_sym[b] <= S.  Stream b codes the first
+ * n_sym[b] symbols of its row of symbols [B][S] (tables: row b*S + s of cdf [B][S][card], or the static ones) and flushes there:
+ * its bytes are those of ldc_ac_encode on the item alone with S = n_sym[b].  The decoder writes 0 behind n_sym[b] symbols.
+ * A count outside [0, S]: nbytes_out[b] = -1 / status_out[b] = 3. */
+int ldc_ac_encode_ragged(ldc_ctx* ctx, const int32_t* symbols, const int32_t* n_sym, const int32_t* cdf, int B, int S, int card,
+                         int n_static, int total_range_bits, uint8_t* out, int64_t out_stride, int64_t* nbytes_out, void* stream);
+int ldc_ac_decode_ragged(ldc_ctx* ctx, const uint8_t* in, int64_t in_stride, const int64_t* nbytes, const int32_t* n_sym,
+                         const int32_t* cdf, int B, int S, int card, int n_static, int total_range_bits, int32_t* symbols_out,
+                         int32_t* status_out, void* stream);
 
 /* audio front end -- SURVEY.md section 8(f) row 4: torchaudio.functional.resample(wav, orig_freq, new_freq) with its defaults
  * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), the call at srcs/sample.py:84.  wav [C][T] -> out [C][ldc_resample_out_len]. */

@@ -155,9 +155,11 @@ class Bitstream:
         self.eng._exit()
         return cdf
 
-    def ac_encode(self, symbols, cdf, static: bool = False, total_range_bits: int = 24, capacity: tp.Optional[int] = None):
+    def ac_encode(self, symbols, cdf, static: bool = False, total_range_bits: int = 24, capacity: tp.Optional[int] = None,
+                  n_sym: tp.Optional[tp.Sequence[int]] = None):
         """symbols [B, S]; cdf [B, S, card] (static=False) or [n, card] with symbol s using table s % n (static=True).
-        -> list of B `bytes` (ArithmeticCoder pushes + flush of every stream)."""
+        -> list of B `bytes` (ArithmeticCoder pushes + flush of every stream).  n_sym (optional, B counts <= S): stream b codes its
+        first n_sym[b] symbols only (ldc_ac_encode_ragged) -- the bytes of a call on the item alone with S = n_sym[b]."""
         t = self.torch
         symbols = symbols.to(self.eng.device, t.int32).contiguous()
         cdf = cdf.to(self.eng.device, t.int32).contiguous()
@@ -167,8 +169,14 @@ class Bitstream:
         out = t.empty(B, cap, dtype=t.uint8, device=self.eng.device)
         nbytes = t.empty(B, dtype=t.int64, device=self.eng.device)
         s = self.eng._enter()
-        L.check(self.lib.ldc_ac_encode(self.eng._ctx, symbols.data_ptr(), cdf.data_ptr(), B, S, card, cdf.shape[0] if static else 0,
-                                       total_range_bits, out.data_ptr(), out.stride(0), nbytes.data_ptr(), s))
+        if n_sym is None:
+            L.check(self.lib.ldc_ac_encode(self.eng._ctx, symbols.data_ptr(), cdf.data_ptr(), B, S, card, cdf.shape[0] if static else 0,
+                                           total_range_bits, out.data_ptr(), out.stride(0), nbytes.data_ptr(), s))
+        else:
+            cnt = self._counts(n_sym, B, S)
+            L.check(self.lib.ldc_ac_encode_ragged(self.eng._ctx, symbols.data_ptr(), cnt.data_ptr(), cdf.data_ptr(), B, S, card,
+                                                  cdf.shape[0] if static else 0, total_range_bits, out.data_ptr(), out.stride(0),
+                                                  nbytes.data_ptr(), s))
         self.eng._exit()
         n = nbytes.cpu().tolist()
         if min(n) < 0:
@@ -176,8 +184,16 @@ class Bitstream:
         host = out.cpu().numpy()
         return [host[b, :n[b]].tobytes() for b in range(B)]
 
-    def ac_decode(self, streams: tp.Sequence[bytes], S: int, cdf, static: bool = False, total_range_bits: int = 24):
-        """-> symbols [B, S] int32; raises EOFError where ArithmeticDecoder.pull would return None (compress.py:148-149)."""
+    def _counts(self, n_sym, B: int, S: int):
+        n_sym = [int(v) for v in n_sym]
+        if len(n_sym) != B or min(n_sym) < 0 or max(n_sym) > S:
+            raise ValueError(f"n_sym: {B} counts in [0, {S}] expected")
+        return self.torch.tensor(n_sym, dtype=self.torch.int32, device=self.eng.device)
+
+    def ac_decode(self, streams: tp.Sequence[bytes], S: int, cdf, static: bool = False, total_range_bits: int = 24,
+                  n_sym: tp.Optional[tp.Sequence[int]] = None):
+        """-> symbols [B, S] int32; raises EOFError where ArithmeticDecoder.pull would return None (compress.py:148-149).
+        n_sym (optional): stream b holds n_sym[b] <= S symbols (ldc_ac_decode_ragged); the symbols behind them come out 0."""
         import numpy as np
         t = self.torch
         B = len(streams)
@@ -191,9 +207,15 @@ class Bitstream:
         symbols = t.zeros(B, S, dtype=t.int32, device=self.eng.device)
         status = t.zeros(B, dtype=t.int32, device=self.eng.device)
         s = self.eng._enter()
-        L.check(self.lib.ldc_ac_decode(self.eng._ctx, data.data_ptr(), data.stride(0), nbytes.data_ptr(), cdf.data_ptr(), B, S,
-                                       cdf.shape[-1], cdf.shape[0] if static else 0, total_range_bits, symbols.data_ptr(),
-                                       status.data_ptr(), s))
+        if n_sym is None:
+            L.check(self.lib.ldc_ac_decode(self.eng._ctx, data.data_ptr(), data.stride(0), nbytes.data_ptr(), cdf.data_ptr(), B, S,
+                                           cdf.shape[-1], cdf.shape[0] if static else 0, total_range_bits, symbols.data_ptr(),
+                                           status.data_ptr(), s))
+        else:
+            cnt = self._counts(n_sym, B, S)
+            L.check(self.lib.ldc_ac_decode_ragged(self.eng._ctx, data.data_ptr(), data.stride(0), nbytes.data_ptr(), cnt.data_ptr(),
+                                                  cdf.data_ptr(), B, S, cdf.shape[-1], cdf.shape[0] if static else 0, total_range_bits,
+                                                  symbols.data_ptr(), status.data_ptr(), s))
         self.eng._exit()
         st = status.cpu().tolist()
         if any(v == 1 for v in st):
@@ -210,21 +232,31 @@ class Bitstream:
         Header fields as compress.py:47-71 writes them; `lm` keeps the reference's meaning (payload arithmetic-coded with the
         model's LM pdfs, compress.py:118-141), which this library never produces, so it is always false.  A payload coded with
         a caller-supplied static per-codebook table says so in its own field `ac: "static"`; a reference decoder that meets
-        it reads `lm: false`, plain-unpacks and finds the stream too short instead of silently mis-decoding."""
+        it reads `lm: false`, plain-unpacks and finds the stream too short instead of silently mis-decoding.
+
+        audio_length: one length for the batch, or a list of B lengths for items of different lengths (codes right-padded to F =
+        the longest item's frames, ZERO behind an item's frames, as Engine.get_cond_ragged returns them).  Either way one device
+        call; every container is byte-identical to the one the item gives alone: a plain payload is the first
+        packed_bytes(n_q, F_b, bits) bytes of its padded row (zero codes behind F_b leave the last partial byte as the solo pack
+        writes it), a static one codes n_q * F_b symbols (ac_encode's n_sym)."""
         n_q, B, F = codes.shape
+        ragged = hasattr(audio_length, "__len__")
+        als = [int(v) for v in audio_length] if ragged else [int(audio_length)] * B
+        frames = [-(-al // int(hop_length)) for al in als]
+        if len(als) != B or max(frames) != F or min(frames) < 1:
+            raise ValueError(f"audio_length {audio_length} does not give {F} frames at hop {hop_length}")
         if static_cdf is None:
-            payloads = [bytes(r) for r in self.pack_codes(codes, bits).cpu().numpy()]
+            rows = self.pack_codes(codes, bits).cpu().numpy()
+            payloads = [bytes(r[:packed_bytes(n_q, fb, bits)]) for r, fb in zip(rows, frames)]
         else:
             if static_cdf.shape[0] != n_q:
                 raise ValueError(f"static_cdf has {static_cdf.shape[0]} tables for {n_q} codebooks (symbol s uses table s % n_q)")
             sym = codes.permute(1, 2, 0).reshape(B, F * n_q)          # push order: t outer, k inner
-            payloads = self.ac_encode(sym, static_cdf, static=True)
-        if -(-int(audio_length) // int(hop_length)) != F:
-            raise ValueError(f"audio_length {audio_length} does not give {F} frames at hop {hop_length}")
+            payloads = self.ac_encode(sym, static_cdf, static=True, n_sym=[n_q * fb for fb in frames] if ragged else None)
         out = []
         for b in range(B):
             fo = io.BytesIO()
-            meta = ecdc_meta(audio_length, n_q, model_name, hop_length)
+            meta = ecdc_meta(als[b], n_q, model_name, hop_length)
             if static_cdf is not None:
                 meta["ac"] = "static"
             write_ecdc_header(fo, meta)
@@ -232,9 +264,14 @@ class Bitstream:
             out.append(fo.getvalue())
         return out
 
-    def decompress_codes(self, blobs: tp.Sequence[bytes], F: tp.Optional[int] = None, bits: int = 10, static_cdf=None):
-        """-> (codes [n_q, B, F] int64, list of metadata).  F is derived from the header (`al`, `hop`) and, when given, must agree."""
+    def decompress_codes(self, blobs: tp.Sequence[bytes], F: tp.Optional[int] = None, bits: int = 10, static_cdf=None,
+                         ragged: bool = False):
+        """-> (codes [n_q, B, F] int64, list of metadata).  F is derived from the header (`al`, `hop`) and, when given, must agree.
+        ragged: the containers may differ in length -- codes [n_q, B, Fmax], zero behind an item's own frames (its header's), still
+        one device call."""
         import numpy as np
+        if ragged:
+            return self._decompress_ragged(blobs, bits, static_cdf)
         metas, payloads = [], []
         for blob in blobs:
             fo = io.BytesIO(blob)
@@ -269,3 +306,42 @@ class Bitstream:
             raise ValueError(f"static_cdf has {static_cdf.shape[0]} tables for {n_q} codebooks")
         sym = self.ac_decode(payloads, F * n_q, static_cdf, static=True)
         return sym.reshape(len(payloads), F, n_q).permute(2, 0, 1).contiguous().to(self.torch.int64), metas
+
+    def _decompress_ragged(self, blobs, bits, static_cdf):
+        import numpy as np
+        t = self.torch
+        metas, payloads = [], []
+        for blob in blobs:
+            fo = io.BytesIO(blob)
+            metas.append(read_ecdc_header(fo))
+            payloads.append(fo.read())
+        n_q = metas[0]["nc"]
+        if any(m["nc"] != n_q for m in metas):
+            raise ValueError("streams of one batch must share the number of codebooks")
+        for m in metas:
+            if m.get("lm"):
+                raise ValueError("stream is coded with a language model (lm: true): not produced nor decodable here")
+            mode = m.get("ac", "none")
+            if mode not in ("none", "static"):
+                raise ValueError(f"unknown entropy-coding mode {mode!r}")
+            if (mode == "static") != (static_cdf is not None):
+                raise ValueError("stream is static-table arithmetic-coded: pass the table it was coded with" if mode == "static"
+                                 else "stream is plainly packed: static_cdf must not be given")
+        frames = [-(-int(m["al"]) // int(m.get("hop", 320))) for m in metas]
+        B, F = len(blobs), max(frames)
+        if static_cdf is not None:
+            if static_cdf.shape[0] != n_q:
+                raise ValueError(f"static_cdf has {static_cdf.shape[0]} tables for {n_q} codebooks")
+            sym = self.ac_decode(payloads, F * n_q, static_cdf, static=True, n_sym=[n_q * fb for fb in frames])
+            return sym.reshape(B, F, n_q).permute(2, 0, 1).contiguous().to(t.int64), metas
+        if any(len(p) < packed_bytes(n_q, fb, bits) for p, fb in zip(payloads, frames)):
+            raise EOFError("The stream ended sooner than expected.")
+        # rows are zero behind a payload's own bytes; the spare bits of an item's last byte are whatever its writer left there, so the
+        # codes behind its frames are cleared explicitly
+        host = np.zeros((B, max(packed_bytes(n_q, F, bits), 1)), np.uint8)
+        for b, (p, fb) in enumerate(zip(payloads, frames)):
+            nb = packed_bytes(n_q, fb, bits)
+            host[b, :nb] = np.frombuffer(p[:nb], np.uint8)
+        codes = self.unpack_codes(t.from_numpy(host), n_q, F, bits)
+        keep = t.arange(F, device=codes.device)[None, :] < t.tensor(frames, device=codes.device)[:, None]
+        return codes * keep[None].to(codes.dtype), metas

@@ -7,6 +7,10 @@ in batches of `--batch_size` (sample.plan_batches), the codes computed at `--con
 (compress.py:28-84 with use_lm False: keys m, al = trimmed length, nc, lm, hop) and the payload; a file of C > 1 channels
 becomes one container with the extra key `ch: C` and its C payloads back to back.  `python -m ladiffcodec_amd.decompress`
 turns the containers back into audio.
+
+`--ragged [--ragged_waste W]` packs mono files of DIFFERENT lengths into shared encoder batches (sample.plan_ragged_batches at the
+same 640-sample trim -- the sender does not know the receiver's UNet quantum -- and Engine.get_cond_ragged): every container is
+byte-identical to the one the run without the flag writes.
 """
 from __future__ import annotations
 
@@ -17,13 +21,27 @@ from typing import List
 from .sample import build_parser
 
 BITS = 10      # log2(bins): compress.py's BitPacker width
+TRIM = 640     # sample.py:87
+
+
+def ragged_options(a):
+    """sample.ragged_options for the codec-end CLIs, which refuse a --ragged_waste that nothing would read."""
+    from .sample import ragged_options as base
+    ragged, waste = base(a)
+    if not ragged and hasattr(a, "ragged_waste"):
+        raise SystemExit("--ragged_waste needs --ragged")
+    if waste < 0:
+        raise SystemExit("--ragged_waste must be >= 0")
+    return ragged, waste
 
 
 def compress_files(eng, files: List[str], inp_args, rank: int = 0, world: int = 1) -> List[str]:
     """Encode and write this rank's files; -> the container paths written."""
     from .bitstream import Bitstream, ecdc_container
-    from .sample import LazyWavs, output_path, plan_batches
+    from .bitstream import packed_bytes
+    from .sample import LazyWavs, output_path, plan_batches, plan_ragged_batches
 
+    ragged, waste = ragged_options(inp_args)
     bs = Bitstream(eng)
     wavs = LazyWavs(files, eng)
     keep = [i for i, sh in enumerate(wavs.shapes) if sh[1] // 640 * 640 > 0]                  # sample.py:87-88
@@ -31,14 +49,24 @@ def compress_files(eng, files: List[str], inp_args, rank: int = 0, world: int = 
     lengths, channels = [sh[1] for sh in wavs.shapes], [sh[0] for sh in wavs.shapes]
     dev = eng.device
     written = []
-    for idxs, joint in plan_batches(lengths, channels, rank, world, inp_args.batch_size):
-        n = lengths[idxs[0]] // 640 * 640
-        batch = wavs.batch(idxs, joint, n).to(dev)
-        _, codes = eng.get_cond(batch, bandwidth=float(inp_args.cond_bandwidth), return_codes=True)
+    if ragged:
+        work = plan_ragged_batches(lengths, channels, rank, world, inp_args.batch_size, waste, TRIM)
+    else:
+        work = plan_batches(lengths, channels, rank, world, inp_args.batch_size)
+    for idxs, joint in work:
+        ns = [lengths[i] // TRIM * TRIM for i in idxs]
+        if ragged and not joint and len(set(ns)) > 1:
+            # codes are zero behind an item's frames, so the first packed_bytes(n_q, F_b) bytes of its padded row are its solo pack
+            _, codes = eng.get_cond_ragged(wavs.padded_batch(idxs, ns).to(dev), ns, bandwidth=float(inp_args.cond_bandwidth), return_codes=True)
+        else:
+            _, codes = eng.get_cond(wavs.batch(idxs, joint, ns[0]).to(dev), bandwidth=float(inp_args.cond_bandwidth), return_codes=True)
         rows = bs.pack_codes(codes, BITS).cpu().numpy()                                          # [B, packed bytes]
         n_q = int(codes.shape[0])
-        groups = [(idxs[0], [r.tobytes() for r in rows])] if joint else [(i, [rows[k].tobytes()]) for k, i in enumerate(idxs)]
-        for i, payloads in groups:
+        if joint:
+            groups = [(idxs[0], ns[0], [r.tobytes() for r in rows])]
+        else:
+            groups = [(i, n, [rows[k][:packed_bytes(n_q, n // 320, BITS)].tobytes()]) for k, (i, n) in enumerate(zip(idxs, ns))]
+        for i, n, payloads in groups:
             path = output_path(files[i], inp_args.input_dir, inp_args.output_dir, ".wav", ".ecdc")
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             with open(path, "wb") as fo:
@@ -54,6 +82,7 @@ def compress(inp_args) -> List[str]:
     from .sample import _unsupported, build_engines
 
     _unsupported(inp_args)
+    ragged_options(inp_args)                    # (refusals before anything is loaded)
     rank, local_rank, world = parallel.init_process_group("nccl")
     files = sorted(glob.glob(os.path.join(inp_args.input_dir, "**/*.wav"), recursive=True))
     inp_args.in_flight = 1                      # one engine: the encode has nothing to keep in flight
@@ -64,10 +93,18 @@ def compress(inp_args) -> List[str]:
         eng.close()
 
 
-def main(argv=None):
+def build_cli_parser():
     p = build_parser()
     p.description = "compress wav files to ECDC containers of their RVQ codes"
-    return compress(p.parse_args(argv))
+    for act in p._actions:      # the shared flags, described for this CLI
+        if act.dest == "ragged":
+            act.help = ("encode mono files of DIFFERENT lengths in shared batches (Engine.get_cond_ragged); files are trimmed to 640 "
+                        "samples as without the flag and every container is byte-identical to the one written without it")
+    return p
+
+
+def main(argv=None):
+    return compress(build_cli_parser().parse_args(argv))
 
 
 if __name__ == "__main__":

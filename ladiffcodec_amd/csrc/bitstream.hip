@@ -127,18 +127,23 @@ __device__ __forceinline__ const int* cdf_row(const int* cdf, int card, int mode
   return cdf + (size_t)(mode == 0 ? (size_t)b * S + s : (size_t)(s % period)) * card;
 }
 
+// RAGGED: stream b codes its first n_sym[b] <= S symbols of the padded row (tables: row b*S + s as before, or the static ones) and
+// flushes there, so its bytes are those of a call of its own with S = n_sym[b]; the decoder writes 0 behind them.
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void ac_encode_kernel(const int* symbols, const int* cdf, int B, int S, int card, int mode,
                                                        int period, int trb, uint8_t* out, int64_t out_stride, int64_t cap,
-                                                       int64_t* nbytes) {
+                                                       int64_t* nbytes, const int* n_sym) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
+  const int Sb = RAGGED ? n_sym[b] : S;
+  if (RAGGED && (Sb < 0 || Sb > S)) { nbytes[b] = -1; return; }
   BitSink sink{out + (size_t)b * out_stride, cap, 0, 0u, 0, false};
   unsigned long long low = 0, high = 0;
   int max_bit = -1;
   const unsigned long long full = 1ull << trb;
   const double inv = 1.0 / (double)full;
   bool bad = false;
-  for (int s = 0; s < S && !bad; ++s) {
+  for (int s = 0; s < Sb && !bad; ++s) {
     const int sym = symbols[(size_t)b * S + s];
     const int* q = cdf_row(cdf, card, mode, period, b, S, s);
     if (sym < 0 || sym >= card) { bad = true; break; }
@@ -166,11 +171,17 @@ __global__ __launch_bounds__(64) void ac_encode_kernel(const int* symbols, const
   nbytes[b] = (bad || sink.overflow) ? -1 : sink.n;
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void ac_decode_kernel(const uint8_t* in, int64_t in_stride, const int64_t* nbytes, const int* cdf,
                                                        int B, int S, int card, int mode, int period, int trb, int* symbols,
-                                                       int* status) {
+                                                       int* status, const int* n_sym) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
+  const int Sb = RAGGED ? n_sym[b] : S;
+  if (RAGGED) {
+    if (Sb < 0 || Sb > S) { status[b] = 3; return; }   // a count outside [0, S]
+    for (int s = Sb; s < S; ++s) symbols[(size_t)b * S + s] = 0;
+  }
   const uint8_t* p = in + (size_t)b * in_stride;
   const int64_t nbits = 8 * nbytes[b];
   int64_t bitpos = 0;
@@ -179,7 +190,7 @@ __global__ __launch_bounds__(64) void ac_decode_kernel(const uint8_t* in, int64_
   const unsigned long long full = 1ull << trb;
   const double inv = 1.0 / (double)full;
   int st = 0;
-  for (int s = 0; s < S && st == 0; ++s) {
+  for (int s = 0; s < Sb && st == 0; ++s) {
     const int* q = cdf_row(cdf, card, mode, period, b, S, s);
     while (high - low + 1 < full) {                                                              // ac.py:228-236
       if (bitpos >= nbits) { st = 1; break; }                                                    // stream exhausted
@@ -219,17 +230,25 @@ __global__ __launch_bounds__(64) void ac_decode_kernel(const uint8_t* in, int64_
 }
 
 hipError_t launch_ac_encode(const int* symbols, const int* cdf, int B, int S, int card, int mode, int period, int trb, uint8_t* out,
-                            int64_t out_stride, int64_t cap, int64_t* nbytes, hipStream_t s) {
+                            int64_t out_stride, int64_t cap, int64_t* nbytes, hipStream_t s, const int* n_sym) {
   if (B <= 0) return hipSuccess;
-  hipLaunchKernelGGL(ac_encode_kernel, dim3((B + 63) / 64), dim3(64), 0, s, symbols, cdf, B, S, card, mode, period, trb, out, out_stride,
-                     cap, nbytes);
+  if (n_sym)
+    hipLaunchKernelGGL(ac_encode_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, s, symbols, cdf, B, S, card, mode, period, trb, out,
+                       out_stride, cap, nbytes, n_sym);
+  else
+    hipLaunchKernelGGL(ac_encode_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, s, symbols, cdf, B, S, card, mode, period, trb, out,
+                       out_stride, cap, nbytes, n_sym);
   return hipGetLastError();
 }
 hipError_t launch_ac_decode(const uint8_t* in, int64_t in_stride, const int64_t* nbytes, const int* cdf, int B, int S, int card, int mode,
-                            int period, int trb, int* symbols, int* status, hipStream_t s) {
+                            int period, int trb, int* symbols, int* status, hipStream_t s, const int* n_sym) {
   if (B <= 0) return hipSuccess;
-  hipLaunchKernelGGL(ac_decode_kernel, dim3((B + 63) / 64), dim3(64), 0, s, in, in_stride, nbytes, cdf, B, S, card, mode, period, trb,
-                     symbols, status);
+  if (n_sym)
+    hipLaunchKernelGGL(ac_decode_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, s, in, in_stride, nbytes, cdf, B, S, card, mode, period,
+                       trb, symbols, status, n_sym);
+  else
+    hipLaunchKernelGGL(ac_decode_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, s, in, in_stride, nbytes, cdf, B, S, card, mode, period,
+                       trb, symbols, status, n_sym);
   return hipGetLastError();
 }
 

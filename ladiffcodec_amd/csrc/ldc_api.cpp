@@ -2764,7 +2764,46 @@ struct FrontSrc {
   int bits = 0, n_q = 0;
 };
 
-// rag (ldc_decode_ragged): the items' own lengths in samples (host, validated); T is then the padded length
+// The sender's front end of a right-padded batch (ldc_decode_ragged, ldc_get_cond_ragged): cond encoder -> RVQ -> mask over items
+// b0 .. b0 + Bk - 1 of `wav` [B][T] (zero behind every item).  lens: the whole batch's lengths in samples (host); flens_dev: its
+// condition frames per item (device).  The rows (scratch, [Bk * F][D]) and the codes ([n_q][B][F]; only with b0 = 0, Bk = B) of an
+// item are those of get_cond_rows on the item alone, and 0 behind its last frame (RVQ is per frame).
+static int ragged_cond_rows(ldc_ctx* c, const float* wav, int B, int b0, int Bk, int T, const int32_t* lens, const int* flens_dev,
+                            float bandwidth, Arena& ar, bool dry, hipStream_t sk, float** q_rows, int* F_out, int64_t* codes_out,
+                            int teams) {
+  const Codec& cc = c->codec[LDC_MODEL_COND];
+  const int F = T / cc.hop, D = c->cfg.rep_dims, n_q = n_q_for_bandwidth(c, bandwidth);
+  if (codes_out && (b0 != 0 || Bk != B)) return fail(LDC_E_INVALID, "internal: the codes of a ragged batch are written for the whole batch");
+  float* qr = nullptr;
+  int Fq = 0;
+  LDCCHK(get_cond_rows(c, wav + (size_t)b0 * T, Bk, T, bandwidth, ar, dry, sk, &qr, &Fq, codes_out, teams));
+  if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
+  // an item with no more frames than the encoder's last conv pads on the left (k - 1 = 6) is NOT a prefix of its padded self -- the
+  // reference's reflect padding falls back to zeros plus a shorter reflection when the input is that short (conv.py:81-98) -- so such
+  // an item is encoded once more on its own and its rows and codes replace the batch's
+  const int short_max = cc.enc.empty() ? 0 : cc.enc.back().k - 1;
+  for (int b = b0; b < b0 + Bk; ++b) {
+    const int Fb = lens[b] / cc.hop;
+    if (Fb > short_max) continue;
+    float* q1 = nullptr;
+    int F1 = 0;
+    int64_t* codes1 = codes_out ? (int64_t*)ar.alloc((size_t)n_q * Fb * 8) : nullptr;
+    LDCCHK(get_cond_rows(c, wav + (size_t)b * T, 1, lens[b], bandwidth, ar, dry, sk, &q1, &F1, codes1, teams));
+    if (dry) continue;
+    HIPCHK(hipMemcpyAsync(qr + (size_t)(b - b0) * F * D, q1, (size_t)F1 * D * 4, hipMemcpyDeviceToDevice, sk));
+    if (codes_out)
+      HIPCHK(hipMemcpy2DAsync(codes_out + (size_t)b * F, (size_t)B * F * 8, codes1, (size_t)F1 * 8, (size_t)F1 * 8, n_q, hipMemcpyDeviceToDevice, sk));
+  }
+  if (!dry) {   // codes and condition behind an item's last frame are 0
+    if (codes_out) HIPCHK(launch_mask_codes(codes_out, n_q, Bk, F, flens_dev + b0, sk));
+    HIPCHK(launch_mask_rows(DT_F32, qr, Bk, F, D, flens_dev + b0, 0, sk));
+  }
+  *q_rows = qr;
+  *F_out = F;
+  return LDC_OK;
+}
+
+// rag (ldc_decode_ragged, ldc_decode_codes_ragged): the items' own lengths in samples (host, validated); T is then the padded length
 static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_steps, bool ddim, bool draws, const float* noise, int per_item,
                        float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream, const int32_t* rag = nullptr) {
   const Codec& cc = c->codec[LDC_MODEL_COND];
@@ -2799,12 +2838,14 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
     if (rag) {
       lens_all = (int*)ar.alloc((size_t)B * 4);
       flens_all = (int*)ar.alloc((size_t)B * 4);
-      float* wm = (float*)ar.alloc((size_t)B * T * 4);
+      float* wm = src.wav ? (float*)ar.alloc((size_t)B * T * 4) : nullptr;
       if (!dry) {
         HIPCHK(launch_lens_write(lens_all, rag_lat.data(), B, s));
         HIPCHK(launch_lens_write(flens_all, rag_fr.data(), B, s));
-        HIPCHK(hipMemcpyAsync(wm, src.wav, (size_t)B * T * 4, hipMemcpyDeviceToDevice, s));
-        HIPCHK(launch_mask_rows(DT_F32, wm, B, L, mc.hop, lens_all, 0, s));
+        if (wm) {
+          HIPCHK(hipMemcpyAsync(wm, src.wav, (size_t)B * T * 4, hipMemcpyDeviceToDevice, s));
+          HIPCHK(launch_mask_rows(DT_F32, wm, B, L, mc.hop, lens_all, 0, s));
+        }
       }
       wav_in = wm;
     }
@@ -2825,35 +2866,15 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
       float* qr = nullptr;
       int Fq = 0;
       if (src.wav) {
-        LDCCHK(get_cond_rows(c, wav_in + (size_t)b0 * T, Bk, T, 0.f, ar, dry, sk, &qr, &Fq, codes_out, n_front));
-        // ragged: an item with no more frames than the encoder's last conv pads on the left (k - 1 = 6) is NOT a prefix of its padded
-        // self -- the reference's reflect padding falls back to zeros plus a shorter reflection when the input is that short
-        // (conv.py:81-98) -- so such an item is encoded once more on its own and its rows and codes replace the batch's
-        if (rag) {
-          const int short_max = cc.enc.empty() ? 0 : cc.enc.back().k - 1;
-          const int n_q = n_q_for_bandwidth(c, 0.f);
-          for (int b = b0; b < b0 + Bk; ++b) {
-            if (rag_fr[b] > short_max) continue;
-            float* q1 = nullptr;
-            int F1 = 0;
-            int64_t* codes1 = codes_out ? (int64_t*)ar.alloc((size_t)n_q * rag_fr[b] * 8) : nullptr;
-            LDCCHK(get_cond_rows(c, wav_in + (size_t)b * T, 1, rag[b], 0.f, ar, dry, sk, &q1, &F1, codes1, n_front));
-            if (dry) continue;
-            HIPCHK(hipMemcpyAsync(qr + (size_t)(b - b0) * F * D, q1, (size_t)F1 * D * 4, hipMemcpyDeviceToDevice, sk));
-            if (codes_out)
-              HIPCHK(hipMemcpy2DAsync(codes_out + (size_t)b * F, (size_t)B * F * 8, codes1, (size_t)F1 * 8, (size_t)F1 * 8, n_q, hipMemcpyDeviceToDevice, sk));
-          }
-        }
-        if (rag && !dry) {   // codes and condition behind an item's last frame are 0 (RVQ is per frame)
-          if (codes_out) HIPCHK(launch_mask_codes(codes_out, n_q_for_bandwidth(c, 0.f), Bk, F, flens_all + b0, sk));
-          HIPCHK(launch_mask_rows(DT_F32, qr, Bk, F, D, flens_all + b0, 0, sk));
-        }
+        if (rag) LDCCHK(ragged_cond_rows(c, wav_in, B, b0, Bk, T, rag, flens_all, 0.f, ar, dry, sk, &qr, &Fq, codes_out, n_front));
+        else LDCCHK(get_cond_rows(c, wav_in + (size_t)b0 * T, Bk, T, 0.f, ar, dry, sk, &qr, &Fq, codes_out, n_front));
       } else {
         qr = (float*)ar.alloc((size_t)Bk * F * D * 4);
         Fq = F;
+        // ragged: rows behind an item's frames are 0 and their codes are never read (a packed item ends after its own bytes)
         if (!dry)
           HIPCHK(launch_rvq_dequant(src.codes, src.packed, src.packed_stride, src.bits, src.n_q, B, b0, Bk, F, cc.codebooks, cc.bins, D, qr,
-                                    c->dev_flag_dev, sk));
+                                    c->dev_flag_dev, sk, rag ? flens_all + b0 : nullptr));
       }
       if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
       // start image: upsample, /= max|.|+1e-8 (sample.py:125-129)
@@ -2961,6 +2982,35 @@ extern "C" int ldc_decode_ragged(ldc_ctx* c, const float* wav, const int32_t* le
   return decode_body(c, src, B, Tmax, n_steps, t_start > 0, draws, noise, 1, wav_out, latents_out, cond_out, codes_out, stream, lengths_host);
 }
 
+// ldc_get_cond on a right-padded batch (the sender side of ragged batches): every item's rows and codes as if encoded alone, 0 behind
+// its lengths[b] / hop frames.  Lengths are positive multiples of the cond hop: nothing here needs the UNet's quantum.
+extern "C" int ldc_get_cond_ragged(ldc_ctx* c, const float* wav, const int32_t* lengths_host, int B, int Tmax, float bandwidth, float* cond_out,
+                                   int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_COND));
+  if (!wav || !cond_out || B <= 0 || Tmax <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  const Codec& cc = c->codec[LDC_MODEL_COND];
+  LDCCHK(check_ragged_lengths(lengths_host, B, Tmax, cc.hop, "samples"));
+  hipStream_t s = pick_stream(c, stream);
+  const int F = Tmax / cc.hop, D = c->cfg.rep_dims;
+  std::vector<int> fr(B);
+  for (int b = 0; b < B; ++b) fr[b] = lengths_host[b] / cc.hop;
+  LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
+    int* flens = (int*)ar.alloc((size_t)B * 4);
+    float* wm = (float*)ar.alloc((size_t)B * Tmax * 4);   // the waveform with zeros behind every item
+    if (!dry) {
+      HIPCHK(launch_lens_write(flens, fr.data(), B, s));
+      HIPCHK(hipMemcpyAsync(wm, wav, (size_t)B * Tmax * 4, hipMemcpyDeviceToDevice, s));
+      HIPCHK(launch_mask_rows(DT_F32, wm, B, F, cc.hop, flens, 0, s));
+    }
+    float* qr = nullptr;
+    int Fq = 0;
+    LDCCHK(ragged_cond_rows(c, wm, B, 0, B, Tmax, lengths_host, flens, bandwidth, ar, dry, s, &qr, &Fq, codes_out, 1));
+    if (!dry) HIPCHK(launch_from_cl(DT_F32, qr, cond_out, B, D, F, nullptr, 0, 0.f, s));
+    return LDC_OK;
+  }));
+  return finish_stream(c, stream);
+}
+
 // the receiver side: ldc_decode / ldc_decode_ddim from RVQ codes.  The context-free refusals come first (a NULL context sees them
 // too); then those that need the codec; bad code VALUES are found on the device (LDC_E_INVALID "[bad_code]", see check_dev_flag).
 static int codes_args(const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B, int F,
@@ -3020,6 +3070,39 @@ extern "C" int ldc_decode_codes_ddim(ldc_ctx* c, const int64_t* codes, const uin
   bool draws = false;
   LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
   return decode_body(c, src, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, nullptr, stream);
+}
+// ldc_decode_codes / ldc_decode_codes_ddim with the length semantics of ldc_decode_ragged: frames_host[b] frames of item b are its own
+// (multiples of the ragged quantum / 320), the codes behind them are never read, a packed item's stream is ldc_packed_bytes(n_q,
+// frames_host[b], bits) long; t_start 0: DDPM halfway sampling, > 0: DDIM; per-item normalisation; outputs 0 beyond an item's length.
+extern "C" int ldc_decode_codes_ragged(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                                       int Fmax, const int32_t* frames_host, int t_start, int n_steps, float eta, const float* noise,
+                                       float* wav_out, float* latents_out, float* cond_out, void* stream) {
+  if ((codes == nullptr) == (packed == nullptr)) return fail(LDC_E_INVALID, "exactly one of codes / packed must be given");
+  if (!wav_out || B <= 0 || Fmax <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (!frames_host) return fail(LDC_E_INVALID, "null lengths");
+  if (n_q < 1) return fail(LDC_E_INVALID, "n_q must be >= 1");
+  if (packed && (bits < 1 || bits > 16)) return fail(LDC_E_INVALID, "bits must be in [1,16]");
+  if (t_start < 0) return fail(LDC_E_INVALID, "t_start must be >= 0 (0: DDPM halfway sampling)");
+  if (n_steps < 1) return fail(LDC_E_INVALID, "n_steps must be >= 1");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  const Codec& cc = c->codec[LDC_MODEL_COND];
+  const long long quantum = lcm_ll(cc.hop, (long long)c->codec[LDC_MODEL_MAIN].hop << unet_halvings(c)) / cc.hop;
+  LDCCHK(check_ragged_lengths(frames_host, B, Fmax, quantum, "condition frames"));
+  if (packed) {   // a row holds its longest item; shorter items end sooner
+    int64_t need = 0;
+    for (int b = 0; b < B; ++b) need = std::max(need, (int64_t)ldc_packed_bytes(n_q, frames_host[b], bits));
+    if (packed_stride < need) return fail(LDC_E_INVALID, "packed_stride %lld < %lld packed bytes of the longest item", (long long)packed_stride, (long long)need);
+  }
+  if (c->w8) return fail(LDC_E_INVALID, "ragged batches are not available on the fp8 engine (its fused forms have no length-aware variant): use dtype bf16 or f32");
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Fmax, &src, &T));
+  bool draws = true;
+  if (t_start > 0) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  else if (n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
+  std::vector<int32_t> lens(B);
+  for (int b = 0; b < B; ++b) lens[b] = frames_host[b] * cc.hop;
+  return decode_body(c, src, B, T, n_steps, t_start > 0, draws, noise, 1, wav_out, latents_out, cond_out, nullptr, stream, lens.data());
 }
 
 

@@ -64,6 +64,31 @@ extern "C" int ldc_ac_decode(ldc_ctx* c, const uint8_t* in, int64_t in_stride, c
   return finish_stream(c, stream);
 }
 
+// ldc_ac_encode / ldc_ac_decode with a symbol count per stream (n_sym [B] int32 in device memory, 0 <= n_sym[b] <= S): the static-mode
+// payloads of containers of unequal length in one call.  A count outside [0, S] gives nbytes -1 / status 3 for that stream.
+extern "C" int ldc_ac_encode_ragged(ldc_ctx* c, const int32_t* symbols, const int32_t* n_sym, const int32_t* cdf, int B, int S, int card,
+                                    int n_static, int total_range_bits, uint8_t* out, int64_t out_stride, int64_t* nbytes_out, void* stream) {
+  LDCCHK(check_dev(c));
+  if (!symbols || !n_sym || !cdf || !out || !nbytes_out || B < 1 || S < 0 || card < 1 || n_static < 0 || out_stride < 1) return fail(LDC_E_INVALID, "bad arguments");
+  if (total_range_bits < 2 || total_range_bits > 30) return fail(LDC_E_INVALID, "total_range_bits must be <= 30 (ac.py:98)");
+  hipStream_t s = pick_stream(c, stream);
+  HIPCHK(launch_ac_encode(symbols, cdf, B, S, card, n_static ? 1 : 0, std::max(1, n_static), total_range_bits, out, out_stride, out_stride,
+                          nbytes_out, s, n_sym));
+  return finish_stream(c, stream);
+}
+
+extern "C" int ldc_ac_decode_ragged(ldc_ctx* c, const uint8_t* in, int64_t in_stride, const int64_t* nbytes, const int32_t* n_sym,
+                                    const int32_t* cdf, int B, int S, int card, int n_static, int total_range_bits, int32_t* symbols_out,
+                                    int32_t* status_out, void* stream) {
+  LDCCHK(check_dev(c));
+  if (!in || !nbytes || !n_sym || !cdf || !symbols_out || !status_out || B < 1 || S < 0 || card < 1 || n_static < 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (total_range_bits < 2 || total_range_bits > 30) return fail(LDC_E_INVALID, "total_range_bits must be <= 30 (ac.py:98)");
+  hipStream_t s = pick_stream(c, stream);
+  HIPCHK(launch_ac_decode(in, in_stride, nbytes, cdf, B, S, card, n_static ? 1 : 0, std::max(1, n_static), total_range_bits, symbols_out,
+                          status_out, s, n_sym));
+  return finish_stream(c, stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // audio front end: torchaudio.functional.resample as srcs/sample.py:84 calls it
 // ------------------------------------------------------------------------------------------------

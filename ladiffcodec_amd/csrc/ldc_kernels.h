@@ -315,7 +315,8 @@ hipError_t launch_rvq(const float* z_rows, int rows, int D, const float* codeboo
 // = LDC_DEV_BAD_CODE (flag: the context's host-mapped words; (codebook << 56 | item << 32 | frame) of one bad code in words 2..3).
 constexpr unsigned LDC_DEV_BAD_CODE = 3u;
 hipError_t launch_rvq_dequant(const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B_total, int b0,
-                              int Bk, int F, const float* codebooks, int bins, int D, float* quantized_rows, unsigned* flag, hipStream_t s);
+                              int Bk, int F, const float* codebooks, int bins, int D, float* quantized_rows, unsigned* flag, hipStream_t s,
+                              const int* flens = nullptr);
 hipError_t launch_sqnorm_rows(const float* x, int rows, int D, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
@@ -389,8 +390,8 @@ hipError_t launch_build_cdf(const float* pdf, int rows, int card, int total_rang
                             hipStream_t s);
 // mode 0: cdf table per (stream, step) [B*S][card]; mode 1: `period` static tables, symbol s uses table s % period
 hipError_t launch_ac_encode(const int* symbols, const int* cdf, int B, int S, int card, int mode, int period, int total_range_bits,
-                            uint8_t* out, int64_t out_stride, int64_t cap, int64_t* nbytes, hipStream_t s);
+                            uint8_t* out, int64_t out_stride, int64_t cap, int64_t* nbytes, hipStream_t s, const int* n_sym = nullptr);
 hipError_t launch_ac_decode(const uint8_t* in, int64_t in_stride, const int64_t* nbytes, const int* cdf, int B, int S, int card, int mode,
-                            int period, int total_range_bits, int* symbols, int* status, hipStream_t s);
+                            int period, int total_range_bits, int* symbols, int* status, hipStream_t s, const int* n_sym = nullptr);
 
 }  // namespace ldc

@@ -321,19 +321,32 @@ __global__ __launch_bounds__(256) void rvq_tiled_kernel(const float* __restrict_
 // stage order from 0.f, as rvq_tiled_kernel's qout and the reference (core_vq.py:338-340): the rows are bit-identical to the encode
 // side's.  A code outside [0, bins) is never used as an index: its row is NaN and the host-mapped flag word takes LDC_DEV_BAD_CODE,
 // with (codebook, item, frame) of one such code in words 2..3.
-template <bool PACKED, bool VEC2>
+// RAGGED (a right-padded batch): flens[i] frames of item b0 + i are its own.  Rows t < flens[i] are computed exactly as above (same
+// gather, same order of the sum: bit-identical to the rectangular kernel on the same codes); rows behind them are written as 0.f
+// without their codes being read or checked, and a packed item's stream ends after the bytes of ITS frames: nothing behind byte
+// ldc_packed_bytes(n_q, flens[i], bits) of its row is read, so the payloads of unequal containers sit side by side at any stride.
+template <bool PACKED, bool VEC2, bool RAGGED>
 __global__ __launch_bounds__(256) void rvq_dequant_kernel(const int64_t* __restrict__ codes, const uint8_t* __restrict__ packed,
                                                           int64_t stride, int bits, int n_q, int B_total, int b0, int rows, int F,
                                                           const float* __restrict__ cb, int bins, int D, float* __restrict__ qout,
-                                                          unsigned* flag) {
+                                                          unsigned* flag, const int* __restrict__ flens) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;   // (wave-uniform)
   const int b = b0 + r / F, t = r % F;
+  int Fb = F;   // the item's own frames
+  if (RAGGED) {
+    Fb = min(max(flens[r / F], 0), F);
+    if (t >= Fb) {   // (wave-uniform) padding: zero rows, no code read
+      float* z = qout + (size_t)r * D;
+      for (int c = lane; c < D; c += 64) z[c] = 0.f;
+      return;
+    }
+  }
   int64_t code = 0;
   if (lane < n_q) {
     if (PACKED) {
-      const int64_t bit0 = ((int64_t)t * n_q + lane) * bits, j0 = bit0 >> 3, nbytes = ((int64_t)n_q * F * bits + 7) / 8;
+      const int64_t bit0 = ((int64_t)t * n_q + lane) * bits, j0 = bit0 >> 3, nbytes = ((int64_t)n_q * Fb * bits + 7) / 8;
       const uint8_t* row = packed + (size_t)b * stride;
       uint32_t acc = 0;
 #pragma unroll
@@ -418,21 +431,33 @@ hipError_t launch_rvq(const float* z_rows, int rows, int D, const float* codeboo
   return hipGetLastError();
 }
 
+template <bool PACKED, bool VEC2, bool RAGGED>
+static void launch_rvq_dequant_as(dim3 grid, hipStream_t s, const int64_t* codes, const uint8_t* packed, int64_t stride, int bits, int n_q,
+                                  int B_total, int b0, int rows, int F, const float* cb, int bins, int D, float* qout, unsigned* flag,
+                                  const int* flens) {
+  hipLaunchKernelGGL((rvq_dequant_kernel<PACKED, VEC2, RAGGED>), grid, dim3(256), 0, s, codes, packed, stride, bits, n_q, B_total, b0, rows, F, cb,
+                     bins, D, qout, flag, flens);
+}
+
 hipError_t launch_rvq_dequant(const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B_total, int b0,
-                              int Bk, int F, const float* codebooks, int bins, int D, float* quantized_rows, unsigned* flag, hipStream_t s) {
+                              int Bk, int F, const float* codebooks, int bins, int D, float* quantized_rows, unsigned* flag, hipStream_t s,
+                              const int* flens) {
   if ((codes == nullptr) == (packed == nullptr) || !flag || n_q < 1 || n_q > 64 || Bk < 1 || F < 1 || D < 1 || b0 < 0) return hipErrorInvalidValue;
   if (packed && (bits < 1 || bits > 16)) return hipErrorInvalidValue;
   if (codes && b0 + Bk > B_total) return hipErrorInvalidValue;
   const int rows = Bk * F;
-  const dim3 grid((rows + 3) / 4), block(256);
+  const dim3 grid((rows + 3) / 4);
   const bool v2 = D % 128 == 0;
-  if (packed) {
-    if (v2) hipLaunchKernelGGL((rvq_dequant_kernel<true, true>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
-    else hipLaunchKernelGGL((rvq_dequant_kernel<true, false>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
+#define LDC_DEQUANT(P, V, R) \
+  launch_rvq_dequant_as<P, V, R>(grid, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag, flens)
+  if (flens) {
+    if (packed) { if (v2) LDC_DEQUANT(true, true, true); else LDC_DEQUANT(true, false, true); }
+    else { if (v2) LDC_DEQUANT(false, true, true); else LDC_DEQUANT(false, false, true); }
   } else {
-    if (v2) hipLaunchKernelGGL((rvq_dequant_kernel<false, true>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
-    else hipLaunchKernelGGL((rvq_dequant_kernel<false, false>), grid, block, 0, s, codes, packed, packed_stride, bits, n_q, B_total, b0, rows, F, codebooks, bins, D, quantized_rows, flag);
+    if (packed) { if (v2) LDC_DEQUANT(true, true, false); else LDC_DEQUANT(true, false, false); }
+    else { if (v2) LDC_DEQUANT(false, true, false); else LDC_DEQUANT(false, false, false); }
   }
+#undef LDC_DEQUANT
   return hipGetLastError();
 }
 

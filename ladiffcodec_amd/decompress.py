@@ -9,6 +9,11 @@ from them (Engine.decode_codes): the cond encoder does not run.  Batching, per-i
 mono stream under `--chunk_sec` is cut at frame counts that are multiples of chunk_quantum / 320, its chunks decoded as batch
 items and their raw decoder outputs joined and normalised over the whole recording.  The codes of such a recording come from
 a whole-file encode, so that output is not `srcs.sample --chunk_sec` of the waveform.
+
+`--ragged [--ragged_waste W]` decodes mono containers of DIFFERENT lengths in shared batches (plan_container_batches,
+Engine.decode_codes_ragged): containers are grouped by (nc, bits, mode) and those whose frame count -- from the header -- is a
+multiple of chunk_quantum / 320 are packed within the waste bound; the others (a sender trims to 640 samples, not to the receiver's
+quantum) and multi-channel files keep the per-length batches, untrimmed.  Every file decodes as it does without the flag.
 """
 from __future__ import annotations
 
@@ -34,7 +39,39 @@ def build_parser() -> argparse.ArgumentParser:
     p.description = "decompress ECDC containers of RVQ codes to wav files"
     for flag, kw in _FLAGS:
         p.add_argument(flag, **kw)
+    for act in p._actions:      # the shared flag, described for this CLI
+        if act.dest == "ragged":
+            act.help = ("decode mono containers of DIFFERENT lengths in shared batches (Engine.decode_codes_ragged); only containers "
+                        "whose frame count is a multiple of the chunk quantum / 320 (8 frames for --enc_ratios 8 4) are packed, the "
+                        "others keep the equal-length batches; nothing is trimmed")
     return p
+
+
+def plan_container_batches(metas: List[dict], rank: int, world: int, batch_size: int, waste: float, quantum: int,
+                           bits: int = BITS) -> List[Tuple[List[int], bool, bool]]:
+    """--ragged work list of one rank over container headers: [(indices, joint, ragged)].  The files are dealt to the ranks as
+    plan_batches deals them (parallel.shard_utterances over `al`); a batch shares (nc, bits, mode).  Mono containers whose length is
+    a positive multiple of `quantum` samples are packed by plan_ragged_batches' rule (longest first, at most batch_size, closed before
+    B * Tmax exceeds (1 + waste) x the samples held) -- ragged; every other container falls back to plan_batches' equal-length
+    batches (multi-channel ones alone, joint) -- not ragged."""
+    from . import parallel
+    from .sample import plan_batches, plan_ragged_batches
+    lengths = [int(m["al"]) for m in metas]
+    mine = parallel.shard_utterances(lengths, rank, world)
+    groups: Dict[tuple, List[int]] = {}
+    for i in mine:
+        groups.setdefault((int(metas[i]["nc"]), int(bits), str(metas[i].get("ac", "none"))), []).append(i)
+    work: List[Tuple[List[int], bool, bool]] = []
+    for _, idx in sorted(groups.items()):
+        is_al = [int(metas[i].get("ch", 1)) == 1 and lengths[i] % quantum == 0 for i in idx]
+        aligned = [i for i, ok in zip(idx, is_al) if ok]
+        rest = [i for i, ok in zip(idx, is_al) if not ok]
+        # (rank 0 of a world of 1: the sub-lists are this rank's already)
+        for sub, _ in plan_ragged_batches([lengths[i] for i in aligned], [1] * len(aligned), 0, 1, batch_size, waste, quantum):
+            work.append(([aligned[k] for k in sub], False, True))
+        for sub, joint in plan_batches([lengths[i] for i in rest], [int(metas[i].get("ch", 1)) for i in rest], 0, 1, batch_size):
+            work.append(([rest[k] for k in sub], joint, False))
+    return work
 
 
 def sampler_from_args(a):
@@ -89,6 +126,22 @@ class EcdcSource:
             raise ValueError(f"one batch mixes numbers of codebooks {sorted(n_q)}")
         return CodesBatch(packed=torch.from_numpy(np.array(rows)), n_q=n_q.pop(), F=n // 320, bits=BITS)
 
+    def plan_ragged(self, rank: int, world: int, batch_size: int, waste: float, quantum: int):
+        return plan_container_batches([m for m, _, _ in self.parsed], rank, world, batch_size, waste, quantum)
+
+    def ragged_batch(self, idxs: List[int], quantum: int):
+        """-> (RaggedCodesBatch: row b = container idxs[b]'s own payload, zeros behind it; the items' lengths in samples)"""
+        import torch
+        from .sample import RaggedCodesBatch
+        n_q = {self.n_q(i) for i in idxs}
+        if len(n_q) != 1:
+            raise ValueError(f"one batch mixes numbers of codebooks {sorted(n_q)}")
+        rows = [self.parsed[i][1][0] for i in idxs]
+        packed = np.zeros((len(idxs), max(len(r) for r in rows)), np.uint8)
+        for b, r in enumerate(rows):
+            packed[b, :len(r)] = r
+        return RaggedCodesBatch(torch.from_numpy(packed), n_q.pop(), [self.parsed[i][2] for i in idxs], BITS), [self.shapes[i][1] for i in idxs]
+
     def chunk_batch(self, part: List[Tuple[int, int, int]], ln: int) -> CodesBatch:
         """codes [n_q, len(part), ln // 320] of chunks (file, order, start sample) of mono streams"""
         import torch
@@ -106,7 +159,9 @@ def decompress(inp_args) -> List[str]:
     from .sample import _unsupported, build_engines, decode_files
     from .spec import CodecConfig
 
+    from .compress import ragged_options
     _unsupported(inp_args)
+    ragged_options(inp_args)                        # (refusals before anything is loaded)
     sampler = sampler_from_args(inp_args)
     # the codebooks the cond quantizer is built with (as build_engines builds it: ratios [8,5,4,2] at --cond_bandwidth)
     n_q_layers = CodecConfig(enc_ratios=(8, 5, 4, 2), quantization=True, bandwidth=inp_args.cond_bandwidth).n_q_layers

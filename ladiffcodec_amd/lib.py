@@ -22,7 +22,7 @@ EXPORTS = [
     "ldc_last_error", "ldc_version", "ldc_create", "ldc_destroy", "ldc_reseed", "ldc_set_option", "ldc_quantize_e4m3", "ldc_set_weight", "ldc_finalize_weights",
     "ldc_seanet_encode", "ldc_seanet_decode", "ldc_rvq_encode", "ldc_rvq_decode", "ldc_get_cond",
     "ldc_cond_upsample", "ldc_unet_forward", "ldc_p_sample", "ldc_denoise", "ldc_p_sample_loop", "ldc_infilling", "ldc_output_normalise", "ldc_decode", "ldc_ddim_times", "ldc_ddim_sample", "ldc_decode_ddim", "ldc_decode_codes", "ldc_decode_codes_ddim",
-    "ldc_decode_ragged", "ldc_unet_forward_ragged",
+    "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
     "ldc_sconv1d", "ldc_sconvtr1d", "ldc_slstm", "ldc_unet_debug_tap", "ldc_unet_step_cost", "ldc_profile_enable",
     "ldc_profile_read", "ldc_profile_read_classes", "ldc_conv_microbench", "ldc_conv_compare", "ldc_conv_compare_fp8", "ldc_ln_fold_compare", "ldc_gn_microbench", "ldc_host_stats", "ldc_stream_info", "ldc_clock_sample", "ldc_debug_raise_failure", "ldc_debug_attn_core", "ldc_debug_attention_block", "ldc_debug_sea_conv", "ldc_debug_sea_op", "ldc_debug_sync_count", "ldc_xcc_census", "ldc_timeline_enable", "ldc_timeline_read", "ldc_kstamps_enable", "ldc_kstamps_reset", "ldc_kstamps_read", "ldc_packed_bytes", "ldc_pack_codes", "ldc_unpack_codes",
     "ldc_ac_build_cdf", "ldc_ac_encode", "ldc_ac_decode", "ldc_train_q_sample", "ldc_train_num_timesteps", "ldc_train_predict_x_start", "ldc_train_neg_sdsdr", "ldc_train_l1_loss", "ldc_train_block_ws_floats",
@@ -107,6 +107,10 @@ def load() -> C.CDLL:
     lib.ldc_decode_codes.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, fp, i32, fp, fp, fp, vp]
     lib.ldc_decode_codes_ddim.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, C.c_float, fp, i32, fp, fp, fp, vp]
     lib.ldc_decode_ragged.argtypes = [vp, fp, C.POINTER(C.c_int32), i32, i32, i32, i32, C.c_float, fp, fp, fp, fp, vp, vp]
+    lib.ldc_get_cond_ragged.argtypes = [vp, fp, C.POINTER(C.c_int32), i32, i32, C.c_float, fp, vp, vp]
+    lib.ldc_decode_codes_ragged.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, C.c_float, fp, fp, fp, fp, vp]
+    lib.ldc_ac_encode_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
+    lib.ldc_ac_decode_ragged.argtypes = [vp, vp, C.c_int64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldc_unet_forward_ragged.argtypes = [vp, fp, i32, fp, C.POINTER(C.c_int32), i32, i32, i32, fp, vp]
     lib.ldc_sconv1d.argtypes = [vp, fp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, fp, vp]
     lib.ldc_sconvtr1d.argtypes = [vp, fp, i32, i32, i32, vp, vp, i32, i32, i32, i32, fp, vp]

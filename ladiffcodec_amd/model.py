@@ -214,6 +214,25 @@ class Engine:
         self._exit()
         return (cond, codes) if return_codes else cond
 
+    def get_cond_ragged(self, wav, lengths, bandwidth: float = 0.0, return_codes: bool = False):
+        """`get_cond` of items of different lengths in one call (the sender side of a ragged batch): wav [B, 1, Tmax] right-padded,
+        lengths[b] samples of item b (multiples of the cond hop, 320).  Every item's rows and codes are those of `get_cond` on the item
+        alone; cond [B, D, Fmax] and codes [n_q, B, Fmax] are zero behind lengths[b] // 320 frames."""
+        wav = self._f32(wav)
+        B, _, T = wav.shape
+        lens = self._lengths(list(lengths), B)
+        F = T // self.cond_codec.hop_length
+        n_q = self.cond_codec.n_q_for_bandwidth(bandwidth if bandwidth > 0 else None)
+        cond = self._empty(B, self.cond_codec.rep_dims, F)
+        codes = self._empty(n_q, B, F, dtype=self.torch.int64) if return_codes else None
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_get_cond_ragged(self._ctx, wav.data_ptr(), lens, B, T, float(bandwidth), cond.data_ptr(),
+                                                 codes.data_ptr() if codes is not None else None, s))
+        finally:
+            self._exit()
+        return (cond, codes) if return_codes else cond
+
     def cond_upsample(self, cond, normalise: int = 0):
         cond = self._f32(cond)
         B, Cc, F = cond.shape
@@ -559,6 +578,35 @@ class Engine:
         L.check(self.lib.ldc_decode_codes_ddim(self._ctx, cp, pp, stride, int(bits), n_q, B, F, int(t_start), int(n_steps), float(eta),
                                                p(noise), int(per_item), out.data_ptr(), p(lat), p(cond), s))
         self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond}
+        return out
+
+    def decode_codes_ragged(self, codes=None, packed=None, frames=None, bits: int = 10, n_steps: Optional[int] = None, t_start: int = 0,
+                            eta: float = 0.0, noise=None, want_stages: bool = False, n_q: Optional[int] = None, F: Optional[int] = None):
+        """`decode_codes` (t_start 0) / `decode_codes_ddim` (t_start > 0) of items of different lengths in one call: frames[b] condition
+        frames of item b are its own (multiples of chunk_quantum // 320).  codes [n_q, B, Fmax] int64, or packed [B, stride] uint8 whose
+        row b holds item b's own payload of packed_bytes(n_q, frames[b], bits) bytes (n_q passed in; Fmax = F or max(frames)); what
+        lies behind an item's frames / bytes is never read.  Every item comes out as if decoded alone; outputs are zero beyond an
+        item's length.  want_stages: {"wav", "latents", "cond"}."""
+        if n_steps is None:
+            raise ValueError("n_steps is required")
+        if frames is None:
+            raise ValueError("frames is required")
+        frames = [int(v) for v in frames]
+        if packed is not None and F is None:
+            F = max(frames)
+        cp, pp, stride, n_q, B, F, keep = self._codes_args(codes, packed, bits, n_q, F)
+        fr = self._lengths(frames, B)
+        out, lat, cond = self._codes_outputs(B, F, want_stages)
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        try:
+            L.check(self.lib.ldc_decode_codes_ragged(self._ctx, cp, pp, stride, int(bits), n_q, B, F, fr, int(t_start), int(n_steps),
+                                                     float(eta), p(noise), out.data_ptr(), p(lat), p(cond), s))
+        finally:
+            self._exit()
         if want_stages:
             return {"wav": out, "latents": lat, "cond": cond}
         return out

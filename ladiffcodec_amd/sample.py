@@ -245,6 +245,17 @@ class LazyWavs:
         import torch
         return torch.from_numpy(np.stack([self[i][0, st:st + ln] for i, _, st in part])[:, None, :])
 
+    def plan_ragged(self, rank: int, world: int, batch_size: int, waste: float, quantum: int) -> List[Tuple[List[int], bool, bool]]:
+        """--ragged work list of one rank: [(file indices, joint, ragged)] -- plan_ragged_batches; its sub-quantum files are not ragged."""
+        lengths, channels = [sh[1] for sh in self.shapes], [sh[0] for sh in self.shapes]
+        return [(idxs, joint, not joint and lengths[idxs[0]] >= quantum)
+                for idxs, joint in plan_ragged_batches(lengths, channels, rank, world, batch_size, waste, quantum)]
+
+    def ragged_batch(self, idxs: List[int], quantum: int):
+        """-> (RaggedBatch of the files trimmed to whole quanta, their lengths in samples)"""
+        lens = [self.shapes[i][1] // quantum * quantum for i in idxs]
+        return RaggedBatch(self.padded_batch(idxs, lens), lens), lens
+
 
 def output_path(wav_file: str, input_dir: str, output_dir: str, in_ext: str = ".wav", out_ext: str = ".wav") -> str:
     """sample.py:75-81,136: save_path = output_dir + wav_file[len(input_dir):][:-4]; file = save_path + '.wav'.
@@ -308,14 +319,31 @@ class CodesBatch:
         return CodesBatch(mv(self.packed), mv(self.codes), self.n_q, self.F, self.bits)
 
 
+class RaggedCodesBatch:
+    """Containers of different lengths as one engine call: packed [B, stride] uint8, row b = item b's own payload (zeros behind it),
+    frames[b] condition frames of item b (multiples of chunk_quantum // 320).  CodesSampler routes it to Engine.decode_codes_ragged."""
+
+    def __init__(self, packed, n_q: int, frames, bits: int = 10):
+        self.packed, self.n_q, self.frames, self.bits = packed, int(n_q), [int(f) for f in frames], int(bits)
+
+    def to(self, device, non_blocking: bool = False):
+        return RaggedCodesBatch(self.packed.to(device, non_blocking=non_blocking), self.n_q, self.frames, self.bits)
+
+
 class CodesSampler:
-    """The decode of `inner` (DdpmSampler / DdimSampler) started from a CodesBatch: Engine.decode_codes / decode_codes_ddim."""
+    """The decode of `inner` (DdpmSampler / DdimSampler) started from a CodesBatch: Engine.decode_codes / decode_codes_ddim; from a
+    RaggedCodesBatch: Engine.decode_codes_ragged."""
 
     def __init__(self, inner):
         self.inner = inner
         self.n_steps = self.draws = inner.draws
 
     def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        if isinstance(batch, RaggedCodesBatch):
+            ddim = isinstance(self.inner, DdimSampler)
+            return eng.decode_codes_ragged(packed=batch.packed, frames=batch.frames, bits=batch.bits, n_q=batch.n_q,
+                                           n_steps=self.inner.n_steps, t_start=self.inner.t_start if ddim else 0,
+                                           eta=self.inner.eta if ddim else 0.0, noise=noise, want_stages=want_stages)
         kw = dict(codes=batch.codes, packed=batch.packed, bits=batch.bits, n_q=batch.n_q, F=batch.F, noise=noise, per_item=per_item,
                   want_stages=want_stages)
         if isinstance(self.inner, DdimSampler):
@@ -597,16 +625,15 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
             wavfile.write(path, 16000, np.ascontiguousarray(data))
             written.append(path)
 
-    if ragged:
-        work = plan_ragged_batches(lengths, channels, rank, world, inp_args.batch_size, ragged_waste, quantum)
+    if ragged:     # the source's own plan: (indices, joint, ragged) -- files it keeps out of ragged batches take the equal-length path
+        work = wavs.plan_ragged(rank, world, inp_args.batch_size, ragged_waste, quantum)
     else:
-        work = plan_batches(lengths, channels, rank, world, inp_args.batch_size)
-    for j, (idxs, joint) in enumerate(work):
+        work = [(idxs, joint, False) for idxs, joint in plan_batches(lengths, channels, rank, world, inp_args.batch_size)]
+    for j, (idxs, joint, is_ragged) in enumerate(work):
         lens = None
-        if ragged and not joint and lengths[idxs[0]] >= quantum:     # (plan_ragged_batches keeps sub-quantum files apart)
-            lens = [lengths[i] // quantum * quantum for i in idxs]
+        if is_ragged:
+            batch, lens = wavs.ragged_batch(idxs, quantum)
             n = max(lens)
-            batch = RaggedBatch(wavs.padded_batch(idxs, lens), lens)
         else:
             n = lengths[idxs[0]] // 640 * 640
             batch = wavs.batch(idxs, joint, n)

@@ -7,7 +7,8 @@
     python tools/ragged_time.py --case corpus [--files 256] [--waste 0.1 0.25 0.5]
         a seeded synthetic corpus of mono files with lengths uniform over 1.6-16 s on the 2560-sample quantum, decoded through the
         CLI path (sample.decode_files, one engine) without --ragged and with --ragged at every --waste: audio-seconds per
-        wall-second, mean batch size and padded fraction per setting.
+        wall-second, mean batch size and padded fraction per setting.  --codes: the corpus is compressed once (compress --ragged's
+        path, untimed) and the settings decode its CONTAINERS (decompress's path: EcdcSource, Engine.decode_codes[_ragged]).
 
 Each case is one process; run each under its own `timeout`, chained, nothing retried.  Prints text lines and one JSON line."""
 import argparse
@@ -78,7 +79,7 @@ def case_plan(rounds):
     e.close()
 
 
-def case_corpus(n_files, wastes, batch_size):
+def case_corpus(n_files, wastes, batch_size, codes=False):
     import numpy as np
     import torch
     from scipy.io import wavfile
@@ -99,26 +100,37 @@ def case_corpus(n_files, wastes, batch_size):
         files.sort()
         order = [int(os.path.basename(f)[1:5]) for f in files]
         flen = [lens[k] for k in order]
+        source = sampler = None
+        if codes:     # the receiver's side: the same files as containers (names keep the order)
+            from ladiffcodec_amd import compress, decompress
+            enc = os.path.join(tmp, "enc")
+            cargs = sample.build_parser().parse_args(["--model_for_cond", "x", "--input_dir", ind + "/", "--output_dir", enc + "/",
+                                                      "--batch_size", str(batch_size), "--ragged"])
+            files = sorted(compress.compress_files(e, files, cargs))
+            source = decompress.EcdcSource(files, e.cond_codec.n_q_layers)
+            sampler = sample.CodesSampler(sample.DdpmSampler(50))
         for label, extra in [("equal_length", [])] + [(f"ragged_w{w}", ["--ragged", "--ragged_waste", str(w)]) for w in wastes]:
             args = sample.build_parser().parse_args(["--model_for_cond", "x", "--enc_ratios", "8", "4", "--upsampling_ratios", "5", "2",
                                                      "--input_dir", ind + "/", "--output_dir", os.path.join(tmp, label) + "/",
                                                      "--midway_t", "50", "--batch_size", str(batch_size)] + extra)
             ragged, waste = sample.ragged_options(args)
-            if ragged:
+            if ragged and codes:
+                work = [w[:2] for w in source.plan_ragged(0, 1, batch_size, waste, q)]
+            elif ragged:
                 work = sample.plan_ragged_batches(flen, [1] * n_files, 0, 1, batch_size, waste, q)
             else:
                 work = sample.plan_batches(flen, [1] * n_files, 0, 1, batch_size)
             padded = sum(len(ix) * max(flen[i] for i in ix) for ix, _ in work)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            written = sample.decode_files(e, files, args, 0, 1, 0)
+            written = sample.decode_files(e, files, args, 0, 1, 0, sampler=sampler, source=source)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             assert len(written) == n_files
             out[label] = {"audio_s_per_wall_s": round(sum(flen) / 16000 / dt, 1), "wall_s": round(dt, 2), "batches": len(work),
                           "mean_batch": round(n_files / len(work), 2), "padded_fraction": round(1.0 - sum(flen) / padded, 4)}
             print(label, out[label])
-    print(json.dumps({"case": "corpus", "files": n_files, "audio_s": sum(lens) / 16000, "results": out}))
+    print(json.dumps({"case": "corpus_codes" if codes else "corpus", "files": n_files, "audio_s": sum(lens) / 16000, "results": out}))
     e.close()
 
 
@@ -129,11 +141,12 @@ def main():
     ap.add_argument("--files", type=int, default=256)
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--waste", type=float, nargs="+", default=[0.1, 0.25, 0.5])
+    ap.add_argument("--codes", action="store_true", help="--case corpus: decode the corpus' containers instead of its waveforms")
     a = ap.parse_args()
     if a.case == "plan":
         case_plan(a.rounds)
     else:
-        case_corpus(a.files, a.waste, a.batch_size)
+        case_corpus(a.files, a.waste, a.batch_size, a.codes)
 
 
 if __name__ == "__main__":
