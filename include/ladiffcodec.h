@@ -169,6 +169,39 @@ int ldc_get_cond(ldc_ctx* ctx, const float* wav, int B, int T, float bandwidth, 
  * and cond_out [B,D,Fmax] are zero behind lengths_host[b] / 320 frames.  What the padding of wav holds is never read into a value. */
 int ldc_get_cond_ragged(ldc_ctx* ctx, const float* wav, const int32_t* lengths_host, int B, int Tmax, float bandwidth,
                         float* cond_out, int64_t* codes_out, void* stream);
+/* stream sessions ------------------------------------------------------------------------------
+ * Both SEANet codecs are causal, so their ends can run chunk by chunk.  A stream object holds, for B independent streams of one
+ * (codec, side), what a chunk needs from the past: every conv's most recent input rows, the transposed convs' previous input row
+ * and the LSTM layers' (h, c).  Contract: split a sequence into chunks any way you like and push them through one item of a
+ * stream -- the item's concatenated outputs are what ldc_seanet_encode / ldc_seanet_decode / ldc_get_cond return for the whole
+ * sequence (same fp32 arithmetic; a chunk may take another split-K factor or LSTM kernel than the whole call, which moves
+ * values in the last bits only).  An item is FRESH after create / reset: its next chunk starts a sequence (left reflect padding as
+ * in the whole-sequence call, no previous transposed-conv row, h = c = 0).  Fresh items and items with history may share a call;
+ * all items advance by the same T (or L).  Refused with LDC_E_INVALID before any GPU work, ldc_last_error() naming the value: a T
+ * that is not a positive multiple of the codec's hop (an L <= 0), a call with a fresh item whose length is below
+ * ldc_stream_min_first, a stream object of the other side / another context, ldc_get_cond_stream on anything but the cond encoder's
+ * stream, a null pointer, B <= 0, and a (B, chunk) whose conv launches would not fit their LDS window (one-row chunks of thousands of
+ * items).  Calls on one stream object must be issued in order on one HIP stream.  A call that fails AFTER its GPU work has started
+ * (LDC_E_HIP, LDC_E_NOMEM) leaves part of the state advanced: the object then refuses every call with LDC_E_STATE until
+ * ldc_stream_reset with a NULL mask. */
+typedef struct ldc_stream ldc_stream;
+#define LDC_STREAM_ENCODER 0
+#define LDC_STREAM_DECODER 1
+/* host-only, no context or GPU needed (like ldc_ddim_times): smallest length of the FIRST chunk of a stream, in input units
+ * (samples for an encoder, latent frames for a decoder), for the codec described by cfg: the smallest multiple of the hop at which
+ * no conv of that side reads an input no longer than its left padding (below it the reference's pad1d zero-extends before it
+ * reflects and the result depends on what follows).  2240 samples = 7 frames for the cond encoder.  Negative: LDC_E_*. */
+int ldc_stream_min_first(const ldc_config* cfg, int which, int side);
+int ldc_stream_create(ldc_ctx* ctx, int which, int side, int B, ldc_stream** out);     /* B independent streams, all fresh */
+int ldc_stream_reset(ldc_stream* st, const uint8_t* item_mask_host /* [B], NULL = all */, void* stream);
+int ldc_stream_destroy(ldc_stream* st);   /* waits for the stream of the session's last call */
+/* wav [B,1,T] -> z_out [B,rep_dims,T/hop] */
+int ldc_seanet_encode_stream(ldc_ctx* ctx, ldc_stream* st, const float* wav, int T, float* z_out, void* stream);
+/* z [B,rep_dims,L] -> wav_out [B,1,L*hop] */
+int ldc_seanet_decode_stream(ldc_ctx* ctx, ldc_stream* st, const float* z, int L, float* wav_out, void* stream);
+/* the cond encoder's stream only: wav [B,1,T] -> cond_out [B,rep_dims,T/320], codes_out [n_q,B,T/320] (may be NULL) */
+int ldc_get_cond_stream(ldc_ctx* ctx, ldc_stream* st, const float* wav, int T, float bandwidth, float* cond_out, int64_t* codes_out,
+                        void* stream);
 /* for layer in diff_model.upsampling_layers: img = layer(img)   (sample.py:125-128, unet.py:372-377)
  * normalise: 0 = raw; 1 = img /= max|img|+1e-8 over the whole tensor (sample.py:129);
  *            2 = the same per batch item (a batch of independent utterances). cond [B,C,F] -> [B,C,L] */

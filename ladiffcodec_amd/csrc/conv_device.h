@@ -96,6 +96,16 @@ struct ConvKArgs {
   int* bm_out;             // host-only: dry run -- rows per tile the fast kernel would use (0: generic kernel); bm_out[1] = wave rows WM, bm_out[2] = split-K factor, bm_out[3] = columns per tile
 };
 
+// Stream sessions (ConvCall::ctx): second argument of conv_gemm_stream_kernel, the generic kernel's instantiation for context-carrying
+// launches.  The input such a launch sees is VIRTUAL -- per item `rows` context rows followed by the chunk's L_in - rows rows -- and only the
+// window staging knows (stream_row_src below).  Plain launches, and every other conv kernel, never see this structure.
+struct ConvStreamArgs {
+  const char* ctx;         // [B][rows][C1] most recent input rows of every item before this chunk
+  const int* fresh;        // [B] != 0: the item starts a sequence -- its context is the left reflect padding (or zero rows: `zero`)
+  int rows, zero;
+  FastDivU lin_div;        // division by L_in
+};
+
 // ---- geometry of one launch of the pipelined kernel (conv_fast.inc), decided on the host ----
 struct FastGeom {
   int a_rows;        // window rows per plane (multiple of 16 * waves); each plane is followed by a zero row
@@ -178,6 +188,22 @@ __device__ __forceinline__ int gather_row(const KA& a, int b, int l, int toff) {
   }
   if (u < 0 || u >= leff) return -1;
   return b * a.L_in + (u >> a.ups);
+}
+
+// Stream sessions: where virtual flat row v of a context-carrying launch lives.  Item b = v / L_in; position j = v % L_in - ctx_rows of
+// the chunk.  j >= 0 is the chunk's own row; j < 0 is row ctx_rows + j of the item's context when it has history, and for a fresh item
+// what the whole-sequence call pads with: the reflected chunk row -j (the first chunk of a stream is longer than every conv's padding:
+// ldc_stream_min_first) or, for a transposed conv, nothing (*zero).  Rows are stored before the prologue activation on both sides.
+template <typename T, typename KA>
+__device__ __forceinline__ const char* stream_row_src(const KA& a, const ConvStreamArgs& sa, const char* x, int ld, int v, bool* zero) {
+  const int b = (int)fdiv((unsigned)v, sa.lin_div);
+  const int lc = a.L_in - sa.rows;
+  const int j = v - b * a.L_in - sa.rows;
+  *zero = false;
+  if (j >= 0) return x + ((size_t)b * lc + j) * ld * sizeof(T);
+  if (!sa.fresh[b]) return sa.ctx + ((size_t)b * sa.rows + sa.rows + j) * ld * sizeof(T);
+  *zero = sa.zero != 0;
+  return x + ((size_t)b * lc + (sa.zero ? 0 : min(-j, lc - 1))) * ld * sizeof(T);
 }
 
 // [R_lo, R_hi]: flat input rows a BM-row tile starting at m0 touches (zero-pad convs; monotone in m and tap)

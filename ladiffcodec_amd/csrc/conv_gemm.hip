@@ -66,8 +66,9 @@ __device__ __forceinline__ uint4 expand_fp8x8_generic(const uint2& v) {
   return make_uint4(hw_bf16x2(a[0], a[1]), hw_bf16x2(b[0], b[1]), hw_bf16x2(c[0], c[1]), hw_bf16x2(d[0], d[1]));
 }
 
-template <typename T, int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const ConvKArgs a) {
+// CTX: the stream-session instantiation (conv_gemm_stream_kernel); false compiles to the kernel as it always was
+template <typename T, int WM, int WN, int TM, int TN, bool CTX>
+__device__ __forceinline__ void conv_gemm_body(const ConvKArgs& a, const ConvStreamArgs& sa) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
   constexpr int EPV = 16 / (int)sizeof(T);        // elements per 16-byte vector
   constexpr int BKE = kRowBytes / (int)sizeof(T);  // channels per chunk
@@ -133,7 +134,14 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const ConvKArgs 
       for (int q = 0; q < A_MAX; ++q) {
         const int idx = min(base + q * NT + tid, nrows * 4 - 1);   // clamped: unconditional load keeps v[] in registers
         const int r = idx >> 2, p = idx & 3;
-        v[q] = *reinterpret_cast<const uint4*>(src + ((size_t)(R_lo + r) * ld + coff + p * EPV) * sizeof(T));
+        if constexpr (CTX) {   // stream session: the window is virtual (context rows | chunk rows per item)
+          bool zero;
+          const char* rp = stream_row_src<T>(a, sa, src, ld, R_lo + r, &zero);
+          v[q] = *reinterpret_cast<const uint4*>(rp + ((size_t)coff + p * EPV) * sizeof(T));
+          if (zero) v[q] = make_uint4(0u, 0u, 0u, 0u);
+        } else {
+          v[q] = *reinterpret_cast<const uint4*>(src + ((size_t)(R_lo + r) * ld + coff + p * EPV) * sizeof(T));
+        }
       }
 #pragma unroll
       for (int q = 0; q < A_MAX; ++q) {
@@ -249,6 +257,15 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const ConvKArgs 
       }
     }
   }
+}
+
+template <typename T, int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const ConvKArgs a) {
+  conv_gemm_body<T, WM, WN, TM, TN, false>(a, ConvStreamArgs{});
+}
+template <typename T, int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(WM* WN * 64) void conv_gemm_stream_kernel(const ConvKArgs a, const ConvStreamArgs sa) {
+  conv_gemm_body<T, WM, WN, TM, TN, true>(a, sa);
 }
 
 // Split-K of the generic kernel (few-tile, long-K layers: the SEANet stacks' last strided convs, k=7 bottleneck convs and first
@@ -423,6 +440,22 @@ void pack_convtr_weights(const ConvLayer& ly, const float* w, int cin, int cout,
   });
 }
 
+// f32 only: the codec ends are fp32
+template <int WM, int WN, int TM, int TN>
+static hipError_t launch_cfg_stream(const ConvKArgs& a, const ConvStreamArgs& sa, int M, size_t lds, hipStream_t s) {
+  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  dim3 grid((M + BM - 1) / BM, a.n_pad / BN, std::max(1, a.ksplit));
+  auto kern = conv_gemm_stream_kernel<float, WM, WN, TM, TN>;
+  static bool lds_opt_in = false;
+  if (!lds_opt_in) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    lds_opt_in = true;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, s, a, sa);
+  return hipGetLastError();
+}
+
 template <typename T, int WM, int WN, int TM, int TN>
 static hipError_t launch_cfg(const ConvKArgs& a, int M, size_t lds, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -524,11 +557,60 @@ long long conv_generic_splitk_floats(const ConvLayer& ly, const ConvCall& c) {
   return ks > 1 ? (long long)ks * M * ly.n_pad : 0;
 }
 
+// Stream session launch: the generic kernel's context instantiation on the same tiles, split-K rule and epilogues as a plain launch.
+// The LDS window is sized from the tiles themselves: between the last GEMM row of an item and the first of the next the virtual input
+// advances by the context rows on top of the stride, so a tile that crosses item seams touches more rows (a one-row chunk: every row).
+static hipError_t launch_conv_stream(const ConvLayer& ly, const ConvCall& c, ConvKArgs& a, int M, hipStream_t s) {
+  if (conv_fast_eligible(ly) || ly.dt != DT_F32 || ly.w8 || ly.cin2 || ly.ups || ly.pad_left || !c.ctx_fresh || c.ctx_rows <= 0 || c.ctx_rows >= c.L_in ||
+      c.gn_sum || c.gn_part || c.colmax || c.y2 || c.qkv_ctx_ws || ly.ln_s)
+    return hipErrorInvalidValue;
+  ConvStreamArgs sa;
+  sa.ctx = (const char*)c.ctx; sa.fresh = c.ctx_fresh; sa.rows = c.ctx_rows; sa.zero = c.ctx_zero;
+  sa.lin_div = make_fastdiv((unsigned)c.L_in);
+  int bn = ly.bn;
+  const long tiles128 = (long)((M + 127) / 128) * (ly.n_pad / bn);
+  const bool small = tiles128 < 128 && ly.n_pad % 64 == 0 && bn >= 64;
+  if (small) bn = 64;
+  const int bm = small ? 64 : 128;
+  int need = 1;
+  for (int m0 = 0; m0 < M; m0 += bm) {   // tile_window (conv_device.h) on the host: pad_left 0, no reflection, ups 0
+    const int m1 = std::min(m0 + bm, M) - 1;
+    const long lo = (long)(m0 / c.L_rows) * c.L_in + std::min((m0 % c.L_rows) * ly.stride, c.L_in - 1);
+    const long hi = (long)(m1 / c.L_rows) * c.L_in + std::min((m1 % c.L_rows) * ly.stride + (ly.taps - 1) * ly.dil, c.L_in - 1);
+    need = std::max<long>(need, hi - lo + 1);
+  }
+  a.win_rows = need + 1;
+  a.tg = std::max(1, std::min(ly.taps, (40 * 1024) / (bn * kPitch)));
+  const size_t lds = (size_t)(a.win_rows + 1) * kPitch + (size_t)a.tg * bn * kPitch;
+  if (lds > 160 * 1024) return hipErrorOutOfMemory;   // (sea_conv_stream asks this in its dry pass and refuses the call before any GPU work)
+  if (c.check_only) return hipSuccess;
+  auto report = [&](int wm, int wn, int tm, int tn) {
+    if (!c.route_out) return;
+    const int r[8] = {CONV_ROUTE_GENERIC, wm, wn, tm, tn, a.ksplit, a.tg, bn};
+    std::copy(r, r + 8, c.route_out);
+  };
+  if (small) {
+    const int ks = generic_splitk(ly, c, M);
+    if (ks > 1) a.ksplit = ks;
+    report(2, 2, 1, 1);
+    hipError_t e = launch_cfg_stream<2, 2, 1, 1>(a, sa, M, lds, s);
+    if (e != hipSuccess || ks <= 1) return e;
+    const long n4 = (long)M * (a.n_pad / 4);
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel<float>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a, M);
+    return hipGetLastError();
+  }
+  if (bn == 128) { report(2, 2, 2, 2); return launch_cfg_stream<2, 2, 2, 2>(a, sa, M, lds, s); }
+  if (bn == 64) { report(2, 2, 2, 1); return launch_cfg_stream<2, 2, 2, 1>(a, sa, M, lds, s); }
+  report(4, 1, 1, 1);
+  return launch_cfg_stream<4, 1, 1, 1>(a, sa, M, lds, s);
+}
+
 hipError_t launch_conv(const ConvLayer& ly, const ConvCall& c, hipStream_t s) {
   ConvKArgs a;
   int M = 0, span = 0;
   hipError_t e0 = conv_kargs(ly, c, a, &M, &span);
   if (e0 != hipSuccess || M <= 0) return e0;
+  if (c.ctx) return launch_conv_stream(ly, c, a, M, s);
   if (!(c.tune && c.tune->force_generic) && conv_fast_eligible(ly)) {
     bool launched = false;
     hipError_t e = launch_conv_fast(ly, a, M, span, s, &launched);

@@ -1006,7 +1006,62 @@ int conv_out_len(const ConvLayer& ly, int L) {
 }
 
 
+// stream session: the conv's context entry, or null when the layer never reads before its chunk (k = 1)
+static int stream_conv_state(SeaRun& R, int rows, int ch, StreamConvState** out) {
+  *out = nullptr;
+  if (!R.st || rows <= 0) return LDC_OK;
+  if (R.st->conv_at >= R.st->convs.size() || R.st->convs[R.st->conv_at].rows != rows || R.st->convs[R.st->conv_at].ch != ch)
+    return fail(LDC_E_STATE, "stream state does not match the layer table (conv %zu: %d rows x %d channels)", R.st->conv_at, rows, ch);
+  *out = &R.st->convs[R.st->conv_at++];
+  return LDC_OK;
+}
+
+// A conv of a stream session: the launch sees (context | chunk) per item and pads nothing itself; the context of the next chunk is
+// written to the other buffer by a copy launch of its own
+static int sea_conv_stream(SeaRun& R, const ConvLayer& ly, StreamConvState& cs, const void* x, const void* residual, int L_in, void** y, int* L_out, int cout) {
+  if (!ly.tr_stride && L_in % ly.stride) return fail(LDC_E_INVALID, "stream chunk of %d rows is not a multiple of the layer's stride %d", L_in, ly.stride);
+  ConvLayer lv = ly;
+  lv.pad_left = 0;
+  ConvCall cc;
+  cc.B = R.B; cc.L_in = L_in + cs.rows; cc.x1 = x; cc.residual = residual; cc.tune = &R.c->tune; cc.route_out = R.route;
+  cc.ctx = cs.buf[R.st->parity]; cc.ctx_fresh = R.st->fresh_dev; cc.ctx_rows = cs.rows; cc.ctx_zero = ly.tr_stride ? 1 : 0;
+  if (ly.tr_stride) {   // row q of the 2-tap GEMM reads virtual rows q (the previous input row) and q + 1; the row the whole-sequence call trims is never formed
+    cc.L_rows = L_in;
+    cc.L_final = L_in * ly.tr_stride;
+    *L_out = cc.L_final;
+    cc.y_ld = ly.tr_cout;
+  } else {
+    cc.L_rows = L_in / ly.stride;
+    *L_out = cc.L_rows;
+    cc.y_ld = cout;
+  }
+  *y = R.ar->alloc((size_t)R.B * (*L_out) * cc.y_ld * 4);
+  cc.y = *y;
+  if (R.c->sea_splitk) {
+    const long long fl = conv_generic_splitk_floats(lv, cc);
+    if (fl > 0) {
+      cc.sk_part = (float*)R.ar->alloc((size_t)fl * 4);
+      cc.sk_part_cap = fl;
+      cc.generic_split = 1;
+    }
+  }
+  if (R.dry) {   // refused here, before any GPU work of the call: a launch whose tiles cross so many item seams that its LDS window does not fit
+    ConvCall chk = cc;
+    chk.check_only = 1; chk.route_out = nullptr;
+    if (launch_conv(lv, chk, R.s) != hipSuccess)
+      return fail(LDC_E_INVALID, "stream chunk of %d rows x B = %d items: the LDS window of a layer (%d context rows per item, stride %d) does not fit; "
+                                 "use longer chunks or fewer items per session", L_in, R.B, cs.rows, ly.stride);
+  } else {
+    HIPCHK(launch_conv(lv, cc, R.s));
+    HIPCHK(launch_stream_ctx_update((const float*)x, cs.buf[R.st->parity], cs.buf[R.st->parity ^ 1], R.st->fresh_dev, R.B, L_in, cs.rows, cs.ch, cc.ctx_zero, R.s));
+  }
+  return LDC_OK;
+}
+
 int sea_conv(SeaRun& R, const ConvLayer& ly, const void* x, const void* residual, int L_in, void** y, int* L_out, int cout) {
+  StreamConvState* cs = nullptr;
+  LDCCHK(stream_conv_state(R, ly.tr_stride ? 1 : ly.pad_left, ly.cin1, &cs));
+  if (cs) return sea_conv_stream(R, ly, *cs, x, residual, L_in, y, L_out, cout);
   ConvCall cc;
   cc.B = R.B; cc.L_in = L_in; cc.x1 = x; cc.residual = residual; cc.tune = &R.c->tune; cc.route_out = R.route;
   if (ly.tr_stride) {
@@ -1043,7 +1098,12 @@ int run_seanet(SeaRun& R, const std::vector<SeaOp>& ops, const void* x_in, int L
       case SeaOp::CONV_CIN1: {
         if (L <= op.k - 1) return fail(LDC_E_INVALID, "input no longer than the first conv's reflect padding is not supported (L=%d pad=%d)", L, op.k - 1);
         y = R.ar->alloc((size_t)R.B * L * op.cout * 4);
-        if (!R.dry) HIPCHK(launch_conv_cin1(DT_F32, (const float*)x, y, op.w1, op.b1, R.B, L, op.cout, op.k, R.s));
+        StreamConvState* cs = nullptr;
+        LDCCHK(stream_conv_state(R, op.k - 1, 1, &cs));
+        if (!R.dry && cs) {
+          HIPCHK(launch_conv_cin1(DT_F32, (const float*)x, y, op.w1, op.b1, R.B, L, op.cout, op.k, R.s, nullptr, cs->buf[R.st->parity], R.st->fresh_dev));
+          HIPCHK(launch_stream_ctx_update((const float*)x, cs->buf[R.st->parity], cs->buf[R.st->parity ^ 1], R.st->fresh_dev, R.B, L, cs->rows, 1, 0, R.s));
+        } else if (!R.dry) HIPCHK(launch_conv_cin1(DT_F32, (const float*)x, y, op.w1, op.b1, R.B, L, op.cout, op.k, R.s));
         C = op.cout;
         break;
       }
@@ -1069,7 +1129,7 @@ int run_seanet(SeaRun& R, const std::vector<SeaOp>& ops, const void* x_in, int L
         // time chunks: layer 0 writes its chunk time-major, the side stream runs layer 1's input GEMM over exactly those rows (contiguous
         // in that layout) and layer 1's chunk while layer 0 is on its next one; the recurrent state travels through [B][2H] buffers.
         // 5 chunk times instead of 8 on paper; measured (tools/lstm_pipe_time.py) it does not pay on this runtime -- see ldc_ctx::lstm_pipe -- and is off.
-        const bool pipe = R.c->lstm_pipe && R.side >= 0 && R.side < 2 && R.c->aux_stream[2 + R.side] && op.lstm.size() == 2 && lstm_seq_supported(H) && !op.lstm[0].w_rm && !op.lstm[1].w_rm &&
+        const bool pipe = !R.st && R.c->lstm_pipe && R.side >= 0 && R.side < 2 && R.c->aux_stream[2 + R.side] && op.lstm.size() == 2 && lstm_seq_supported(H) && !op.lstm[0].w_rm && !op.lstm[1].w_rm &&
                           L >= 64 * ldc_ctx::kLstmChunks;
         if (pipe) {
           constexpr int NCH = ldc_ctx::kLstmChunks;
@@ -1113,16 +1173,22 @@ int run_seanet(SeaRun& R, const std::vector<SeaOp>& ops, const void* x_in, int L
           void* o = R.ar->alloc((size_t)R.B * L * H * 4);
           const bool coop = op.lstm[n].w_rm && !R.c->lstm_stream_only && R.c->coop_resident[H == 512 ? 1 : 0];
           void* lws = coop ? R.ar->alloc(lstm_coop_ws_bytes(H)) : nullptr;
+          LstmCarry carry;   // stream session: (h | c) in and out; the kernel is picked per chunk by the same rule as for a whole sequence
+          if (R.st) {
+            if (R.st->lstm_at >= R.st->lstm.size()) return fail(LDC_E_STATE, "stream state does not match the layer table (LSTM layer %zu)", R.st->lstm_at);
+            carry.state = R.st->lstm[R.st->lstm_at++];
+            carry.fresh = R.st->fresh_dev;
+          }
           if (!R.dry) {
             ConvCall cc;
             cc.B = R.B; cc.L_in = L; cc.L_rows = L; cc.x1 = in; cc.y = pre; cc.y_ld = 4 * H; cc.tune = &R.c->tune;
             HIPCHK(launch_conv(op.lstm[n].in_proj, cc, R.s));
             const bool lastl = n + 1 == op.lstm.size();
             hipError_t le = hipErrorCooperativeLaunchTooLarge;
-            if (coop) le = launch_lstm_coop(DT_F32, pre, op.lstm[n].w_rm, o, lastl ? x : nullptr, R.B, L, H, lws, R.c->dev_flag_dev, (R.c->lstm_xcd && R.c->xcd_resident[H == 512 ? 1 : 0] >= 2 * R.teams) ? 2 : R.c->coop_launch, R.s);
+            if (coop) le = launch_lstm_coop(DT_F32, pre, op.lstm[n].w_rm, o, lastl ? x : nullptr, R.B, L, H, lws, R.c->dev_flag_dev, (R.c->lstm_xcd && R.c->xcd_resident[H == 512 ? 1 : 0] >= 2 * R.teams) ? 2 : R.c->coop_launch, R.s, carry);
             if (le == hipErrorCooperativeLaunchTooLarge) {   // (or not eligible): one workgroup per item, W_hh streamed from L2
               (void)hipGetLastError();
-              le = launch_lstm_layer(DT_F32, pre, op.lstm[n].w_hh, o, lastl ? x : nullptr, R.B, L, H, R.s);
+              le = launch_lstm_layer(DT_F32, pre, op.lstm[n].w_hh, o, lastl ? x : nullptr, R.B, L, H, R.s, carry);
             }
             HIPCHK(le);
           }
@@ -1194,7 +1260,7 @@ extern "C" int ldc_seanet_decode(ldc_ctx* c, int which, const float* z, int B, i
 // ------------------------------------------------------------------------------------------------
 // RVQ
 // ------------------------------------------------------------------------------------------------
-static int rvq_rows(ldc_ctx* c, const float* z_rows, int rows, int n_q, int64_t* codes, float* q_rows, Arena& ar, bool dry,
+int rvq_rows(ldc_ctx* c, const float* z_rows, int rows, int n_q, int64_t* codes, float* q_rows, Arena& ar, bool dry,
                     hipStream_t s) {
   const Codec& cd = c->codec[LDC_MODEL_COND];
   int64_t* cw = codes;
@@ -1203,7 +1269,7 @@ static int rvq_rows(ldc_ctx* c, const float* z_rows, int rows, int n_q, int64_t*
   return LDC_OK;
 }
 
-static int n_q_for_bandwidth(ldc_ctx* c, float bandwidth) {
+int n_q_for_bandwidth(ldc_ctx* c, float bandwidth) {
   // vq.py:86-98 with frame_rate = 16000/320 = 50: bw_per_q = log2(1024)*50/1000 = 0.5
   const Codec& cd = c->codec[LDC_MODEL_COND];
   const double bw = bandwidth > 0 ? bandwidth : c->cfg.cond_bandwidth;

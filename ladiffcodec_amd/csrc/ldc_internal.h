@@ -442,6 +442,29 @@ struct ConvSpec {
   int act8 = 0;                // fp8 inputs as well (dt is then DT_FP8): the fp8 x fp8 MFMA path
 };
 
+// State of a stream session (ldc_stream_create): what one SEANet stack of B independent streams carries from chunk to chunk.
+//   convs : in the order run_seanet reaches them, one entry per conv that reads before its chunk -- `rows` = (k - 1) dil - (stride - 1)
+//           most recent input rows per item ([B][rows][ch] fp32, channels-last, before the ELU prologue), one row for a transposed conv,
+//           k - 1 samples for the Cin = 1 conv.  Two buffers each: a call reads buf[parity] and writes buf[parity ^ 1] (a chunk may be
+//           shorter than the context, which is then shifted, and no launch reads what the same call writes).
+//   lstm  : one [B][2H] (h | c) per LSTM layer.
+//   fresh : per item, device memory (+ a host copy for the first-chunk check): set by create / reset, cleared at the end of every call.
+struct StreamConvState { int rows = 0, ch = 0; float* buf[2] = {nullptr, nullptr}; };
+struct ldc_stream {
+  ldc_ctx* ctx = nullptr;
+  int which = 0, side = 0, B = 0, hop = 1, min_first = 0;
+  std::vector<StreamConvState> convs;
+  std::vector<float*> lstm;
+  int* fresh_dev = nullptr;
+  std::vector<int> fresh_host;
+  int parity = 0;
+  size_t conv_at = 0, lstm_at = 0;   // cursors of the run in progress
+  hipStream_t last_stream = nullptr;   // where the last call or reset was issued: what ldc_stream_destroy waits for
+  bool touched = false;    // the call in progress has started its GPU work
+  bool poisoned = false;   // a call failed after it started: part of the state has advanced, part has not -- only a reset of every item helps
+  DevMem mem;
+};
+
 struct SeaRun {   // measures or runs a SEANet stack
   ldc_ctx* c;
   Arena* ar;
@@ -451,6 +474,7 @@ struct SeaRun {   // measures or runs a SEANet stack
   int side = -1;   // 0 / 1: aux_stream[2 + side] and lstm_ev[side] may carry the second stage of the two-layer LSTM pipeline (run_seanet)
   int teams = 1;   // batch parts whose codec ends may be in flight together: the XCD-local LSTM wants room for twice that many teams on its XCD
   int* route = nullptr;   // test hook (ldc_debug_sea_conv): ConvCall::route_out of the convs this run launches
+  ldc_stream* st = nullptr;   // stream session: the stack reads and updates this state (null: whole sequences, reflect padding, zero LSTM state)
 };
 
 // ldc_api.cpp
@@ -464,6 +488,8 @@ int conv_out_len(const ConvLayer& ly, int L);
 int sea_conv(SeaRun& R, const ConvLayer& ly, const void* x, const void* residual, int L_in, void** y, int* L_out, int cout);
 int run_seanet(SeaRun& R, const std::vector<SeaOp>& ops, const void* x_in, int L, void** out, int* L_out, int* C_out);
 int check_ready(ldc_ctx* c, int which, bool need_cond_codec = false);
+int rvq_rows(ldc_ctx* c, const float* z_rows, int rows, int n_q, int64_t* codes, float* q_rows, Arena& ar, bool dry, hipStream_t s);
+int n_q_for_bandwidth(ldc_ctx* c, float bandwidth);
 int check_unet_args(ldc_ctx* c, int B, int L, int F);
 int upsample_factor(const ldc_ctx* c);
 int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F);

@@ -112,6 +112,14 @@ struct ConvCall {
   unsigned long long* kst = nullptr;   // timed-mode stamps of this launch (ConvKArgs::kst), pipelined kernel only
   const int* kst_step = nullptr;
   int kst_stride = 0;
+  // Stream sessions (generic kernel, one input, SEANet layers): the launch reads a virtual input of L_in rows per item whose first
+  // ctx_rows rows are the item's context and whose remaining L_in - ctx_rows rows are x1 (the chunk, [B][L_in - ctx_rows][cin1]).  The layer
+  // passed with such a call pads nothing itself (pad_left 0).  ctx_fresh[b] != 0: the item starts a sequence and its context is the
+  // reflected start of the chunk, as the whole-sequence call pads (ctx_zero: zero rows -- a transposed conv sees no previous row)
+  const void* ctx = nullptr;        // [B][ctx_rows][cin1]
+  const int* ctx_fresh = nullptr;   // [B], device
+  int ctx_rows = 0, ctx_zero = 0;
+  int check_only = 0;               // with ctx: no launch -- hipErrorOutOfMemory when the launch's LDS window would not fit, else hipSuccess
   const ConvTune* tune = nullptr;   // null: defaults
   long long* sk_need = nullptr;     // dry run: no launch, *sk_need = split-K workspace floats this call would use
   int* route_out = nullptr;         // test hook: int[8] = route (CONV_ROUTE_*), then for the generic kernel WM, WN, TM, TN, split-K factor, taps per LDS group tg, N tile
@@ -273,7 +281,12 @@ size_t output_normalise_ws_bytes(int B);
 // ------------------------------------------------------------------------------------------------
 // First SEANet conv: Cin = 1, causal reflect pad.  x [B][L] fp32 -> y [B][L][Cout] dt.  w [Cout][k] fp32.
 hipError_t launch_conv_cin1(int dt, const float* x, void* y, const float* w, const float* bias, int B, int L, int Cout,
-                            int k, hipStream_t s, int* route_out = nullptr);   // route_out (test hook): *route_out = CONV_ROUTE_CIN1_*
+                            int k, hipStream_t s, int* route_out = nullptr,   // route_out (test hook): *route_out = CONV_ROUTE_CIN1_*
+                            const float* ctx = nullptr, const int* fresh = nullptr);   // stream sessions: ctx [B][k - 1] samples before the chunk, used where !fresh[b]
+// Stream sessions: the context of the NEXT chunk, nxt[b] = the last P rows of (cur[b] | x[b]) for an item with history, of (left padding |
+// x[b]) for a fresh one (zero_pad: zeros, else the reflected start of x).  x [B][L][C] fp32, cur / nxt [B][P][C]; nxt must not alias cur
+hipError_t launch_stream_ctx_update(const float* x, const float* cur, float* nxt, const int* fresh, int B, int L, int P, int C, int zero_pad,
+                                    hipStream_t s);
 // LSTM recurrence over T for one layer.  pre [B][T][4H] dt_pre (input GEMM + both biases), w_hh [4H][H]
 // fp32, out [B][T][H]; if skip != null: out = h + skip (SLSTM skip, lstm.py:25-26).
 // a stretch of time steps of one LSTM layer on the register kernel: rows are item * bs + t * ts (in rows of 4H / H values), the
@@ -282,12 +295,19 @@ struct LstmSeq {
   int t0 = 0, t1 = 0;
   long long pre_bs = 0, pre_ts = 1, out_bs = 0, out_ts = 1, skip_bs = 0, skip_ts = 1;
   float* state = nullptr;
+  const int* fresh = nullptr;   // stream sessions: [B] device flags -- the state is read for the items with fresh[b] == 0 (whatever t0), always written
+};
+// recurrent state of a stream session for the kernels below: state [B][2H] (h | c) is read for the items with fresh[b] == 0 (the others
+// start from zero) and written after the last step; null: every item starts from zero and nothing is kept
+struct LstmCarry {
+  float* state = nullptr;
+  const int* fresh = nullptr;
 };
 bool lstm_seq_supported(int H);
 hipError_t launch_lstm_seq(int dt, const void* pre, const float* w_hh, void* out, const void* skip, int B, int H, const LstmSeq& q,
                            hipStream_t s);
 hipError_t launch_lstm_layer(int dt, const void* pre, const float* w_hh, void* out, const void* skip, int B, int T,
-                             int H, hipStream_t s);
+                             int H, hipStream_t s, LstmCarry carry = LstmCarry());
 // Cooperative weight-stationary variant for H = 256 / 512 (H/4 workgroups exchange h through `ws`); w_rm is the
 // row-major [4H][H] matrix.
 bool lstm_coop_eligible(int H);
@@ -301,7 +321,7 @@ int conv_fused_gn_wgs_per_cu(int dt, bool w8);   // occupancy query: workgroups 
 int lstm_xcd_resident(int H);   // teams of sixteen workgroups one XCD holds
 // occupancy query x CU count (with a margin) >= the H/4 workgroups that must be co-resident
 hipError_t launch_lstm_coop(int dt, const void* pre, const float* w_rm, void* out, const void* skip, int B, int T, int H,
-                            void* ws, unsigned* host_flag, int coop_launch, hipStream_t s);
+                            void* ws, unsigned* host_flag, int coop_launch, hipStream_t s, LstmCarry carry = LstmCarry());
 
 // ------------------------------------------------------------------------------------------------
 // rvq.hip

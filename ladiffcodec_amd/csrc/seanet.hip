@@ -35,19 +35,21 @@ __device__ __forceinline__ void sst<__bf16>(void* p, size_t i, float v) {
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void conv_cin1_kernel(const float* x, void* y, const float* w, const float* bias,
-                                                        int L, int Cout, int k) {
+                                                        int L, int Cout, int k, const float* ctx, const int* fresh) {
   extern __shared__ float sw[];   // [Cout][k] + [Cout]
   for (int i = threadIdx.x; i < Cout * k; i += 256) sw[i] = w[i];
   for (int i = threadIdx.x; i < Cout; i += 256) sw[Cout * k + i] = bias ? bias[i] : 0.f;
   __syncthreads();
   const int b = blockIdx.y;
   const int pad = k - 1;
+  const float* hist = (ctx && !fresh[b]) ? ctx + (size_t)b * pad + pad : nullptr;   // stream session: the pad samples before the chunk
   const size_t total = (size_t)L * Cout;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
     const int l = (int)(idx / Cout), co = (int)(idx % Cout);
     float acc = sw[Cout * k + co];
     for (int t = 0; t < k; ++t) {
       int u = l + t - pad;
+      if (u < 0 && hist) { acc += sw[co * k + t] * hist[u]; continue; }
       if (u < 0) u = -u;            // causal reflect (left only; L > pad)
       if (u >= L) u = 2 * (L - 1) - u;
       acc += sw[co * k + t] * x[(size_t)b * L + u];
@@ -61,7 +63,7 @@ __global__ __launch_bounds__(256) void conv_cin1_kernel(const float* x, void* y,
 // T*Cout*4 bytes per item and reads T*4: store width is what matters.
 template <typename T>
 __global__ __launch_bounds__(256) void conv_cin1_rows_kernel(const float* x, void* y, const float* w, const float* bias,
-                                                             int L, int Cout, int k, int rows_per_block) {
+                                                             int L, int Cout, int k, int rows_per_block, const float* ctx, const int* fresh) {
   const int b = blockIdx.y;
   const int tpr = Cout / 4;   // threads per row
   const int c4 = (threadIdx.x % tpr) * 4, r0 = threadIdx.x / tpr, rstep = 256 / tpr;
@@ -75,13 +77,15 @@ __global__ __launch_bounds__(256) void conv_cin1_rows_kernel(const float* x, voi
   const int pad = k - 1;
   const int lbeg = blockIdx.x * rows_per_block, lend = min(L, lbeg + rows_per_block);
   const float* xb = x + (size_t)b * L;
+  const float* hist = (ctx && !fresh[b]) ? ctx + (size_t)b * pad + pad : nullptr;   // stream session: the pad samples before the chunk
   for (int l = lbeg + r0; l < lend; l += rstep) {
     float xv[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       int u = l + t - pad;
+      const bool h = u < 0 && hist && t < k;
       if (u < 0) u = -u;            // causal reflect (left only; L > pad)
-      xv[t] = t < k ? xb[u] : 0.f;
+      xv[t] = t < k ? (h ? hist[-u] : xb[u]) : 0.f;
     }
     float acc[4];
 #pragma unroll
@@ -100,23 +104,53 @@ __global__ __launch_bounds__(256) void conv_cin1_rows_kernel(const float* x, voi
 }
 
 hipError_t launch_conv_cin1(int dt, const float* x, void* y, const float* w, const float* bias, int B, int L, int Cout,
-                            int k, hipStream_t s, int* route_out) {
-  if (L <= k - 1) return hipErrorInvalidValue;
+                            int k, hipStream_t s, int* route_out, const float* ctx, const int* fresh) {
+  if (L <= k - 1 || (ctx && !fresh)) return hipErrorInvalidValue;
   if (Cout % 4 == 0 && Cout <= 1024 && 256 % (Cout / 4) == 0 && k <= 8) {
     if (route_out) *route_out = CONV_ROUTE_CIN1_ROWS;
     const int rpb = 8 * (1024 / Cout);
     dim3 grid((L + rpb - 1) / rpb, B);
-    if (dt == DT_F32) hipLaunchKernelGGL(conv_cin1_rows_kernel<float>, grid, dim3(256), 0, s, x, y, w, bias, L, Cout, k, rpb);
-    else hipLaunchKernelGGL(conv_cin1_rows_kernel<__bf16>, grid, dim3(256), 0, s, x, y, w, bias, L, Cout, k, rpb);
+    if (dt == DT_F32) hipLaunchKernelGGL(conv_cin1_rows_kernel<float>, grid, dim3(256), 0, s, x, y, w, bias, L, Cout, k, rpb, ctx, fresh);
+    else hipLaunchKernelGGL(conv_cin1_rows_kernel<__bf16>, grid, dim3(256), 0, s, x, y, w, bias, L, Cout, k, rpb, ctx, fresh);
     return hipGetLastError();
   }
   if (route_out) *route_out = CONV_ROUTE_CIN1_GENERIC;
   const size_t lds = (size_t)(Cout * k + Cout) * sizeof(float);
   int bx = (int)std::min<size_t>(((size_t)L * Cout + 255) / 256, 512);
   if (dt == DT_F32)
-    hipLaunchKernelGGL(conv_cin1_kernel<float>, dim3(bx, B), dim3(256), lds, s, x, y, w, bias, L, Cout, k);
+    hipLaunchKernelGGL(conv_cin1_kernel<float>, dim3(bx, B), dim3(256), lds, s, x, y, w, bias, L, Cout, k, ctx, fresh);
   else
-    hipLaunchKernelGGL(conv_cin1_kernel<__bf16>, dim3(bx, B), dim3(256), lds, s, x, y, w, bias, L, Cout, k);
+    hipLaunchKernelGGL(conv_cin1_kernel<__bf16>, dim3(bx, B), dim3(256), lds, s, x, y, w, bias, L, Cout, k, ctx, fresh);
+  return hipGetLastError();
+}
+
+// Stream sessions: the context of the next chunk (ldc_kernels.h: launch_stream_ctx_update).  One thread per V floats of nxt.
+template <int V>
+__global__ __launch_bounds__(256) void stream_ctx_update_kernel(const float* x, const float* cur, float* nxt, const int* fresh, int B, int L,
+                                                                int P, int C, int zero_pad) {
+  const int cv = C / V;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)B * P * cv) return;
+  const int c = (int)(idx % cv) * V;
+  const int i = (int)((idx / cv) % P), b = (int)(idx / ((long)cv * P));
+  const int j = L + i - P;   // position in the chunk of row i of the new context (negative: before the chunk)
+  const float* src = nullptr;
+  if (j >= 0) src = x + ((size_t)b * L + j) * C + c;
+  else if (!fresh[b]) src = cur + ((size_t)b * P + P + j) * C + c;
+  else if (!zero_pad) src = x + ((size_t)b * L + min(-j, L - 1)) * C + c;
+  float* dst = nxt + ((size_t)b * P + i) * C + c;
+  if (V == 4) *reinterpret_cast<float4*>(dst) = src ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
+  else *dst = src ? *src : 0.f;
+}
+
+hipError_t launch_stream_ctx_update(const float* x, const float* cur, float* nxt, const int* fresh, int B, int L, int P, int C, int zero_pad,
+                                    hipStream_t s) {
+  if (B <= 0 || L <= 0 || P <= 0 || C <= 0 || !fresh || cur == nxt) return hipErrorInvalidValue;
+  const int V = C % 4 == 0 ? 4 : 1;
+  const long n = (long)B * P * (C / V);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (V == 4) hipLaunchKernelGGL(stream_ctx_update_kernel<4>, grid, dim3(256), 0, s, x, cur, nxt, fresh, B, L, P, C, zero_pad);
+  else hipLaunchKernelGGL(stream_ctx_update_kernel<1>, grid, dim3(256), 0, s, x, cur, nxt, fresh, B, L, P, C, zero_pad);
   return hipGetLastError();
 }
 
@@ -147,7 +181,7 @@ __global__ __launch_bounds__(4 * H) void lstm_reg_kernel(const void* pre, const 
       w[q][k] = v.x; w[q][k + 1] = v.y; w[q][k + 2] = v.z; w[q][k + 3] = v.w;
     }
   const int row = tid;               // gate phase: one thread per hidden unit (tid < H); it fetches the unit's four pre-activations a step ahead
-  const bool resume = q.state && q.t0 > 0;
+  const bool resume = q.state && (q.fresh ? !q.fresh[b] : q.t0 > 0);
   float c = (resume && row < H) ? q.state[(size_t)b * 2 * H + H + row] : 0.f;
   float h_last = (resume && row < H) ? q.state[(size_t)b * 2 * H + row] : 0.f;
   if (row < H) sh[row + 4 * (row / KS)] = h_last;
@@ -218,15 +252,21 @@ __global__ __launch_bounds__(4 * H) void lstm_reg_kernel(const void* pre, const 
 // [H/4][4H][4] so that a wavefront reads 1 KiB contiguous per instruction from L2.
 template <typename T>
 __global__ __launch_bounds__(1024) void lstm_stream_kernel(const void* pre, const float* w_km, void* out, const void* skip,
-                                                           int T_len, int H) {
+                                                           int T_len, int H, const LstmCarry carry) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* sh = sm;            // [H]
   float* sg = sm + H;        // [4H]
   const int b = blockIdx.x, tid = threadIdx.x;
   const int G = 4 * H;
-  for (int i = tid; i < H; i += 1024) sh[i] = 0.f;
+  // stream session: (h | c) of an item with history comes from carry.state and goes back there after the last step
+  const float* st_in = (carry.state && !carry.fresh[b]) ? carry.state + (size_t)b * 2 * H : nullptr;
+  for (int i = tid; i < H; i += 1024) sh[i] = st_in ? st_in[i] : 0.f;
   // cell state lives with the threads that own rows < H
   float c_state[4] = {0.f, 0.f, 0.f, 0.f};   // up to H = 4096
+  if (st_in) {
+    int ci = 0;
+    for (int j = tid; j < H; j += 1024, ++ci) c_state[ci] = st_in[H + j];
+  }
   __syncthreads();
   for (int t = 0; t < T_len; ++t) {
     for (int row = tid; row < G; row += 1024) {
@@ -256,6 +296,13 @@ __global__ __launch_bounds__(1024) void lstm_stream_kernel(const void* pre, cons
     }
     __syncthreads();
   }
+  if (carry.state) {
+    int ci = 0;
+    for (int j = tid; j < H; j += 1024, ++ci) {
+      carry.state[(size_t)b * 2 * H + j] = sh[j];
+      carry.state[(size_t)b * 2 * H + H + j] = c_state[ci];
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -276,7 +323,9 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 template <typename T, int H>
 __global__ __launch_bounds__(256) void lstm_coop_kernel(const void* pre, const float* w_hh, void* out, const void* skip,
-                                                        int B, int T_len, float* hbuf, unsigned* sync, unsigned* host_flag) {
+                                                        int B, int T_len, float* hbuf, unsigned* sync, unsigned* host_flag, const LstmCarry carry) {
+  // carry.state (stream session): lstm_state_publish_kernel has put h_{-1} of every item (zeros for a fresh one) into the exchange
+  // buffer that step 0 reads, so step 0 runs the mat-vec like every other step -- without a wait: the launch boundary ordered it
   constexpr int KW = H / 4;      // k range of one wave
   constexpr int NI = KW / 16;    // float4 k-groups per lane
   __shared__ float part[4][2][16][16];
@@ -305,7 +354,9 @@ __global__ __launch_bounds__(256) void lstm_coop_kernel(const void* pre, const f
 #pragma unroll
     for (int g = 0; g < 4; ++g) pnext[g] = sld<T>(pre, ((size_t)ob * T_len) * (4 * H) + g * H + 4 * j + ou);
     if (skip) sknext = sld<T>(skip, ((size_t)ob * T_len) * H + 4 * j + ou);
+    if (carry.state && !carry.fresh[ob]) c_state = carry.state[(size_t)ob * 2 * H + H + 4 * j + ou];
   }
+  float h_last = 0.f;
   __syncthreads();
   bool dead = false;
   int t = 0;
@@ -329,6 +380,8 @@ __global__ __launch_bounds__(256) void lstm_coop_kernel(const void* pre, const f
       }
       __syncthreads();
       if (s_dead) { dead = true; break; }
+    }
+    if (t > 0 || carry.state) {
       // agent-scope (sc0 sc1) 16-byte loads of the freshly published h: they go past the non-coherent L2 themselves, so
       // no acquire fence (= L2 invalidate) is needed; issued through asm, released by one vmcnt(0)
       const float* hp = hbuf + (size_t)((t + 1) & 1) * 32 * H;
@@ -378,6 +431,7 @@ __global__ __launch_bounds__(256) void lstm_coop_kernel(const void* pre, const f
       const float gg = tanhf(gates[2]), og = sigmoid_acc(gates[3]);
       c_state = fg * c_state + ig * gg;
       const float h = og * tanhf(c_state);
+      h_last = h;
       __hip_atomic_store(hbuf + (size_t)(t & 1) * 32 * H + (size_t)ob * H + 4 * j + ou, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the h store has reached memory; nothing else of this thread is in flight here)
       const size_t o = ((size_t)ob * T_len + t) * H + 4 * j + ou;
@@ -394,6 +448,10 @@ __global__ __launch_bounds__(256) void lstm_coop_kernel(const void* pre, const f
   }
   if (dead && owner) {
     for (int tt = t; tt < T_len; ++tt) sst<T>(out, ((size_t)ob * T_len + tt) * H + 4 * j + ou, __builtin_nanf(""));
+  }
+  if (carry.state && owner) {   // (after a timeout: NaN, like the output)
+    carry.state[(size_t)ob * 2 * H + 4 * j + ou] = dead ? __builtin_nanf("") : h_last;
+    carry.state[(size_t)ob * 2 * H + H + 4 * j + ou] = dead ? __builtin_nanf("") : c_state;
   }
   // the host learns about the timeout through a mapped word it checks at the next API call / synchronisation
   if (dead && tid == 0 && host_flag) __hip_atomic_store(host_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -431,7 +489,8 @@ __device__ __forceinline__ float dpp_sum_group(float v) {
 
 template <typename T, int H>
 __global__ __launch_bounds__(1024) void lstm_xcd_kernel(const void* pre, const float* w_hh, void* out, const void* skip,
-                                                        int B, int T_len, float* hbuf, unsigned* sync, unsigned* host_flag, unsigned long long* dbg = nullptr) {
+                                                        int B, int T_len, float* hbuf, unsigned* sync, unsigned* host_flag, unsigned long long* dbg = nullptr,
+                                                        const LstmCarry carry = LstmCarry()) {
   constexpr int NB = 16;              // workgroups of the team
   constexpr int U = H / NB;           // hidden units of a workgroup
   constexpr int ROWS = 4 * U;         // gate rows of a workgroup
@@ -474,7 +533,9 @@ __global__ __launch_bounds__(1024) void lstm_xcd_kernel(const void* pre, const f
 #pragma unroll
     for (int gg = 0; gg < 4; ++gg) pnext[gg] = sld<T>(pre, ((size_t)ob * T_len) * (4 * H) + gg * H + j * U + ou);
     if (skip) sknext = sld<T>(skip, ((size_t)ob * T_len) * H + j * U + ou);
+    if (carry.state && !carry.fresh[ob]) c_state = carry.state[(size_t)ob * 2 * H + H + j * U + ou];   // (stream session: see lstm_coop_kernel)
   }
+  float h_last = 0.f;
   bool dead = false;
   int t = 0;
   for (; t < T_len; ++t) {
@@ -484,8 +545,8 @@ __global__ __launch_bounds__(1024) void lstm_xcd_kernel(const void* pre, const f
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0;
     const bool rec = dbg && j == 3 && tid == 0 && t >= 16 && t < 48;
     if (rec) st0 = __builtin_amdgcn_s_memtime();
-    if (t > 0) {
-      if (w == 0) {
+    if (t > 0 || carry.state) {
+      if (t > 0 && w == 0) {
         const unsigned long long t0 = wall_clock64();
         for (unsigned spins = 0;; ++spins) {
           const bool ok = lane >= NB || __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)t;
@@ -549,6 +610,7 @@ __global__ __launch_bounds__(1024) void lstm_xcd_kernel(const void* pre, const f
       const float gv = tanhf(gates[2]), og = sigmoid_acc(gates[3]);
       c_state = fg * c_state + ig * gv;
       const float h = og * tanhf(c_state);
+      h_last = h;
       // plain store: the line stays in this XCD's L2, where the team's sc1 loads find it
       asm volatile("global_store_dword %0, %1, off" ::"v"(hbuf + (size_t)(t & 1) * 32 * H + (size_t)ob * H + j * U + ou), "v"(h) : "memory");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (only the h store is outstanding here: the flag may follow it at once)
@@ -570,12 +632,24 @@ __global__ __launch_bounds__(1024) void lstm_xcd_kernel(const void* pre, const f
   if (dead && owner) {
     for (int tt = t; tt < T_len; ++tt) sst<T>(out, ((size_t)ob * T_len + tt) * H + j * U + ou, __builtin_nanf(""));
   }
+  if (carry.state && owner) {
+    carry.state[(size_t)ob * 2 * H + j * U + ou] = dead ? __builtin_nanf("") : h_last;
+    carry.state[(size_t)ob * 2 * H + H + j * U + ou] = dead ? __builtin_nanf("") : c_state;
+  }
   if (dead && tid == 0 && host_flag) __hip_atomic_store(host_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// stream session: h_{-1} of the (<= 32) items of a cooperative launch into the exchange buffer its step 0 reads ([32][H]; zeros for a fresh item)
+__global__ __launch_bounds__(256) void lstm_state_publish_kernel(const LstmCarry carry, float* hdst, int nb, int H) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= nb * H) return;
+  const int b = idx / H, u = idx - b * H;
+  hdst[(size_t)b * H + u] = carry.fresh[b] ? 0.f : carry.state[(size_t)b * 2 * H + u];
 }
 
 template <typename T>
 static hipError_t lstm_coop_launch(const void* pre, const float* w_rm, void* out, const void* skip, int B, int T_len, int H,
-                                   void* ws, unsigned* host_flag, int coop_launch, hipStream_t s) {
+                                   void* ws, unsigned* host_flag, int coop_launch, hipStream_t s, const LstmCarry carry_all) {
   float* hbuf = reinterpret_cast<float*>(ws);
   unsigned* sync = reinterpret_cast<unsigned*>(hbuf + (size_t)2 * 32 * H);
   const size_t esz = sizeof(T);
@@ -593,14 +667,21 @@ static hipError_t lstm_coop_launch(const void* pre, const float* w_rm, void* out
     // stream).  `coop_launch` (LDC_COOP_LAUNCH=1) restores it.  A grid that does not become resident at run time (another process holding
     // the CUs) still ends in the bounded spin's timeout: NaN output + the host-mapped failure flag.
     const void* pp = p; void* oo = o; const void* kk = k; int nbv = nb, tl = T_len;
-    void* args[] = {&pp, &w_rm, &oo, &kk, &nbv, &tl, &hbuf, &sync, &host_flag};
+    LstmCarry carry;
+    if (carry_all.state) {
+      carry.state = carry_all.state + (size_t)b0 * 2 * H;
+      carry.fresh = carry_all.fresh + b0;
+      hipLaunchKernelGGL(lstm_state_publish_kernel, dim3((nb * H + 255) / 256), dim3(256), 0, s, carry, hbuf + (size_t)32 * H, nb, H);   // step 0 reads buffer (0 + 1) & 1
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    void* args[] = {&pp, &w_rm, &oo, &kk, &nbv, &tl, &hbuf, &sync, &host_flag, &carry};
     const void* fn = H == 512 ? reinterpret_cast<const void*>(lstm_coop_kernel<T, 512>) : reinterpret_cast<const void*>(lstm_coop_kernel<T, 256>);
     if (coop_launch == 2 && nb <= 2) {   // one or two items: XCD-local exchange, 8 x 16 workgroups of 1024 threads, the ones on XCC 0 form the team
       const void* fx = H == 512 ? reinterpret_cast<const void*>(lstm_xcd_kernel<T, 512>) : reinterpret_cast<const void*>(lstm_xcd_kernel<T, 256>);
       static unsigned long long* dbg = nullptr;
       static int dbg_n = 0;
       if (getenv("LDC_LSTM_STAMPS") && !dbg) (void)hipMalloc((void**)&dbg, 32 * 6 * 8);
-      void* args2[] = {&pp, &w_rm, &oo, &kk, &nbv, &tl, &hbuf, &sync, &host_flag, &dbg};
+      void* args2[] = {&pp, &w_rm, &oo, &kk, &nbv, &tl, &hbuf, &sync, &host_flag, &dbg, &carry};
       e = hipLaunchKernel(fx, dim3(8 * 16), dim3(1024), args2, 0, s);
       if (dbg && ++dbg_n == 20) {   // tuning aid: one launch's per-step phase stamps (shader cycles) of workgroup 3
         (void)hipStreamSynchronize(s);
@@ -653,10 +734,10 @@ bool lstm_coop_resident(int H) {
 
 // w_rm: row-major [4H][H] fp32; ws: lstm_coop_ws_bytes(H) bytes of device scratch owned by the caller
 hipError_t launch_lstm_coop(int dt, const void* pre, const float* w_rm, void* out, const void* skip, int B, int T, int H,
-                            void* ws, unsigned* host_flag, int coop_launch, hipStream_t s) {
-  if (!lstm_coop_eligible(H)) return hipErrorInvalidValue;
-  return dt == DT_F32 ? lstm_coop_launch<float>(pre, w_rm, out, skip, B, T, H, ws, host_flag, coop_launch, s)
-                      : lstm_coop_launch<__bf16>(pre, w_rm, out, skip, B, T, H, ws, host_flag, coop_launch, s);
+                            void* ws, unsigned* host_flag, int coop_launch, hipStream_t s, LstmCarry carry) {
+  if (!lstm_coop_eligible(H) || (carry.state && !carry.fresh)) return hipErrorInvalidValue;
+  return dt == DT_F32 ? lstm_coop_launch<float>(pre, w_rm, out, skip, B, T, H, ws, host_flag, coop_launch, s, carry)
+                      : lstm_coop_launch<__bf16>(pre, w_rm, out, skip, B, T, H, ws, host_flag, coop_launch, s, carry);
 }
 
 // w_hh points at: [4H][H] row-major for the register variants (H = 64, 128), k-major [H/4][4H][4] otherwise.
@@ -677,16 +758,16 @@ hipError_t launch_lstm_seq(int dt, const void* pre, const float* w_hh, void* out
 }
 
 hipError_t launch_lstm_layer(int dt, const void* pre, const float* w_hh, void* out, const void* skip, int B, int T,
-                             int H, hipStream_t s) {
-  if (H % 8 || H > 4096) return hipErrorInvalidValue;
+                             int H, hipStream_t s, LstmCarry carry) {
+  if (H % 8 || H > 4096 || (carry.state && !carry.fresh)) return hipErrorInvalidValue;
   if (H == 64 || H == 128) {
     LstmSeq q;
-    q.t0 = 0; q.t1 = T; q.pre_bs = q.out_bs = q.skip_bs = T; q.pre_ts = q.out_ts = q.skip_ts = 1; q.state = nullptr;
+    q.t0 = 0; q.t1 = T; q.pre_bs = q.out_bs = q.skip_bs = T; q.pre_ts = q.out_ts = q.skip_ts = 1; q.state = carry.state; q.fresh = carry.fresh;
     return launch_lstm_seq(dt, pre, w_hh, out, skip, B, H, q, s);
   } else {
     const size_t lds = (size_t)5 * H * sizeof(float);
-    if (dt == DT_F32) hipLaunchKernelGGL(lstm_stream_kernel<float>, dim3(B), dim3(1024), lds, s, pre, w_hh, out, skip, T, H);
-    else hipLaunchKernelGGL(lstm_stream_kernel<__bf16>, dim3(B), dim3(1024), lds, s, pre, w_hh, out, skip, T, H);
+    if (dt == DT_F32) hipLaunchKernelGGL(lstm_stream_kernel<float>, dim3(B), dim3(1024), lds, s, pre, w_hh, out, skip, T, H, carry);
+    else hipLaunchKernelGGL(lstm_stream_kernel<__bf16>, dim3(B), dim3(1024), lds, s, pre, w_hh, out, skip, T, H, carry);
   }
   return hipGetLastError();
 }

@@ -17,12 +17,14 @@ LDC_F32, LDC_BF16, LDC_BF16_W8 = 0, 1, 2
 DTYPES = {"f32": LDC_F32, "bf16": LDC_BF16, "fp8": LDC_BF16_W8}
 MODEL_MAIN, MODEL_COND = 0, 1
 MAX_RATIOS = 8
+STREAM_ENCODER, STREAM_DECODER = 0, 1
 
 EXPORTS = [
     "ldc_last_error", "ldc_version", "ldc_create", "ldc_destroy", "ldc_reseed", "ldc_set_option", "ldc_quantize_e4m3", "ldc_set_weight", "ldc_finalize_weights",
     "ldc_seanet_encode", "ldc_seanet_decode", "ldc_rvq_encode", "ldc_rvq_decode", "ldc_get_cond",
     "ldc_cond_upsample", "ldc_unet_forward", "ldc_p_sample", "ldc_denoise", "ldc_p_sample_loop", "ldc_infilling", "ldc_output_normalise", "ldc_decode", "ldc_ddim_times", "ldc_ddim_sample", "ldc_decode_ddim", "ldc_decode_codes", "ldc_decode_codes_ddim",
     "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
+    "ldc_stream_min_first", "ldc_stream_create", "ldc_stream_reset", "ldc_stream_destroy", "ldc_seanet_encode_stream", "ldc_seanet_decode_stream", "ldc_get_cond_stream",
     "ldc_sconv1d", "ldc_sconvtr1d", "ldc_slstm", "ldc_unet_debug_tap", "ldc_unet_step_cost", "ldc_profile_enable",
     "ldc_profile_read", "ldc_profile_read_classes", "ldc_conv_microbench", "ldc_conv_compare", "ldc_conv_compare_fp8", "ldc_ln_fold_compare", "ldc_gn_microbench", "ldc_host_stats", "ldc_stream_info", "ldc_clock_sample", "ldc_debug_raise_failure", "ldc_debug_attn_core", "ldc_debug_attention_block", "ldc_debug_sea_conv", "ldc_debug_sea_op", "ldc_debug_sync_count", "ldc_xcc_census", "ldc_timeline_enable", "ldc_timeline_read", "ldc_kstamps_enable", "ldc_kstamps_reset", "ldc_kstamps_read", "ldc_packed_bytes", "ldc_pack_codes", "ldc_unpack_codes",
     "ldc_ac_build_cdf", "ldc_ac_encode", "ldc_ac_decode", "ldc_train_q_sample", "ldc_train_num_timesteps", "ldc_train_predict_x_start", "ldc_train_neg_sdsdr", "ldc_train_l1_loss", "ldc_train_block_ws_floats",
@@ -112,6 +114,13 @@ def load() -> C.CDLL:
     lib.ldc_ac_encode_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
     lib.ldc_ac_decode_ragged.argtypes = [vp, vp, C.c_int64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldc_unet_forward_ragged.argtypes = [vp, fp, i32, fp, C.POINTER(C.c_int32), i32, i32, i32, fp, vp]
+    lib.ldc_stream_min_first.argtypes = [C.POINTER(LdcConfig), i32, i32]
+    lib.ldc_stream_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
+    lib.ldc_stream_reset.argtypes = [vp, vp, vp]
+    lib.ldc_stream_destroy.argtypes = [vp]
+    lib.ldc_seanet_encode_stream.argtypes = [vp, vp, fp, i32, fp, vp]
+    lib.ldc_seanet_decode_stream.argtypes = [vp, vp, fp, i32, fp, vp]
+    lib.ldc_get_cond_stream.argtypes = [vp, vp, fp, i32, C.c_float, fp, vp, vp]
     lib.ldc_sconv1d.argtypes = [vp, fp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, fp, vp]
     lib.ldc_sconvtr1d.argtypes = [vp, fp, i32, i32, i32, vp, vp, i32, i32, i32, i32, fp, vp]
     lib.ldc_slstm.argtypes = [vp, fp, i32, i32, i32, C.POINTER(vp), i32, fp, vp]
@@ -194,6 +203,15 @@ def ddim_times(t_start: int, n_steps: int):
     out = (C.c_int * (int(n_steps) + 1))() if n_steps >= 0 else (C.c_int * 1)()
     check(load().ldc_ddim_times(int(t_start), int(n_steps), out))
     return list(out)
+
+
+def stream_min_first(cfg: LdcConfig, which: int, side: int) -> int:
+    """Smallest first chunk of a stream session, in input units (samples for an encoder, latent frames for a decoder):
+    ldc_stream_min_first, host-only."""
+    n = load().ldc_stream_min_first(C.byref(cfg), int(which), int(side))
+    if n < 0:
+        check(n)
+    return n
 
 
 def check(rc: int) -> None:

@@ -65,10 +65,12 @@ class Engine:
         if cond_codec is not None and cond_codec.final_activation != main_codec.final_activation:
             raise ValueError("both models are built with the same --final_activation (sample.py:54,63)")
         cfg.final_activation = L.FINAL_ACTIVATIONS[main_codec.final_activation]
+        self._cfg = cfg
         self._ctx = C.c_void_p()
         L.check(self.lib.ldc_create(C.byref(cfg), device, C.byref(self._ctx)))
         self.stream = torch.cuda.Stream(device=self.device)
         self._finalized = False
+        self._streams = []                  # open stream sessions (CodecStream)
 
     def set_option(self, name: str, value: int) -> None:
         """ldc_set_option: 'split' (chains per batch), 'lstm_stream' (no cooperative LSTM), 'side_streams', 'fp8_act',
@@ -110,6 +112,8 @@ class Engine:
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx:
             self.torch.cuda.synchronize(self.device)
+            for st in list(getattr(self, "_streams", [])):      # a session holds a pointer to the context: it goes first
+                st.close()
             self.lib.ldc_destroy(self._ctx)
             self._ctx = None
 
@@ -232,6 +236,12 @@ class Engine:
         finally:
             self._exit()
         return (cond, codes) if return_codes else cond
+
+    def open_stream(self, which: int, side: int, B: int) -> "CodecStream":
+        """A stream session over one end of a SEANet codec (ldc_stream_create): B independent streams, all fresh.  Chunks pushed through
+        `encode` / `decode` / `get_cond` give, joined, what the whole-sequence call gives; the first chunk of a fresh item is at least
+        `min_first` long."""
+        return CodecStream(self, which, side, B)
 
     def cond_upsample(self, cond, normalise: int = 0):
         cond = self._f32(cond)
@@ -710,6 +720,81 @@ class Engine:
 # --------------------------------------------------------------------------------------------------
 # reference-shaped facade
 # --------------------------------------------------------------------------------------------------
+class CodecStream:
+    """B independent streams through the encoder (side = lib.STREAM_ENCODER) or decoder (lib.STREAM_DECODER) of one codec; the state a
+    chunk needs from the past -- conv context rows, transposed-conv rows, LSTM (h, c) -- lives on the device (Engine.open_stream)."""
+
+    def __init__(self, eng: Engine, which: int, side: int, B: int):
+        self.eng, self.which, self.side, self.B = eng, int(which), int(side), int(B)
+        self._st = C.c_void_p()
+        L.check(eng.lib.ldc_stream_create(eng._ctx, self.which, self.side, self.B, C.byref(self._st)))
+        eng._streams.append(self)           # (Engine.close destroys the sessions it still has before the context)
+        self.hop = (eng.cond_codec if which == L.MODEL_COND else eng.main_codec).hop_length
+        self.min_first = L.stream_min_first(eng._cfg, self.which, self.side)
+
+    def _call(self, fn, *args):
+        s = self.eng._enter()
+        try:
+            L.check(fn(self.eng._ctx, self._st, *args, s))
+        finally:
+            self.eng._exit()
+
+    def encode(self, wav):
+        """wav [B, 1, T], T a multiple of the hop -> z [B, D, T / hop]"""
+        e = self.eng
+        wav = e._f32(wav)
+        T = wav.shape[-1]
+        z = e._empty(self.B, e.main_codec.rep_dims, max(0, T // self.hop))
+        self._call(e.lib.ldc_seanet_encode_stream, wav.data_ptr(), int(T), z.data_ptr())
+        return z
+
+    def decode(self, z):
+        """z [B, D, L] -> wav [B, 1, L * hop]"""
+        e = self.eng
+        z = e._f32(z)
+        Lz = z.shape[-1]
+        wav = e._empty(self.B, 1, max(0, Lz * self.hop))
+        self._call(e.lib.ldc_seanet_decode_stream, z.data_ptr(), int(Lz), wav.data_ptr())
+        return wav
+
+    def get_cond(self, wav, bandwidth: Optional[float] = None, return_codes: bool = False):
+        """the cond encoder's stream: wav [B, 1, T] -> cond [B, D, T / 320] (and codes [n_q, B, T / 320])"""
+        e = self.eng
+        wav = e._f32(wav)
+        T = wav.shape[-1]
+        F = max(0, T // self.hop)
+        bw = float(bandwidth) if bandwidth else 0.0
+        n_q = e.cond_codec.n_q_for_bandwidth(bw if bw > 0 else None) if e.cond_codec is not None else 1
+        cond = e._empty(self.B, e.main_codec.rep_dims, F)
+        codes = e._empty(n_q, self.B, F, dtype=e.torch.int64) if return_codes else None
+        self._call(e.lib.ldc_get_cond_stream, wav.data_ptr(), int(T), bw, cond.data_ptr(), codes.data_ptr() if codes is not None else None)
+        return (cond, codes) if return_codes else cond
+
+    def reset(self, mask=None):
+        """make the items with mask[b] true (all when mask is None) fresh: their next chunk starts a sequence"""
+        m = None
+        if mask is not None:
+            m = (C.c_uint8 * self.B)(*[1 if bool(v) else 0 for v in mask])
+        s = self.eng._enter()
+        try:
+            L.check(self.eng.lib.ldc_stream_reset(self._st, m, s))
+        finally:
+            self.eng._exit()
+
+    def close(self):
+        if getattr(self, "_st", None) is not None and self._st:
+            self.eng.lib.ldc_stream_destroy(self._st)
+            self._st = None
+            if self in self.eng._streams:
+                self.eng._streams.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _Upsampler:
     """Stands for `diff_model.upsampling_layers`: iterating yields one callable that applies the WHOLE
     stack (the reference applies them in sequence, sample.py:127-128), so `for layer in
