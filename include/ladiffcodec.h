@@ -208,7 +208,7 @@ int ldc_get_cond_stream(ldc_ctx* ctx, ldc_stream* st, const float* wav, int T, f
 int ldc_cond_upsample(ldc_ctx* ctx, const float* cond, int B, int F, int normalise, float* img_out, void* stream);
 /* diff_model(x, t, cond)  (Unet1D.forward, unet.py:422-469).  cond is the RAW condition [B,C,F]
  * (process_cond runs inside, as in the reference).  t is one timestep for the whole batch: the sampler
- * only ever calls the model with torch.full((b,), t) (ddpm_loss.py:247); per-item t is not supported. */
+ * only ever calls the model with torch.full((b,), t) (ddpm_loss.py:247); ldc_unet_forward_items takes one per item. */
 int ldc_unet_forward(ldc_ctx* ctx, const float* x, int t, const float* cond, int B, int L, int F, float* eps_out,
                      void* stream);
 /* diffusion.p_sample(x, t, cond) (ddpm_loss.py:244-251).  noise [B,C,L] or NULL (NULL: Philox draw;
@@ -275,6 +275,47 @@ int ldc_decode_ragged(ldc_ctx* ctx, const float* wav, const int32_t* lengths_hos
  * an item's length. */
 int ldc_unet_forward_ragged(ldc_ctx* ctx, const float* x, int t, const float* cond, const int32_t* latent_lens_host,
                             int B, int Lmax, int Fmax, float* eps_out, void* stream);
+/* Unet1D.forward with a timestep per item (unet.py:422-437); latent_lens_host NULL = every item Lmax long (still the per-item plan).
+ * With NULL lengths Lmax need not be on the ragged quantum: it must equal Fmax x prod(upsampling_ratios) and survive the UNet's
+ * halvings, as for ldc_unet_forward.
+ * t_host[B] (host memory), each in [0, timesteps).  The per-item plan is the ragged plan with the items' timesteps in device memory
+ * too: eps_out of item b is what ldc_unet_forward gives for it alone at t_host[b], within rounding, and zero beyond its length. */
+int ldc_unet_forward_items(ldc_ctx* ctx, const float* x, const int32_t* t_host /*[B]*/, const float* cond,
+                           const int32_t* latent_lens_host, int B, int Lmax, int Fmax, float* eps_out, void* stream);
+
+/* decode pools -----------------------------------------------------------------------------------
+ * A pool is a fixed set of slots that step together on one captured step graph per batch part, while every slot keeps its own
+ * timestep, iteration, noise (tape or Philox key), length and "is running" flag in device memory.  Items are admitted into free
+ * slots and taken out of finished ones while the others keep stepping.
+ * Contract: an item's latents are those of ldc_denoise(img, cond, noise, n_steps, B = 1, L, F) on the item alone -- whatever the
+ * other slots hold, whenever it was admitted, whichever slot it sits in -- within rounding (the unfused GroupNorm statistics are
+ * summed with atomics: the contract of ldc_decode_ragged, not bit identity).  Only the halfway DDPM sampler runs in a pool; DDIM
+ * would need a schedule table per item and has no pool entry point.
+ * An idle slot (free, or finished and not yet taken) is computed on and discarded: its latents are not stored, so a finished item
+ * keeps its latents bit for bit until it is taken, and its noise tape is not read after its last step.
+ * The step graphs are keyed by (slots, Lmax, Fmax, pool) in the context's plan and graph caches and replayed for every state; the
+ * pool's plans hold its state and are never evicted (an option that rebuilds every plan is refused with LDC_E_STATE while a pool
+ * lives).  Admit, take and evict are small stream-ordered writes and copies (admit also runs process_cond for the one item);
+ * warm calls issue no device-wide synchronisation.  Calls on one pool must be issued in order on one HIP stream; stream == NULL
+ * makes a call synchronous on the context's own stream.  Destroy a context's pools before the context.
+ * Refused with LDC_E_INVALID before any GPU work, ldc_last_error() naming the value: a slot outside [0, slots); admit into a slot
+ * that is not free; L off the ragged latent quantum or above Lmax; n_steps outside [1, timesteps]; n <= 0; slots <= 0; a pool of
+ * another context; a null pointer; an fp8 engine.  ldc_pool_take of a slot that is not finished: LDC_E_STATE.  After a refusal the
+ * pool goes on as if the call had not been made.  A call that fails AFTER its GPU work began (LDC_E_HIP, LDC_E_NOMEM) marks the
+ * pool: it then refuses with LDC_E_STATE until every slot has been evicted. */
+typedef struct ldc_pool ldc_pool;
+int ldc_pool_create(ldc_ctx* ctx, int slots, int Lmax, ldc_pool** out);      /* all slots free; Lmax on the ragged latent quantum */
+int ldc_pool_destroy(ldc_pool* pool);                                         /* waits for the stream of the pool's last call */
+/* img [1,C,L] start image, cond [1,C,F] raw condition (F = L / prod(upsampling_ratios)), L on the ragged latent quantum, <= Lmax;
+ * n_steps in [1, timesteps]: the item will run t = n_steps-1 .. 0.  noise [n_steps,1,C,L] (device; kept alive by the caller until the
+ * item has finished) or NULL: Philox with key = seed, i.e. the tape ldc_reseed(ctx, seed) gives the first ldc_denoise at B = 1. */
+int ldc_pool_admit(ldc_ctx* ctx, ldc_pool* pool, int slot, const float* img, const float* cond, int L, int n_steps,
+                   const float* noise, uint64_t seed, void* stream);
+int ldc_pool_step(ldc_ctx* ctx, ldc_pool* pool, int n, void* stream);         /* n steps of every running slot; a slot stops behind t = 0 */
+int ldc_pool_remaining(const ldc_pool* pool, int32_t* remaining_host /*[slots]*/);   /* host mirror, no GPU work: -1 free, 0 finished, k > 0 running */
+int ldc_pool_take(ldc_ctx* ctx, ldc_pool* pool, int slot, float* latents_out /*[1,C,L]*/, void* stream);   /* finished slots only; frees the slot */
+int ldc_pool_peek(ldc_ctx* ctx, ldc_pool* pool, int slot, float* latents_out /*[1,C,L]*/, void* stream);   /* ldc_pool_take without freeing the slot */
+int ldc_pool_evict(ldc_pool* pool, int slot);                                 /* drop a running or finished item; frees the slot (a free slot: no-op) */
 
 /* The decode of ldc_decode / ldc_decode_ddim started from RVQ codes instead of a waveform (the receiver side):
  * quantizer.decode(codes) -> upsample, /= max|.| -> sampling -> decoder -> output normalisation.

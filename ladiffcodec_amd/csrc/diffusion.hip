@@ -634,6 +634,130 @@ hipError_t launch_lens_write(int* dst, const int* src, int n, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-item step state (ItemState, ldc_kernels.h): the kernels of a per-item plan that read or move it.
+// ---------------------------------------------------------------------------------------------
+constexpr int kItemChunk = 32;
+struct ItemChunk { ItemState v[kItemChunk]; };
+__global__ void items_write_kernel(ItemState* dst, ItemChunk src, int n, int* lens, int* flens, int up) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  dst[i] = src.v[i];
+  if (lens) lens[i] = src.v[i].len;
+  if (flens) flens[i] = src.v[i].len / up;
+}
+hipError_t launch_items_write(ItemState* dst, const ItemState* src, int n, int* lens, int* flens, int up, hipStream_t s) {
+  if (up < 1) return hipErrorInvalidValue;
+  for (int i0 = 0; i0 < n; i0 += kItemChunk) {
+    ItemChunk ch{};
+    const int m = std::min(kItemChunk, n - i0);
+    for (int i = 0; i < m; ++i) ch.v[i] = src[i0 + i];
+    hipLaunchKernelGGL(items_write_kernel, dim3(1), dim3(kItemChunk), 0, s, dst + i0, ch, m, lens ? lens + i0 : nullptr,
+                       flens ? flens + i0 : nullptr, up);
+  }
+  return hipGetLastError();
+}
+
+// step_begin_kernel for a per-item plan.  Workgroup 0 owns the items' states: active = remaining > 0, a running item moves on when asked to
+// (t - 1, j + 1, one step less remaining: a slot stops behind t = 0 by itself), the part's epoch word is counted up once.  No row is
+// copied: gn_apply reads the (scale | shift) row of each item's t from the table.  Every other workgroup clears the accumulator region.
+__global__ __launch_bounds__(1024) void step_begin_items_kernel(ItemState* items, int B, int* st, uint4* zero, long long zero_n16, int advance) {
+  constexpr int nthr = 1024;
+  if (blockIdx.x == 0) {
+    for (int b = threadIdx.x; b < B; b += nthr) {
+      ItemState* it = items + b;
+      const int run = it->remaining > 0;
+      if (run && advance) {
+        it->t -= 1;
+        it->j += 1;
+        it->remaining -= 1;
+      }
+      it->active = run;
+    }
+    if (threadIdx.x == 0) st[4] = st[4] + 1;
+    if (gridDim.x > 1) return;
+  }
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  const long long nb = gridDim.x > 1 ? gridDim.x - 1 : 1, bi = gridDim.x > 1 ? blockIdx.x - 1 : 0;
+  for (long long i = bi * nthr + threadIdx.x; i < zero_n16; i += nb * nthr) zero[i] = z;
+}
+hipError_t launch_step_begin_items(ItemState* items, int B, int* st, void* zero, size_t zero_bytes, int advance, hipStream_t s) {
+  const long long n16 = (long long)((zero_bytes + 15) / 16);
+  const long long want = n16 > 0 ? 1 + (n16 + 4095) / 4096 : 1;
+  hipLaunchKernelGGL(step_begin_items_kernel, dim3((unsigned)std::min<long long>(256, want)), dim3(1024), 0, s, items, B, st,
+                     reinterpret_cast<uint4*>(zero), n16, advance);
+  return hipGetLastError();
+}
+
+// p_sample_update_kernel with everything about the step read from the item's record.  Same 32 x 32 tiling; the item's state is [C][len]
+// on its own length, so a tile behind the item's end (and every tile of an idle item) leaves before it touches memory.
+template <typename T>
+__global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int C,
+                                                                    int Lmax, StepTables tb, const ItemState* items, int n_t) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const ItemState it = items[b];
+  const int L = min(it.len, Lmax);
+  if (!it.active || l0 >= L) return;   // (uniform over the workgroup) idle: neither x nor x_cl is stored, the tape is not dereferenced
+  float* xb = x + (size_t)b * x_item_stride;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  float ev[4], xin[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int l = l0 + i, c = c0 + tx;
+    ev[ii] = (l < L && c < C) ? dld<T>(eps_cl, ((size_t)b * Lmax + l) * C + c) : 0.f;
+    const int cc = c0 + i, ll = l0 + tx;
+    xin[ii] = (cc < C && ll < L) ? xb[(size_t)cc * L + ll] : 0.f;
+  }
+  const int t = min(max(it.t, 0), n_t - 1), j = it.j;
+  const uint64_t seed = ((uint64_t)it.key_hi << 32) | (uint64_t)it.key_lo;
+  const float recip = tb.sqrt_recip_alphas_cumprod[t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[t];
+  const float c1 = tb.posterior_mean_coef1[t], c2 = tb.posterior_mean_coef2[t];
+  const float sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
+  __syncthreads();
+  float newv[4];
+  // one Philox block per thread at the index of its first element IN THE ITEM ALONE (c * len + l): what ldc_denoise draws for it at B = 1
+  float zz[4] = {0.f, 0.f, 0.f, 0.f};
+  if (t > 0 && !it.noise) philox_normal4(seed, (unsigned)j, (uint64_t)(c0 + ty) * L + l0 + tx, zz);
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int c = c0 + i, l = l0 + tx;
+    newv[ii] = 0.f;
+    if (c < C && l < L) {
+      const size_t idx = (size_t)c * L + l;
+      const float xv = xin[ii];
+      const float e = tile[tx][i];
+      float x0 = recip * xv - recipm1 * e;
+      x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+      float v = c1 * x0 + c2 * xv;
+      if (t > 0) v += sigma * (it.noise ? it.noise[(size_t)j * C * L + idx] : zz[ii]);
+      xb[idx] = v;
+      newv[ii] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][l]
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int l = l0 + i, c = c0 + tx;
+    if (l < L && c < C) dst<T>(x_cl, ((size_t)b * Lmax + l) * C + c, tile[tx][i]);
+  }
+}
+hipError_t launch_p_sample_update_items(int dt, float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int B, int C, int Lmax,
+                                        StepTables tb, const ItemState* items, int T, hipStream_t s) {
+  dim3 grid((Lmax + 31) / 32, (C + 31) / 32, B);
+  if (dt == DT_F32)
+    hipLaunchKernelGGL(p_sample_update_items_kernel<float>, grid, dim3(256), 0, s, x, x_item_stride, eps_cl, x_cl, C, Lmax, tb, items, T);
+  else
+    hipLaunchKernelGGL(p_sample_update_items_kernel<__bf16>, grid, dim3(256), 0, s, x, x_item_stride, eps_cl, x_cl, C, Lmax, tb, items, T);
+  return hipGetLastError();
+}
+
 }  // namespace ldc
 
 // ---------------------------------------------------------------------------------------------

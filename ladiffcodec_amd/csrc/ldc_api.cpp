@@ -900,6 +900,8 @@ extern "C" int ldc_set_option(ldc_ctx* c, const char* name, int value) {
   if (value < r.lo || value > r.hi) return fail(LDC_E_INVALID, "option %s must be in %d..%d", name, r.lo, r.hi);
   if (n == "side_streams" && value && c->split_batch != 1) return fail(LDC_E_INVALID, "side streams need a single chain (split 1)");
   if (value == *r.p) return LDC_OK;
+  if (r.replan && c->live_pools > 0)
+    return fail(LDC_E_STATE, "option %s rebuilds every plan, and %d decode pool(s) keep their items' state in theirs: destroy the pools first", name, c->live_pools);
   if (r.replan && !c->plans.empty()) { HIPCHK(hipSetDevice(c->device)); drop_plans(c); }   // plans of one shape differ by the value: start clean
   *r.p = value;
   if (n == "split" && value != 1) c->side_streams = 0;
@@ -1566,6 +1568,10 @@ struct PlanBuilder {
     const int rows = B * L, dt = c->dt, g = c->unet.groups, Bn = B;
     const UnetW* u = &c->unet;
     const float* cur_ss = pl->cur_ss;
+    // per-item plan: block1's gn_apply takes the (scale | shift) row of each item's own t from the table
+    const int* item_t = pl->items ? &pl->item_state->t : nullptr;
+    const float* ss_tab = u->ss_table + r.ss_off;
+    const int ss_stride = u->ss_stride, n_t = u->timesteps;
     // fp8-weight context: block1's output feeds block2's conv alone, so it is produced in fp8 and that conv runs fp8 x fp8
     const bool f8 = c->w8 && c->fp8_act && r.c2_f8.w != nullptr;
     const int* ln = lens();   // ragged plan: conv -> gn_stats -> gn_apply, statistics over the valid rows, padding rows written as zero
@@ -1642,6 +1648,9 @@ struct PlanBuilder {
       conv(c1, x1, x2, a, nullptr, L, L, fuse_stats ? st1 : nullptr);
       if (!fuse_stats) add([=](hipStream_t s) { return launch_gn_stats(dt, a, Bn, L, rp->cout, g, st1, s, ln, sh); });
       add([=](hipStream_t s) {
+        if (item_t)
+          return launch_gn_apply(dt, a, b, nullptr, Bn, L, rp->cout, g, st1, rp->g1, rp->b1, ss_tab, ss_stride, item_t, ACT_SILU, s, nullptr,
+                                 nullptr, 0, ln, sh, kItemStateInts, n_t);
         return launch_gn_apply(dt, a, b, nullptr, Bn, L, rp->cout, g, st1, rp->g1, rp->b1, cur_ss + rp->ss_off,
                                0, nullptr, ACT_SILU, s, nullptr, nullptr, f8 ? 1 : 0, ln, sh);
       }, false, 0, LDC_CLASS_GN_APPLY, (f8 ? 1.5 : 2.0) * Bn * L * rp->cout * es);
@@ -1753,7 +1762,7 @@ struct PlanBuilder {
 
 int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
   const UnetW& u = c->unet;
-  pl->B = B; pl->L = L; pl->F = F;
+  pl->B = B; pl->L = L; pl->F = F; pl->init_pc = nullptr;
   pl->cond_ops.clear(); pl->step_ops.clear(); pl->step_is_conv.clear(); pl->step_where.clear(); pl->step_flops.clear(); pl->step_class.clear(); pl->step_bytes.clear(); pl->step_info.clear(); pl->taps.clear();
   pl->flops = 0; pl->act_bytes = 0; pl->conv_bytes = 0; pl->sk_need_max = 0; pl->part_need = 0;
   const int dt = c->dt;
@@ -1789,6 +1798,8 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
   pl->x_cl = ar.alloc((size_t)B * L * Cx * es);
   pl->eps_cl = ar.alloc((size_t)B * L * Cx * es);
   pl->cond_cl = ar.alloc((size_t)B * L * Cc * es);
+  if (pl->items && !pl->ragged) return fail(LDC_E_INVALID, "a per-item plan is a ragged plan");
+  pl->item_state = pl->items ? (ItemState*)ar.alloc((size_t)B * sizeof(ItemState)) : nullptr;
   if (pl->ragged) {
     if (c->w8) return fail(LDC_E_INVALID, "ragged batches are not available on the fp8 engine (its fused forms have no length-aware variant): use dtype bf16 or f32");
     pl->lens = (int*)ar.alloc((size_t)B * 4);
@@ -1865,6 +1876,7 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
   if (c->split_init && !c->w8 && !c->cfg.unet_scale_x && u.init_c.w && u.init_x.w) {
     // the condition's half of init_conv once per sampler call (behind process_cond), the x half + that tensor every step
     void* pc = pb.act(B * L, u.dim);
+    pl->init_pc = pc;
     {
       ConvCall cc;
       cc.B = B; cc.L_in = L; cc.L_rows = L; cc.x1 = pl->cond_cl; cc.y = pc; cc.y_ld = u.init_c.n; cc.tune = &c->tune;
@@ -1946,7 +1958,7 @@ static void evict_plan(ldc_ctx* c, size_t idx) {
   (void)counted_device_sync();
   Plan* pl = c->plans[idx].get();
   for (size_t g = 0; g < c->graphs.size();) {
-    if (c->graphs[g].L == pl->L && c->graphs[g].F == pl->F) {
+    if (c->graphs[g].L == pl->L && c->graphs[g].F == pl->F && c->graphs[g].pool_id == pl->pool_id) {
       c->graphs[g].destroy();
       c->graphs.erase(c->graphs.begin() + g);
     } else {
@@ -1961,15 +1973,17 @@ static void evict_plan(ldc_ctx* c, size_t idx) {
   c->plans.erase(c->plans.begin() + idx);
 }
 
-static int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false) {
+int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id) {
   for (auto& p : c->plans)
-    if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged) {
+    if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged && p->items == items && p->pool_id == pool_id) {
       p->last_use = ++c->use_tick;
       *out = p.get();
       return LDC_OK;
     }
   std::unique_ptr<Plan> pl(new Plan());
   pl->ragged = ragged;
+  pl->items = items;
+  pl->pool_id = pool_id;
   {   // pass 1: what do the convs of this plan need as split-K workspace?
     Arena dry;
     LDCCHK(build_plan(c, pl.get(), dry, B, L, F));
@@ -1991,7 +2005,7 @@ static int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Pl
     if (!over) break;
     size_t victim = c->plans.size();
     for (size_t i = 0; i < c->plans.size(); ++i)
-      if (c->plans[i]->last_use <= c->call_tick && (victim == c->plans.size() || c->plans[i]->last_use < c->plans[victim]->last_use)) victim = i;
+      if (c->plans[i]->pool_id == 0 && c->plans[i]->last_use <= c->call_tick && (victim == c->plans.size() || c->plans[i]->last_use < c->plans[victim]->last_use)) victim = i;
     if (victim == c->plans.size()) break;   // everything cached belongs to this call: let hipMalloc decide
     evict_plan(c, victim);
   }
@@ -2023,7 +2037,7 @@ static int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Pl
 // such a stream; which streams share depends on what else the process created before -- torch's pool, RCCL, other contexts).  So the part
 // streams are CHOSEN, once per caller stream: a candidate is accepted when a 150 us single-workgroup spin on it and on every stream
 // accepted so far takes one spin, not two.  ~2 ms, the first time a batch is decoded in parts on a stream; never inside a capture.
-static int calibrate_part_streams(ldc_ctx* c, hipStream_t s) {
+int calibrate_part_streams(ldc_ctx* c, hipStream_t s) {
   if (!c->calib || (c->calibrated && c->calib_stream == s)) return LDC_OK;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return LDC_OK; }
@@ -2077,7 +2091,7 @@ static int calibrate_part_streams(ldc_ctx* c, hipStream_t s) {
   return LDC_OK;
 }
 
-static int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool ragged = false) {
+int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool ragged, bool items, int pool_id) {
   *h = Halves();
   c->call_tick = c->use_tick;   // plans touched from here on belong to the call being served (not evictable)
   // Independent chains the batch is decoded as (utterances never interact inside the UNet).  A chain is a
@@ -2089,14 +2103,14 @@ static int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h,
   for (int k = 0; k < h->n; ++k) {
     const int lo = (int)((long long)B * k / h->n), hi = (int)((long long)B * (k + 1) / h->n);
     h->b0[k] = lo;
-    LDCCHK(get_plan(c, hi - lo, L, F, k, s, &h->p[k], ragged));
+    LDCCHK(get_plan(c, hi - lo, L, F, k, s, &h->p[k], ragged, items, pool_id));
   }
   c->last_halves = *h;
   return LDC_OK;
 }
 
-static int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step,
-                   hipStream_t s) {
+int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step,
+            hipStream_t s) {
   const bool use_side = is_step && !c->profile && c->side_streams;
   hipStream_t side = c->side_stream[pl->slot];
   if (use_side && pl->marker_events.empty()) {
@@ -2155,7 +2169,7 @@ static int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipErro
   return LDC_OK;
 }
 
-static int load_cond(ldc_ctx* c, const Halves& h, const float* cond, hipStream_t s) {
+int load_cond(ldc_ctx* c, const Halves& h, const float* cond, hipStream_t s) {
   for (int k = 0; k < h.n; ++k) {
     Plan* pl = h.p[k];
     const float* src = cond + (size_t)h.b0[k] * c->unet.cond_channels * pl->F;
@@ -2216,7 +2230,7 @@ static long long lcm_ll(long long a, long long b) {
   return a / x * b;
 }
 // latent frames an item's length must be a multiple of: whole condition frames and the halvings
-static int ragged_latent_quantum(const ldc_ctx* c) { return (int)lcm_ll(upsample_factor(c), 1ll << unet_halvings(c)); }
+int ragged_latent_quantum(const ldc_ctx* c) { return (int)lcm_ll(upsample_factor(c), 1ll << unet_halvings(c)); }
 // every length of a ragged call, before any GPU work: `unit` is what the lengths count (latent frames or samples)
 static int check_ragged_lengths(const int32_t* lens, int B, int maxlen, long long quantum, const char* unit) {
   if (!lens) return fail(LDC_E_INVALID, "null lengths");
@@ -2378,16 +2392,16 @@ static int stamp_loop_end(ldc_ctx* c, const Halves& h, int k, hipStream_t s) {
   return LDC_OK;
 }
 
-static bool parts_parallel(ldc_ctx* c, const Halves& h) {
+bool parts_parallel(ldc_ctx* c, const Halves& h) {
   return h.n >= 2 && !c->profile && !c->serial_parts;   // LDC_SERIAL (diagnostics): parts back to back, eager
 }
 // the parts' streams pick up after everything queued on s / s waits for every part
-static int fork_parts(ldc_ctx* c, const Halves& h, hipStream_t s) {
+int fork_parts(ldc_ctx* c, const Halves& h, hipStream_t s) {
   HIPCHK(hipEventRecord(c->ev_fork, s));
   for (int k = 1; k < h.n; ++k) HIPCHK(hipStreamWaitEvent(c->aux_stream[k], c->ev_fork, 0));
   return LDC_OK;
 }
-static int join_parts(ldc_ctx* c, const Halves& h, hipStream_t s) {
+int join_parts(ldc_ctx* c, const Halves& h, hipStream_t s) {
   for (int k = 1; k < h.n; ++k) {
     HIPCHK(hipEventRecord(c->ev_join[k], c->aux_stream[k]));
     HIPCHK(hipStreamWaitEvent(s, c->ev_join[k], 0));
@@ -2430,6 +2444,43 @@ extern "C" int ldc_p_sample(ldc_ctx* c, float* x, int t, const float* cond, cons
   return finish_stream(c, stream);
 }
 
+// The per-part graphs of sg replayed for n_rep rounds: pexec[k][0] (the K-step graph) for the first n_big rounds, pexec[k][1] (one step)
+// for the rest (single_len: K == 1, pexec[k][0] throughout).  One single-stream graph per part, replayed from recorded AQL packets.  The
+// parts' replays are issued INTERLEAVED (graph j of every part before graph j + 1 of any) behind a bounded look-ahead per part: through
+// round 3 all of part 0's replays were issued first, hipGraphLaunch blocked on the full hardware queue for most of the decode (76-105 ms
+// "inside hipGraphLaunch") and part 1 started late.  Waiting happens on events of this context, outside hipGraphLaunch.  The caller forks
+// the parts in front and joins them behind, whatever this returns (*what names the call that failed).
+hipError_t replay_parts(ldc_ctx* c, const Halves& h, StepGraph* sg, int n_big, int n_rep, bool single_len, hipStream_t s, const char** what) {
+  const int depth = std::max(1, std::min(c->flow_depth > 0 ? c->flow_depth : 3, 3));
+  std::vector<hipEvent_t>& evs = sg->part_ev;
+  hipError_t err = hipSuccess;
+  while ((int)evs.size() < h.n * depth && err == hipSuccess) {
+    hipEvent_t e = nullptr;
+    err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (err == hipSuccess) evs.push_back(e);
+    else *what = "hipEventCreateWithFlags";
+  }
+  for (int j = 0; j < n_rep && err == hipSuccess; ++j)
+    for (int k = 0; k < h.n && err == hipSuccess; ++k) {
+      hipStream_t sk = k == 0 ? s : c->aux_stream[k];
+      hipEvent_t ev = evs[(size_t)k * depth + j % depth];
+      if (j >= depth) {
+        const auto t0 = std::chrono::steady_clock::now();
+        err = hipEventSynchronize(ev);   // replay j - depth of this part has finished
+        c->host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (err != hipSuccess) { *what = "hipEventSynchronize"; break; }
+      }
+      const auto t0 = std::chrono::steady_clock::now();
+      err = hipGraphLaunch(sg->pexec[k][(j < n_big || single_len) ? 0 : 1], sk);
+      c->host_graph_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      ++c->host_graph_launches;
+      if (err != hipSuccess) { *what = "hipGraphLaunch"; break; }
+      err = hipEventRecord(ev, sk);
+      if (err != hipSuccess) *what = "hipEventRecord";
+    }
+  return err;
+}
+
 // the denoise loop on prepared plans (cond already processed, x_cl already set)
 // left_forked (optional): the caller continues per part on the parts' streams; the per-part replay path then leaves them un-joined and says so
 // ddim (optional): n_steps DDIM iterations on the schedule already written to c->ddim_table (ddim == c->ddim_table); else DDPM
@@ -2450,16 +2501,18 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   const int rag = h.p[0]->ragged ? 1 : 0;   // the steps of ragged plans are graphs of their own, replayed for any set of lengths
   const int kind = ddim ? 1 : 0;   // a DDPM loop never replays a DDIM graph or the reverse; both stay cached side by side
   for (auto& g : c->graphs)
-    if (g.B == B && g.L == L && g.F == F && g.ddim == kind && g.ragged == rag) sg = &g;
+    if (g.B == B && g.L == L && g.F == F && g.ddim == kind && g.ragged == rag && g.pool_id == 0) sg = &g;
   if (!sg) {
     // graphs of shapes whose plans are gone were dropped with them (evict_plan); additionally keep at most 16 alive
     if (c->graphs.size() >= 16) {
-      size_t victim = 0;
-      for (size_t i = 1; i < c->graphs.size(); ++i)
-        if (c->graphs[i].last_use < c->graphs[victim].last_use) victim = i;
-      HIPCHK(counted_device_sync());
-      c->graphs[victim].destroy();
-      c->graphs.erase(c->graphs.begin() + victim);
+      size_t victim = c->graphs.size();   // (a decode pool's graphs leave with the pool)
+      for (size_t i = 0; i < c->graphs.size(); ++i)
+        if (c->graphs[i].pool_id == 0 && (victim == c->graphs.size() || c->graphs[i].last_use < c->graphs[victim].last_use)) victim = i;
+      if (victim < c->graphs.size()) {
+        HIPCHK(counted_device_sync());
+        c->graphs[victim].destroy();
+        c->graphs.erase(c->graphs.begin() + victim);
+      }
     }
     c->graphs.push_back(StepGraph());
     sg = &c->graphs.back();
@@ -2577,37 +2630,12 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     // were issued first, hipGraphLaunch blocked on the full hardware queue for most of the decode (76-105 ms "inside
     // hipGraphLaunch") and part 1 started late.  Waiting happens on events of this context, outside hipGraphLaunch.
     LDCCHK(fork_parts(c, h, s));
-    const int depth = std::max(1, std::min(c->flow_depth > 0 ? c->flow_depth : 3, 3));
-    std::vector<hipEvent_t>& evs = sg->part_ev;
     const int n_big = (n_steps - done) / K, n_rep = n_big + ((n_steps - done) - n_big * K);
-    while ((int)evs.size() < h.n * depth) {
-      hipEvent_t e = nullptr;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      evs.push_back(e);
-    }
     // (a failure between fork and join must still join: the auxiliary streams would otherwise be left with work that is unordered
-    // against the caller's stream -- ADVICE r4.  Note for asynchronous callers: the look-ahead wait below blocks the HOST for up to
+    // against the caller's stream -- ADVICE r4.  Note for asynchronous callers: the look-ahead wait blocks the HOST for up to
     // `depth` replays of a part, on events of this context.)
-    hipError_t err = hipSuccess;
     const char* what = "";
-    for (int j = 0; j < n_rep && err == hipSuccess; ++j)
-      for (int k = 0; k < h.n && err == hipSuccess; ++k) {
-        hipStream_t sk = k == 0 ? s : c->aux_stream[k];
-        hipEvent_t ev = evs[(size_t)k * depth + j % depth];
-        if (j >= depth) {
-          const auto t0 = std::chrono::steady_clock::now();
-          err = hipEventSynchronize(ev);   // replay j - depth of this part has finished
-          c->host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-          if (err != hipSuccess) { what = "hipEventSynchronize"; break; }
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        err = hipGraphLaunch(sg->pexec[k][(j < n_big || K == 1) ? 0 : 1], sk);
-        c->host_graph_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        ++c->host_graph_launches;
-        if (err != hipSuccess) { what = "hipGraphLaunch"; break; }
-        err = hipEventRecord(ev, sk);
-        if (err != hipSuccess) what = "hipEventRecord";
-      }
+    hipError_t err = replay_parts(c, h, sg, n_big, n_rep, K == 1, s, &what);
     for (int k = 0; k < h.n && err == hipSuccess; ++k)
       if (stamp_loop_end(c, h, k, k == 0 ? s : c->aux_stream[k]) != LDC_OK) { err = hipErrorUnknown; what = "the loop-end stamp"; }
     if (err == hipSuccess && left_forked) {   // the caller's per-part work follows on the same streams and joins behind it

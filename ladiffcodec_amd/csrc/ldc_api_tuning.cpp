@@ -360,6 +360,7 @@ extern "C" int ldc_timeline_enable(ldc_ctx* c, int on) {
 // Per-launch stamps of the pipelined conv kernel in the timed mode: plans are rebuilt with (or without) a stamp buffer.
 extern "C" int ldc_kstamps_enable(ldc_ctx* c, int on) {
   if (!c) return fail(LDC_E_INVALID, "null ctx");
+  if (c->live_pools > 0) return fail(LDC_E_STATE, "ldc_kstamps_enable rebuilds every plan, and %d decode pool(s) keep their items' state in theirs", c->live_pools);
   HIPCHK(hipSetDevice(c->device));
   drop_plans(c);
   c->kstamps = on != 0;

@@ -180,6 +180,12 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
   bool ragged = false;
   int* lens = nullptr;          // [B] latent frames at level 0 (a level's lengths are lens[b] >> level)
   int* flens = nullptr;         // [B] condition frames
+  // Per-item plan (ldc_unet_forward_items, decode pools): a ragged plan whose timestep is per item too.  The item-state
+  // table takes the place of step_state's {t, j, key} and of cur_ss: gn_apply selects each item's (scale | shift) row from the table by its t
+  bool items = false;
+  ItemState* item_state = nullptr;   // [B]
+  int pool_id = 0;              // != 0: the plan of a decode pool (part of the cache key; holds the pool's state of record, never evicted by the LRU)
+  void* init_pc = nullptr;      // split init_conv: the condition's half [B*L][dim] (a pool admits an item by copying its rows in)
   uint64_t last_use = 0;        // LRU tick (ldc_ctx::use_tick)
   long long sk_floats = 0;      // split-K workspace this plan's convs need (sized by a dry run of the launchers)
   long long sk_need_max = 0;
@@ -226,6 +232,7 @@ static constexpr int kKstOps = 256;   // stamp slots per step (one per op of the
 struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update, step_advance}
   int B = 0, L = 0, F = 0, n = 0;
   int ragged = 0;    // (part of the cache key) the steps of ragged plans
+  int pool_id = 0;   // (part of the cache key) != 0: the step graphs of that decode pool's plans
   int ddim = 0;      // sampler kind (part of the cache key): 1 = DDIM steps (the schedule table's address is captured, not its contents)
   const float* noise = nullptr;
   float* x = nullptr;
@@ -338,6 +345,7 @@ struct ldc_ctx {
   uint64_t use_tick = 0, call_tick = 0;
   size_t plan_bytes = 0, plan_bytes_cap = (size_t)48 << 30;   // LDC_PLAN_CACHE_GB
   int plan_count_cap = 24;                                     // LDC_PLAN_CACHE_N
+  int live_pools = 0, next_pool_id = 1;                        // decode pools (ldc_pool_create): their plans are pinned in the cache
   // device-drawn noise: every sampler call that draws advances the epoch, so no two calls share a realisation
   uint64_t noise_epoch = 0, cur_key = 0;
   // asynchronous device-side failure flag, host-mapped: word 0 = 1 cooperative LSTM timeout, 2 fused GroupNorm wait timeout,
@@ -465,6 +473,23 @@ struct ldc_stream {
   DevMem mem;
 };
 
+// A decode pool (ldc_pool_create): `slots` items that step together on one captured graph per batch part while each
+// keeps its own timestep, iteration, noise and length.  The state of record is on the device: the items' records, x_cl, the processed
+// condition (in the pool's pinned per-item plans) and the fp32 latents x [slots][C * Lmax] (item b: [C][len_b] at b * C * Lmax).  The host
+// keeps a mirror of the step counts only.
+struct ldc_pool {
+  ldc_ctx* ctx = nullptr;
+  int id = 0, slots = 0, Lmax = 0, Fmax = 0;
+  Halves h;                          // the pool's plans (pinned: Plan::pool_id)
+  float* x = nullptr;                // [slots][C * Lmax] fp32
+  std::vector<int> remaining;        // -1 free, 0 finished, k > 0 running
+  std::vector<int> len;              // latent frames of the slot's item (the minimum length while free)
+  hipStream_t last_stream = nullptr;
+  bool warm = false;                 // the first step of the pool has run eagerly (code objects loaded outside a capture)
+  bool touched = false, poisoned = false;   // as ldc_stream
+  DevMem mem;
+};
+
 struct SeaRun {   // measures or runs a SEANet stack
   ldc_ctx* c;
   Arena* ar;
@@ -494,6 +519,17 @@ int check_unet_args(ldc_ctx* c, int B, int L, int F);
 int upsample_factor(const ldc_ctx* c);
 int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F);
 int check_dev(ldc_ctx* c);   // hipSetDevice only: calls that need no weights
+// what ldc_api_pool.cpp shares with the samplers of ldc_api.cpp
+int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false, bool items = false, int pool_id = 0);
+int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step, hipStream_t s);
+int calibrate_part_streams(ldc_ctx* c, hipStream_t s);
+bool parts_parallel(ldc_ctx* c, const Halves& h);
+int fork_parts(ldc_ctx* c, const Halves& h, hipStream_t s);
+int join_parts(ldc_ctx* c, const Halves& h, hipStream_t s);
+hipError_t replay_parts(ldc_ctx* c, const Halves& h, StepGraph* sg, int n_big, int n_rep, bool single_len, hipStream_t s, const char** what);
+int ragged_latent_quantum(const ldc_ctx* c);
+int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool ragged = false, bool items = false, int pool_id = 0);
+int load_cond(ldc_ctx* c, const Halves& h, const float* cond, hipStream_t s);
 
 // runs `body` twice: once against a measuring arena, then (after sizing the scratch) for real
 template <typename F>

@@ -161,7 +161,8 @@ hipError_t launch_gn_stats(int dt, const void* x, int B, int L, int C, int group
 hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual, int B, int L, int C, int groups,
                            const float* stats, const float* gamma, const float* beta, const float* ss_table,
                            int ss_stride, const int* t_ptr, int act, hipStream_t s, void* y_ln = nullptr, const float* ln_g = nullptr, int out8 = 0,
-                           const int* lens = nullptr, int shift = 0);
+                           const int* lens = nullptr, int shift = 0,
+                           int t_stride = 0, int t_rows = 0);   // per-item plan: item b's timestep is t_ptr[b * t_stride], clamped to the table's t_rows rows (t_stride 0: one timestep for the launch)
 // y_ln != null: also write channel-LayerNorm(y) * ln_g (needs gn_apply_ln_fusable(C) and ACT_SILU)
 bool gn_apply_ln_fusable(int C);
 // channel LayerNorm (gain only, biased var, eps 1e-5) per row; y = LN(x)*g (+ residual)
@@ -230,6 +231,31 @@ hipError_t launch_axpby(float* x, const float* y, float a, float b, int64_t n, h
 hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                                   void* x_cl, int B, int C, int L, StepTables tb, const int* st,
                                   uint64_t elem_base, hipStream_t s, const int* lens = nullptr);   // lens [B] (positions): x and x_cl stay zero behind them
+// Per-item step state (per-item plans: ldc_unet_forward_items, decode pools): one record per item / pool slot in
+// device memory.  Nothing about an item's progress is a kernel argument, so one captured step graph replays for any mix of states.
+struct ItemState {
+  int t;                // timestep of the step being executed (unet.py:422-437: one per item)
+  int j;                // iteration: which entry of the noise tape / Philox step the update uses
+  unsigned key_lo, key_hi;   // Philox key of the item
+  int remaining;        // steps not yet begun (0 = idle: finished, evicted or never admitted)
+  int len;              // the item's own latent frames (the ragged plan's lens[] holds the same value)
+  int active;           // set by the step's first kernel: this step runs for the item (an idle item is computed on and discarded)
+  int pad_;
+  const float* noise;   // the item's tape [n_steps][C][len] (contiguous for its OWN length) or null: Philox draws
+};
+constexpr int kItemStateInts = (int)(sizeof(ItemState) / sizeof(int));
+// dst[0..n) = src_host[0..n), stream-ordered (kernel arguments carry the records); lens / flens (optional): lens[i] = len, flens[i] = len / up
+hipError_t launch_items_write(ItemState* dst, const ItemState* src_host, int n, int* lens, int* flens, int up, hipStream_t s);
+// First kernel of a step of a per-item plan: for every item, active = remaining > 0 and, with `advance`, a running item moves on
+// (t - 1, j + 1, remaining - 1); counts the part's epoch word st[4] up once; clears the step's accumulator region as launch_step_begin does.
+// The timestep's (scale | shift) row is NOT copied: gn_apply selects it from the table by the item's t (launch_gn_apply, t_stride).
+hipError_t launch_step_begin_items(ItemState* items, int B, int* st, void* zero, size_t zero_bytes, int advance, hipStream_t s);
+// launch_p_sample_update per item: coefficients from the item's t, noise = tape[j] of the item's own tape or a Philox draw with the item's
+// key, step j and group index c * len + l (what the item draws alone at B = 1); no noise at t == 0.  x: item b at x + b * x_item_stride,
+// [C][len] fp32; eps_cl / x_cl [B][Lmax][C].  An item with active == 0 is not stored (neither x nor x_cl) and its tape is not dereferenced;
+// rows >= len are never touched (x_cl stays zero there from the admission).  T = timesteps (t is clamped to the tables)
+hipError_t launch_p_sample_update_items(int dt, float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int B, int C, int Lmax,
+                                        StepTables tb, const ItemState* items, int T, hipStream_t s);
 // One iteration of DDIM sampling (reference ddpm_loss.py ddim_sample, clip_denoised): the host fills one entry per
 // iteration j (ldc_api.cpp: ddim_schedule) into a device table that the step state indexes.
 struct DdimStep {

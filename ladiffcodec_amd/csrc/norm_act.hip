@@ -158,7 +158,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const void* x, void* y, const void* residual, int B, int L, int C,
                                                        int groups, const float* stats, const float* gamma,
                                                        const float* beta, const float* ss_table, int ss_stride,
-                                                       const int* t_ptr, int act, const int* lens, int shift) {
+                                                       const int* t_ptr, int act, const int* lens, int shift, int t_stride, int t_rows) {
   const int vec_per_row = C / 8;
   const size_t total = (size_t)B * L * vec_per_row;
   const int cpg = C / groups;
@@ -170,6 +170,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const void* x, void* y, c
     const int b = (int)(row / L);
     const int Lv = valid_rows(lens, shift, b, L);
     const float inv_n = 1.0f / ((float)Lv * (float)cpg);
+    if (ss_table && t_stride) ss = ss_table + (size_t)min(max(t_ptr[(size_t)b * t_stride], 0), t_rows - 1) * ss_stride;   // per-item plan: the row of item b's own timestep (clamped to the table)
     float f[8], o[8];
     Vec8<T>::load(x, row * C + v * 8, f);
 #pragma unroll
@@ -209,7 +210,8 @@ __global__ __launch_bounds__(256) void gn_apply_cols_kernel(const void* x, void*
                                                             int groups, int rows_per_block, const float* stats,
                                                             const float* gamma, const float* beta, const float* ss_table,
                                                             int ss_stride, const int* t_ptr, int act, int dbg,
-                                                            void* y_ln, const float* ln_g, int out8, const int* lens, int shift) {
+                                                            void* y_ln, const float* ln_g, int out8, const int* lens, int shift,
+                                                            int t_stride, int t_rows) {
   __shared__ __attribute__((aligned(16))) float s_a[2048];
   __shared__ __attribute__((aligned(16))) float s_b[2048];
   __shared__ float s_red[LN ? 2 * 4 * 8 : 1];   // [sum | sumsq][wave][q]
@@ -234,7 +236,8 @@ __global__ __launch_bounds__(256) void gn_apply_cols_kernel(const void* x, void*
   const int Lv = valid_rows(lens, shift, b, L);   // (the statistics were summed over Lv rows)
   const float inv_n = 1.0f / ((float)Lv * (float)cpg);
   const float* ss = nullptr;
-  if (ss_table) ss = ss_table + (size_t)(t_ptr ? *t_ptr : 0) * ss_stride;
+  // (t_stride != 0, per-item plan: the (scale | shift) row of item b's own timestep -- the only place the timestep enters the unfused UNet step)
+  if (ss_table) ss = ss_table + (size_t)(t_ptr ? (t_stride ? min(max(t_ptr[(size_t)b * t_stride], 0), t_rows - 1) : *t_ptr) : 0) * ss_stride;
   for (int c = threadIdx.x; c < C; c += 256) {
     if (dbg & 1) { s_a[c] = 1.0f; s_b[c] = 0.5f; continue; }
     const int g = c / cpg;
@@ -372,25 +375,27 @@ static int gn_pick_u(int B, int L, int vpr) {
 template <typename T, int ACT, bool LN, int VPR>
 static void gn_launch_u(int U, dim3 grid, hipStream_t s, const void* x, void* y, const void* residual, int L, int C, int groups, int rpb,
                         const float* stats, const float* gamma, const float* beta, const float* ss_table, int ss_stride,
-                        const int* t_ptr, int act, int dbg, void* y_ln, const float* ln_g, int out8, const int* lens, int shift) {
+                        const int* t_ptr, int act, int dbg, void* y_ln, const float* ln_g, int out8, const int* lens, int shift, int t_stride, int t_rows) {
 #define LDC_GN_GO(UU)                                                                                                     \
   hipLaunchKernelGGL((gn_apply_cols_kernel<T, ACT, LN, VPR, UU>), grid, dim3(256), 0, s, x, y, residual, L, C, groups, rpb, \
-                     stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8, lens, shift)
+                     stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8, lens, shift, t_stride, t_rows)
   if (U == 8) LDC_GN_GO(8); else if (U == 4) LDC_GN_GO(4); else if (U == 2) LDC_GN_GO(2); else LDC_GN_GO(1);
 #undef LDC_GN_GO
 }
 
 hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual, int B, int L, int C, int groups,
                            const float* stats, const float* gamma, const float* beta, const float* ss_table,
-                           int ss_stride, const int* t_ptr, int act, hipStream_t s, void* y_ln, const float* ln_g, int out8, const int* lens, int shift) {
+                           int ss_stride, const int* t_ptr, int act, hipStream_t s, void* y_ln, const float* ln_g, int out8, const int* lens, int shift,
+                           int t_stride, int t_rows) {
   const int vpr = C / 8;
+  if (t_stride && (!ss_table || !t_ptr || t_rows <= 0)) return hipErrorInvalidValue;
   if (y_ln && (!gn_apply_ln_fusable(C) || act != ACT_SILU)) return hipErrorInvalidValue;
   if (C % 8 == 0 && vpr <= 256 && 256 % vpr == 0 && C <= 2048) {
     const int U = gn_pick_u(B, L, vpr);
     const int rpb = (256 / vpr) * U;   // one U-row trip per thread
     const int dbg = 0;
     dim3 grid((L + rpb - 1) / rpb, B);
-#define LDC_GN_ARGS grid, s, x, y, residual, L, C, groups, rpb, stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8, lens, shift
+#define LDC_GN_ARGS grid, s, x, y, residual, L, C, groups, rpb, stats, gamma, beta, ss_table, ss_stride, t_ptr, act, dbg, y_ln, ln_g, out8, lens, shift, t_stride, t_rows
     if (y_ln) {
       if (dt == DT_F32) {
         if (vpr == 32) gn_launch_u<float, ACT_SILU, true, 32>(U, LDC_GN_ARGS);
@@ -414,10 +419,10 @@ hipError_t launch_gn_apply(int dt, const void* x, void* y, const void* residual,
   if (blocks < 1) blocks = 1;
   if (dt == DT_F32)
     hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(blocks), dim3(256), 0, s, x, y, residual, B, L, C, groups, stats,
-                       gamma, beta, ss_table, ss_stride, t_ptr, act, lens, shift);
+                       gamma, beta, ss_table, ss_stride, t_ptr, act, lens, shift, t_stride, t_rows);
   else
     hipLaunchKernelGGL(gn_apply_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, x, y, residual, B, L, C, groups, stats,
-                       gamma, beta, ss_table, ss_stride, t_ptr, act, lens, shift);
+                       gamma, beta, ss_table, ss_stride, t_ptr, act, lens, shift, t_stride, t_rows);
   return hipGetLastError();
 }
 

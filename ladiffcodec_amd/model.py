@@ -71,6 +71,7 @@ class Engine:
         self.stream = torch.cuda.Stream(device=self.device)
         self._finalized = False
         self._streams = []                  # open stream sessions (CodecStream)
+        self._pools = []                    # open decode pools (DecodePool)
 
     def set_option(self, name: str, value: int) -> None:
         """ldc_set_option: 'split' (chains per batch), 'lstm_stream' (no cooperative LSTM), 'side_streams', 'fp8_act',
@@ -114,6 +115,8 @@ class Engine:
             self.torch.cuda.synchronize(self.device)
             for st in list(getattr(self, "_streams", [])):      # a session holds a pointer to the context: it goes first
                 st.close()
+            for pool in list(getattr(self, "_pools", [])):      # (so does a decode pool)
+                pool.close()
             self.lib.ldc_destroy(self._ctx)
             self._ctx = None
 
@@ -535,6 +538,85 @@ class Engine:
             self._exit()
         return eps
 
+    def unet_forward_items(self, x, t, cond, lens=None):
+        """`unet_forward` with a timestep per item (Unet1D.forward's `time[B]`): t a sequence of B timesteps; lens (optional) per-item
+        latent lengths as in `unet_forward_ragged`.  eps is zero beyond an item's length."""
+        x, cond = self._f32(x), self._f32(cond)
+        B, Cx, Lx = x.shape
+        ts = self._lengths([int(v) for v in t], B)
+        ln = self._lengths(list(lens), B) if lens is not None else None
+        eps = self._empty(B, Cx, Lx)
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_unet_forward_items(self._ctx, x.data_ptr(), ts, cond.data_ptr(), ln, B, Lx, cond.shape[2], eps.data_ptr(), s))
+        finally:
+            self._exit()
+        return eps
+
+    def open_pool(self, slots: int, max_samples: int, sampler: str = "ddpm") -> "DecodePool":
+        """A decode pool (ldc_pool_create): `slots` items of up to max_samples samples step together on one captured step graph while each
+        keeps its own timestep, step count, noise and length; items are submitted and popped while the others keep stepping.  Only the
+        halfway DDPM sampler runs in a pool (DDIM would need a schedule table per item)."""
+        if sampler != "ddpm":
+            raise ValueError(f"sampler {sampler!r}: a decode pool runs the halfway DDPM sampler only")
+        return DecodePool(self, slots, max_samples)
+
+    # ---- the calls a DecodePool makes (a stub engine without a GPU provides these) ------------
+    def pool_create(self, slots: int, Lmax: int):
+        h = C.c_void_p()
+        L.check(self.lib.ldc_pool_create(self._ctx, int(slots), int(Lmax), C.byref(h)))
+        return h
+
+    def pool_destroy(self, h) -> None:
+        self.lib.ldc_pool_destroy(h)
+
+    def pool_remaining(self, h, slots: int):
+        out = (C.c_int32 * slots)()
+        L.check(self.lib.ldc_pool_remaining(h, out))
+        return list(out)
+
+    def pool_front(self, wav=None, codes=None):
+        """the B = 1 front end of one item: -> (start image [1, C, L], raw condition [1, C, F])"""
+        if (wav is None) == (codes is None):
+            raise ValueError("exactly one of wav / codes")
+        cond = self.get_cond(wav) if wav is not None else self.rvq_decode(codes)
+        return self.cond_upsample(cond, 2), cond
+
+    def pool_admit(self, h, slot: int, img, cond, n_steps: int, noise=None, seed: int = 0) -> None:
+        img, cond = self._f32(img), self._f32(cond)
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_pool_admit(self._ctx, h, int(slot), img.data_ptr(), cond.data_ptr(), int(img.shape[-1]), int(n_steps),
+                                            noise.data_ptr() if noise is not None else None, int(seed) & (2 ** 64 - 1), s))
+        finally:
+            self._exit()
+        return noise                       # (the tape the library reads: the pool keeps it alive until the item has finished)
+
+    def pool_step(self, h, n: int) -> None:
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_pool_step(self._ctx, h, int(n), s))
+        finally:
+            self._exit()
+
+    def pool_take(self, h, slot: int, Lz: int, keep: bool = False):
+        """the latents of a finished slot; keep = True leaves the item in its slot (ldc_pool_peek)"""
+        lat = self._empty(1, self.main_codec.rep_dims, int(Lz))
+        s = self._enter()
+        try:
+            L.check((self.lib.ldc_pool_peek if keep else self.lib.ldc_pool_take)(self._ctx, h, int(slot), lat.data_ptr(), s))
+        finally:
+            self._exit()
+        return lat
+
+    def pool_evict(self, h, slot: int) -> None:
+        L.check(self.lib.ldc_pool_evict(h, int(slot)))
+
+    def pool_back(self, latents):
+        """the B = 1 back end of one item: latents [1, C, L] -> waveform [1, 1, L * hop], normalised per item"""
+        return self.output_normalise(self.decode_latents(L.MODEL_MAIN, latents), per_item=True)
+
     def _codes_args(self, codes, packed, bits, n_q, F):
         """-> (codes ptr, packed ptr, packed stride, n_q, B, F, kept tensors) for ldc_decode_codes*"""
         t = self.torch
@@ -795,6 +877,97 @@ class CodecStream:
             pass
 
 
+class DecodePool:
+    """A fixed set of slots that step together (Engine.open_pool, ldc_pool_*): `submit` admits an item into a free slot, `step`
+    advances every running item, `finished` lists the tickets whose items are done, `pop` takes one out and decodes its waveform.
+    An item comes out as `Engine.denoise` gives it alone at B = 1, whatever the other slots hold (within rounding).  The bookkeeping
+    here is plain Python over the library's host mirror (`pool_remaining`); the engine may be any object with the `pool_*` methods."""
+
+    def __init__(self, eng, slots: int, max_samples: int):
+        self.eng, self.slots = eng, int(slots)
+        hop = eng.main_codec.hop_length
+        if max_samples <= 0 or max_samples % hop:
+            raise ValueError(f"max_samples {max_samples} must be a positive multiple of the hop {hop}")
+        self.hop, self.Lmax = hop, int(max_samples) // hop
+        self._h = eng.pool_create(self.slots, self.Lmax)
+        if hasattr(eng, "_pools"):
+            eng._pools.append(self)         # (Engine.close destroys the pools it still has before the context)
+        self._slot_of = {}                  # ticket -> slot
+        self._info = {}                     # ticket -> (latent length, noise tape kept alive)
+        self._next = 0
+
+    def remaining(self):
+        """per slot: -1 free, 0 finished, k > 0 steps to go"""
+        return self.eng.pool_remaining(self._h, self.slots)
+
+    def free_slots(self):
+        return [i for i, r in enumerate(self.remaining()) if r < 0]
+
+    def submit(self, wav=None, codes=None, n_steps: int = 50, noise=None, seed=None) -> int:
+        """wav [1, 1, T] or codes [n_q, 1, F] of ONE item; noise [n_steps, 1, C, L] or None (Philox with key `seed`, the ticket number when
+        None).  -> ticket.  Raises when no slot is free."""
+        free = self.free_slots()
+        if not free:
+            raise RuntimeError(f"no free slot in a pool of {self.slots}: step until an item has finished and pop it")
+        img, cond = self.eng.pool_front(wav=wav, codes=codes)
+        ticket = self._next
+        kept = self.eng.pool_admit(self._h, free[0], img, cond, int(n_steps), noise, ticket if seed is None else int(seed))
+        self._next += 1
+        self._slot_of[ticket] = free[0]
+        self._info[ticket] = (int(img.shape[-1]), kept)
+        return ticket
+
+    def step(self, n: int = 1) -> None:
+        self.eng.pool_step(self._h, int(n))
+
+    def finished(self):
+        """tickets whose items are done, in submission order"""
+        rem = self.remaining()
+        return [t for t in sorted(self._slot_of) if rem[self._slot_of[t]] == 0]
+
+    def running(self):
+        rem = self.remaining()
+        return [t for t in sorted(self._slot_of) if rem[self._slot_of[t]] > 0]
+
+    def pop(self, ticket: int):
+        """-> {"wav" [1, 1, T], "latents" [1, C, L]} of a finished item; its slot is free again"""
+        if ticket not in self._slot_of:
+            raise KeyError(f"ticket {ticket} is not in the pool")
+        slot = self._slot_of[ticket]
+        lat = self.eng.pool_take(self._h, slot, self._info[ticket][0])
+        del self._slot_of[ticket], self._info[ticket]
+        return {"wav": self.eng.pool_back(lat), "latents": lat}
+
+    def peek(self, ticket: int):
+        """the latents [1, C, L] of a finished item that stays in its slot"""
+        return self.eng.pool_take(self._h, self._slot_of[ticket], self._info[ticket][0], keep=True)
+
+    def evict(self, ticket: int) -> None:
+        slot = self._slot_of.pop(ticket)
+        del self._info[ticket]
+        self.eng.pool_evict(self._h, slot)
+
+    def run_until_done(self) -> None:
+        while True:
+            rem = [r for r in self.remaining() if r > 0]
+            if not rem:
+                return
+            self.step(min(rem))             # (to the next item that finishes: nothing idles longer than it must)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            self.eng.pool_destroy(self._h)
+            self._h = None
+            if self in getattr(self.eng, "_pools", []):
+                self.eng._pools.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _Upsampler:
     """Stands for `diff_model.upsampling_layers`: iterating yields one callable that applies the WHOLE
     stack (the reference applies them in sequence, sample.py:127-128), so `for layer in
@@ -819,8 +992,8 @@ class _DiffModel:
 
     def __call__(self, x, time, x_cond=None):
         t = int(time.reshape(-1)[0].item()) if hasattr(time, "reshape") else int(time)
-        if hasattr(time, "reshape") and bool((time != t).any()):
-            raise ValueError("per-item timesteps are not supported (the sampler never uses them)")
+        if hasattr(time, "reshape") and bool((time != t).any()):      # a timestep per item (unet.py:422-437): the per-item plan
+            return self._eng.unet_forward_items(x, [int(v) for v in time.reshape(-1).tolist()], x_cond)
         return self._eng.unet_forward(x, t, x_cond)
 
 
