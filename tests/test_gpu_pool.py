@@ -1,6 +1,7 @@
 """A timestep per item and the decode pool on the GPU.  References are the CPU oracle's SOLO results (every item alone, at its own
-timestep / with its own tape and step count), never the engine under test -- except the Philox checks, which compare with the
-engine's own unchanged B = 1 path because the oracle has no Philox.
+timestep / with its own tape and step count), never the engine under test -- except the Philox checks here, which compare with the
+engine's own unchanged B = 1 path; tests/test_gpu_noise.py ties both, the pool item and the B = 1 path, to the oracle's exact Philox
+(oracle/philox_oracle.py).
 
 Items: the four lengths of tests/test_gpu_ragged.py (3, 1, 5, 2 quanta for `r84`, the same sample counts for `r8`) cut from the same
 waveforms, plus a fifth item E (5120 samples) that enters the slot B leaves.  n_steps 10, 6, 10, 4, 7.
