@@ -285,12 +285,17 @@ int ldc_unet_forward_items(ldc_ctx* ctx, const float* x, const int32_t* t_host /
 
 /* decode pools -----------------------------------------------------------------------------------
  * A pool is a fixed set of slots that step together on one captured step graph per batch part, while every slot keeps its own
- * timestep, iteration, noise (tape or Philox key), length and "is running" flag in device memory.  Items are admitted into free
- * slots and taken out of finished ones while the others keep stepping.
- * Contract: an item's latents are those of ldc_denoise(img, cond, noise, n_steps, B = 1, L, F) on the item alone -- whatever the
- * other slots hold, whenever it was admitted, whichever slot it sits in -- within rounding (the unfused GroupNorm statistics are
- * summed with atomics: the contract of ldc_decode_ragged, not bit identity).  Only the halfway DDPM sampler runs in a pool; DDIM
- * would need a schedule table per item and has no pool entry point.
+ * sampler, timestep, iteration, noise (tape or Philox key), length and "is running" flag in device memory.  Items are admitted into
+ * free slots and taken out of finished ones while the others keep stepping.
+ * The sampler is a property of an item, not of the pool: ldc_pool_admit admits a halfway-DDPM item, ldc_pool_admit_ddim a DDIM item
+ * with a schedule (t_start, n_steps, eta) of its own, into the same pool, in any mix; an 8-iteration DDIM item leaves its slot while a
+ * 50-step DDPM neighbour keeps going.  The pool owns one schedule row per slot (timesteps entries, 32 KB), allocated with the pool.
+ * Contract: a DDPM item's latents are those of ldc_denoise(img, cond, noise, n_steps, B = 1, L, F) on the item alone, a DDIM item's
+ * those of ldc_ddim_sample(img, cond, noise, fill_start = 0, t_start, n_steps, eta, B = 1, L, F) -- whatever the other slots hold
+ * (either sampler, any schedule), whenever it was admitted, whichever slot it sits in -- within rounding (the unfused GroupNorm
+ * statistics are summed with atomics: the contract of ldc_decode_ragged, not bit identity).
+ * What stays out of a pool: the fp8 engine, the fused GroupNorm and attention launch forms (a per-item plan takes the unfused ones),
+ * and fill_start (a start image drawn on the device: the caller passes img).
  * An idle slot (free, or finished and not yet taken) is computed on and discarded: its latents are not stored, so a finished item
  * keeps its latents bit for bit until it is taken, and its noise tape is not read after its last step.
  * The step graphs are keyed by (slots, Lmax, Fmax, pool) in the context's plan and graph caches and replayed for every state; the
@@ -300,7 +305,8 @@ int ldc_unet_forward_items(ldc_ctx* ctx, const float* x, const int32_t* t_host /
  * makes a call synchronous on the context's own stream.  Destroy a context's pools before the context.
  * Refused with LDC_E_INVALID before any GPU work, ldc_last_error() naming the value: a slot outside [0, slots); admit into a slot
  * that is not free; L off the ragged latent quantum or above Lmax; n_steps outside [1, timesteps]; n <= 0; slots <= 0; a pool of
- * another context; a null pointer; an fp8 engine.  ldc_pool_take of a slot that is not finished: LDC_E_STATE.  After a refusal the
+ * another context; a null pointer; an fp8 engine; for a DDIM item t_start outside [1, timesteps], n_steps outside [1, t_start], eta
+ * outside [0, 1] or not finite.  ldc_pool_take of a slot that is not finished: LDC_E_STATE.  After a refusal the
  * pool goes on as if the call had not been made.  A call that fails AFTER its GPU work began (LDC_E_HIP, LDC_E_NOMEM) marks the
  * pool: it then refuses with LDC_E_STATE until every slot has been evicted. */
 typedef struct ldc_pool ldc_pool;
@@ -311,7 +317,12 @@ int ldc_pool_destroy(ldc_pool* pool);                                         /*
  * item has finished) or NULL: Philox with key = seed, i.e. the tape ldc_reseed(ctx, seed) gives the first ldc_denoise at B = 1. */
 int ldc_pool_admit(ldc_ctx* ctx, ldc_pool* pool, int slot, const float* img, const float* cond, int L, int n_steps,
                    const float* noise, uint64_t seed, void* stream);
-int ldc_pool_step(ldc_ctx* ctx, ldc_pool* pool, int n, void* stream);         /* n steps of every running slot; a slot stops behind t = 0 */
+/* A DDIM item: n_steps iterations on the timesteps ldc_ddim_times(t_start, n_steps) with the coefficients of ldc_ddim_sample.  noise
+ * [n_steps,1,C,L], entry j at iteration j (the last entry is never read, none is at eta == 0), or NULL: Philox with key = seed, i.e.
+ * what ldc_reseed(ctx, seed) gives the first ldc_ddim_sample at B = 1.  ldc_pool_remaining counts its iterations. */
+int ldc_pool_admit_ddim(ldc_ctx* ctx, ldc_pool* pool, int slot, const float* img, const float* cond, int L, int t_start, int n_steps,
+                        float eta, const float* noise, uint64_t seed, void* stream);
+int ldc_pool_step(ldc_ctx* ctx, ldc_pool* pool, int n, void* stream);         /* n steps of every running slot; a slot stops behind its last step */
 int ldc_pool_remaining(const ldc_pool* pool, int32_t* remaining_host /*[slots]*/);   /* host mirror, no GPU work: -1 free, 0 finished, k > 0 running */
 int ldc_pool_take(ldc_ctx* ctx, ldc_pool* pool, int slot, float* latents_out /*[1,C,L]*/, void* stream);   /* finished slots only; frees the slot */
 int ldc_pool_peek(ldc_ctx* ctx, ldc_pool* pool, int slot, float* latents_out /*[1,C,L]*/, void* stream);   /* ldc_pool_take without freeing the slot */

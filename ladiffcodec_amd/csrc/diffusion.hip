@@ -659,7 +659,8 @@ hipError_t launch_items_write(ItemState* dst, const ItemState* src, int n, int* 
 }
 
 // step_begin_kernel for a per-item plan.  Workgroup 0 owns the items' states: active = remaining > 0, a running item moves on when asked to
-// (t - 1, j + 1, one step less remaining: a slot stops behind t = 0 by itself), the part's epoch word is counted up once.  No row is
+// (t - 1, j + 1, one step less remaining: a slot stops behind t = 0 by itself; an item with a schedule takes t from entry j + 1 of it and
+// stops behind its last entry), the part's epoch word is counted up once.  No row is
 // copied: gn_apply reads the (scale | shift) row of each item's t from the table.  Every other workgroup clears the accumulator region.
 __global__ __launch_bounds__(1024) void step_begin_items_kernel(ItemState* items, int B, int* st, uint4* zero, long long zero_n16, int advance) {
   constexpr int nthr = 1024;
@@ -668,8 +669,10 @@ __global__ __launch_bounds__(1024) void step_begin_items_kernel(ItemState* items
       ItemState* it = items + b;
       const int run = it->remaining > 0;
       if (run && advance) {
-        it->t -= 1;
-        it->j += 1;
+        const DdimStep* sc = it->sched;
+        const int j = it->j + 1;
+        it->t = sc ? sc[max(j, 0)].t : it->t - 1;   // DDIM: the timestep of iteration j of the item's own strided schedule
+        it->j = j;
         it->remaining -= 1;
       }
       it->active = run;
@@ -690,7 +693,9 @@ hipError_t launch_step_begin_items(ItemState* items, int B, int* st, void* zero,
 }
 
 // p_sample_update_kernel with everything about the step read from the item's record.  Same 32 x 32 tiling; the item's state is [C][len]
-// on its own length, so a tile behind the item's end (and every tile of an idle item) leaves before it touches memory.
+// on its own length, so a tile behind the item's end (and every tile of an idle item) leaves before it touches memory.  The sampler is
+// the item's too: a record with a schedule takes ddim_update_kernel's arithmetic with the coefficients of sched[j], a record without
+// one p_sample's.  The branch is uniform over the workgroup (one item per blockIdx.z), so one launch serves any mix of the two.
 template <typename T>
 __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int C,
                                                                     int Lmax, StepTables tb, const ItemState* items, int n_t) {
@@ -698,9 +703,10 @@ __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, in
   const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
   const ItemState it = items[b];
   const int L = min(it.len, Lmax);
-  if (!it.active || l0 >= L) return;   // (uniform over the workgroup) idle: neither x nor x_cl is stored, the tape is not dereferenced
+  if (!it.active || l0 >= L) return;   // (uniform over the workgroup) idle: neither x nor x_cl is stored, neither the tape nor the schedule is dereferenced
   float* xb = x + (size_t)b * x_item_stride;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  // the tensor loads need the record only: issue them before the dependent chain schedule entry -> coefficient tables
   float ev[4], xin[4];
 #pragma unroll
   for (int ii = 0; ii < 4; ++ii) {
@@ -710,18 +716,29 @@ __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, in
     const int cc = c0 + i, ll = l0 + tx;
     xin[ii] = (cc < C && ll < L) ? xb[(size_t)cc * L + ll] : 0.f;
   }
-  const int t = min(max(it.t, 0), n_t - 1), j = it.j;
+  const int j = it.j;
   const uint64_t seed = ((uint64_t)it.key_hi << 32) | (uint64_t)it.key_lo;
+  const bool ddim = it.sched != nullptr;
+  DdimStep sp{};
+  if (ddim) sp = it.sched[min(max(j, 0), n_t - 1)];   // (the pool's arena row holds n_t entries)
+  const int t = min(max(ddim ? sp.t : it.t, 0), n_t - 1);
   const float recip = tb.sqrt_recip_alphas_cumprod[t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[t];
-  const float c1 = tb.posterior_mean_coef1[t], c2 = tb.posterior_mean_coef2[t];
-  const float sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
+  float c1 = 0.f, c2 = 0.f, sigma = sp.sigma;
+  if (!ddim) {
+    c1 = tb.posterior_mean_coef1[t];
+    c2 = tb.posterior_mean_coef2[t];
+    sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
+  }
+  // noise is read or drawn only here: DDPM at t > 0, DDIM on an iteration that is not the last and has sigma > 0
+  const bool draw = ddim ? (!sp.last && sp.sigma > 0.f) : t > 0;
 #pragma unroll
   for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
   __syncthreads();
   float newv[4];
-  // one Philox block per thread at the index of its first element IN THE ITEM ALONE (c * len + l): what ldc_denoise draws for it at B = 1
+  // one Philox block per thread at the index of its first element IN THE ITEM ALONE (c * len + l): what ldc_denoise / ldc_ddim_sample draw
+  // for it at B = 1
   float zz[4] = {0.f, 0.f, 0.f, 0.f};
-  if (t > 0 && !it.noise) philox_normal4(seed, (unsigned)j, (uint64_t)(c0 + ty) * L + l0 + tx, zz);
+  if (draw && !it.noise) philox_normal4(seed, (unsigned)j, (uint64_t)(c0 + ty) * L + l0 + tx, zz);
 #pragma unroll
   for (int ii = 0; ii < 4; ++ii) {
     const int i = ty + ii * 8;
@@ -733,8 +750,17 @@ __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, in
       const float e = tile[tx][i];
       float x0 = recip * xv - recipm1 * e;
       x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-      float v = c1 * x0 + c2 * xv;
-      if (t > 0) v += sigma * (it.noise ? it.noise[(size_t)j * C * L + idx] : zz[ii]);
+      float v;
+      if (ddim) {
+        v = x0;
+        if (!sp.last) {
+          v = x0 * sp.sqrt_an + sp.c * e;
+          if (draw) v += sigma * (it.noise ? it.noise[(size_t)j * C * L + idx] : zz[ii]);
+        }
+      } else {
+        v = c1 * x0 + c2 * xv;
+        if (draw) v += sigma * (it.noise ? it.noise[(size_t)j * C * L + idx] : zz[ii]);
+      }
       xb[idx] = v;
       newv[ii] = v;
     }

@@ -2763,8 +2763,9 @@ extern "C" int ldc_ddim_times(int t_start, int n_steps, int* times_out) {
   return LDC_OK;
 }
 
-// the per-iteration coefficients into c->ddim_host; float32 in the reference's order of operations.  *draws: some sigma > 0
-static int ddim_schedule(ldc_ctx* c, int t_start, int n_steps, float eta, bool* draws) {
+// the per-iteration coefficients of a DDIM schedule into `out` (n_steps entries); float32 in the reference's order of operations.
+// *draws: some sigma > 0.  The context's samplers fill c->ddim_host (ddim_schedule below), a decode pool the row of one slot.
+int ddim_schedule_fill(ldc_ctx* c, int t_start, int n_steps, float eta, std::vector<DdimStep>* out, bool* draws) {
   if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "eta must be a finite value in [0, 1]");
   if (t_start < 1 || t_start > c->unet.timesteps) return fail(LDC_E_INVALID, "t_start must be in [1,%d]", c->unet.timesteps);
   if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps must be in [1, t_start = %d] (more would repeat timesteps)", t_start);
@@ -2772,10 +2773,10 @@ static int ddim_schedule(ldc_ctx* c, int t_start, int n_steps, float eta, bool* 
   std::vector<int> times(n_steps + 1);
   LDCCHK(ldc_ddim_times(t_start, n_steps, times.data()));
   const std::vector<float>& ac = c->alphas_cumprod;
-  c->ddim_host.assign(n_steps, DdimStep{});
+  out->assign(n_steps, DdimStep{});
   *draws = false;
   for (int j = 0; j < n_steps; ++j) {
-    DdimStep& e = c->ddim_host[j];
+    DdimStep& e = (*out)[j];
     const int t = times[j], tn = times[j + 1];
     e.t = t;
     e.last = tn < 0;
@@ -2788,6 +2789,9 @@ static int ddim_schedule(ldc_ctx* c, int t_start, int n_steps, float eta, bool* 
     *draws = *draws || sigma > 0.0f;
   }
   return LDC_OK;
+}
+static int ddim_schedule(ldc_ctx* c, int t_start, int n_steps, float eta, bool* draws) {
+  return ddim_schedule_fill(c, t_start, n_steps, eta, &c->ddim_host, draws);
 }
 
 // c->ddim_host -> the context's device table, ordered on s behind everything queued there before (earlier calls' replays read it)

@@ -475,13 +475,16 @@ struct ldc_stream {
 
 // A decode pool (ldc_pool_create): `slots` items that step together on one captured graph per batch part while each
 // keeps its own timestep, iteration, noise and length.  The state of record is on the device: the items' records, x_cl, the processed
-// condition (in the pool's pinned per-item plans) and the fp32 latents x [slots][C * Lmax] (item b: [C][len_b] at b * C * Lmax).  The host
-// keeps a mirror of the step counts only.
+// condition (in the pool's pinned per-item plans), the fp32 latents x [slots][C * Lmax] (item b: [C][len_b] at b * C * Lmax) and the
+// schedule arena (one row of DdimStep per slot: the record of a DDIM item points into its slot's row).  The host keeps a mirror of the
+// step counts only.
 struct ldc_pool {
   ldc_ctx* ctx = nullptr;
   int id = 0, slots = 0, Lmax = 0, Fmax = 0;
   Halves h;                          // the pool's plans (pinned: Plan::pool_id)
   float* x = nullptr;                // [slots][C * Lmax] fp32
+  DdimStep* sched = nullptr;         // [slots][timesteps]: allocated with the pool, so a warm DDIM admit allocates nothing
+  std::vector<DdimStep> sched_host;  // the row being written by an admit (kept: no allocation on a warm call)
   std::vector<int> remaining;        // -1 free, 0 finished, k > 0 running
   std::vector<int> len;              // latent frames of the slot's item (the minimum length while free)
   hipStream_t last_stream = nullptr;
@@ -530,6 +533,7 @@ hipError_t replay_parts(ldc_ctx* c, const Halves& h, StepGraph* sg, int n_big, i
 int ragged_latent_quantum(const ldc_ctx* c);
 int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool ragged = false, bool items = false, int pool_id = 0);
 int load_cond(ldc_ctx* c, const Halves& h, const float* cond, hipStream_t s);
+int ddim_schedule_fill(ldc_ctx* c, int t_start, int n_steps, float eta, std::vector<DdimStep>* out, bool* draws);
 
 // runs `body` twice: once against a measuring arena, then (after sizing the scratch) for real
 template <typename F>

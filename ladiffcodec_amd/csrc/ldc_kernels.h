@@ -232,7 +232,9 @@ hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const fl
                                   void* x_cl, int B, int C, int L, StepTables tb, const int* st,
                                   uint64_t elem_base, hipStream_t s, const int* lens = nullptr);   // lens [B] (positions): x and x_cl stay zero behind them
 // Per-item step state (per-item plans: ldc_unet_forward_items, decode pools): one record per item / pool slot in
-// device memory.  Nothing about an item's progress is a kernel argument, so one captured step graph replays for any mix of states.
+// device memory.  Nothing about an item's progress or its sampler is a kernel argument, so one captured step graph replays for any mix
+// of states, DDPM and DDIM items side by side.
+struct DdimStep;
 struct ItemState {
   int t;                // timestep of the step being executed (unet.py:422-437: one per item)
   int j;                // iteration: which entry of the noise tape / Philox step the update uses
@@ -242,18 +244,22 @@ struct ItemState {
   int active;           // set by the step's first kernel: this step runs for the item (an idle item is computed on and discarded)
   int pad_;
   const float* noise;   // the item's tape [n_steps][C][len] (contiguous for its OWN length) or null: Philox draws
+  const DdimStep* sched;   // the item's DDIM schedule, entry j for iteration j (the pool's arena row of its slot), or null: DDPM p_sample
 };
 constexpr int kItemStateInts = (int)(sizeof(ItemState) / sizeof(int));
 // dst[0..n) = src_host[0..n), stream-ordered (kernel arguments carry the records); lens / flens (optional): lens[i] = len, flens[i] = len / up
 hipError_t launch_items_write(ItemState* dst, const ItemState* src_host, int n, int* lens, int* flens, int up, hipStream_t s);
 // First kernel of a step of a per-item plan: for every item, active = remaining > 0 and, with `advance`, a running item moves on
-// (t - 1, j + 1, remaining - 1); counts the part's epoch word st[4] up once; clears the step's accumulator region as launch_step_begin does.
+// (j + 1, remaining - 1; t - 1 for a DDPM item, t = sched[j].t for an item with a schedule); counts the part's epoch word st[4] up once;
+// clears the step's accumulator region as launch_step_begin does.
 // The timestep's (scale | shift) row is NOT copied: gn_apply selects it from the table by the item's t (launch_gn_apply, t_stride).
 hipError_t launch_step_begin_items(ItemState* items, int B, int* st, void* zero, size_t zero_bytes, int advance, hipStream_t s);
 // launch_p_sample_update per item: coefficients from the item's t, noise = tape[j] of the item's own tape or a Philox draw with the item's
 // key, step j and group index c * len + l (what the item draws alone at B = 1); no noise at t == 0.  x: item b at x + b * x_item_stride,
-// [C][len] fp32; eps_cl / x_cl [B][Lmax][C].  An item with active == 0 is not stored (neither x nor x_cl) and its tape is not dereferenced;
-// rows >= len are never touched (x_cl stays zero there from the admission).  T = timesteps (t is clamped to the tables)
+// [C][len] fp32; eps_cl / x_cl [B][Lmax][C].  An item with active == 0 is not stored (neither x nor x_cl) and neither its tape nor its
+// schedule is dereferenced; rows >= len are never touched (x_cl stays zero there from the admission).  T = timesteps (t is clamped to the
+// tables).  An item with a schedule (ItemState::sched) takes launch_ddim_update's arithmetic instead, in the same launch (the branch is
+// uniform over a workgroup): coefficients of sched[j], noise read or drawn only where !last && sigma > 0, same tape layout and Philox group.
 hipError_t launch_p_sample_update_items(int dt, float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int B, int C, int Lmax,
                                         StepTables tb, const ItemState* items, int T, hipStream_t s);
 // One iteration of DDIM sampling (reference ddpm_loss.py ddim_sample, clip_denoised): the host fills one entry per

@@ -555,10 +555,12 @@ class Engine:
 
     def open_pool(self, slots: int, max_samples: int, sampler: str = "ddpm") -> "DecodePool":
         """A decode pool (ldc_pool_create): `slots` items of up to max_samples samples step together on one captured step graph while each
-        keeps its own timestep, step count, noise and length; items are submitted and popped while the others keep stepping.  Only the
-        halfway DDPM sampler runs in a pool (DDIM would need a schedule table per item)."""
+        keeps its own sampler, timestep, step count, noise and length; items are submitted and popped while the others keep stepping.
+        The sampler is a property of an item, not of the pool: `DecodePool.submit(..., t_start=..., eta=...)` admits a DDIM item beside
+        DDPM ones.  `sampler` is kept for callers that pass "ddpm"; nothing else is a sampler of a pool."""
         if sampler != "ddpm":
-            raise ValueError(f"sampler {sampler!r}: a decode pool runs the halfway DDPM sampler only")
+            raise ValueError(f"sampler {sampler!r}: a pool has no sampler of its own, every item brings one: "
+                             "open the pool without it and pass submit(t_start=..., eta=...) for a DDIM item")
         return DecodePool(self, slots, max_samples)
 
     # ---- the calls a DecodePool makes (a stub engine without a GPU provides these) ------------
@@ -592,6 +594,19 @@ class Engine:
         finally:
             self._exit()
         return noise                       # (the tape the library reads: the pool keeps it alive until the item has finished)
+
+    def pool_admit_ddim(self, h, slot: int, img, cond, t_start: int, n_steps: int, eta: float, noise=None, seed: int = 0):
+        """ldc_pool_admit_ddim: n_steps DDIM iterations from t_start; noise [n_steps, 1, C, L] or None (Philox with key `seed`)"""
+        img, cond = self._f32(img), self._f32(cond)
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_pool_admit_ddim(self._ctx, h, int(slot), img.data_ptr(), cond.data_ptr(), int(img.shape[-1]), int(t_start),
+                                                 int(n_steps), float(eta), noise.data_ptr() if noise is not None else None,
+                                                 int(seed) & (2 ** 64 - 1), s))
+        finally:
+            self._exit()
+        return noise                       # (as pool_admit)
 
     def pool_step(self, h, n: int) -> None:
         s = self._enter()
@@ -880,7 +895,8 @@ class CodecStream:
 class DecodePool:
     """A fixed set of slots that step together (Engine.open_pool, ldc_pool_*): `submit` admits an item into a free slot, `step`
     advances every running item, `finished` lists the tickets whose items are done, `pop` takes one out and decodes its waveform.
-    An item comes out as `Engine.denoise` gives it alone at B = 1, whatever the other slots hold (within rounding).  The bookkeeping
+    An item comes out as `Engine.denoise` (a DDPM item) or `Engine.ddim_sample` (a DDIM item, `submit(t_start=...)`) gives it alone
+    at B = 1, whatever the other slots hold -- either sampler, any schedule -- within rounding.  The bookkeeping
     here is plain Python over the library's host mirror (`pool_remaining`); the engine may be any object with the `pool_*` methods."""
 
     def __init__(self, eng, slots: int, max_samples: int):
@@ -903,15 +919,20 @@ class DecodePool:
     def free_slots(self):
         return [i for i, r in enumerate(self.remaining()) if r < 0]
 
-    def submit(self, wav=None, codes=None, n_steps: int = 50, noise=None, seed=None) -> int:
+    def submit(self, wav=None, codes=None, n_steps: int = 50, noise=None, seed=None, t_start: int = 0, eta: float = 0.0) -> int:
         """wav [1, 1, T] or codes [n_q, 1, F] of ONE item; noise [n_steps, 1, C, L] or None (Philox with key `seed`, the ticket number when
-        None).  -> ticket.  Raises when no slot is free."""
+        None).  t_start 0 (the convention of `Engine.decode_ragged`): halfway DDPM sampling, n_steps steps; t_start > 0: n_steps DDIM
+        iterations from t_start with `eta`, and `remaining` counts iterations.  -> ticket.  Raises when no slot is free."""
         free = self.free_slots()
         if not free:
             raise RuntimeError(f"no free slot in a pool of {self.slots}: step until an item has finished and pop it")
         img, cond = self.eng.pool_front(wav=wav, codes=codes)
         ticket = self._next
-        kept = self.eng.pool_admit(self._h, free[0], img, cond, int(n_steps), noise, ticket if seed is None else int(seed))
+        key = ticket if seed is None else int(seed)
+        if t_start:
+            kept = self.eng.pool_admit_ddim(self._h, free[0], img, cond, int(t_start), int(n_steps), float(eta), noise, key)
+        else:
+            kept = self.eng.pool_admit(self._h, free[0], img, cond, int(n_steps), noise, key)
         self._next += 1
         self._slot_of[ticket] = free[0]
         self._info[ticket] = (int(img.shape[-1]), kept)
