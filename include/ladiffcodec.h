@@ -362,6 +362,38 @@ int ldc_decode_codes_ragged(ldc_ctx* ctx, const int64_t* codes, const uint8_t* p
                             int B, int Fmax, const int32_t* frames_host, int t_start, int n_steps, float eta, const float* noise,
                             float* wav_out, float* latents_out, float* cond_out, void* stream);
 
+/* DPM-Solver++(2M) sampling, data-prediction form (Lu et al. 2022): the second-order multistep solver on DDIM's timestep list and
+ * DDIM's clipped x0.  Deterministic: no noise argument, nothing is drawn, the noise epoch of the context is not advanced.
+ * Per timestep t, from the checkpoint's float32 tables promoted to double: R = sqrt_recip_alphas_cumprod[t] (1 / alpha),
+ * M = sqrt_recipm1_alphas_cumprod[t] (sigma / alpha), alpha = 1 / R, sigma = M / R, lambda = -ln M.
+ * times = ldc_ddim_times(t_start, n_steps); iteration j, (t, tn) = (times[j], times[j + 1]):
+ *   x0_j = clamp(R_t img - M_t eps(img, t, cond), -1, 1)
+ *   tn < 0 (the final iteration): img = x0_j, the history is not read; else
+ *   h = lambda_tn - lambda_t, phi = -alpha_tn expm1(-h), a = sigma_tn / sigma_t,
+ *   j == 0: img = a img + phi x0_0;  j >= 1: r = (lambda_t - lambda_times[j-1]) / h,
+ *                                            img = a img + phi (1 + 1/(2r)) x0_j - (phi / (2r)) x0_{j-1}.
+ * The coefficients are computed on the host in double and rounded once to float; the update runs in float32.
+ * ldc_dpm_schedule: that table for any pair of tables of `timesteps` entries; host-only, needs no context or GPU (like ldc_ddim_times).
+ * t_out [n_steps]; coef_out [n_steps][3], rows (a, b0, b1) of img = a img + b0 x0_j + b1 x0_{j-1}: b1 == 0 on row 0, the final row
+ * is (0, 1, 0).
+ * Refused by every call here (LDC_E_INVALID, before any GPU work, ldc_last_error() naming the value; a NULL context sees the
+ * context-free ones): t_start outside [1, timesteps], n_steps outside [1, t_start], null pointers, and the shape refusals of the
+ * DDIM call each one mirrors.  The steps replay captured graphs keyed by (B, L, F) and the sampler kind: every n_steps reuses them,
+ * and no call replays a DDPM or DDIM graph.  The x0 history lives with the cached plan of each batch part.
+ * Not available: decode pools, ldc_decode_codes_ragged, the SDE and third-order variants. */
+int ldc_dpm_schedule(const float* sqrt_recip, const float* sqrt_recipm1, int timesteps, int t_start, int n_steps, int* t_out,
+                     float* coef_out);
+/* ldc_ddim_sample's arguments without noise, fill_start and eta: img holds the start image. */
+int ldc_dpm_sample(ldc_ctx* ctx, float* img_inout, const float* cond, int t_start, int n_steps, int B, int L, int F, void* stream);
+/* ldc_decode_ddim / ldc_decode_codes_ddim / ldc_decode_ragged (the fp8 engine refused, as for every ragged call) with this sampler. */
+int ldc_decode_dpm(ldc_ctx* ctx, const float* wav, int B, int T, int t_start, int n_steps, int per_item, float* wav_out,
+                   float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+int ldc_decode_codes_dpm(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                         int F, int t_start, int n_steps, int per_item, float* wav_out, float* latents_out, float* cond_out,
+                         void* stream);
+int ldc_decode_ragged_dpm(ldc_ctx* ctx, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps,
+                          float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+
 /* bit-stream layer: the on-wire format between ldc_rvq_encode and ldc_rvq_decode -- SURVEY.md section 8(f) row 3 ------------
  * Every batch item is an independent stream.  All results are bit-exact with the reference classes.  These calls need no
  * weights (any context of the device).

@@ -418,6 +418,95 @@ hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src, int n, hi
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// DPM-Solver++(2M) update, data-prediction form: the ddim_update tiling; coefficients of iteration
+// j = st[1] from the host-written table.  x0_prev (the layout of x) is loaded only where the entry says has_prev and written
+// on every iteration but the last; nothing is drawn.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void dpm_update_kernel(float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, int L,
+                                                         StepTables tb, const DpmStep* sched, const int* st, const int* lens) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int Lv = valid_rows(lens, 0, b, L);   // as p_sample_update_kernel
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  float ev[4], xin[4], pv[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int l = l0 + i, c = c0 + tx;
+    ev[ii] = (l < L && c < C) ? dld<T>(eps_cl, ((size_t)b * L + l) * C + c) : 0.f;
+    const int cc = c0 + i, ll = l0 + tx;
+    xin[ii] = (cc < C && ll < L) ? x[((size_t)b * C + cc) * L + ll] : 0.f;
+  }
+  const DpmStep sp = sched[st[1]];
+  const float recip = tb.sqrt_recip_alphas_cumprod[sp.t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[sp.t];
+  const bool hist = !sp.last && sp.has_prev;   // (uniform over the grid) the only case in which the history is read
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int cc = c0 + ty + ii * 8, ll = l0 + tx;
+    pv[ii] = (hist && cc < C && ll < Lv) ? x0_prev[((size_t)b * C + cc) * L + ll] : 0.f;
+  }
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
+  __syncthreads();
+  float newv[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int c = c0 + i, l = l0 + tx;
+    newv[ii] = 0.f;
+    if (c < C && l < L) {
+      const size_t idx = ((size_t)b * C + c) * L + l;
+      const float e = tile[tx][i];
+      float x0 = recip * xin[ii] - recipm1 * e;
+      x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+      float v = x0;
+      if (!sp.last) {
+        v = sp.a * xin[ii] + sp.b0 * x0;
+        if (hist) v += sp.b1 * pv[ii];
+        x0_prev[idx] = l < Lv ? x0 : 0.f;
+      }
+      v = l < Lv ? v : 0.f;
+      x[idx] = v;
+      newv[ii] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][l]
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int l = l0 + i, c = c0 + tx;
+    if (l < L && c < C) dst<T>(x_cl, ((size_t)b * L + l) * C + c, tile[tx][i]);
+  }
+}
+
+hipError_t launch_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int B, int C, int L, StepTables tb,
+                             const DpmStep* sched, const int* st, hipStream_t s, const int* lens) {
+  dim3 grid((L + 31) / 32, (C + 31) / 32, B);
+  if (dt == DT_F32)
+    hipLaunchKernelGGL(dpm_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, L, tb, sched, st, lens);
+  else
+    hipLaunchKernelGGL(dpm_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, L, tb, sched, st, lens);
+  return hipGetLastError();
+}
+
+// the DPM schedule table written on the stream, as launch_ddim_table_write writes its table
+struct DpmChunk { DpmStep e[kDdimChunk]; };
+__global__ void dpm_table_write_kernel(DpmStep* dst, DpmChunk src, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = src.e[threadIdx.x];
+}
+hipError_t launch_dpm_table_write(DpmStep* dst, const DpmStep* src, int n, hipStream_t s) {
+  for (int i0 = 0; i0 < n; i0 += kDdimChunk) {
+    DpmChunk ch{};
+    const int m = std::min(kDdimChunk, n - i0);
+    for (int i = 0; i < m; ++i) ch.e[i] = src[i0 + i];
+    hipLaunchKernelGGL(dpm_table_write_kernel, dim3(1), dim3(kDdimChunk), 0, s, dst + i0, ch, m);
+  }
+  return hipGetLastError();
+}
+
 // tl (optional): device-side timeline of the timed (graph-replayed, multi-stream) mode: constant-rate clock (100 MHz,
 // s_memrealtime) at the begin and the end of every step of this batch part, slot = the step's iteration index
 __global__ void step_advance_kernel(int* st, unsigned long long* tl) {
@@ -438,7 +527,7 @@ __global__ void step_set_kernel(int* st, int t, int j, unsigned key_lo, unsigned
 // split-K counters, k-max keys: until round 3 a memset node of its own): zero_n16 16-byte pieces starting at `zero`.
 __global__ __launch_bounds__(1024) void step_begin_kernel(const float* table, int stride, int* st, float* cur,
                                                           unsigned long long* tl, uint4* zero, long long zero_n16, int advance,
-                                                          const DdimStep* ddim) {
+                                                          const int* t_words, int t_stride) {
   constexpr int nthr = 1024;
   if (blockIdx.x == 0) {
     __shared__ int sh_t;
@@ -453,8 +542,8 @@ __global__ __launch_bounds__(1024) void step_begin_kernel(const float* table, in
         st[0] = t;
         st[1] = j;
       }
-      if (ddim) {   // DDIM: the timestep of iteration j comes from the strided schedule
-        t = ddim[max(j, 0)].t;
+      if (t_words) {   // DDIM, DPM: the timestep of iteration j comes from the strided schedule (the `t` word of the table's entry j)
+        t = t_words[(size_t)max(j, 0) * t_stride];
         st[0] = t;
       }
       if (tl) tl[2 * (j & 2047)] = now;
@@ -487,13 +576,18 @@ __global__ __launch_bounds__(1024) void step_begin_kernel(const float* table, in
   const long long nb = gridDim.x > 1 ? gridDim.x - 1 : 1, bi = gridDim.x > 1 ? blockIdx.x - 1 : 0;
   for (long long i = bi * nthr + threadIdx.x; i < zero_n16; i += nb * nthr) zero[i] = z;
 }
-hipError_t launch_step_begin(const float* table, int stride, int* st, float* cur, unsigned long long* tl, hipStream_t s,
-                             void* zero, size_t zero_bytes, int advance, const DdimStep* ddim) {
+hipError_t launch_step_begin_sched(const float* table, int stride, int* st, float* cur, unsigned long long* tl, hipStream_t s, void* zero,
+                                   size_t zero_bytes, int advance, const int* t_words, int t_stride_ints) {
   const long long n16 = (long long)((zero_bytes + 15) / 16);
   const long long want = n16 > 0 ? 1 + (n16 + 4095) / 4096 : 1;
   hipLaunchKernelGGL(step_begin_kernel, dim3((unsigned)std::min<long long>(256, want)), dim3(1024), 0, s, table, stride, st, cur, tl,
-                     reinterpret_cast<uint4*>(zero), n16, advance, ddim);
+                     reinterpret_cast<uint4*>(zero), n16, advance, t_words, t_stride_ints);
   return hipGetLastError();
+}
+hipError_t launch_step_begin(const float* table, int stride, int* st, float* cur, unsigned long long* tl, hipStream_t s,
+                             void* zero, size_t zero_bytes, int advance, const DdimStep* ddim) {
+  return launch_step_begin_sched(table, stride, st, cur, tl, s, zero, zero_bytes, advance, ddim ? &ddim->t : nullptr,
+                                 (int)(sizeof(DdimStep) / sizeof(int)));
 }
 // one workgroup that holds its CU slot for `us` microseconds of the 100 MHz wall clock (bounded): the stream-overlap calibration of ldc_api.cpp
 __global__ void spin_us_kernel(unsigned us) {

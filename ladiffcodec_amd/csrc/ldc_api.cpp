@@ -585,6 +585,8 @@ static int build_unet(ldc_ctx* c, std::string* missing) {
     LDCCHK(c->wmem.upload(&d, t->data));
     dev[n] = d;
     if (std::string(n) == "alphas_cumprod") c->alphas_cumprod = t->data;
+    if (std::string(n) == "sqrt_recip_alphas_cumprod") c->sqrt_recip_ac = t->data;
+    if (std::string(n) == "sqrt_recipm1_alphas_cumprod") c->sqrt_recipm1_ac = t->data;
   }
   c->sched.sqrt_recip_alphas_cumprod = dev["sqrt_recip_alphas_cumprod"];
   c->sched.sqrt_recipm1_alphas_cumprod = dev["sqrt_recipm1_alphas_cumprod"];
@@ -779,6 +781,7 @@ void drop_plans(ldc_ctx* c) {
   for (auto& pl : c->plans) {
     for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
     if (pl->arena_base) (void)hipFree(pl->arena_base);
+    if (pl->x0_prev) (void)hipFree(pl->x0_prev);
   }
   c->plans.clear();
   c->plan_bytes = 0;
@@ -794,6 +797,7 @@ extern "C" int ldc_destroy(ldc_ctx* c) {
   if (c->outnorm_ws) (void)hipFree(c->outnorm_ws);
   if (c->state_buf) (void)hipFree(c->state_buf);
   if (c->ddim_table) (void)hipFree(c->ddim_table);
+  if (c->dpm_table) (void)hipFree(c->dpm_table);
   if (c->step_state) (void)hipFree(c->step_state);
   if (c->dev_flag_host) (void)hipHostFree(c->dev_flag_host);
   if (c->tl_buf) (void)hipFree(c->tl_buf);
@@ -1969,6 +1973,7 @@ static void evict_plan(ldc_ctx* c, size_t idx) {
     if (c->last_halves.p[k] == pl) c->last_halves = Halves();
   for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
   if (pl->arena_base) (void)hipFree(pl->arena_base);
+  if (pl->x0_prev) (void)hipFree(pl->x0_prev);   // (every captured DPM graph of the plan went above)
   c->plan_bytes -= pl->arena_bytes;
   c->plans.erase(c->plans.begin() + idx);
 }
@@ -2366,19 +2371,29 @@ extern "C" int ldc_debug_attention_block(ldc_ctx* c, const char* name, const flo
 
 // one reverse-diffusion step of batch part k on stream s: select the timestep row, run the UNet, update the state,
 // advance this part's step counter.  Parts never interact, so each is a self-contained chain.
-// ddim (null: DDPM p_sample): the device schedule table of a DDIM loop (step_begin takes t from it, ddim_update the coefficients)
+// sm (default: DDPM p_sample): the sampler kind and the device schedule table of a DDIM / DPM loop (step_begin takes t from it, the
+// update kernel the coefficients)
 static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* noise, int64_t noise_stride, hipStream_t s,
-                     const DdimStep* ddim = nullptr) {
+                     const StepSampler& sm = StepSampler()) {
   Plan* pl = h.p[k];
   const size_t off = (size_t)h.b0[k] * c->unet.channels * pl->L;
   unsigned long long* tl = c->timeline ? c->tl_buf + (size_t)k * 2048 * 2 : nullptr;
   // (the step state moves on in the step's FIRST kernel: the callers start a loop from (t + 1, iteration - 1), set_steps)
-  HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, tl, s, pl->zero_ptr, pl->zero_bytes, c->merge_advance,
-                           ddim));
+  if (sm.kind == SAMPLER_DPM) {
+    if (!sm.dpm || !pl->x0_prev) return fail(LDC_E_STATE, "internal: a DPM step without its schedule table or history buffer");
+    HIPCHK(launch_step_begin_sched(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, tl, s, pl->zero_ptr, pl->zero_bytes,
+                                   c->merge_advance, &sm.dpm->t, (int)(sizeof(DpmStep) / sizeof(int))));
+  } else {
+    HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, tl, s, pl->zero_ptr, pl->zero_bytes, c->merge_advance,
+                             sm.kind == SAMPLER_DDIM ? sm.ddim : nullptr));
+  }
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
-  if (ddim)
+  if (sm.kind == SAMPLER_DPM)
+    HIPCHK(launch_dpm_update(c->dt, x + off, pl->eps_cl, pl->x0_prev, pl->x_cl, pl->B, c->unet.channels, pl->L, c->sched, sm.dpm,
+                             pl->step_state, s, pl->ragged ? pl->lens : nullptr));
+  else if (sm.kind == SAMPLER_DDIM)
     HIPCHK(launch_ddim_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
-                              c->unet.channels, pl->L, c->sched, ddim, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr));
+                              c->unet.channels, pl->L, c->sched, sm.ddim, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr));
   else
     HIPCHK(launch_p_sample_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
                                   c->unet.channels, pl->L, c->sched, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr));
@@ -2416,13 +2431,13 @@ static int set_steps(ldc_ctx* c, const Halves& h, int t, int j, hipStream_t s) {
 
 // one step of every part, eagerly: part 0 on s, the others on the auxiliary streams, joined at the end
 static int one_step(ldc_ctx* c, const Halves& h, float* x, const float* noise, int64_t noise_stride, hipStream_t s,
-                    const DdimStep* ddim = nullptr) {
+                    const StepSampler& sm = StepSampler()) {
   if (parts_parallel(c, h)) {
     LDCCHK(fork_parts(c, h, s));
-    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, k == 0 ? s : c->aux_stream[k], ddim));
+    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, k == 0 ? s : c->aux_stream[k], sm));
     LDCCHK(join_parts(c, h, s));
   } else {
-    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, s, ddim));
+    for (int k = 0; k < h.n; ++k) LDCCHK(half_step(c, h, k, x, noise, noise_stride, s, sm));
   }
   return LDC_OK;
 }
@@ -2483,25 +2498,26 @@ hipError_t replay_parts(ldc_ctx* c, const Halves& h, StepGraph* sg, int n_big, i
 
 // the denoise loop on prepared plans (cond already processed, x_cl already set)
 // left_forked (optional): the caller continues per part on the parts' streams; the per-part replay path then leaves them un-joined and says so
-// ddim (optional): n_steps DDIM iterations on the schedule already written to c->ddim_table (ddim == c->ddim_table); else DDPM
-// steps from t = n_steps - 1 down to 0
+// sm (optional): SAMPLER_DDIM / SAMPLER_DPM: n_steps iterations on the schedule already written to c->ddim_table / c->dpm_table (DPM:
+// the parts' history buffers exist, ensure_history); else DDPM steps from t = n_steps - 1 down to 0
 static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const float* noise, int n_steps, hipStream_t s, bool* left_forked = nullptr,
-                        const DdimStep* ddim = nullptr) {
+                        const StepSampler& sm = StepSampler()) {
   if (left_forked) *left_forked = false;
+  const bool strided = sm.kind != SAMPLER_DDPM;   // a strided schedule, DDIM or DPM: the graph lengths below are theirs alike
   const int L = h.p[0]->L, F = h.p[0]->F;
   const int64_t stride = (int64_t)B * c->unet.channels * L;
   LDCCHK(set_steps(c, h, n_steps - 1, 0, s));   // (DDIM: t is overwritten from the table in every step's first kernel)
   if (c->profile || c->serial_parts || n_steps < 3) {
     if (left_forked && h.n >= 2) LDCCHK(join_parts(c, h, s));   // (the caller's per-part work is on the auxiliary streams; these steps may all run on s)
-    for (int i = 0; i < n_steps; ++i) LDCCHK(one_step(c, h, x, noise, stride, s, ddim));
+    for (int i = 0; i < n_steps; ++i) LDCCHK(one_step(c, h, x, noise, stride, s, sm));
     for (int k = 0; k < h.n; ++k) LDCCHK(stamp_loop_end(c, h, k, s));
     return LDC_OK;
   }
   StepGraph* sg = nullptr;
   const int rag = h.p[0]->ragged ? 1 : 0;   // the steps of ragged plans are graphs of their own, replayed for any set of lengths
-  const int kind = ddim ? 1 : 0;   // a DDPM loop never replays a DDIM graph or the reverse; both stay cached side by side
+  const int kind = sm.kind;   // a loop never replays another sampler's graph (DDPM, DDIM, DPM); all stay cached side by side
   for (auto& g : c->graphs)
-    if (g.B == B && g.L == L && g.F == F && g.ddim == kind && g.ragged == rag && g.pool_id == 0) sg = &g;
+    if (g.B == B && g.L == L && g.F == F && g.sampler == kind && g.ragged == rag && g.pool_id == 0) sg = &g;
   if (!sg) {
     // graphs of shapes whose plans are gone were dropped with them (evict_plan); additionally keep at most 16 alive
     if (c->graphs.size() >= 16) {
@@ -2516,7 +2532,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     }
     c->graphs.push_back(StepGraph());
     sg = &c->graphs.back();
-    sg->B = B; sg->L = L; sg->F = F; sg->ddim = kind; sg->ragged = rag;
+    sg->B = B; sg->L = L; sg->F = F; sg->sampler = kind; sg->ragged = rag;
   }
   sg->last_use = ++c->use_tick;
   const bool par = parts_parallel(c, h);
@@ -2527,8 +2543,8 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   // 10 / 25 steps 2 % / 16 % slower), 10 steps of a single chain (5 steps 2.8 % slower; 8 / 10 / 25 equal).  A remainder of
   // single-step replays is slow (13 or 17 steps per graph: 154 instead of 124 ms), so the defaults divide the usual 50.
   int k_want = c->graph_steps > 0 ? c->graph_steps : (h.n == 1 ? 10 : 5);
-  if (ddim) {
-    // DDIM: one graph length whatever the step count, so that every S and eta replays the same captured graphs (a DDIM decode has
+  if (strided) {
+    // DDIM, DPM: one graph length whatever the step count, so that every S and eta replays the same captured graphs (a DDIM decode has
     // a few to a few tens of steps: 5 steps per graph, and single-step replays for the remainder)
     k_want = c->graph_steps > 0 ? c->graph_steps : 5;
   } else if (c->graph_steps == 0) {   // prefer a graph length that divides the step count (within the flat part of the measured range)
@@ -2538,7 +2554,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
       if (n_steps % k == 0 && (best == 0 || std::abs(k - k_want) < std::abs(best - k_want))) best = k;
     if (best) k_want = best;
   }
-  const int K = ddim ? k_want : std::min(k_want, std::max(1, n_steps - 1));
+  const int K = strided ? k_want : std::min(k_want, std::max(1, n_steps - 1));
   int done = 0;
   if (!sg->any() || sg->noise != noise || sg->x != x || sg->stream != s || sg->n != h.n * 100 + K + ((par && c->part_graphs && (h.n == 2 || c->part_graphs >= 2)) ? 100000 : 0)) {
     if (sg->any()) {
@@ -2548,7 +2564,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
       sg->destroy();
     }
     // first step eagerly: loads code objects / sets function attributes outside of the capture
-    LDCCHK(one_step(c, h, x, noise, stride, s, ddim));
+    LDCCHK(one_step(c, h, x, noise, stride, s, sm));
     done = 1;
     const bool per_part = par && c->part_graphs && (h.n == 2 || c->part_graphs >= 2);   // (LDC_PART_GRAPHS=2: also for three / four parts)   // (three parts on per-part graphs measured 45 % slower than the fork/join graph)
     if (per_part) {
@@ -2564,7 +2580,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
           hipGraph_t g = nullptr;
           HIPCHK(hipStreamBeginCapture(sk, hipStreamCaptureModeRelaxed));
           int r = LDC_OK;
-          for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, sk, ddim);
+          for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, sk, sm);
           hipError_t e = hipStreamEndCapture(sk, &g);
           if (r != LDC_OK) { if (g) (void)hipGraphDestroy(g); return r; }
           if (e != hipSuccess) return fail(LDC_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
@@ -2586,7 +2602,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
       int r = LDC_OK;
       if (par) r = fork_parts(c, h, s);
       for (int k = 0; k < h.n && r == LDC_OK; ++k)
-        for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, (k == 0 || !par) ? s : c->aux_stream[k], ddim);
+        for (int i = 0; i < steps && r == LDC_OK; ++i) r = half_step(c, h, k, x, noise, stride, (k == 0 || !par) ? s : c->aux_stream[k], sm);
       if (par && r == LDC_OK) r = join_parts(c, h, s);
       hipError_t e = hipStreamEndCapture(s, &g);
       if (r != LDC_OK) { if (g) (void)hipGraphDestroy(g); return r; }
@@ -2825,7 +2841,125 @@ extern "C" int ldc_ddim_sample(ldc_ctx* c, float* img, const float* cond, const 
   LDCCHK(ensure_state(c, nbytes));
   HIPCHK(hipMemcpyAsync(c->state_buf, img, nbytes, hipMemcpyDeviceToDevice, s));
   LDCCHK(load_x(c, h, c->state_buf, s));
-  LDCCHK(denoise_loop(c, h, B, c->state_buf, noise, n_steps, s, nullptr, c->ddim_table));
+  StepSampler sm;
+  sm.kind = SAMPLER_DDIM;
+  sm.ddim = c->ddim_table;
+  LDCCHK(denoise_loop(c, h, B, c->state_buf, noise, n_steps, s, nullptr, sm));
+  HIPCHK(hipMemcpyAsync(img, c->state_buf, nbytes, hipMemcpyDeviceToDevice, s));
+  return finish_stream(c, stream);
+}
+
+// ---- DPM-Solver++(2M), data-prediction form: second-order multistep on the timestep grid of DDIM -------------
+// Per timestep t, from the checkpoint's fp32 tables promoted to double: R = sqrt_recip_alphas_cumprod[t] = 1 / alpha,
+// M = sqrt_recipm1_alphas_cumprod[t] = sigma / alpha, lambda = -ln M.  (The x0 formula uses these two tables, so x = alpha x0 + sigma eps
+// inverts it exactly; 1 - alphas_cumprod in fp32 loses three digits at small t.)  Row j for (t, tn) = (times[j], times[j + 1]):
+// tn < 0: (0, 1, 0), x <- x0.  Else h = lambda_tn - lambda_t, phi = -alpha_tn expm1(-h), a = sigma_tn / sigma_t; j = 0: (a, phi, 0);
+// j >= 1: r = (lambda_t - lambda_times[j-1]) / h, (a, phi (1 + 1/(2r)), -phi / (2r)).  Double arithmetic, rounded once to float.
+static int dpm_args(int timesteps, int t_start, int n_steps) {
+  if (t_start < 1 || t_start > timesteps) return fail(LDC_E_INVALID, "t_start %d: must be in [1,%d]", t_start, timesteps);
+  if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps %d: must be in [1, t_start = %d] (more would repeat timesteps)", n_steps, t_start);
+  return LDC_OK;
+}
+extern "C" int ldc_dpm_schedule(const float* sqrt_recip, const float* sqrt_recipm1, int timesteps, int t_start, int n_steps, int* t_out,
+                                float* coef_out) {
+  if (!sqrt_recip || !sqrt_recipm1 || !t_out || !coef_out) return fail(LDC_E_INVALID, "null pointer");
+  if (timesteps < 1) return fail(LDC_E_INVALID, "timesteps %d: must be >= 1", timesteps);
+  LDCCHK(dpm_args(timesteps, t_start, n_steps));
+  std::vector<int> times(n_steps + 1);
+  LDCCHK(ldc_ddim_times(t_start, n_steps, times.data()));
+  auto alpha = [&](int t) { return 1.0 / (double)sqrt_recip[t]; };
+  auto sigma = [&](int t) { return (double)sqrt_recipm1[t] / (double)sqrt_recip[t]; };
+  auto lambda = [&](int t) { return -std::log((double)sqrt_recipm1[t]); };
+  for (int j = 0; j < n_steps; ++j) {
+    const int t = times[j], tn = times[j + 1];
+    if (t < 0 || t >= timesteps || tn >= t) return fail(LDC_E_INVALID, "internal: timestep list is not strictly decreasing inside [0,%d)", timesteps);
+    t_out[j] = t;
+    float* row = coef_out + (size_t)j * 3;
+    if (tn < 0) { row[0] = 0.f; row[1] = 1.f; row[2] = 0.f; continue; }
+    const double h = lambda(tn) - lambda(t);
+    const double phi = -alpha(tn) * std::expm1(-h);
+    row[0] = (float)(sigma(tn) / sigma(t));
+    if (j == 0) {
+      row[1] = (float)phi;
+      row[2] = 0.f;
+    } else {
+      const double r = (lambda(t) - lambda(times[j - 1])) / h;
+      row[1] = (float)(phi * (1.0 + 0.5 / r));
+      row[2] = (float)(-phi * 0.5 / r);
+    }
+  }
+  return LDC_OK;
+}
+
+// the schedule of a DPM call into c->dpm_host (the context's host copies of the two tables)
+static int dpm_schedule(ldc_ctx* c, int t_start, int n_steps) {
+  const int T = c->unet.timesteps;
+  LDCCHK(dpm_args(T, t_start, n_steps));
+  if ((int)c->sqrt_recip_ac.size() != T || (int)c->sqrt_recipm1_ac.size() != T) return fail(LDC_E_STATE, "no sqrt_recip / sqrt_recipm1 schedule loaded");
+  std::vector<int> ts(n_steps);
+  std::vector<float> coef((size_t)n_steps * 3);
+  LDCCHK(ldc_dpm_schedule(c->sqrt_recip_ac.data(), c->sqrt_recipm1_ac.data(), T, t_start, n_steps, ts.data(), coef.data()));
+  c->dpm_host.assign(n_steps, DpmStep{});
+  for (int j = 0; j < n_steps; ++j) {
+    DpmStep& e = c->dpm_host[j];
+    e.t = ts[j];
+    e.last = j == n_steps - 1;   // (the timestep list ends in -1: the final iteration, and only it)
+    e.has_prev = j >= 1 && !e.last;
+    e.a = coef[(size_t)j * 3]; e.b0 = coef[(size_t)j * 3 + 1]; e.b1 = coef[(size_t)j * 3 + 2];
+  }
+  return LDC_OK;
+}
+
+// c->dpm_host -> the context's device table, ordered on s behind everything queued there before (as ddim_upload)
+static int dpm_upload(ldc_ctx* c, hipStream_t s) {
+  if (!c->dpm_table) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, (size_t)(c->unet.timesteps + 1) * sizeof(DpmStep)));
+    c->dpm_table = (DpmStep*)p;
+  }
+  HIPCHK(launch_dpm_table_write(c->dpm_table, c->dpm_host.data(), (int)c->dpm_host.size(), s));
+  return LDC_OK;
+}
+
+// The history buffers of the parts' plans: allocated by the first DPM call on a plan, outside of any capture, and kept until the plan
+// goes (evict_plan, ldc_destroy), so every captured DPM graph of the plan keeps a valid address.  Never cleared: the first iteration
+// of a loop does not load it.
+static int ensure_history(ldc_ctx* c, const Halves& h) {
+  for (int k = 0; k < h.n; ++k) {
+    Plan* pl = h.p[k];
+    if (pl->x0_prev) continue;
+    void* p = nullptr;
+    const size_t bytes = (size_t)pl->B * c->unet.channels * pl->L * 4;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the DPM history failed: %s", bytes, hipGetErrorString(e));
+    pl->x0_prev = (float*)p;
+  }
+  return LDC_OK;
+}
+
+// DPM-Solver++(2M) over prepared arguments, as ldc_ddim_sample with fill_start 0: deterministic, nothing is drawn, the Philox epoch
+// stays where it is
+extern "C" int ldc_dpm_sample(ldc_ctx* c, float* img, const float* cond, int t_start, int n_steps, int B, int L, int F, void* stream) {
+  if (t_start < 1) return fail(LDC_E_INVALID, "t_start %d: must be >= 1", t_start);
+  if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps %d: must be in [1, t_start = %d] (more would repeat timesteps)", n_steps, t_start);
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  LDCCHK(check_unet_args(c, B, L, F));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  hipStream_t s = pick_stream(c, stream);
+  LDCCHK(dpm_upload(c, s));
+  Halves h;
+  LDCCHK(get_halves(c, B, L, F, s, &h));
+  LDCCHK(ensure_history(c, h));
+  LDCCHK(load_cond(c, h, cond, s));
+  const size_t nbytes = (size_t)B * c->unet.channels * L * 4;
+  LDCCHK(ensure_state(c, nbytes));
+  HIPCHK(hipMemcpyAsync(c->state_buf, img, nbytes, hipMemcpyDeviceToDevice, s));
+  LDCCHK(load_x(c, h, c->state_buf, s));
+  StepSampler sm;
+  sm.kind = SAMPLER_DPM;
+  sm.dpm = c->dpm_table;
+  LDCCHK(denoise_loop(c, h, B, c->state_buf, nullptr, n_steps, s, nullptr, sm));
   HIPCHK(hipMemcpyAsync(img, c->state_buf, nbytes, hipMemcpyDeviceToDevice, s));
   return finish_stream(c, stream);
 }
@@ -2902,7 +3036,8 @@ static int ragged_cond_rows(ldc_ctx* c, const float* wav, int B, int b0, int Bk,
 }
 
 // rag (ldc_decode_ragged, ldc_decode_codes_ragged): the items' own lengths in samples (host, validated); T is then the padded length
-static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_steps, bool ddim, bool draws, const float* noise, int per_item,
+// sampler: SAMPLER_DDPM, SAMPLER_DDIM (the schedule in c->ddim_host) or SAMPLER_DPM (c->dpm_host; draws false, noise null)
+static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_steps, int sampler, bool draws, const float* noise, int per_item,
                        float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream, const int32_t* rag = nullptr) {
   const Codec& cc = c->codec[LDC_MODEL_COND];
   const Codec& mc = c->codec[LDC_MODEL_MAIN];
@@ -2911,9 +3046,11 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
   LDCCHK(check_unet_args(c, B, L, F));
   LDCCHK(ensure_outnorm(c, B));
   hipStream_t s = pick_stream(c, stream);
-  if (ddim) LDCCHK(ddim_upload(c, s));   // (in front of everything: the parts' streams fork from s behind it)
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));   // (in front of everything: the parts' streams fork from s behind it)
+  if (sampler == SAMPLER_DPM) LDCCHK(dpm_upload(c, s));
   Halves h;
   LDCCHK(get_halves(c, B, L, F, s, &h, rag != nullptr));
+  if (sampler == SAMPLER_DPM) LDCCHK(ensure_history(c, h));
   std::vector<int> rag_lat, rag_fr;   // ragged: latent / condition frames per item
   if (rag) {
     for (int b = 0; b < B; ++b) { rag_lat.push_back(rag[b] / mc.hop); rag_fr.push_back(rag[b] / cc.hop); }
@@ -3004,8 +3141,11 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
       if (split_ends && c->ends_join) { parts_open = false; LDCCHK(join_parts(c, h, s)); }
       next_noise_key(c, noise == nullptr && draws);
       bool forked = false;
-      const int dr = denoise_loop(c, h, B, x, noise, n_steps, s, (split_ends && !c->ends_join) ? &forked : nullptr,
-                                  ddim ? c->ddim_table : nullptr);
+      StepSampler sm;
+      sm.kind = sampler;
+      sm.ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
+      sm.dpm = sampler == SAMPLER_DPM ? c->dpm_table : nullptr;
+      const int dr = denoise_loop(c, h, B, x, noise, n_steps, s, (split_ends && !c->ends_join) ? &forked : nullptr, sm);
       if (dr != LDC_OK) return bail(dr);
       if (split_ends && !forked) { parts_open = false; LDCCHK(fork_parts(c, h, s)); }   // (the loop joined, or never left s)
       parts_open = split_ends;
@@ -3047,7 +3187,7 @@ extern "C" int ldc_decode(ldc_ctx* c, const float* wav, int B, int T, int n_step
   if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
   FrontSrc src;
   src.wav = wav;
-  return decode_body(c, src, B, T, n_steps, false, true, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+  return decode_body(c, src, B, T, n_steps, SAMPLER_DDPM, true, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
 }
 
 // the decode with DDIM sampling from t_start (the DDIM counterpart of halfway_sampling: the start image is the upsampled,
@@ -3060,7 +3200,7 @@ extern "C" int ldc_decode_ddim(ldc_ctx* c, const float* wav, int B, int T, int t
   LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
   FrontSrc src;
   src.wav = wav;
-  return decode_body(c, src, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+  return decode_body(c, src, B, T, n_steps, SAMPLER_DDIM, draws, noise, per_item, wav_out, latents_out, cond_out, codes_out, stream);
 }
 
 // ldc_decode / ldc_decode_ddim on a batch of items of different lengths (right-padded to Tmax): one call, every item as if alone
@@ -3077,7 +3217,8 @@ extern "C" int ldc_decode_ragged(ldc_ctx* c, const float* wav, const int32_t* le
   else if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
   FrontSrc src;
   src.wav = wav;
-  return decode_body(c, src, B, Tmax, n_steps, t_start > 0, draws, noise, 1, wav_out, latents_out, cond_out, codes_out, stream, lengths_host);
+  return decode_body(c, src, B, Tmax, n_steps, t_start > 0 ? SAMPLER_DDIM : SAMPLER_DDPM, draws, noise, 1, wav_out, latents_out, cond_out, codes_out,
+                     stream, lengths_host);
 }
 
 // ldc_get_cond on a right-padded batch (the sender side of ragged batches): every item's rows and codes as if encoded alone, 0 behind
@@ -3151,7 +3292,7 @@ extern "C" int ldc_decode_codes(ldc_ctx* c, const int64_t* codes, const uint8_t*
   FrontSrc src;
   int T = 0;
   LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, F, &src, &T));
-  return decode_body(c, src, B, T, n_steps, false, true, noise, per_item, wav_out, latents_out, cond_out, nullptr, stream);
+  return decode_body(c, src, B, T, n_steps, SAMPLER_DDPM, true, noise, per_item, wav_out, latents_out, cond_out, nullptr, stream);
 }
 
 extern "C" int ldc_decode_codes_ddim(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
@@ -3167,7 +3308,7 @@ extern "C" int ldc_decode_codes_ddim(ldc_ctx* c, const int64_t* codes, const uin
   LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, F, &src, &T));
   bool draws = false;
   LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
-  return decode_body(c, src, B, T, n_steps, true, draws, noise, per_item, wav_out, latents_out, cond_out, nullptr, stream);
+  return decode_body(c, src, B, T, n_steps, SAMPLER_DDIM, draws, noise, per_item, wav_out, latents_out, cond_out, nullptr, stream);
 }
 // ldc_decode_codes / ldc_decode_codes_ddim with the length semantics of ldc_decode_ragged: frames_host[b] frames of item b are its own
 // (multiples of the ragged quantum / 320), the codes behind them are never read, a packed item's stream is ldc_packed_bytes(n_q,
@@ -3200,7 +3341,55 @@ extern "C" int ldc_decode_codes_ragged(ldc_ctx* c, const int64_t* codes, const u
   else if (n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
   std::vector<int32_t> lens(B);
   for (int b = 0; b < B; ++b) lens[b] = frames_host[b] * cc.hop;
-  return decode_body(c, src, B, T, n_steps, t_start > 0, draws, noise, 1, wav_out, latents_out, cond_out, nullptr, stream, lens.data());
+  return decode_body(c, src, B, T, n_steps, t_start > 0 ? SAMPLER_DDIM : SAMPLER_DDPM, draws, noise, 1, wav_out, latents_out, cond_out, nullptr, stream,
+                     lens.data());
+}
+
+// ---- the decodes with DPM-Solver++(2M) sampling from t_start: ldc_decode_ddim / ldc_decode_ragged / ldc_decode_codes_ddim without eta
+// and noise.  The context-free refusals come first (a NULL context sees them too).
+static int dpm_front_args(int t_start, int n_steps) {
+  if (t_start < 1) return fail(LDC_E_INVALID, "t_start %d: must be >= 1", t_start);
+  if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps %d: must be in [1, t_start = %d] (more would repeat timesteps)", n_steps, t_start);
+  return LDC_OK;
+}
+
+extern "C" int ldc_decode_dpm(ldc_ctx* c, const float* wav, int B, int T, int t_start, int n_steps, int per_item, float* wav_out,
+                              float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  if (!wav || !wav_out || B <= 0 || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  FrontSrc src;
+  src.wav = wav;
+  return decode_body(c, src, B, T, n_steps, SAMPLER_DPM, false, nullptr, per_item, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
+extern "C" int ldc_decode_ragged_dpm(ldc_ctx* c, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps,
+                                     float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  if (!wav || !wav_out || B <= 0 || Tmax <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (!lengths_host) return fail(LDC_E_INVALID, "null lengths");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  const long long quantum = lcm_ll(c->codec[LDC_MODEL_COND].hop, (long long)c->codec[LDC_MODEL_MAIN].hop << unet_halvings(c));
+  LDCCHK(check_ragged_lengths(lengths_host, B, Tmax, quantum, "samples"));
+  if (c->w8) return fail(LDC_E_INVALID, "ragged batches are not available on the fp8 engine (its fused forms have no length-aware variant): use dtype bf16 or f32");
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  FrontSrc src;
+  src.wav = wav;
+  return decode_body(c, src, B, Tmax, n_steps, SAMPLER_DPM, false, nullptr, 1, wav_out, latents_out, cond_out, codes_out, stream, lengths_host);
+}
+
+extern "C" int ldc_decode_codes_dpm(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                                    int F, int t_start, int n_steps, int per_item, float* wav_out, float* latents_out, float* cond_out,
+                                    void* stream) {
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, B, F, wav_out));
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, F, &src, &T));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  return decode_body(c, src, B, T, n_steps, SAMPLER_DPM, false, nullptr, per_item, wav_out, latents_out, cond_out, nullptr, stream);
 }
 
 

@@ -203,6 +203,9 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
   float* maxabs = nullptr;      // [B]
   int* step_state = nullptr;    // device int[2] {t, j} of THIS part: the parts of a batch advance independently
   float* cur_ss = nullptr;      // [ss_stride] timestep-MLP row of the step this part is executing
+  float* x0_prev = nullptr;     // DPM-Solver++(2M) history of this part: x0 of the previous iteration, [B][channels][L] fp32.  An allocation of
+                                // its own, made by the first DPM call on the plan (before any capture) and freed with the plan: captured DPM
+                                // graphs keep its address
   std::vector<std::function<hipError_t(hipStream_t)>> cond_ops;   // process_cond (once per denoise)
   std::vector<std::function<hipError_t(hipStream_t)>> step_ops;   // Unet1D.forward after process_cond
   std::vector<int> step_is_conv;                                   // 1 where step_ops[i] is a conv-GEMM launch
@@ -229,11 +232,19 @@ struct Halves {                // (the name dates from the two-way split; n part
 
 static constexpr int kKstOps = 256;   // stamp slots per step (one per op of the step list)
 
-struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update, step_advance}
+// what a denoise step runs behind the UNet (half_step): the sampler kind and its device schedule table
+enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_DPM = 2 };
+struct StepSampler {
+  int kind = SAMPLER_DDPM;
+  const DdimStep* ddim = nullptr;   // SAMPLER_DDIM: c->ddim_table (step_begin takes t from it, ddim_update the coefficients)
+  const DpmStep* dpm = nullptr;     // SAMPLER_DPM: c->dpm_table (likewise; dpm_update also reads and writes the plan's x0_prev)
+};
+
+struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update | dpm_update, step_advance}
   int B = 0, L = 0, F = 0, n = 0;
   int ragged = 0;    // (part of the cache key) the steps of ragged plans
   int pool_id = 0;   // (part of the cache key) != 0: the step graphs of that decode pool's plans
-  int ddim = 0;      // sampler kind (part of the cache key): 1 = DDIM steps (the schedule table's address is captured, not its contents)
+  int sampler = SAMPLER_DDPM;   // sampler kind (part of the cache key): a loop never replays another kind's graph (DDIM, DPM: the schedule table's address is captured, not its contents)
   const float* noise = nullptr;
   float* x = nullptr;
   hipStream_t stream = nullptr;
@@ -271,6 +282,9 @@ struct ldc_ctx {
   std::vector<float> alphas_cumprod;   // host copy of the schedule buffer: the DDIM coefficients are computed on the host
   DdimStep* ddim_table = nullptr;      // device [timesteps + 1]: allocated once, so captured DDIM graphs keep a valid address
   std::vector<DdimStep> ddim_host;     // the last schedule written to it
+  std::vector<float> sqrt_recip_ac, sqrt_recipm1_ac;   // host copies of the two x0 tables: the DPM coefficients are computed from them on the host
+  DpmStep* dpm_table = nullptr;        // device [timesteps + 1]: allocated once, like ddim_table
+  std::vector<DpmStep> dpm_host;       // the last DPM schedule written to it
   int* step_state = nullptr;    // device int[2]: t, j
   std::vector<std::unique_ptr<Plan>> plans;
   std::vector<StepGraph> graphs;

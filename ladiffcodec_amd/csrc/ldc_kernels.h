@@ -279,6 +279,23 @@ hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src_host, int 
 hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                               void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
                               uint64_t elem_base, hipStream_t s, const int* lens = nullptr);
+// One iteration of DPM-Solver++(2M) in its data-prediction form: the host fills one entry per iteration j
+// (ldc_api.cpp: ldc_dpm_schedule, double arithmetic rounded once to float) into a device table that the step state indexes.
+struct DpmStep {
+  int t;           // UNet timestep of iteration j
+  int last;        // time_next < 0: x <- x0
+  int has_prev;    // j >= 1: the update reads x0 of iteration j - 1; 0: the history is NOT loaded (it may hold anything)
+  float a;         // sigma_next / sigma_t
+  float b0;        // phi (1 + 1 / (2 r)); phi on the first iteration
+  float b1;        // -phi / (2 r); 0 on the first iteration
+  float pad_[2];
+};
+// x0 = clamp(sqrt_recip_ac[t] x - sqrt_recipm1_ac[t] eps, -1, 1); x <- last ? x0 : a x + b0 x0 + (has_prev ? b1 x0_prev : 0), in fp32;
+// then x0_prev <- x0 on every iteration but the last.  Same layouts and `lens` rule as launch_ddim_update (x, x_cl and x0_prev are
+// zero behind an item's length); x0_prev [B][C][L] fp32, the layout of x.  No noise: nothing is drawn.
+hipError_t launch_dpm_table_write(DpmStep* dst, const DpmStep* src_host, int n, hipStream_t s);   // dst[0..n) = src_host[0..n), stream-ordered
+hipError_t launch_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int B, int C, int L, StepTables tb,
+                             const DpmStep* sched, const int* st, hipStream_t s, const int* lens = nullptr);
 // x /= (maxabs[b or 0] + eps) in place on a raw element stream (n_per_item elements per item)
 hipError_t launch_scale_by_maxabs(int dt, void* x, int B, int64_t n_per_item, const float* maxabs, int per_item,
                                   float eps, hipStream_t s);
@@ -295,6 +312,10 @@ hipError_t launch_step_advance(int* st, unsigned long long* tl, hipStream_t s); 
 // ddim (DDIM loops, else null): then t = ddim[j].t, the timestep of iteration j of the strided schedule
 hipError_t launch_step_begin(const float* table, int stride, int* st, float* cur, unsigned long long* tl, hipStream_t s,
                              void* zero = nullptr, size_t zero_bytes = 0, int advance = 0, const DdimStep* ddim = nullptr);
+// the same kernel for any schedule table: t = t_words[j * t_stride_ints], the `t` word of entry j of a table whose entries are
+// t_stride_ints ints apart (DdimStep, DpmStep); t_words null: no table (DDPM)
+hipError_t launch_step_begin_sched(const float* table, int stride, int* st, float* cur, unsigned long long* tl, hipStream_t s, void* zero,
+                                   size_t zero_bytes, int advance, const int* t_words, int t_stride_ints);
 hipError_t launch_step_set(int* st, int t, int j, uint64_t noise_key, hipStream_t s);
 hipError_t launch_clock_sample(unsigned long long* out2, hipStream_t s);   // out2[0] = 100 MHz wall clock, out2[1] = s_memtime (shader cycles)
 hipError_t launch_spin_us(unsigned us, hipStream_t s);   // one workgroup busy for `us` microseconds (stream-overlap calibration)

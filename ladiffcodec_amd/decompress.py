@@ -1,7 +1,9 @@
 """`python -m ladiffcodec_amd.decompress` -- the receiver: every `**/*.ecdc` under `--input_dir` becomes `<output_dir><rel>.wav`.
 
 Flags: those of `srcs.sample` plus `--ddim_steps` (0: the DDPM halfway sampling of `--midway_t` steps, the default) and
-`--ddim_eta`, checked as `sample_ddim` checks them.  Every container is validated on the host first (magic, version, `m`,
+`--ddim_eta`, checked as `sample_ddim` checks them, and `--dpm_steps` (0: off, the default; > 0: DPM-Solver++(2M) from `--midway_t`,
+checked as `sample_dpm` checks it; refused together with `--ddim_steps` > 0 and, having no ragged decode from codes, with
+`--ragged`).  Every container is validated on the host first (magic, version, `m`,
 `lm` false, no `ac`, nc <= the codebooks of the model, hop 320, payload exactly ch x packed bytes); a file that fails stops the
 run before anything is decoded, with an error naming it.  The payload rows go to the GPU as they are and the decode starts
 from them (Engine.decode_codes): the cond encoder does not run.  Batching, per-item / joint normalisation, `--in_flight`,
@@ -31,6 +33,9 @@ BITS = 10
 _FLAGS = [
     ("--ddim_steps", dict(type=int, default=0, help="DDIM iterations from --midway_t (at most --midway_t); 0 = DDPM halfway sampling")),
     ("--ddim_eta", dict(type=float, default=0.0, help="DDIM eta in [0, 1]")),
+    # (absent from the parsed namespace unless given: read with dpm_steps(a))
+    ("--dpm_steps", dict(type=int, default=argparse.SUPPRESS,
+                         help="DPM-Solver++(2M) iterations from --midway_t (at most --midway_t); 0 or absent = off; not with --ddim_steps > 0")),
 ]
 
 
@@ -74,9 +79,22 @@ def plan_container_batches(metas: List[dict], rank: int, world: int, batch_size:
     return work
 
 
+def dpm_steps(a) -> int:
+    return int(getattr(a, "dpm_steps", 0) or 0)
+
+
 def sampler_from_args(a):
     from .sample import CodesSampler, DdpmSampler
     from .sample_ddim import sampler_from_args as ddim_sampler
+    if dpm_steps(a) < 0:
+        raise SystemExit(f"--dpm_steps {a.dpm_steps}: must be >= 0")
+    if dpm_steps(a) > 0:
+        from .sample_dpm import sampler_from_args as dpm_sampler
+        if a.ddim_steps > 0:
+            raise SystemExit(f"--dpm_steps {a.dpm_steps} and --ddim_steps {a.ddim_steps}: choose one sampler")
+        if getattr(a, "ragged", False):
+            raise SystemExit("--dpm_steps has no ragged decode from codes: run without --ragged")
+        return CodesSampler(dpm_sampler(a))
     return CodesSampler(ddim_sampler(a) if a.ddim_steps > 0 else DdpmSampler(a.midway_t))
 
 

@@ -23,6 +23,7 @@ EXPORTS = [
     "ldc_last_error", "ldc_version", "ldc_create", "ldc_destroy", "ldc_reseed", "ldc_set_option", "ldc_quantize_e4m3", "ldc_set_weight", "ldc_finalize_weights",
     "ldc_seanet_encode", "ldc_seanet_decode", "ldc_rvq_encode", "ldc_rvq_decode", "ldc_get_cond",
     "ldc_cond_upsample", "ldc_unet_forward", "ldc_p_sample", "ldc_denoise", "ldc_p_sample_loop", "ldc_infilling", "ldc_output_normalise", "ldc_decode", "ldc_ddim_times", "ldc_ddim_sample", "ldc_decode_ddim", "ldc_decode_codes", "ldc_decode_codes_ddim",
+    "ldc_dpm_schedule", "ldc_dpm_sample", "ldc_decode_dpm", "ldc_decode_codes_dpm", "ldc_decode_ragged_dpm",
     "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
     "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
     "ldc_stream_min_first", "ldc_stream_create", "ldc_stream_reset", "ldc_stream_destroy", "ldc_seanet_encode_stream", "ldc_seanet_decode_stream", "ldc_get_cond_stream",
@@ -112,6 +113,11 @@ def load() -> C.CDLL:
     lib.ldc_decode_ragged.argtypes = [vp, fp, C.POINTER(C.c_int32), i32, i32, i32, i32, C.c_float, fp, fp, fp, fp, vp, vp]
     lib.ldc_get_cond_ragged.argtypes = [vp, fp, C.POINTER(C.c_int32), i32, i32, C.c_float, fp, vp, vp]
     lib.ldc_decode_codes_ragged.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, C.c_float, fp, fp, fp, fp, vp]
+    lib.ldc_dpm_schedule.argtypes = [fp, fp, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.ldc_dpm_sample.argtypes = [vp, fp, fp, i32, i32, i32, i32, i32, vp]
+    lib.ldc_decode_dpm.argtypes = [vp, fp, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp]
+    lib.ldc_decode_codes_dpm.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp]
+    lib.ldc_decode_ragged_dpm.argtypes = [vp, fp, C.POINTER(C.c_int32), i32, i32, i32, i32, fp, fp, fp, vp, vp]
     lib.ldc_ac_encode_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
     lib.ldc_ac_decode_ragged.argtypes = [vp, vp, C.c_int64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldc_unet_forward_ragged.argtypes = [vp, fp, i32, fp, C.POINTER(C.c_int32), i32, i32, i32, fp, vp]
@@ -214,6 +220,20 @@ def ddim_times(t_start: int, n_steps: int):
     out = (C.c_int * (int(n_steps) + 1))() if n_steps >= 0 else (C.c_int * 1)()
     check(load().ldc_ddim_times(int(t_start), int(n_steps), out))
     return list(out)
+
+
+def dpm_schedule(sqrt_recip, sqrt_recipm1, t_start: int, n_steps: int):
+    """The DPM-Solver++(2M) table of ldc_dpm_schedule (host-only) from the checkpoint's sqrt_recip_alphas_cumprod /
+    sqrt_recipm1_alphas_cumprod tables: -> (t [n_steps] int32, coef [n_steps, 3] float32 rows (a, b0, b1))."""
+    import numpy as np
+    R = np.ascontiguousarray(np.asarray(sqrt_recip, dtype=np.float32))
+    M = np.ascontiguousarray(np.asarray(sqrt_recipm1, dtype=np.float32))
+    if R.ndim != 1 or R.shape != M.shape:
+        raise ValueError("the two tables must be one-dimensional and of one length")
+    n = max(int(n_steps), 1)
+    t_out, coef = (C.c_int * n)(), (C.c_float * (3 * n))()
+    check(load().ldc_dpm_schedule(R.ctypes.data, M.ctypes.data, int(R.shape[0]), int(t_start), int(n_steps), t_out, coef))
+    return np.array(t_out, dtype=np.int32), np.array(coef, dtype=np.float32).reshape(n, 3)
 
 
 def stream_min_first(cfg: LdcConfig, which: int, side: int) -> int:

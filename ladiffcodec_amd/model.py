@@ -443,6 +443,21 @@ class Engine:
         self._exit()
         return img
 
+    def dpm_sample(self, cond, t_start: int, n_steps: int, img):
+        """DPM-Solver++(2M) sampling (data-prediction form, clipped x0) from `t_start`: n_steps iterations on DDIM's timestep list
+        from `img`.  Deterministic: nothing is drawn and the engine's noise epoch stays where it is."""
+        cond = self._f32(cond)
+        B, _, F = cond.shape
+        if img is None:
+            raise ValueError("dpm_sample takes its start image from the caller (there is no device-drawn one)")
+        img = self._f32(img).clone()
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_dpm_sample(self._ctx, img.data_ptr(), cond.data_ptr(), int(t_start), int(n_steps), B, img.shape[2], F, s))
+        finally:
+            self._exit()
+        return img
+
     def output_normalise(self, wav, per_item: bool = False):
         wav = self._f32(wav).clone()
         B = wav.shape[0]
@@ -492,6 +507,27 @@ class Engine:
             return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
         return out
 
+    def decode_dpm(self, wav, t_start: int, n_steps: int, per_item: bool = False, want_stages: bool = False):
+        """`decode` with DPM-Solver++(2M) sampling: n_steps iterations from t_start, starting at the upsampled, normalised condition."""
+        wav = self._f32(wav)
+        B, _, T = wav.shape
+        F, Lz = T // self.cond_codec.hop_length, T // self.main_codec.hop_length
+        out = self._empty(B, 1, T)
+        lat = self._empty(B, self.main_codec.rep_dims, Lz) if want_stages else None
+        cond = self._empty(B, self.main_codec.rep_dims, F) if want_stages else None
+        n_q = self.cond_codec.n_q_for_bandwidth(None)
+        codes = self._empty(n_q, B, F, dtype=self.torch.int64) if want_stages else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        try:
+            L.check(self.lib.ldc_decode_dpm(self._ctx, wav.data_ptr(), B, T, int(t_start), int(n_steps), int(per_item), out.data_ptr(),
+                                            p(lat), p(cond), p(codes), s))
+        finally:
+            self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
+        return out
+
     @staticmethod
     def _lengths(lengths, B: int):
         arr = (C.c_int32 * B)(*[int(v) for v in lengths])
@@ -518,6 +554,29 @@ class Engine:
         try:
             L.check(self.lib.ldc_decode_ragged(self._ctx, wav.data_ptr(), lens, B, T, int(t_start), int(n_steps), float(eta), p(noise),
                                                out.data_ptr(), p(lat), p(cond), p(codes), s))
+        finally:
+            self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
+        return out
+
+    def decode_ragged_dpm(self, wav, lengths, t_start: int, n_steps: int, want_stages: bool = False):
+        """`decode_dpm` of items of different lengths in one call (the layout and rules of `decode_ragged`): every item comes out as
+        if decoded alone, outputs are zero beyond an item's length."""
+        wav = self._f32(wav)
+        B, _, T = wav.shape
+        F, Lz = T // self.cond_codec.hop_length, T // self.main_codec.hop_length
+        lens = self._lengths(list(lengths), B)
+        out = self._empty(B, 1, T)
+        lat = self._empty(B, self.main_codec.rep_dims, Lz) if want_stages else None
+        cond = self._empty(B, self.main_codec.rep_dims, F) if want_stages else None
+        n_q = self.cond_codec.n_q_for_bandwidth(None)
+        codes = self._empty(n_q, B, F, dtype=self.torch.int64) if want_stages else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        try:
+            L.check(self.lib.ldc_decode_ragged_dpm(self._ctx, wav.data_ptr(), lens, B, T, int(t_start), int(n_steps), out.data_ptr(),
+                                                   p(lat), p(cond), p(codes), s))
         finally:
             self._exit()
         if want_stages:
@@ -685,6 +744,22 @@ class Engine:
         L.check(self.lib.ldc_decode_codes_ddim(self._ctx, cp, pp, stride, int(bits), n_q, B, F, int(t_start), int(n_steps), float(eta),
                                                p(noise), int(per_item), out.data_ptr(), p(lat), p(cond), s))
         self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond}
+        return out
+
+    def decode_codes_dpm(self, codes=None, packed=None, bits: int = 10, t_start: int = 100, n_steps: int = 10, per_item: bool = False,
+                         want_stages: bool = False, n_q: Optional[int] = None, F: Optional[int] = None):
+        """`decode_dpm` started from RVQ codes; the code arguments as decode_codes."""
+        cp, pp, stride, n_q, B, F, keep = self._codes_args(codes, packed, bits, n_q, F)
+        out, lat, cond = self._codes_outputs(B, F, want_stages)
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        try:
+            L.check(self.lib.ldc_decode_codes_dpm(self._ctx, cp, pp, stride, int(bits), n_q, B, F, int(t_start), int(n_steps), int(per_item),
+                                                  out.data_ptr(), p(lat), p(cond), s))
+        finally:
+            self._exit()
         if want_stages:
             return {"wav": out, "latents": lat, "cond": cond}
         return out

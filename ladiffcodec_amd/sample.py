@@ -305,6 +305,21 @@ class DdimSampler:
         return eng.decode_ddim(batch, self.t_start, self.n_steps, self.eta, noise=noise, per_item=per_item, want_stages=want_stages)
 
 
+class DpmSampler:
+    """DPM-Solver++(2M) decode (Engine.decode_dpm): `n_steps` second-order multistep iterations from `t_start` on DDIM's timestep
+    list.  Deterministic: `draws` is 0, so no noise provider is asked for a tape and none is passed on."""
+
+    draws = 0
+
+    def __init__(self, t_start: int, n_steps: int):
+        self.t_start, self.n_steps = int(t_start), int(n_steps)
+
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        if isinstance(batch, RaggedBatch):
+            return eng.decode_ragged_dpm(batch.wav, batch.lengths, self.t_start, self.n_steps, want_stages=want_stages)
+        return eng.decode_dpm(batch, self.t_start, self.n_steps, per_item=per_item, want_stages=want_stages)
+
+
 class CodesBatch:
     """A batch of RVQ codes for CodesSampler: packed [B, >= packed bytes] uint8 (the container payload rows, `bits` per code) or
     codes [n_q, B, F] int64.  `.to(device)` as a tensor batch, so decode_with_retry and the in-flight retire path take it as is."""
@@ -331,21 +346,28 @@ class RaggedCodesBatch:
 
 
 class CodesSampler:
-    """The decode of `inner` (DdpmSampler / DdimSampler) started from a CodesBatch: Engine.decode_codes / decode_codes_ddim; from a
-    RaggedCodesBatch: Engine.decode_codes_ragged."""
+    """The decode of `inner` (DdpmSampler / DdimSampler / DpmSampler) started from a CodesBatch: Engine.decode_codes /
+    decode_codes_ddim / decode_codes_dpm; from a RaggedCodesBatch: Engine.decode_codes_ragged (DDPM and DDIM only)."""
 
     def __init__(self, inner):
         self.inner = inner
         self.n_steps = self.draws = inner.draws
 
     def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+        dpm = isinstance(self.inner, DpmSampler)
         if isinstance(batch, RaggedCodesBatch):
+            if dpm:
+                raise ValueError("DPM-Solver++ sampling has no ragged decode from codes (Engine.decode_codes_ragged takes DDPM and DDIM "
+                                 "only): decode the containers in equal-length batches, without --ragged")
             ddim = isinstance(self.inner, DdimSampler)
             return eng.decode_codes_ragged(packed=batch.packed, frames=batch.frames, bits=batch.bits, n_q=batch.n_q,
                                            n_steps=self.inner.n_steps, t_start=self.inner.t_start if ddim else 0,
                                            eta=self.inner.eta if ddim else 0.0, noise=noise, want_stages=want_stages)
         kw = dict(codes=batch.codes, packed=batch.packed, bits=batch.bits, n_q=batch.n_q, F=batch.F, noise=noise, per_item=per_item,
                   want_stages=want_stages)
+        if dpm:
+            del kw["noise"]
+            return eng.decode_codes_dpm(t_start=self.inner.t_start, n_steps=self.inner.n_steps, **kw)
         if isinstance(self.inner, DdimSampler):
             return eng.decode_codes_ddim(t_start=self.inner.t_start, n_steps=self.inner.n_steps, eta=self.inner.eta, **kw)
         return eng.decode_codes(n_steps=self.inner.n_steps, **kw)
@@ -356,7 +378,7 @@ def _sampler(inp_args, sampler):
 
 
 def synthesis(inp_args, sampler=None) -> List[str]:
-    """`sampler`: DdpmSampler (default, --midway_t steps) or DdimSampler."""
+    """`sampler`: DdpmSampler (default, --midway_t steps), DdimSampler or DpmSampler."""
     from . import parallel
 
     _unsupported(inp_args)
@@ -545,7 +567,8 @@ def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: i
             # test seam (see decode_files): keys are (file index, chunk number)
             provider = getattr(inp_args, "noise_provider", None)
             hop = int(np.prod(getattr(inp_args, "enc_ratios", [8])))
-            noise = provider([(i, k) for i, k, _ in part], sampler.draws, ln // hop).to(dev) if provider is not None else None
+            # (a sampler that draws nothing -- DpmSampler -- never asks for a tape)
+            noise = provider([(i, k) for i, k, _ in part], sampler.draws, ln // hop).to(dev) if provider is not None and sampler.draws > 0 else None
             stages = sampler(eng, batch.to(dev), noise, True, want_stages=True)
             wav_raw = eng.decode_latents(L.MODEL_MAIN, stages["latents"])          # un-normalised decoder output
             for j, (i, k, _) in enumerate(part):
@@ -642,7 +665,7 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
             retire(pending.pop(0))             # the batch this engine decoded last: its output is read before the slot is reused
         # test seam: a callable (file indices, steps, latent length) -> noise [steps, B, 128, L] replaces the device-drawn noise
         provider = getattr(inp_args, "noise_provider", None)
-        noise = provider(idxs, steps, n // hop).to(dev) if provider is not None else None
+        noise = provider(idxs, steps, n // hop).to(dev) if provider is not None and steps > 0 else None
         if streams[slot] is not None:
             with torch.cuda.stream(streams[slot]):
                 out = decode_with_retry(engines[slot], batch.to(dev, non_blocking=True), steps, noise, not joint, sampler)

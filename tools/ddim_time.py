@@ -3,6 +3,12 @@ weights), in one process on one engine: DDPM 50 steps, DDIM from t_start 50 with
 and timed with device events after warm-up.  Prints one line per sampler (median ms per batch) and a JSON line.
 
     python tools/ddim_time.py [rounds]
+
+`--dpm`: the DPM-Solver++(2M) denoise loop beside the DDIM loop instead (Engine.dpm_sample / Engine.ddim_sample at eta 0 on one start
+image and condition, no codec ends), from t_start 50 with S = 10 and S = 20; per sampler the median ms per call, that over S, and the
+marginal ms per step (S = 20 minus S = 10, over 10) with the spread of the rounds.
+
+    python tools/ddim_time.py --dpm [rounds]
 """
 import json
 import os
@@ -18,7 +24,9 @@ def main():
     from ladiffcodec_amd import lib as L, synth
     from ladiffcodec_amd.model import Engine
     from ladiffcodec_amd.spec import CodecConfig, UnetConfig
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+    argv = [a for a in sys.argv[1:] if a != "--dpm"]
+    dpm = "--dpm" in sys.argv[1:]
+    rounds = int(argv[0]) if argv else 5
     B, T = 32, int(2.4 * 16000) // 640 * 640
     cc = CodecConfig(enc_ratios=(8, 5, 4, 2), quantization=True, bandwidth=3.0)
     mc = CodecConfig(enc_ratios=(8, 4), quantization=False)
@@ -31,6 +39,12 @@ def main():
     runs = {"ddpm_50": lambda: e.decode(wav, 50, per_item=True),
             "ddim_50_s10": lambda: e.decode_ddim(wav, 50, 10, 0.0, per_item=True),
             "ddim_50_s25": lambda: e.decode_ddim(wav, 50, 25, 0.0, per_item=True)}
+    if dpm:
+        cond = e.get_cond(wav)
+        up = e.cond_upsample(cond, 0)
+        img = up / (up.abs().amax(dim=(1, 2), keepdim=True) + 1e-8)
+        runs = {"ddim_loop_s10": lambda: e.ddim_sample(cond, 50, 10, 0.0, img=img), "dpm_loop_s10": lambda: e.dpm_sample(cond, 50, 10, img),
+                "ddim_loop_s20": lambda: e.ddim_sample(cond, 50, 20, 0.0, img=img), "dpm_loop_s20": lambda: e.dpm_sample(cond, 50, 20, img)}
     for fn in runs.values():          # warm-up: plans, graph captures, code objects
         for _ in range(2):
             fn()
@@ -48,6 +62,13 @@ def main():
     res = {k: round(statistics.median(v), 2) for k, v in ms.items()}
     for k, v in ms.items():
         print(f"{k}: median {res[k]:.2f} ms per batch of {B} x {T / 16000:.1f} s (min {min(v):.2f}, max {max(v):.2f}, {rounds} rounds)")
+    if dpm:
+        for name in ("ddim", "dpm"):
+            a, b = ms[f"{name}_loop_s10"], ms[f"{name}_loop_s20"]
+            marg = [(y - x) / 10.0 for x, y in zip(a, b)]
+            res[f"{name}_ms_per_step"] = round(statistics.median(marg), 4)
+            print(f"{name}: {res[name + '_loop_s10'] / 10:.3f} ms per step at S = 10, {res[name + '_loop_s20'] / 20:.3f} at S = 20; marginal "
+                  f"{statistics.median(marg):.3f} ms per step (min {min(marg):.3f}, max {max(marg):.3f} over {rounds} rounds)")
     print(json.dumps({"ms_per_batch": res, "batch": B, "seconds": T / 16000, "rounds": rounds}))
     e.close()
 
