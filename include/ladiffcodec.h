@@ -328,6 +328,41 @@ int ldc_pool_take(ldc_ctx* ctx, ldc_pool* pool, int slot, float* latents_out /*[
 int ldc_pool_peek(ldc_ctx* ctx, ldc_pool* pool, int slot, float* latents_out /*[1,C,L]*/, void* stream);   /* ldc_pool_take without freeing the slot */
 int ldc_pool_evict(ldc_pool* pool, int slot);                                 /* drop a running or finished item; frees the slot (a free slot: no-op) */
 
+/* ---- Coupled windows: one recording longer than the UNet's window, decoded on ONE shared latent -------------
+ * The recording's latent [1,C,Ltot] is covered by W windows of Lw frames that overlap by `overlap`; the windows are the items of an
+ * ordinary equal-length batch (B = W, L = Lw, F = Lw / up; up = prod(upsampling_ratios)), process_cond runs per window on its slice
+ * of the raw condition, and after every UNet pass the windows' eps are blended per global frame -- ebar(g) = sum_k w_k(g) eps_k(g - s_k),
+ * fp32, in window order -- and the ONE state is updated from ebar by the sampler's own arithmetic at B = 1, L = Ltot.  Noise is that
+ * of the B = 1, L = Ltot call: a tape [n_steps,1,C,Ltot], or Philox with the key and epoch rule of ldc_denoise / ldc_ddim_sample.
+ * A W = 1 call is ldc_denoise at B = 1; an overlap-0 call is the batch of W independent chunks.
+ * Layout (ldc_window_layout: host-only, needs no context or GPU; returns W or an error): Ltot <= Lw: one window of Ltot frames; else
+ * H = Lw - overlap, W = 1 + ceil((Ltot - Lw) / H), s_k = min(k H, Ltot - Lw) (the last window is right-aligned).  Weights, in double
+ * and rounded once to float: u_k(l) = min(1, (l + 0.5) / Rl_k, (Lw - l - 0.5) / Rr_k) over the terms whose overlap Rl_k (with the
+ * predecessor) / Rr_k (with the successor) is > 0, w_k(g) = u_k(g - s_k) / sum_j u_j(g - s_j): exactly 1.0f on a singly covered frame,
+ * a linear cross-fade on a plain overlap; a frame is covered by at most three windows.  starts_out [32]; weights_out [W][Lw] or NULL.
+ * Refused (LDC_E_INVALID, before any GPU work, ldc_last_error() naming the value): Ltot, Lw or overlap not a multiple of up, overlap
+ * outside [0, Lw / 2], more than 32 windows; by the calls with a context also Ltot != Ftot * up, Lw (when Ltot > Lw) not a multiple of
+ * the latent chunk quantum lcm(up, 2^halvings), the fp8 engine, and what ldc_denoise / ldc_ddim_sample / ldc_decode refuse.
+ * A windows plan is one batch part on one stream whatever `split` says; its cache key holds (Ltot, Lw, overlap), so its step graphs are
+ * its own.  Warm calls allocate nothing and never synchronise the device.
+ * Not available: DPM-Solver++ on windows, decode pools, batch parts, more than 32 windows or several recordings per call, code-driven and
+ * ragged variants, decompress.  Nothing here is a claim about perceived quality. */
+int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out /*[32]*/, float* weights_out /*[W*Lw] or NULL*/);
+/* the blended eps of one UNet pass at timestep t: x [1,C,Ltot], cond [1,Cc,Ftot] (raw), eps_out [1,C,Ltot] */
+int ldc_unet_forward_windows(ldc_ctx* ctx, const float* x, int t, const float* cond, int Ltot, int Ftot, int Lw, int overlap,
+                             float* eps_out, void* stream);
+/* ldc_denoise / ldc_ddim_sample (img holds the start image) of the recording on coupled windows */
+int ldc_denoise_windows(ldc_ctx* ctx, float* img_inout, const float* cond, const float* noise, int n_steps, int Ltot, int Ftot, int Lw,
+                        int overlap, void* stream);
+int ldc_ddim_sample_windows(ldc_ctx* ctx, float* img_inout, const float* cond, const float* noise, int t_start, int n_steps, float eta,
+                            int Ltot, int Ftot, int Lw, int overlap, void* stream);
+/* ldc_decode / ldc_decode_ddim at B = 1 with the denoise loop replaced: get_cond and the normalised start image over the whole
+ * recording wav [1,1,T], the coupled loop, the decoder over the whole latent, output normalisation.  Lw, overlap in latent frames. */
+int ldc_decode_windows(ldc_ctx* ctx, const float* wav, int T, int n_steps, const float* noise, int Lw, int overlap, float* wav_out,
+                       float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+int ldc_decode_ddim_windows(ldc_ctx* ctx, const float* wav, int T, int t_start, int n_steps, float eta, const float* noise, int Lw,
+                            int overlap, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+
 /* The decode of ldc_decode / ldc_decode_ddim started from RVQ codes instead of a waveform (the receiver side):
  * quantizer.decode(codes) -> upsample, /= max|.| -> sampling -> decoder -> output normalisation.
  * Exactly one of codes ([n_q,B,F] int64, device) / packed ([B][packed_stride] bytes, device, `bits` per code in

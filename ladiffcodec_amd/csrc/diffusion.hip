@@ -213,6 +213,27 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, unsigned step, uin
 }
 
 // ---------------------------------------------------------------------------------------------
+// The samplers' arithmetic on one element, shared by every update kernel that applies it (whole batches, windows):
+//   x0 = clamp(sqrt_recip_ac[t] x - sqrt_recipm1_ac[t] eps, -1, 1)                (ddpm_loss.py:175-179, :237-238)
+//   p_sample : c1 x0 + c2 x  (the posterior mean, :199-206; the caller adds sigma z unless t == 0)
+//   DDIM     : last ? x0 : x0 sqrt_an + c eps  (:268-303; the caller adds sigma z where the entry draws)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float clipped_x0(float recip, float recipm1, float xv, float e) {
+  const float x0 = recip * xv - recipm1 * e;
+  return fminf(fmaxf(x0, -1.0f), 1.0f);
+}
+__device__ __forceinline__ float p_sample_mean(float recip, float recipm1, float c1, float c2, float xv, float e) {
+  const float x0 = clipped_x0(recip, recipm1, xv, e);
+  return c1 * x0 + c2 * xv;
+}
+__device__ __forceinline__ float ddim_mean(const DdimStep& sp, float recip, float recipm1, float xv, float e) {
+  const float x0 = clipped_x0(recip, recipm1, xv, e);
+  float v = x0;
+  if (!sp.last) v = x0 * sp.sqrt_an + sp.c * e;
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------
 // p_sample update on [B][C][L] fp32 state, eps arriving channels-last; also emits the channels-last
 // copy of the new state for the next UNet call.  Tile: 32 positions x 32 channels.
 // ---------------------------------------------------------------------------------------------
@@ -257,9 +278,7 @@ __global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const vo
       const size_t idx = ((size_t)b * C + c) * L + l;
       const float xv = xin[ii];
       const float e = tile[tx][i];
-      float x0 = recip * xv - recipm1 * e;
-      x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-      float v = c1 * x0 + c2 * xv;
+      float v = p_sample_mean(recip, recipm1, c1, c2, xv, e);
       if (t > 0 && l < Lv) {
         const float z = noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii];
         v += sigma * z;
@@ -367,13 +386,8 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* 
     if (c < C && l < L) {
       const size_t idx = ((size_t)b * C + c) * L + l;
       const float e = tile[tx][i];
-      float x0 = recip * xin[ii] - recipm1 * e;
-      x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-      float v = x0;
-      if (!sp.last) {
-        v = x0 * sp.sqrt_an + sp.c * e;
-        if (draw && l < Lv) v += sp.sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);
-      }
+      float v = ddim_mean(sp, recip, recipm1, xin[ii], e);
+      if (draw && l < Lv) v += sp.sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);   // (draw: not the last iteration)
       v = l < Lv ? v : 0.f;
       x[idx] = v;
       newv[ii] = v;
@@ -399,6 +413,166 @@ hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float*
   else
     hipLaunchKernelGGL(ddim_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C,
                        L, tb, sched, st, elem_base, lens);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Coupled windows: W overlapping windows of one recording are the batch items of the UNet, ONE fp32 state
+// x [C][Ltot] is what they all read.  This kernel takes the place of the update launch of a step: the 32 x 32 tiling of
+// p_sample_update_kernel over GLOBAL frames.  A tile reads the cover entry (first window | count << 8, count <= 3, consecutive
+// windows) of each of its 32 frames, blends the covering windows' eps rows (channels-last, coalesced over c) with the host-built
+// weights in fp32 and in window order -- a singly covered frame is 1.0f * eps --, applies the sampler's arithmetic to x as the
+// B = 1, L = Ltot kernels above do (same tape index, same Philox block), and stores the new state channels-last into the row of
+// EVERY covering window of the UNet's input buffer.  Each element of that buffer has one writer: the tile that owns its global frame.
+// KIND WIN_BLEND stores the blended eps as [C][Ltot] fp32 and nothing else (ldc_unet_forward_windows).
+// LDS: tile[32][33] fp32 as above -- rows written by 32 consecutive lanes, read transposed at stride 33 dwords: conflict-free.
+// ---------------------------------------------------------------------------------------------
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void windows_update_kernel(float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
+                                                             void* x_cl, float* ebar, int C, WindowTables wt, StepTables tb,
+                                                             const DdimStep* sched, const int* st) {
+  __shared__ float tile[32][33];
+  const int c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int Ltot = wt.Ltot, Lw = wt.Lw;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  // the tensor loads do not depend on the step: cover -> (start, weight, eps) and x are issued before the step-state -> table chain
+  int cov[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int g = l0 + ty + ii * 8;
+    cov[ii] = g < Ltot ? wt.cover[g] : 0;   // (count 0: a frame behind the recording's end blends nothing and is stored nowhere)
+  }
+  float ev[4], xin[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = cov[ii] & 255, n = cov[ii] >> 8;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < n && c < C) {
+        const int k = first + j, l = g - wt.start[k];
+        const float we = wt.weight[(size_t)k * Lw + l] * dld<T>(eps_cl, ((size_t)k * Lw + l) * C + c);
+        acc = j == 0 ? we : acc + we;
+      }
+    ev[ii] = acc;
+    const int cc = c0 + i, ll = l0 + tx;
+    xin[ii] = (KIND != WIN_BLEND && cc < C && ll < Ltot) ? x[(size_t)cc * Ltot + ll] : 0.f;
+  }
+  int t = 0, j = 0;
+  uint64_t seed = 0;
+  float recip = 0.f, recipm1 = 0.f, c1 = 0.f, c2 = 0.f, sigma = 0.f;
+  DdimStep sp{};
+  bool draw = false;
+  if (KIND != WIN_BLEND) {
+    t = st[0]; j = st[1];
+    seed = ((uint64_t)(unsigned)st[3] << 32) | (uint64_t)(unsigned)st[2];
+    if (KIND == WIN_DDIM) { sp = sched[j]; t = sp.t; }
+    recip = tb.sqrt_recip_alphas_cumprod[t]; recipm1 = tb.sqrt_recipm1_alphas_cumprod[t];
+    if (KIND == WIN_DDPM) {
+      c1 = tb.posterior_mean_coef1[t]; c2 = tb.posterior_mean_coef2[t];
+      sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
+      draw = t > 0;
+    } else {
+      sigma = sp.sigma;
+      draw = !sp.last && sp.sigma > 0.f;
+    }
+  }
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
+  __syncthreads();
+  if (KIND == WIN_BLEND) {
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+      const int i = ty + ii * 8;
+      const int c = c0 + i, g = l0 + tx;
+      if (c < C && g < Ltot) ebar[(size_t)c * Ltot + g] = tile[tx][i];
+    }
+    return;
+  }
+  float newv[4];
+  // one Philox block per thread at the index of its first element in the B = 1, L = Ltot layout: what ldc_denoise draws there
+  float zz[4] = {0.f, 0.f, 0.f, 0.f};
+  if (draw && !noise) philox_normal4(seed, (unsigned)j, (uint64_t)(c0 + ty) * Ltot + l0 + tx, zz);
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int c = c0 + i, g = l0 + tx;
+    newv[ii] = 0.f;
+    if (c < C && g < Ltot) {
+      const size_t idx = (size_t)c * Ltot + g;
+      const float e = tile[tx][i];
+      float v = KIND == WIN_DDPM ? p_sample_mean(recip, recipm1, c1, c2, xin[ii], e) : ddim_mean(sp, recip, recipm1, xin[ii], e);
+      if (draw) v += sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);
+      x[idx] = v;
+      newv[ii] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][g]
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = cov[ii] & 255, n = cov[ii] >> 8;
+    const float v = tile[tx][i];
+#pragma unroll
+    for (int jj = 0; jj < 3; ++jj)
+      if (jj < n && c < C) {
+        const int k = first + jj, l = g - wt.start[k];
+        dst<T>(x_cl, ((size_t)k * Lw + l) * C + c, v);
+      }
+  }
+}
+
+template <typename T>
+static hipError_t launch_windows_update_t(int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
+                                          float* ebar, int C, WindowTables wt, StepTables tb, const DdimStep* sched, const int* st,
+                                          hipStream_t s) {
+  dim3 grid((wt.Ltot + 31) / 32, (C + 31) / 32, 1);
+  if (kind == WIN_BLEND)
+    hipLaunchKernelGGL((windows_update_kernel<T, WIN_BLEND>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st);
+  else if (kind == WIN_DDPM)
+    hipLaunchKernelGGL((windows_update_kernel<T, WIN_DDPM>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st);
+  else
+    hipLaunchKernelGGL((windows_update_kernel<T, WIN_DDIM>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st);
+  return hipGetLastError();
+}
+hipError_t launch_windows_update(int dt, int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
+                                 float* ebar, int C, WindowTables wt, StepTables tb, const DdimStep* sched, const int* st, hipStream_t s) {
+  if (kind != WIN_BLEND && kind != WIN_DDPM && kind != WIN_DDIM) return hipErrorInvalidValue;
+  if (wt.Ltot <= 0 || wt.Lw <= 0 || !wt.cover || !wt.weight || !wt.start || (kind == WIN_DDIM && !sched)) return hipErrorInvalidValue;
+  if (kind == WIN_BLEND ? !ebar : (!x || !x_cl || !st)) return hipErrorInvalidValue;
+  if (dt == DT_F32) return launch_windows_update_t<float>(kind, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st, s);
+  return launch_windows_update_t<__bf16>(kind, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st, s);
+}
+
+// the windows' slices of a [C][Ltot] fp32 sequence as the items of a channels-last batch: y[k][l][c] = x[c][start[k] / div + l]
+// (the to_cl_kernel tiling; div = up for the raw condition, whose windows start at start[k] / up condition frames)
+template <typename T>
+__global__ __launch_bounds__(256) void windows_gather_kernel(const float* x, void* y, int C, int Lw, int Ltot, const int* start, int div) {
+  __shared__ float tile[32][33];
+  const int k = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int s0 = start[k] / div;
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, l = l0 + tx;
+    tile[i][tx] = (c < C && l < Lw && s0 + l < Ltot) ? x[(size_t)c * Ltot + s0 + l] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int l = l0 + i, c = c0 + tx;
+    if (l < Lw && c < C) dst<T>(y, ((size_t)k * Lw + l) * C + c, tile[tx][i]);
+  }
+}
+hipError_t launch_windows_gather(int dt, const float* x, void* y, int W, int C, int Lw, int Ltot, const int* start, int div, hipStream_t s) {
+  if (W <= 0 || Lw <= 0 || Ltot < Lw || div < 1 || !start) return hipErrorInvalidValue;
+  dim3 grid((Lw + 31) / 32, (C + 31) / 32, W);
+  if (dt == DT_F32) hipLaunchKernelGGL(windows_gather_kernel<float>, grid, dim3(256), 0, s, x, y, C, Lw, Ltot, start, div);
+  else hipLaunchKernelGGL(windows_gather_kernel<__bf16>, grid, dim3(256), 0, s, x, y, C, Lw, Ltot, start, div);
   return hipGetLastError();
 }
 

@@ -782,6 +782,7 @@ void drop_plans(ldc_ctx* c) {
     for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
     if (pl->arena_base) (void)hipFree(pl->arena_base);
     if (pl->x0_prev) (void)hipFree(pl->x0_prev);
+    if (pl->win_base) (void)hipFree(pl->win_base);
   }
   c->plans.clear();
   c->plan_bytes = 0;
@@ -1974,13 +1975,15 @@ static void evict_plan(ldc_ctx* c, size_t idx) {
   for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
   if (pl->arena_base) (void)hipFree(pl->arena_base);
   if (pl->x0_prev) (void)hipFree(pl->x0_prev);   // (every captured DPM graph of the plan went above)
+  if (pl->win_base) (void)hipFree(pl->win_base);   // (likewise every windows graph: they carry the plan's L and F)
   c->plan_bytes -= pl->arena_bytes;
   c->plans.erase(c->plans.begin() + idx);
 }
 
-int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id) {
+int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id, int win_Ltot, int win_O) {
   for (auto& p : c->plans)
-    if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged && p->items == items && p->pool_id == pool_id) {
+    if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged && p->items == items && p->pool_id == pool_id &&
+        p->win_Ltot == win_Ltot && p->win_O == win_O) {
       p->last_use = ++c->use_tick;
       *out = p.get();
       return LDC_OK;
@@ -1989,6 +1992,8 @@ int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** ou
   pl->ragged = ragged;
   pl->items = items;
   pl->pool_id = pool_id;
+  pl->win_Ltot = win_Ltot;
+  pl->win_O = win_O;
   {   // pass 1: what do the convs of this plan need as split-K workspace?
     Arena dry;
     LDCCHK(build_plan(c, pl.get(), dry, B, L, F));
@@ -2388,7 +2393,11 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
                              sm.kind == SAMPLER_DDIM ? sm.ddim : nullptr));
   }
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
-  if (sm.kind == SAMPLER_DPM)
+  if (pl->win_Ltot) {   // coupled windows: x is the recording's one state, the blend and the update are one launch (noise: the B = 1, L = Ltot tape)
+    if (sm.kind == SAMPLER_DPM || h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part, on DDPM or DDIM");
+    HIPCHK(launch_windows_update(c->dt, sm.kind == SAMPLER_DDIM ? WIN_DDIM : WIN_DDPM, x, pl->eps_cl, noise, noise_stride, pl->x_cl, nullptr,
+                                 c->unet.channels, pl->win, c->sched, sm.ddim, pl->step_state, s));
+  } else if (sm.kind == SAMPLER_DPM)
     HIPCHK(launch_dpm_update(c->dt, x + off, pl->eps_cl, pl->x0_prev, pl->x_cl, pl->B, c->unet.channels, pl->L, c->sched, sm.dpm,
                              pl->step_state, s, pl->ragged ? pl->lens : nullptr));
   else if (sm.kind == SAMPLER_DDIM)
@@ -2505,7 +2514,8 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   if (left_forked) *left_forked = false;
   const bool strided = sm.kind != SAMPLER_DDPM;   // a strided schedule, DDIM or DPM: the graph lengths below are theirs alike
   const int L = h.p[0]->L, F = h.p[0]->F;
-  const int64_t stride = (int64_t)B * c->unet.channels * L;
+  const int wl = h.p[0]->win_Ltot, wo = h.p[0]->win_O;   // a coupled-windows plan: its own graphs, the noise tape of ONE item of wl frames
+  const int64_t stride = wl ? (int64_t)c->unet.channels * wl : (int64_t)B * c->unet.channels * L;
   LDCCHK(set_steps(c, h, n_steps - 1, 0, s));   // (DDIM: t is overwritten from the table in every step's first kernel)
   if (c->profile || c->serial_parts || n_steps < 3) {
     if (left_forked && h.n >= 2) LDCCHK(join_parts(c, h, s));   // (the caller's per-part work is on the auxiliary streams; these steps may all run on s)
@@ -2517,7 +2527,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   const int rag = h.p[0]->ragged ? 1 : 0;   // the steps of ragged plans are graphs of their own, replayed for any set of lengths
   const int kind = sm.kind;   // a loop never replays another sampler's graph (DDPM, DDIM, DPM); all stay cached side by side
   for (auto& g : c->graphs)
-    if (g.B == B && g.L == L && g.F == F && g.sampler == kind && g.ragged == rag && g.pool_id == 0) sg = &g;
+    if (g.B == B && g.L == L && g.F == F && g.sampler == kind && g.ragged == rag && g.pool_id == 0 && g.win_Ltot == wl && g.win_O == wo) sg = &g;
   if (!sg) {
     // graphs of shapes whose plans are gone were dropped with them (evict_plan); additionally keep at most 16 alive
     if (c->graphs.size() >= 16) {
@@ -2532,7 +2542,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     }
     c->graphs.push_back(StepGraph());
     sg = &c->graphs.back();
-    sg->B = B; sg->L = L; sg->F = F; sg->sampler = kind; sg->ragged = rag;
+    sg->B = B; sg->L = L; sg->F = F; sg->sampler = kind; sg->ragged = rag; sg->win_Ltot = wl; sg->win_O = wo;
   }
   sg->last_use = ++c->use_tick;
   const bool par = parts_parallel(c, h);
@@ -3394,6 +3404,250 @@ extern "C" int ldc_decode_codes_dpm(ldc_ctx* c, const int64_t* codes, const uint
 
 
 // calls that need no weights (bit-stream layer, resampler, tuning aids): any context of the device will do
+// ---- coupled windows: a recording longer than the UNet's window, decoded on ONE shared latent ---------------------
+// The W overlapping windows of the recording are the items of an ordinary equal-length batch; after every UNet pass their eps are blended
+// per global frame and the recording's single fp32 state is updated from the blend (windows_update_kernel, in place of the update launch).
+struct WinLayout {
+  int Ltot = 0, Lw = 0, O = 0, W = 0;
+  std::vector<int> start, cover;   // cover[g] = first covering window | count << 8
+  std::vector<float> weight;       // [W][Lw]
+};
+static constexpr int kMaxWindows = 32;
+
+// the layout, the cover table and the weights (double, rounded once to float) of (Ltot, Lw, overlap); every refusal names its value
+static int window_layout(int Ltot, int Lw, int O, int up, WinLayout* out) {
+  if (up < 1) return fail(LDC_E_INVALID, "up %d: the latent frames per condition frame must be >= 1", up);
+  if (Ltot <= 0 || Ltot % up) return fail(LDC_E_INVALID, "Ltot %d: must be a positive multiple of up = %d", Ltot, up);
+  if (Lw <= 0 || Lw % up) return fail(LDC_E_INVALID, "Lw %d: must be a positive multiple of up = %d", Lw, up);
+  if (O < 0 || O % up || O > Lw / 2) return fail(LDC_E_INVALID, "overlap %d: must be a multiple of up = %d in [0, Lw / 2 = %d]", O, up, Lw / 2);
+  if (Ltot <= Lw) Lw = Ltot;   // one window: the recording itself
+  const int H = Lw - O;
+  const long long W = Ltot <= Lw ? 1 : 1 + ((long long)(Ltot - Lw) + H - 1) / H;
+  if (W > kMaxWindows) return fail(LDC_E_INVALID, "Ltot %d needs %lld windows of %d frames at overlap %d: at most %d per call", Ltot, W, Lw, O, kMaxWindows);
+  out->Ltot = Ltot; out->Lw = Lw; out->O = O; out->W = (int)W;
+  out->start.assign((size_t)W, 0);
+  for (int k = 0; k < W; ++k) out->start[k] = (int)std::min<long long>((long long)k * H, Ltot - Lw);   // the last window is right-aligned
+  std::vector<double> u((size_t)W * Lw);
+  for (int k = 0; k < W; ++k) {
+    const int Rl = k > 0 ? out->start[k - 1] + Lw - out->start[k] : 0, Rr = k + 1 < W ? out->start[k] + Lw - out->start[k + 1] : 0;
+    for (int l = 0; l < Lw; ++l) {
+      double v = 1.0;
+      if (Rl > 0) v = std::min(v, (l + 0.5) / Rl);
+      if (Rr > 0) v = std::min(v, (Lw - l - 0.5) / Rr);
+      u[(size_t)k * Lw + l] = v;
+    }
+  }
+  out->cover.assign((size_t)Ltot, 0);
+  out->weight.assign((size_t)W * Lw, 0.f);
+  int first = 0;
+  for (int g = 0; g < Ltot; ++g) {
+    while (out->start[first] + Lw <= g) ++first;   // (starts ascend, so the covering windows are consecutive from here)
+    int n = 0;
+    double sum = 0.0;
+    while (first + n < W && out->start[first + n] <= g) { sum += u[(size_t)(first + n) * Lw + (g - out->start[first + n])]; ++n; }
+    if (n < 1 || n > 3) return fail(LDC_E_STATE, "internal: frame %d is covered by %d windows", g, n);
+    out->cover[g] = first | (n << 8);
+    for (int j = 0; j < n; ++j) {
+      const size_t i = (size_t)(first + j) * Lw + (g - out->start[first + j]);
+      out->weight[i] = (float)(u[i] / sum);
+    }
+  }
+  return LDC_OK;
+}
+
+extern "C" int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out, float* weights_out) {
+  WinLayout lay;
+  LDCCHK(window_layout(Ltot, Lw, overlap, up, &lay));
+  if (starts_out)
+    for (int k = 0; k < kMaxWindows; ++k) starts_out[k] = k < lay.W ? lay.start[k] : 0;
+  if (weights_out) std::copy(lay.weight.begin(), lay.weight.end(), weights_out);
+  return lay.W;
+}
+
+// everything a windows call refuses, before any GPU work; then the plan of the layout (made on its first use: the recording's state and
+// the tables in one allocation, uploaded on s) as a one-part Halves -- the blend couples every window at every step, whatever `split` says
+static int windows_prepare(ldc_ctx* c, int Ltot, int Ftot, int Lw, int O, hipStream_t s, Halves* h) {
+  if (c->w8) return fail(LDC_E_INVALID, "coupled windows are not available on the fp8 engine: use dtype bf16 or f32");
+  const int up = upsample_factor(c), q = ragged_latent_quantum(c);
+  if (Ltot <= 0 || Ftot <= 0 || (long long)Ftot * up != Ltot)
+    return fail(LDC_E_INVALID, "Ltot (%d) must equal Ftot (%d) x prod(upsampling_ratios) (%d)", Ltot, Ftot, up);
+  if (Ltot > Lw && (Lw <= 0 || Lw % q)) return fail(LDC_E_INVALID, "Lw %d: a window must be a positive multiple of %d latent frames (the chunk quantum)", Lw, q);
+  WinLayout lay;
+  LDCCHK(window_layout(Ltot, Lw, O, up, &lay));
+  *h = Halves();
+  c->call_tick = c->use_tick;
+  Plan* pl = nullptr;
+  LDCCHK(get_plan(c, lay.W, lay.Lw, lay.Lw / up, 0, s, &pl, false, false, 0, Ltot, O));
+  if (!pl->win_base) {
+    const int C = c->unet.channels;
+    const size_t nx = ((size_t)C * Ltot * 4 + 255) / 256 * 256, nc = ((size_t)Ltot * 4 + 255) / 256 * 256;
+    const size_t nw = ((size_t)lay.W * lay.Lw * 4 + 255) / 256 * 256, ns = 256;
+    void* base = nullptr;
+    hipError_t e = hipMalloc(&base, nx + nc + nw + ns);
+    if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the windows state failed: %s", nx + nc + nw + ns, hipGetErrorString(e));
+    pl->win_base = base;
+    pl->win_x = (float*)base;
+    int* cover = (int*)((char*)base + nx);
+    float* weight = (float*)((char*)base + nx + nc);
+    int* start = (int*)((char*)base + nx + nc + nw);
+    pl->win_cover_h = lay.cover; pl->win_weight_h = lay.weight; pl->win_start_h = lay.start;
+    HIPCHK(hipMemcpyAsync(cover, pl->win_cover_h.data(), (size_t)Ltot * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(weight, pl->win_weight_h.data(), (size_t)lay.W * lay.Lw * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(start, pl->win_start_h.data(), (size_t)lay.W * 4, hipMemcpyHostToDevice, s));
+    pl->win = WindowTables{cover, weight, start, Ltot, lay.Lw};
+  }
+  h->n = 1;
+  h->p[0] = pl;
+  h->b0[0] = 0;
+  c->last_halves = *h;
+  return LDC_OK;
+}
+
+// the windows' condition slices from cond [Cc][Ftot] through process_cond, as ldc_unet_forward does at B = W
+static int windows_load_cond(ldc_ctx* c, Plan* pl, const float* cond, int Ftot, hipStream_t s) {
+  HIPCHK(launch_windows_gather(DT_F32, cond, pl->cond_in_cl, pl->B, c->unet.cond_channels, pl->F, Ftot, pl->win.start, upsample_factor(c), s));
+  return run_ops(c, pl, pl->cond_ops, false, s);
+}
+// the windows' input rows from the recording's state
+static int windows_load_x(ldc_ctx* c, Plan* pl, const float* x, hipStream_t s) {
+  HIPCHK(launch_windows_gather(c->dt, x, pl->x_cl, pl->B, c->unet.channels, pl->L, pl->win.Ltot, pl->win.start, 1, s));
+  return LDC_OK;
+}
+
+extern "C" int ldc_unet_forward_windows(ldc_ctx* c, const float* x, int t, const float* cond, int Ltot, int Ftot, int Lw, int overlap,
+                                        float* eps_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!x || !cond || !eps_out) return fail(LDC_E_INVALID, "null tensor");
+  if (t < 0 || t >= c->unet.timesteps) return fail(LDC_E_INVALID, "t %d: out of range [0, %d)", t, c->unet.timesteps);
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_prepare(c, Ltot, Ftot, Lw, overlap, s, &h));
+  Plan* pl = h.p[0];
+  LDCCHK(windows_load_cond(c, pl, cond, Ftot, s));
+  LDCCHK(windows_load_x(c, pl, x, s));
+  HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
+  HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
+  LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+  HIPCHK(launch_windows_update(c->dt, WIN_BLEND, nullptr, pl->eps_cl, nullptr, 0, nullptr, eps_out, c->unet.channels, pl->win, c->sched, nullptr,
+                               nullptr, s));
+  return finish_stream(c, stream);
+}
+
+// the coupled loop on the plan's own state: img [1][C][Ltot] in, the loop, img out
+static int windows_sample(ldc_ctx* c, float* img, const float* cond, const float* noise, int n_steps, int sampler, bool draws, int Ltot,
+                          int Ftot, int Lw, int overlap, void* stream) {
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_prepare(c, Ltot, Ftot, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));       // c->ddim_host, filled by the caller
+  StepSampler sm;
+  sm.kind = sampler;
+  sm.ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
+  Plan* pl = h.p[0];
+  LDCCHK(windows_load_cond(c, pl, cond, Ftot, s));
+  const size_t nbytes = (size_t)c->unet.channels * Ltot * 4;
+  HIPCHK(hipMemcpyAsync(pl->win_x, img, nbytes, hipMemcpyDeviceToDevice, s));
+  LDCCHK(windows_load_x(c, pl, pl->win_x, s));
+  next_noise_key(c, noise == nullptr && draws);
+  LDCCHK(denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm));
+  HIPCHK(hipMemcpyAsync(img, pl->win_x, nbytes, hipMemcpyDeviceToDevice, s));
+  return finish_stream(c, stream);
+}
+
+extern "C" int ldc_denoise_windows(ldc_ctx* c, float* img, const float* cond, const float* noise, int n_steps, int Ltot, int Ftot, int Lw,
+                                   int overlap, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+  return windows_sample(c, img, cond, noise, n_steps, SAMPLER_DDPM, true, Ltot, Ftot, Lw, overlap, stream);
+}
+
+extern "C" int ldc_ddim_sample_windows(ldc_ctx* c, float* img, const float* cond, const float* noise, int t_start, int n_steps, float eta,
+                                       int Ltot, int Ftot, int Lw, int overlap, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  bool draws = false;
+  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  return windows_sample(c, img, cond, noise, n_steps, SAMPLER_DDIM, draws, Ltot, Ftot, Lw, overlap, stream);
+}
+
+// ldc_decode / ldc_decode_ddim at B = 1 with the denoise loop replaced by the coupled loop: get_cond and the normalised start image over
+// the whole recording, the windows' loop on the shared latent, the SEANet decoder over the whole latent, output_normalise
+static int decode_windows_body(ldc_ctx* c, const float* wav, int T, int n_steps, int sampler, bool draws, const float* noise, int Lw, int overlap,
+                               float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  const Codec& cc = c->codec[LDC_MODEL_COND];
+  const Codec& mc = c->codec[LDC_MODEL_MAIN];
+  if (T % cc.hop || T % mc.hop) return fail(LDC_E_INVALID, "T %d: must be a multiple of %d and %d (sample.py:87 trims to 640)", T, cc.hop, mc.hop);
+  const int F = T / cc.hop, L = T / mc.hop, D = c->cfg.rep_dims;
+  LDCCHK(check_unet_args(c, 1, L, F));
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_prepare(c, L, F, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
+  LDCCHK(ensure_outnorm(c, 1));
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));
+  Plan* pl = h.p[0];
+  LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
+    float* mx = (float*)ar.alloc(4);
+    float* qr = nullptr;
+    int Fq = 0;
+    LDCCHK(get_cond_rows(c, wav, 1, T, 0.f, ar, dry, s, &qr, &Fq, codes_out, 1));
+    if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
+    void* up = nullptr;
+    int Lu = 0;
+    LDCCHK(upsample_rows(c, qr, 1, F, ar, dry, s, &up, &Lu));
+    if (!dry) {
+      if (cond_out) HIPCHK(launch_from_cl(DT_F32, qr, cond_out, 1, D, F, nullptr, 0, 0.f, s));
+      // start image: upsample, /= max|.|+1e-8 over the whole recording (sample.py:125-129), straight into the plan's state
+      HIPCHK(hipMemsetAsync(mx, 0, 4, s));
+      HIPCHK(launch_maxabs(DT_F32, up, 1, (int64_t)L * D, 0, mx, s));
+      HIPCHK(launch_from_cl(DT_F32, up, pl->win_x, 1, D, L, mx, 0, 1e-8f, s));
+      // process_cond per window: the rows are channels-last fp32 already, a window's slice is one contiguous run of them
+      const int Fw = pl->F, upf = upsample_factor(c);
+      for (int k = 0; k < pl->B; ++k)
+        HIPCHK(hipMemcpyAsync((float*)pl->cond_in_cl + (size_t)k * Fw * D, qr + (size_t)(pl->win_start_h[k] / upf) * D, (size_t)Fw * D * 4,
+                              hipMemcpyDeviceToDevice, s));
+      LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
+      LDCCHK(windows_load_x(c, pl, pl->win_x, s));
+      next_noise_key(c, noise == nullptr && draws);
+      StepSampler sm;
+      sm.kind = sampler;
+      sm.ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
+      LDCCHK(denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm));
+      if (latents_out) HIPCHK(hipMemcpyAsync(latents_out, pl->win_x, (size_t)D * L * 4, hipMemcpyDeviceToDevice, s));
+    }
+    // decoder over the whole latent (quirk Q3: no x18 un-scaling on this path, sample.py:131)
+    SeaRun R{c, &ar, s, dry, 1};
+    void* zc = ar.alloc((size_t)L * D * 4);
+    if (!dry) HIPCHK(launch_to_cl(DT_F32, pl->win_x, zc, 1, D, L, nullptr, 0, 0.f, s));
+    void* y = nullptr;
+    int Lo = 0, Cd = 0;
+    LDCCHK(run_seanet(R, mc.dec, zc, L, &y, &Lo, &Cd));
+    if (!dry) {
+      HIPCHK(hipMemcpyAsync(wav_out, y, (size_t)Lo * 4, hipMemcpyDeviceToDevice, s));
+      HIPCHK(launch_output_normalise(wav_out, 1, Lo, 0, c->outnorm_ws, s, nullptr, mc.hop));
+    }
+    return LDC_OK;
+  }));
+  return finish_stream(c, stream);
+}
+
+extern "C" int ldc_decode_windows(ldc_ctx* c, const float* wav, int T, int n_steps, const float* noise, int Lw, int overlap, float* wav_out,
+                                  float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+  return decode_windows_body(c, wav, T, n_steps, SAMPLER_DDPM, true, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
+extern "C" int ldc_decode_ddim_windows(ldc_ctx* c, const float* wav, int T, int t_start, int n_steps, float eta, const float* noise, int Lw,
+                                       int overlap, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  bool draws = false;
+  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  return decode_windows_body(c, wav, T, n_steps, SAMPLER_DDIM, draws, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
 int check_dev(ldc_ctx* c) {
   if (!c) return fail(LDC_E_INVALID, "null ctx");
   hipError_t e = hipSetDevice(c->device);

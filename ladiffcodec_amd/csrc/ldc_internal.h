@@ -206,6 +206,16 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
   float* x0_prev = nullptr;     // DPM-Solver++(2M) history of this part: x0 of the previous iteration, [B][channels][L] fp32.  An allocation of
                                 // its own, made by the first DPM call on the plan (before any capture) and freed with the plan: captured DPM
                                 // graphs keep its address
+  // Coupled-windows plan (ldc_*_windows): the ordinary equal-length plan at (B = W windows, L = Lw, F = Lw / up) of ONE
+  // recording of win_Ltot latent frames cut with overlap win_O -- both part of the cache key, 0 on every other plan.  One allocation of its
+  // own (win_base, made before any capture, freed with the plan) holds the recording's fp32 state and the layout's tables; the host copies
+  // stay alive with the plan because the upload is asynchronous.
+  int win_Ltot = 0, win_O = 0;
+  void* win_base = nullptr;
+  float* win_x = nullptr;       // [channels][win_Ltot] fp32: the one latent every window reads (captured step graphs keep its address)
+  WindowTables win{};           // cover [win_Ltot], weight [B][L], start [B] (device)
+  std::vector<int> win_cover_h, win_start_h;
+  std::vector<float> win_weight_h;
   std::vector<std::function<hipError_t(hipStream_t)>> cond_ops;   // process_cond (once per denoise)
   std::vector<std::function<hipError_t(hipStream_t)>> step_ops;   // Unet1D.forward after process_cond
   std::vector<int> step_is_conv;                                   // 1 where step_ops[i] is a conv-GEMM launch
@@ -244,6 +254,7 @@ struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sa
   int B = 0, L = 0, F = 0, n = 0;
   int ragged = 0;    // (part of the cache key) the steps of ragged plans
   int pool_id = 0;   // (part of the cache key) != 0: the step graphs of that decode pool's plans
+  int win_Ltot = 0, win_O = 0;   // (part of the cache key) != 0: the steps of that coupled-windows plan (B windows of L frames)
   int sampler = SAMPLER_DDPM;   // sampler kind (part of the cache key): a loop never replays another kind's graph (DDIM, DPM: the schedule table's address is captured, not its contents)
   const float* noise = nullptr;
   float* x = nullptr;
@@ -537,7 +548,8 @@ int upsample_factor(const ldc_ctx* c);
 int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F);
 int check_dev(ldc_ctx* c);   // hipSetDevice only: calls that need no weights
 // what ldc_api_pool.cpp shares with the samplers of ldc_api.cpp
-int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false, bool items = false, int pool_id = 0);
+int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false, bool items = false, int pool_id = 0,
+             int win_Ltot = 0, int win_O = 0);
 int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step, hipStream_t s);
 int calibrate_part_streams(ldc_ctx* c, hipStream_t s);
 bool parts_parallel(ldc_ctx* c, const Halves& h);

@@ -279,6 +279,22 @@ hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src_host, int 
 hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                               void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
                               uint64_t elem_base, hipStream_t s, const int* lens = nullptr);
+// Coupled windows: the host-built tables of one layout (Ltot, Lw, overlap), in device memory.
+struct WindowTables {
+  const int* cover;      // [Ltot]: first covering window | count << 8 (count <= 3, the covering windows have consecutive indices)
+  const float* weight;   // [W][Lw]: w_k(start[k] + l); the weights of the windows that cover a frame sum to 1, a lone window has 1.0f
+  const int* start;      // [W] first global frame of each window
+  int Ltot, Lw;
+};
+enum { WIN_BLEND = 0, WIN_DDPM = 1, WIN_DDIM = 2 };
+// The update launch of a coupled-windows step: blends eps_cl [W][Lw][C] dt into the eps of the global frames, applies p_sample
+// (WIN_DDPM) or the DDIM entry sched[st[1]] (WIN_DDIM) to x [C][Ltot] fp32 exactly as the B = 1, L = Ltot kernels above (noise:
+// [.. j ..][C][Ltot] or null for Philox at elem_base 0) and stores the new state into every covering window's row of x_cl [W][Lw][C] dt.
+// WIN_BLEND: the blended eps into ebar [C][Ltot] fp32, nothing else is read or written.
+hipError_t launch_windows_update(int dt, int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
+                                 float* ebar, int C, WindowTables wt, StepTables tb, const DdimStep* sched, const int* st, hipStream_t s);
+// y [W][Lw][C] dt <- x [C][Ltot] fp32 at frames start[k] / div + l
+hipError_t launch_windows_gather(int dt, const float* x, void* y, int W, int C, int Lw, int Ltot, const int* start, int div, hipStream_t s);
 // One iteration of DPM-Solver++(2M) in its data-prediction form: the host fills one entry per iteration j
 // (ldc_api.cpp: ldc_dpm_schedule, double arithmetic rounded once to float) into a device table that the step state indexes.
 struct DpmStep {

@@ -597,6 +597,87 @@ class Engine:
             self._exit()
         return eps
 
+    # ---- coupled windows: one long recording on one shared latent ----------
+    def window_layout(self, Ltot: int, Lw: int, overlap: int):
+        """ldc_window_layout for this engine's `up`: -> (starts [W], weights [W, min(Lw, Ltot)] float32)."""
+        return L.window_layout(Ltot, Lw, overlap, int(np.prod(self.unet.upsampling_ratios or ())))
+
+    def _one_recording(self, x, what: str):
+        x = self._f32(x)
+        if x.dim() != 3 or x.shape[0] != 1:
+            raise ValueError(f"{what}: coupled windows take one recording per call ([1, C, L]), got {tuple(x.shape)}")
+        return x
+
+    def unet_forward_windows(self, x, t: int, cond, Lw: int, overlap: int):
+        """The blended eps of one UNet pass over the windows of x [1, C, Ltot] (cond [1, C, Ftot], raw): [1, C, Ltot]."""
+        x, cond = self._one_recording(x, "x"), self._one_recording(cond, "cond")
+        eps = self.torch.empty_like(x)
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_unet_forward_windows(self._ctx, x.data_ptr(), int(t), cond.data_ptr(), x.shape[2], cond.shape[2], int(Lw),
+                                                      int(overlap), eps.data_ptr(), s))
+        finally:
+            self._exit()
+        return eps
+
+    def denoise_windows(self, img, cond, n_steps: int, Lw: int, overlap: int, noise=None):
+        """`denoise` of one recording [1, C, Ltot] on coupled windows of Lw frames overlapping by `overlap`; noise [n_steps, 1, C, Ltot]."""
+        img, cond = self._one_recording(img, "img").clone(), self._one_recording(cond, "cond")
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_denoise_windows(self._ctx, img.data_ptr(), cond.data_ptr(), noise.data_ptr() if noise is not None else None,
+                                                 int(n_steps), img.shape[2], cond.shape[2], int(Lw), int(overlap), s))
+        finally:
+            self._exit()
+        return img
+
+    def ddim_sample_windows(self, img, cond, t_start: int, n_steps: int, Lw: int, overlap: int, eta: float = 0.0, noise=None):
+        """`ddim_sample` (from the caller's start image) of one recording on coupled windows."""
+        img, cond = self._one_recording(img, "img").clone(), self._one_recording(cond, "cond")
+        noise = self._f32(noise) if noise is not None else None
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_ddim_sample_windows(self._ctx, img.data_ptr(), cond.data_ptr(), noise.data_ptr() if noise is not None else None,
+                                                     int(t_start), int(n_steps), float(eta), img.shape[2], cond.shape[2], int(Lw),
+                                                     int(overlap), s))
+        finally:
+            self._exit()
+        return img
+
+    def _decode_windows(self, wav, want_stages: bool, call):
+        wav = self._one_recording(wav, "wav")
+        T = wav.shape[2]
+        F, Lz = T // self.cond_codec.hop_length, T // self.main_codec.hop_length
+        out = self._empty(1, 1, T)
+        lat = self._empty(1, self.main_codec.rep_dims, Lz) if want_stages else None
+        cond = self._empty(1, self.main_codec.rep_dims, F) if want_stages else None
+        codes = self._empty(self.cond_codec.n_q_for_bandwidth(None), 1, F, dtype=self.torch.int64) if want_stages else None
+        p = lambda t: t.data_ptr() if t is not None else None
+        s = self._enter()
+        try:
+            L.check(call(wav.data_ptr(), T, out.data_ptr(), p(lat), p(cond), p(codes), s))
+        finally:
+            self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
+        return out
+
+    def decode_windows(self, wav, n_steps: int, Lw: int, overlap: int, noise=None, want_stages: bool = False):
+        """`decode` of one recording wav [1, 1, T] with the denoise loop on coupled windows (Lw, overlap in latent frames)."""
+        noise = self._f32(noise) if noise is not None else None
+        pn = noise.data_ptr() if noise is not None else None
+        return self._decode_windows(wav, want_stages, lambda w, T, o, la, co, cd, s: self.lib.ldc_decode_windows(
+            self._ctx, w, T, int(n_steps), pn, int(Lw), int(overlap), o, la, co, cd, s))
+
+    def decode_ddim_windows(self, wav, t_start: int, n_steps: int, Lw: int, overlap: int, eta: float = 0.0, noise=None,
+                            want_stages: bool = False):
+        """`decode_ddim` of one recording with the loop on coupled windows."""
+        noise = self._f32(noise) if noise is not None else None
+        pn = noise.data_ptr() if noise is not None else None
+        return self._decode_windows(wav, want_stages, lambda w, T, o, la, co, cd, s: self.lib.ldc_decode_ddim_windows(
+            self._ctx, w, T, int(t_start), int(n_steps), float(eta), pn, int(Lw), int(overlap), o, la, co, cd, s))
+
     def unet_forward_items(self, x, t, cond, lens=None):
         """`unet_forward` with a timestep per item (Unet1D.forward's `time[B]`): t a sequence of B timesteps; lens (optional) per-item
         latent lengths as in `unet_forward_ragged`.  eps is zero beyond an item's length."""

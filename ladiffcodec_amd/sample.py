@@ -11,6 +11,8 @@ Same flags, defaults and output naming as the reference.  What differs, by desig
     as torch.randn_like does in the reference (ddpm_loss.py:249);
   * `--ragged` batches mono files of DIFFERENT lengths (plan_ragged_batches, Engine.decode_ragged): every file is still decoded
     as if alone, but trimmed to the chunk quantum (2560 samples for `--enc_ratios 8 4`) instead of the reference's 640;
+  * `--chunk_overlap_sec S` (with `--chunk_sec`) decodes a long mono recording on coupled windows that overlap by S seconds
+    (Engine.decode_windows: one shared latent, no seams) instead of as independent chunks;
   * under `torch.distributed.run` the FILE list is sharded over the ranks (one process per GPU; all channels of a
     file stay on one rank, every output file has exactly one writer).
 Flags that are inert in the reference stay accepted and inert (`--sampling_timesteps`,
@@ -86,6 +88,10 @@ _EXTRA: List[Tuple[str, dict]] = [
                            "trimmed to the chunk quantum (2560 samples for --enc_ratios 8 4, coarser than the reference's 640)")),
     ("--ragged_waste", dict(type=float, default=argparse.SUPPRESS, help="--ragged: a batch is closed before its padded size B * Tmax "
                                                                         "exceeds (1 + this) x the samples it really holds (default 0.25)")),
+    ("--chunk_overlap_sec", dict(type=float, default=argparse.SUPPRESS,
+                                 help="--chunk_sec > 0: decode a long mono recording on COUPLED windows of --chunk_sec that overlap by this "
+                                      "much (Engine.decode_windows: one shared latent, the windows' predictions are cross-faded at every "
+                                      "step, so there are no seams) instead of as independent chunks; at most half of --chunk_sec, 0 allowed")),
 ]
 
 
@@ -99,6 +105,19 @@ def build_parser() -> argparse.ArgumentParser:
 def ragged_options(a) -> Tuple[bool, float]:
     """(--ragged, --ragged_waste) of a parsed namespace, with their defaults: off, 0.25."""
     return bool(getattr(a, "ragged", False)), float(getattr(a, "ragged_waste", 0.25))
+
+
+def windows_options(a):
+    """--chunk_overlap_sec of a parsed namespace: None without the flag, else the overlap in seconds (it needs --chunk_sec > 0 and is
+    at most half of it)."""
+    if not hasattr(a, "chunk_overlap_sec"):
+        return None
+    ov, chunk_sec = float(a.chunk_overlap_sec), float(getattr(a, "chunk_sec", 0.0) or 0.0)
+    if chunk_sec <= 0:
+        raise SystemExit("--chunk_overlap_sec needs --chunk_sec > 0 (the window length)")
+    if not 0.0 <= ov <= chunk_sec / 2:
+        raise SystemExit(f"--chunk_overlap_sec {ov}: must be in [0, --chunk_sec / 2 = {chunk_sec / 2}]")
+    return ov
 
 
 def _unsupported(a) -> None:
@@ -587,6 +606,79 @@ def decode_long_files(eng, files: List[str], wavs, inp_args, rank: int, world: i
     return written
 
 
+MAX_WINDOWS = 32          # windows of one Engine.decode_windows call (ldc_window_layout)
+
+
+def window_grid(chunk_sec: float, overlap_sec: float, enc_ratios, upsampling_ratios) -> Tuple[int, int]:
+    """(Lw, overlap) in latent frames for --chunk_sec / --chunk_overlap_sec: the window on the chunk quantum (as --chunk_sec cuts its
+    chunks), the overlap rounded down to whole condition frames (multiples of prod(upsampling_ratios)) and to at most Lw / 2."""
+    quantum, hop = chunk_quantum(enc_ratios), int(np.prod(list(enc_ratios)))
+    up = int(np.prod(list(upsampling_ratios)))
+    Lw = max(quantum, int(round(chunk_sec * 16000)) // quantum * quantum) // hop
+    ov = min(int(round(overlap_sec * 16000)) // hop, Lw // 2) // up * up
+    return Lw, ov
+
+
+def plan_window_segments(Ltot: int, Lw: int, overlap: int, up: int, max_windows: int = MAX_WINDOWS) -> List[Tuple[int, int]]:
+    """[(first frame, frames)] of a recording of Ltot latent frames cut into segments of at most max_windows coupled windows each
+    (Lw + (max_windows - 1)(Lw - overlap) frames).  A last segment shorter than one window takes the frames it lacks from its
+    predecessor (whole condition frames), so every segment holds at least Lw frames."""
+    seg = Lw + (max_windows - 1) * (Lw - overlap)
+    if Ltot <= seg:
+        return [(0, Ltot)]
+    cuts = list(range(0, Ltot, seg))
+    if Ltot - cuts[-1] < Lw:
+        cuts[-1] -= -(-(Lw - (Ltot - cuts[-1])) // up) * up
+    return [(a, b - a) for a, b in zip(cuts, cuts[1:] + [Ltot])]
+
+
+def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: float, rank: int, world: int, local_rank: int, sampler=None) -> List[str]:
+    """--chunk_overlap_sec: every long mono recording of this rank through Engine.decode_windows / decode_ddim_windows, trimmed to
+    whole 640-sample frames as the whole-file path trims.  A recording that needs more than MAX_WINDOWS windows is cut into segments
+    that are decoded one after another and hard-joined (raw decoder outputs, normalised once over the recording)."""
+    import sys
+    import torch
+    from scipy.io import wavfile
+    from . import lib as L, parallel
+    sampler = _sampler(inp_args, sampler)
+    if not isinstance(sampler, (DdpmSampler, DdimSampler)):
+        raise SystemExit("--chunk_overlap_sec: coupled windows decode with DDPM or DDIM sampling only")
+    enc_ratios = getattr(inp_args, "enc_ratios", [8, 4])
+    hop, up = int(np.prod(list(enc_ratios))), int(np.prod(list(inp_args.upsampling_ratios)))
+    Lw, ov = window_grid(float(inp_args.chunk_sec), overlap_sec, enc_ratios, inp_args.upsampling_ratios)
+    dev = torch.device("cuda", local_rank)
+    provider = getattr(inp_args, "noise_provider", None)
+
+    def one(wav, noise, stages):
+        if isinstance(sampler, DdimSampler):
+            return eng.decode_ddim_windows(wav, sampler.t_start, sampler.n_steps, Lw, ov, eta=sampler.eta, noise=noise, want_stages=stages)
+        return eng.decode_windows(wav, sampler.n_steps, Lw, ov, noise=noise, want_stages=stages)
+
+    written = []
+    for i in parallel.shard_utterances([sh[1] for sh in wavs.shapes], rank, world):
+        n = wavs.shapes[i][1] // 640 * 640
+        x = torch.from_numpy(np.ascontiguousarray(wavs[i][:1, None, :n]))
+        segs = plan_window_segments(n // hop, Lw, ov, up)
+        if len(segs) > 1:
+            print(f"[windows] {files[i]}: {n // hop} latent frames need more than {MAX_WINDOWS} windows; decoded as {len(segs)} "
+                  f"segments, hard-joined", file=sys.stderr)
+        raw = []
+        for k, (f0, fl) in enumerate(segs):
+            # test seam (see decode_files): keys are (file index, segment number)
+            noise = provider([(i, k)], sampler.draws, fl).to(dev) if provider is not None and sampler.draws > 0 else None
+            got = one(x[:, :, f0 * hop:(f0 + fl) * hop].contiguous().to(dev), noise, len(segs) > 1)
+            raw.append(got if len(segs) == 1 else eng.decode_latents(L.MODEL_MAIN, got["latents"]))
+        whole = raw[0] if len(segs) == 1 else eng.output_normalise(torch.cat(raw, dim=-1), per_item=False)
+        if not bool(torch.isfinite(whole).all()):
+            raise RuntimeError(f"non-finite audio decoded for {files[i]}")
+        path = output_path(files[i], inp_args.input_dir, inp_args.output_dir, wavs.in_ext)
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        wavfile.write(path, 16000, np.ascontiguousarray(whole.cpu().numpy()[0, 0]))
+        written.append(path)
+        wavs.drop(i)
+    return written
+
+
 def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_rank: int, sampler=None, source=None) -> List[str]:
     """`eng`: one engine, or a list of engines (one batch in flight per engine, each on its own stream); `sampler`: as synthesis;
     `source`: the batch source over `files` (default LazyWavs; see there)."""
@@ -600,6 +692,9 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
     keep = [i for i, sh in enumerate(wavs.shapes) if sh[1] // 640 * 640 > 0]                  # sample.py:87-88
     files, wavs = [files[i] for i in keep], wavs.subset(keep)
     chunk_sec = float(getattr(inp_args, "chunk_sec", 0.0) or 0.0)
+    overlap_sec = windows_options(inp_args)
+    if overlap_sec is not None and source is not None:
+        raise SystemExit("--chunk_overlap_sec decodes waveforms only (coupled windows have no code-driven variant)")
     if chunk_sec > 0:
         # recordings longer than a chunk (mono) take the long-form path, everything else the reference's whole-file path
         is_long = [sh[0] == 1 and sh[1] > int(round(chunk_sec * 16000)) for sh in wavs.shapes]
@@ -607,7 +702,10 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
         short_i = [i for i, m in enumerate(is_long) if not m]
         long_f, long_w = [files[i] for i in long_i], wavs.subset(long_i)
         files, wavs = [files[i] for i in short_i], wavs.subset(short_i)
-        written_long = decode_long_files(eng, long_f, long_w, inp_args, rank, world, local_rank, sampler=sampler) if long_f else []
+        if overlap_sec is not None:
+            written_long = decode_window_files(eng, long_f, long_w, inp_args, overlap_sec, rank, world, local_rank, sampler=sampler) if long_f else []
+        else:
+            written_long = decode_long_files(eng, long_f, long_w, inp_args, rank, world, local_rank, sampler=sampler) if long_f else []
     else:
         written_long = []
     lengths = [sh[1] for sh in wavs.shapes]
