@@ -345,8 +345,17 @@ int ldc_pool_evict(ldc_pool* pool, int slot);                                 /*
  * the latent chunk quantum lcm(up, 2^halvings), the fp8 engine, and what ldc_denoise / ldc_ddim_sample / ldc_decode refuse.
  * A windows plan is one batch part on one stream whatever `split` says; its cache key holds (Ltot, Lw, overlap), so its step graphs are
  * its own.  Warm calls allocate nothing and never synchronise the device.
- * Not available: DPM-Solver++ on windows, decode pools, batch parts, more than 32 windows or several recordings per call, code-driven and
- * ragged variants, decompress.  Nothing here is a claim about perceived quality. */
+ * DPM-Solver++(2M) on windows (ldc_dpm_sample_windows, ldc_decode_dpm_windows, ldc_decode_codes_dpm_windows): iteration j blends the
+ * windows' eps as above and applies the update documented at ldc_dpm_schedule to the ONE state with ONE history x0_{j-1} [1,C,Ltot] (not
+ * one per window), which lives with the windows plan.  Nothing is drawn and the noise epoch stays where it is; the steps replay graphs
+ * keyed by the layout and the sampler kind (5 steps per graph, single-step remainders), never a DDPM or DDIM graph.  A W = 1 call is
+ * ldc_dpm_sample at B = 1, an overlap-0 call the batch of independent chunks.
+ * The receiver (ldc_decode_codes_windows, ldc_decode_codes_dpm_windows): the same decodes from the RVQ codes of ONE recording of Ftot
+ * condition frames -- quantizer.decode(codes), the start image normalised over the whole recording, per-window condition slices, the
+ * coupled loop, the decoder over the whole latent.  For the codes ldc_decode_windows returns, cond_out is bit-identical to its cond_out.
+ * Sources, packed layout and the "[bad_code]" refusal are those of ldc_decode_codes at B = 1, F = Ftot.
+ * Not available: decode pools, batch parts, more than 32 windows or several recordings per call, ragged variants.  Nothing here is a
+ * claim about perceived quality. */
 int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out /*[32]*/, float* weights_out /*[W*Lw] or NULL*/);
 /* the blended eps of one UNet pass at timestep t: x [1,C,Ltot], cond [1,Cc,Ftot] (raw), eps_out [1,C,Ltot] */
 int ldc_unet_forward_windows(ldc_ctx* ctx, const float* x, int t, const float* cond, int Ltot, int Ftot, int Lw, int overlap,
@@ -362,6 +371,23 @@ int ldc_decode_windows(ldc_ctx* ctx, const float* wav, int T, int n_steps, const
                        float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
 int ldc_decode_ddim_windows(ldc_ctx* ctx, const float* wav, int T, int t_start, int n_steps, float eta, const float* noise, int Lw,
                             int overlap, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+/* ldc_dpm_sample / ldc_decode_dpm of the recording on coupled windows.  Refused first, also with a NULL context: t_start < 1, n_steps
+ * outside [1, t_start]; then what the DDIM windows call refuses. */
+int ldc_dpm_sample_windows(ldc_ctx* ctx, float* img_inout, const float* cond, int t_start, int n_steps, int Ltot, int Ftot, int Lw,
+                           int overlap, void* stream);
+int ldc_decode_dpm_windows(ldc_ctx* ctx, const float* wav, int T, int t_start, int n_steps, int Lw, int overlap, float* wav_out,
+                           float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
+/* The receiver on coupled windows.  codes [n_q,1,Ftot] int64 or packed (exactly one non-NULL); wav_out [1,1,Ftot*320].
+ * ldc_decode_codes_windows: t_start == 0 is halfway DDPM sampling of n_steps (eta unused), t_start > 0 is DDIM -- the convention of
+ * ldc_decode_codes_ragged; noise as in ldc_decode_windows / ldc_decode_ddim_windows.  Refused first, also with a NULL context: both
+ * sources or neither, Ftot or n_q < 1, bits, packed_stride, eta outside [0, 1], t_start < 0 (DPM: < 1), n_steps < 1 or > t_start; then
+ * what ldc_decode_codes at B = 1 and the windows calls refuse. */
+int ldc_decode_codes_windows(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int Ftot,
+                             int t_start, int n_steps, float eta, const float* noise, int Lw, int overlap, float* wav_out,
+                             float* latents_out, float* cond_out, void* stream);
+int ldc_decode_codes_dpm_windows(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
+                                 int Ftot, int t_start, int n_steps, int Lw, int overlap, float* wav_out, float* latents_out,
+                                 float* cond_out, void* stream);
 
 /* The decode of ldc_decode / ldc_decode_ddim started from RVQ codes instead of a waveform (the receiver side):
  * quantizer.decode(codes) -> upsample, /= max|.| -> sampling -> decoder -> output normalisation.
@@ -415,6 +441,7 @@ int ldc_decode_codes_ragged(ldc_ctx* ctx, const int64_t* codes, const uint8_t* p
  * context-free ones): t_start outside [1, timesteps], n_steps outside [1, t_start], null pointers, and the shape refusals of the
  * DDIM call each one mirrors.  The steps replay captured graphs keyed by (B, L, F) and the sampler kind: every n_steps reuses them,
  * and no call replays a DDPM or DDIM graph.  The x0 history lives with the cached plan of each batch part.
+ * On coupled windows: ldc_dpm_sample_windows and its decodes, above.
  * Not available: decode pools, ldc_decode_codes_ragged, the SDE and third-order variants. */
 int ldc_dpm_schedule(const float* sqrt_recip, const float* sqrt_recipm1, int timesteps, int t_start, int n_steps, int* t_out,
                      float* coef_out);

@@ -666,6 +666,107 @@ hipError_t launch_dpm_update(int dt, float* x, const void* eps_cl, float* x0_pre
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Coupled windows, kind WIN_DPM ("DPM-Solver++ windows"): the DPM-Solver++(2M) update of dpm_update_kernel on the
+// recording's ONE state x [C][Ltot] with its ONE history x0_prev [C][Ltot], from the blended eps of windows_update_kernel -- a sibling
+// of that template (its instantiations stay as they are): same tiling over GLOBAL frames, same cover / weight / start tables, same
+// blend (w * eps in fp32, window order, the first term assigned), same stores into x and into the row of every covering window of x_cl.
+// The history is loaded only where the entry says has_prev (and is not the last) and written on every iteration but the last; an entry
+// without has_prev never reads it, so it is never cleared.  Nothing is drawn.
+// Load order: cover -> (start, weight, eps) and x do not depend on the step and go first; the history's load depends on the table row
+// (has_prev), so it follows st -> row and is issued in front of the row -> coefficient-table loads and of everything that consumes them.
+// LDS: tile[32][33] fp32, rows written by 32 consecutive lanes, read transposed at stride 33 dwords: conflict-free.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void windows_dpm_update_kernel(float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WindowTables wt,
+                                                                 StepTables tb, const DpmStep* sched, const int* st) {
+  __shared__ float tile[32][33];
+  const int c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int Ltot = wt.Ltot, Lw = wt.Lw;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  int cov[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int g = l0 + ty + ii * 8;
+    cov[ii] = g < Ltot ? wt.cover[g] : 0;   // (count 0: a frame behind the recording's end blends nothing and is stored nowhere)
+  }
+  float ev[4], xin[4], pv[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = cov[ii] & 255, n = cov[ii] >> 8;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < n && c < C) {
+        const int k = first + j, l = g - wt.start[k];
+        const float we = wt.weight[(size_t)k * Lw + l] * dld<T>(eps_cl, ((size_t)k * Lw + l) * C + c);
+        acc = j == 0 ? we : acc + we;
+      }
+    ev[ii] = acc;
+    const int cc = c0 + i, ll = l0 + tx;
+    xin[ii] = (cc < C && ll < Ltot) ? x[(size_t)cc * Ltot + ll] : 0.f;
+  }
+  const DpmStep sp = sched[st[1]];
+  const bool hist = !sp.last && sp.has_prev;   // (uniform over the grid) the only case in which the history is read
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int cc = c0 + ty + ii * 8, ll = l0 + tx;
+    pv[ii] = (hist && cc < C && ll < Ltot) ? x0_prev[(size_t)cc * Ltot + ll] : 0.f;
+  }
+  const float recip = tb.sqrt_recip_alphas_cumprod[sp.t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[sp.t];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
+  __syncthreads();
+  float newv[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int c = c0 + i, g = l0 + tx;
+    newv[ii] = 0.f;
+    if (c < C && g < Ltot) {
+      const size_t idx = (size_t)c * Ltot + g;
+      const float x0 = clipped_x0(recip, recipm1, xin[ii], tile[tx][i]);
+      float v = x0;
+      if (!sp.last) {
+        v = sp.a * xin[ii] + sp.b0 * x0;
+        if (hist) v += sp.b1 * pv[ii];
+        x0_prev[idx] = x0;
+      }
+      x[idx] = v;
+      newv[ii] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][g]
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = cov[ii] & 255, n = cov[ii] >> 8;
+    const float v = tile[tx][i];
+#pragma unroll
+    for (int jj = 0; jj < 3; ++jj)
+      if (jj < n && c < C) {
+        const int k = first + jj, l = g - wt.start[k];
+        dst<T>(x_cl, ((size_t)k * Lw + l) * C + c, v);
+      }
+  }
+}
+
+hipError_t launch_windows_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WindowTables wt, StepTables tb,
+                                     const DpmStep* sched, const int* st, hipStream_t s) {
+  if (wt.Ltot <= 0 || wt.Lw <= 0 || !wt.cover || !wt.weight || !wt.start) return hipErrorInvalidValue;
+  if (!x || !eps_cl || !x0_prev || !x_cl || !sched || !st || C <= 0) return hipErrorInvalidValue;
+  dim3 grid((wt.Ltot + 31) / 32, (C + 31) / 32, 1);
+  if (dt == DT_F32) hipLaunchKernelGGL(windows_dpm_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, wt, tb, sched, st);
+  else hipLaunchKernelGGL(windows_dpm_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, wt, tb, sched, st);
+  return hipGetLastError();
+}
+
 // the DPM schedule table written on the stream, as launch_ddim_table_write writes its table
 struct DpmChunk { DpmStep e[kDdimChunk]; };
 __global__ void dpm_table_write_kernel(DpmStep* dst, DpmChunk src, int n) {

@@ -2394,9 +2394,12 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
   }
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
   if (pl->win_Ltot) {   // coupled windows: x is the recording's one state, the blend and the update are one launch (noise: the B = 1, L = Ltot tape)
-    if (sm.kind == SAMPLER_DPM || h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part, on DDPM or DDIM");
-    HIPCHK(launch_windows_update(c->dt, sm.kind == SAMPLER_DDIM ? WIN_DDIM : WIN_DDPM, x, pl->eps_cl, noise, noise_stride, pl->x_cl, nullptr,
-                                 c->unet.channels, pl->win, c->sched, sm.ddim, pl->step_state, s));
+    if (h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part");
+    if (sm.kind == SAMPLER_DPM)   // WIN_DPM: x0_prev is the recording's ONE history [C][Ltot] (ensure_windows_history)
+      HIPCHK(launch_windows_dpm_update(c->dt, x, pl->eps_cl, pl->x0_prev, pl->x_cl, c->unet.channels, pl->win, c->sched, sm.dpm, pl->step_state, s));
+    else
+      HIPCHK(launch_windows_update(c->dt, sm.kind == SAMPLER_DDIM ? WIN_DDIM : WIN_DDPM, x, pl->eps_cl, noise, noise_stride, pl->x_cl, nullptr,
+                                   c->unet.channels, pl->win, c->sched, sm.ddim, pl->step_state, s));
   } else if (sm.kind == SAMPLER_DPM)
     HIPCHK(launch_dpm_update(c->dt, x + off, pl->eps_cl, pl->x0_prev, pl->x_cl, pl->B, c->unet.channels, pl->L, c->sched, sm.dpm,
                              pl->step_state, s, pl->ragged ? pl->lens : nullptr));
@@ -3503,6 +3506,33 @@ static int windows_prepare(ldc_ctx* c, int Ltot, int Ftot, int Lw, int O, hipStr
   return LDC_OK;
 }
 
+// The DPM-Solver++(2M) history of a windows plan: ONE x0_prev [channels][Ltot] fp32 for the recording, in the layout of win_x (not one per
+// window).  Like the parts' histories (ensure_history) it is made by the first DPM call on the plan, outside of any capture, kept in
+// pl->x0_prev until the plan goes -- behind the plan's graphs (evict_plan, drop_plans) -- and never cleared: the first iteration does not load it.
+static int ensure_windows_history(ldc_ctx* c, Plan* pl) {
+  if (pl->x0_prev) return LDC_OK;
+  void* p = nullptr;
+  const size_t bytes = (size_t)c->unet.channels * pl->win_Ltot * 4;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the windows DPM history failed: %s", bytes, hipGetErrorString(e));
+  pl->x0_prev = (float*)p;
+  return LDC_OK;
+}
+
+// the sampler of a windows loop: the schedule the caller left in c->ddim_host / c->dpm_host goes to the device in front of everything else
+// (before any capture), a DPM loop gets the plan's history
+static int windows_sampler(ldc_ctx* c, Plan* pl, int sampler, hipStream_t s, StepSampler* sm) {
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));
+  if (sampler == SAMPLER_DPM) {
+    LDCCHK(dpm_upload(c, s));
+    LDCCHK(ensure_windows_history(c, pl));
+  }
+  sm->kind = sampler;
+  sm->ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
+  sm->dpm = sampler == SAMPLER_DPM ? c->dpm_table : nullptr;
+  return LDC_OK;
+}
+
 // the windows' condition slices from cond [Cc][Ftot] through process_cond, as ldc_unet_forward does at B = W
 static int windows_load_cond(ldc_ctx* c, Plan* pl, const float* cond, int Ftot, hipStream_t s) {
   HIPCHK(launch_windows_gather(DT_F32, cond, pl->cond_in_cl, pl->B, c->unet.cond_channels, pl->F, Ftot, pl->win.start, upsample_factor(c), s));
@@ -3539,11 +3569,9 @@ static int windows_sample(ldc_ctx* c, float* img, const float* cond, const float
   hipStream_t s = pick_stream(c, stream);
   Halves h;
   LDCCHK(windows_prepare(c, Ltot, Ftot, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
-  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));       // c->ddim_host, filled by the caller
-  StepSampler sm;
-  sm.kind = sampler;
-  sm.ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
   Plan* pl = h.p[0];
+  StepSampler sm;
+  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));   // c->ddim_host / c->dpm_host, filled by the caller
   LDCCHK(windows_load_cond(c, pl, cond, Ftot, s));
   const size_t nbytes = (size_t)c->unet.channels * Ltot * 4;
   HIPCHK(hipMemcpyAsync(pl->win_x, img, nbytes, hipMemcpyDeviceToDevice, s));
@@ -3571,9 +3599,20 @@ extern "C" int ldc_ddim_sample_windows(ldc_ctx* c, float* img, const float* cond
   return windows_sample(c, img, cond, noise, n_steps, SAMPLER_DDIM, draws, Ltot, Ftot, Lw, overlap, stream);
 }
 
-// ldc_decode / ldc_decode_ddim at B = 1 with the denoise loop replaced by the coupled loop: get_cond and the normalised start image over
+// DPM-Solver++(2M) on coupled windows, as ldc_dpm_sample at B = 1: deterministic, nothing is drawn, the Philox epoch stays where it is
+extern "C" int ldc_dpm_sample_windows(ldc_ctx* c, float* img, const float* cond, int t_start, int n_steps, int Ltot, int Ftot, int Lw, int overlap,
+                                      void* stream) {
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  return windows_sample(c, img, cond, nullptr, n_steps, SAMPLER_DPM, false, Ltot, Ftot, Lw, overlap, stream);
+}
+
+// ldc_decode / ldc_decode_ddim / ldc_decode_dpm (src.wav) or ldc_decode_codes / _ddim / _dpm (src.codes | src.packed) at B = 1 with the
+// denoise loop replaced by the coupled loop: the condition rows (get_cond, or the dequantised codes) and the normalised start image over
 // the whole recording, the windows' loop on the shared latent, the SEANet decoder over the whole latent, output_normalise
-static int decode_windows_body(ldc_ctx* c, const float* wav, int T, int n_steps, int sampler, bool draws, const float* noise, int Lw, int overlap,
+static int decode_windows_body(ldc_ctx* c, const FrontSrc& src, int T, int n_steps, int sampler, bool draws, const float* noise, int Lw, int overlap,
                                float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
   const Codec& cc = c->codec[LDC_MODEL_COND];
   const Codec& mc = c->codec[LDC_MODEL_MAIN];
@@ -3584,13 +3623,22 @@ static int decode_windows_body(ldc_ctx* c, const float* wav, int T, int n_steps,
   Halves h;
   LDCCHK(windows_prepare(c, L, F, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
   LDCCHK(ensure_outnorm(c, 1));
-  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));
   Plan* pl = h.p[0];
+  StepSampler sm;
+  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));
   LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
     float* mx = (float*)ar.alloc(4);
     float* qr = nullptr;
     int Fq = 0;
-    LDCCHK(get_cond_rows(c, wav, 1, T, 0.f, ar, dry, s, &qr, &Fq, codes_out, 1));
+    if (src.wav) {
+      LDCCHK(get_cond_rows(c, src.wav, 1, T, 0.f, ar, dry, s, &qr, &Fq, codes_out, 1));
+    } else {   // the receiver: quantizer.decode(codes) over the whole recording, as decode_body at B = 1 (bad code values raise the device flag)
+      qr = (float*)ar.alloc((size_t)F * D * 4);
+      Fq = F;
+      if (!dry)
+        HIPCHK(launch_rvq_dequant(src.codes, src.packed, src.packed_stride, src.bits, src.n_q, 1, 0, 1, F, cc.codebooks, cc.bins, D, qr,
+                                  c->dev_flag_dev, s, nullptr));
+    }
     if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
     void* up = nullptr;
     int Lu = 0;
@@ -3609,9 +3657,6 @@ static int decode_windows_body(ldc_ctx* c, const float* wav, int T, int n_steps,
       LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
       LDCCHK(windows_load_x(c, pl, pl->win_x, s));
       next_noise_key(c, noise == nullptr && draws);
-      StepSampler sm;
-      sm.kind = sampler;
-      sm.ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
       LDCCHK(denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm));
       if (latents_out) HIPCHK(hipMemcpyAsync(latents_out, pl->win_x, (size_t)D * L * 4, hipMemcpyDeviceToDevice, s));
     }
@@ -3636,7 +3681,9 @@ extern "C" int ldc_decode_windows(ldc_ctx* c, const float* wav, int T, int n_ste
   LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
   if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
   if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
-  return decode_windows_body(c, wav, T, n_steps, SAMPLER_DDPM, true, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_windows_body(c, src, T, n_steps, SAMPLER_DDPM, true, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
 }
 
 extern "C" int ldc_decode_ddim_windows(ldc_ctx* c, const float* wav, int T, int t_start, int n_steps, float eta, const float* noise, int Lw,
@@ -3645,7 +3692,57 @@ extern "C" int ldc_decode_ddim_windows(ldc_ctx* c, const float* wav, int T, int 
   if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
   bool draws = false;
   LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
-  return decode_windows_body(c, wav, T, n_steps, SAMPLER_DDIM, draws, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_windows_body(c, src, T, n_steps, SAMPLER_DDIM, draws, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
+// ldc_decode_dpm of one recording with the loop on coupled windows: no eta, no noise, the Philox epoch stays where it is
+extern "C" int ldc_decode_dpm_windows(ldc_ctx* c, const float* wav, int T, int t_start, int n_steps, int Lw, int overlap, float* wav_out,
+                                      float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  FrontSrc src;
+  src.wav = wav;
+  return decode_windows_body(c, src, T, n_steps, SAMPLER_DPM, false, nullptr, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
+}
+
+// The receiver on coupled windows: ldc_decode_windows / ldc_decode_ddim_windows from the RVQ codes of ONE recording of Ftot condition
+// frames (int64 codes [n_q][1][Ftot] or the packed payload, as ldc_decode_codes).  t_start 0: DDPM halfway sampling of n_steps (eta is not
+// used); > 0: DDIM -- the convention of ldc_decode_codes_ragged.  The context-free refusals come first (a NULL context sees them too).
+extern "C" int ldc_decode_codes_windows(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int Ftot,
+                                        int t_start, int n_steps, float eta, const float* noise, int Lw, int overlap, float* wav_out,
+                                        float* latents_out, float* cond_out, void* stream) {
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, 1, Ftot, wav_out));
+  if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "eta %g: must be a finite value in [0, 1]", (double)eta);
+  if (t_start < 0) return fail(LDC_E_INVALID, "t_start %d: must be >= 0 (0: DDPM halfway sampling)", t_start);
+  if (n_steps < 1) return fail(LDC_E_INVALID, "n_steps %d: must be >= 1", n_steps);
+  if (t_start > 0 && n_steps > t_start)
+    return fail(LDC_E_INVALID, "n_steps %d: must be in [1, t_start = %d] (more would repeat timesteps)", n_steps, t_start);
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Ftot, &src, &T));
+  bool draws = true;
+  if (t_start > 0) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  else if (n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+  return decode_windows_body(c, src, T, n_steps, t_start > 0 ? SAMPLER_DDIM : SAMPLER_DDPM, draws, noise, Lw, overlap, wav_out, latents_out, cond_out,
+                             nullptr, stream);
+}
+
+extern "C" int ldc_decode_codes_dpm_windows(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
+                                            int Ftot, int t_start, int n_steps, int Lw, int overlap, float* wav_out, float* latents_out,
+                                            float* cond_out, void* stream) {
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, 1, Ftot, wav_out));
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Ftot, &src, &T));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  return decode_windows_body(c, src, T, n_steps, SAMPLER_DPM, false, nullptr, Lw, overlap, wav_out, latents_out, cond_out, nullptr, stream);
 }
 
 int check_dev(ldc_ctx* c) {

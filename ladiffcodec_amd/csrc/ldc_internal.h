@@ -205,7 +205,8 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
   float* cur_ss = nullptr;      // [ss_stride] timestep-MLP row of the step this part is executing
   float* x0_prev = nullptr;     // DPM-Solver++(2M) history of this part: x0 of the previous iteration, [B][channels][L] fp32.  An allocation of
                                 // its own, made by the first DPM call on the plan (before any capture) and freed with the plan: captured DPM
-                                // graphs keep its address
+                                // graphs keep its address.  On a coupled-windows plan (below) it is the recording's ONE history instead,
+                                // [channels][win_Ltot] fp32 in win_x's layout (ensure_windows_history), with the same lifetime
   // Coupled-windows plan (ldc_*_windows): the ordinary equal-length plan at (B = W windows, L = Lw, F = Lw / up) of ONE
   // recording of win_Ltot latent frames cut with overlap win_O -- both part of the cache key, 0 on every other plan.  One allocation of its
   // own (win_base, made before any capture, freed with the plan) holds the recording's fp32 state and the layout's tables; the host copies
@@ -247,7 +248,7 @@ enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_DPM = 2 };
 struct StepSampler {
   int kind = SAMPLER_DDPM;
   const DdimStep* ddim = nullptr;   // SAMPLER_DDIM: c->ddim_table (step_begin takes t from it, ddim_update the coefficients)
-  const DpmStep* dpm = nullptr;     // SAMPLER_DPM: c->dpm_table (likewise; dpm_update also reads and writes the plan's x0_prev)
+  const DpmStep* dpm = nullptr;     // SAMPLER_DPM: c->dpm_table (likewise; dpm_update / windows_dpm_update also read and write the plan's x0_prev)
 };
 
 struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update | dpm_update, step_advance}

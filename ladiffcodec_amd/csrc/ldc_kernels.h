@@ -286,7 +286,7 @@ struct WindowTables {
   const int* start;      // [W] first global frame of each window
   int Ltot, Lw;
 };
-enum { WIN_BLEND = 0, WIN_DDPM = 1, WIN_DDIM = 2 };
+enum { WIN_BLEND = 0, WIN_DDPM = 1, WIN_DDIM = 2, WIN_DPM = 3 };   // WIN_DPM: launch_windows_dpm_update below (DpmStep follows)
 // The update launch of a coupled-windows step: blends eps_cl [W][Lw][C] dt into the eps of the global frames, applies p_sample
 // (WIN_DDPM) or the DDIM entry sched[st[1]] (WIN_DDIM) to x [C][Ltot] fp32 exactly as the B = 1, L = Ltot kernels above (noise:
 // [.. j ..][C][Ltot] or null for Philox at elem_base 0) and stores the new state into every covering window's row of x_cl [W][Lw][C] dt.
@@ -312,6 +312,12 @@ struct DpmStep {
 hipError_t launch_dpm_table_write(DpmStep* dst, const DpmStep* src_host, int n, hipStream_t s);   // dst[0..n) = src_host[0..n), stream-ordered
 hipError_t launch_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int B, int C, int L, StepTables tb,
                              const DpmStep* sched, const int* st, hipStream_t s, const int* lens = nullptr);
+// The fourth kind of the coupled-windows update launch (WIN_DPM; a sibling kernel of the WIN_BLEND / WIN_DDPM / WIN_DDIM template): the
+// blend of launch_windows_update, then the update of launch_dpm_update on x [C][Ltot] fp32 with the recording's ONE history x0_prev
+// [C][Ltot] fp32 (loaded only where the entry sched[st[1]] says has_prev, written on every iteration but the last, never cleared); the new
+// state goes into x and into every covering window's row of x_cl [W][Lw][C] dt.  Nothing is drawn.
+hipError_t launch_windows_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WindowTables wt, StepTables tb,
+                                     const DpmStep* sched, const int* st, hipStream_t s);
 // x /= (maxabs[b or 0] + eps) in place on a raw element stream (n_per_item elements per item)
 hipError_t launch_scale_by_maxabs(int dt, void* x, int B, int64_t n_per_item, const float* maxabs, int per_item,
                                   float eps, hipStream_t s);

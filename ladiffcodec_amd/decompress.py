@@ -11,6 +11,9 @@ from them (Engine.decode_codes): the cond encoder does not run.  Batching, per-i
 mono stream under `--chunk_sec` is cut at frame counts that are multiples of chunk_quantum / 320, its chunks decoded as batch
 items and their raw decoder outputs joined and normalised over the whole recording.  The codes of such a recording come from
 a whole-file encode, so that output is not `srcs.sample --chunk_sec` of the waveform.
+`--chunk_sec C --chunk_overlap_sec S` (checked as `srcs.sample` checks them) decodes such a stream on COUPLED windows instead
+(Engine.decode_codes_windows, with `--dpm_steps` Engine.decode_codes_dpm_windows: one shared latent, no seams); a stream that needs
+more than 32 windows is cut into segments of codes at whole condition frames, decoded one after another and hard-joined.
 
 `--ragged [--ragged_waste W]` decodes mono containers of DIFFERENT lengths in shared batches (plan_container_batches,
 Engine.decode_codes_ragged): containers are grouped by (nc, bits, mode) and those whose frame count -- from the header -- is a
@@ -174,12 +177,13 @@ class EcdcSource:
 
 def decompress(inp_args) -> List[str]:
     from . import parallel
-    from .sample import _unsupported, build_engines, decode_files
+    from .sample import _unsupported, build_engines, decode_files, windows_options
     from .spec import CodecConfig
 
     from .compress import ragged_options
     _unsupported(inp_args)
     ragged_options(inp_args)                        # (refusals before anything is loaded)
+    windows_options(inp_args)                       # (likewise: --chunk_overlap_sec needs --chunk_sec and is at most half of it)
     sampler = sampler_from_args(inp_args)
     # the codebooks the cond quantizer is built with (as build_engines builds it: ratios [8,5,4,2] at --cond_bandwidth)
     n_q_layers = CodecConfig(enc_ratios=(8, 5, 4, 2), quantization=True, bandwidth=inp_args.cond_bandwidth).n_q_layers

@@ -25,6 +25,7 @@ EXPORTS = [
     "ldc_cond_upsample", "ldc_unet_forward", "ldc_p_sample", "ldc_denoise", "ldc_p_sample_loop", "ldc_infilling", "ldc_output_normalise", "ldc_decode", "ldc_ddim_times", "ldc_ddim_sample", "ldc_decode_ddim", "ldc_decode_codes", "ldc_decode_codes_ddim",
     "ldc_dpm_schedule", "ldc_dpm_sample", "ldc_decode_dpm", "ldc_decode_codes_dpm", "ldc_decode_ragged_dpm",
     "ldc_window_layout", "ldc_unet_forward_windows", "ldc_denoise_windows", "ldc_ddim_sample_windows", "ldc_decode_windows", "ldc_decode_ddim_windows",
+    "ldc_dpm_sample_windows", "ldc_decode_dpm_windows", "ldc_decode_codes_windows", "ldc_decode_codes_dpm_windows",
     "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
     "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
     "ldc_stream_min_first", "ldc_stream_create", "ldc_stream_reset", "ldc_stream_destroy", "ldc_seanet_encode_stream", "ldc_seanet_decode_stream", "ldc_get_cond_stream",
@@ -125,6 +126,10 @@ def load() -> C.CDLL:
     lib.ldc_ddim_sample_windows.argtypes = [vp, fp, fp, fp, i32, i32, C.c_float, i32, i32, i32, i32, vp]
     lib.ldc_decode_windows.argtypes = [vp, fp, i32, i32, fp, i32, i32, fp, fp, fp, vp, vp]
     lib.ldc_decode_ddim_windows.argtypes = [vp, fp, i32, i32, i32, C.c_float, fp, i32, i32, fp, fp, fp, vp, vp]
+    lib.ldc_dpm_sample_windows.argtypes = [vp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
+    lib.ldc_decode_dpm_windows.argtypes = [vp, fp, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp]
+    lib.ldc_decode_codes_windows.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, C.c_float, fp, i32, i32, fp, fp, fp, vp]
+    lib.ldc_decode_codes_dpm_windows.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp]
     lib.ldc_ac_encode_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
     lib.ldc_ac_decode_ragged.argtypes = [vp, vp, C.c_int64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldc_unet_forward_ragged.argtypes = [vp, fp, i32, fp, C.POINTER(C.c_int32), i32, i32, i32, fp, vp]

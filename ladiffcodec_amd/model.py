@@ -678,6 +678,64 @@ class Engine:
         return self._decode_windows(wav, want_stages, lambda w, T, o, la, co, cd, s: self.lib.ldc_decode_ddim_windows(
             self._ctx, w, T, int(t_start), int(n_steps), float(eta), pn, int(Lw), int(overlap), o, la, co, cd, s))
 
+    def dpm_sample_windows(self, img, cond, t_start: int, n_steps: int, Lw: int, overlap: int):
+        """`dpm_sample` (from the caller's start image) of one recording on coupled windows: ONE state, ONE x0 history.  Deterministic:
+        nothing is drawn and the engine's noise epoch stays where it is."""
+        img, cond = self._one_recording(img, "img").clone(), self._one_recording(cond, "cond")
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_dpm_sample_windows(self._ctx, img.data_ptr(), cond.data_ptr(), int(t_start), int(n_steps), img.shape[2],
+                                                    cond.shape[2], int(Lw), int(overlap), s))
+        finally:
+            self._exit()
+        return img
+
+    def decode_dpm_windows(self, wav, t_start: int, n_steps: int, Lw: int, overlap: int, want_stages: bool = False):
+        """`decode_dpm` of one recording with the loop on coupled windows."""
+        return self._decode_windows(wav, want_stages, lambda w, T, o, la, co, cd, s: self.lib.ldc_decode_dpm_windows(
+            self._ctx, w, T, int(t_start), int(n_steps), int(Lw), int(overlap), o, la, co, cd, s))
+
+    def _decode_codes_windows(self, codes, packed, bits, n_q, F, want_stages: bool, call):
+        if codes is not None and (codes.dim() != 3 or codes.shape[1] != 1):
+            raise ValueError(f"codes: coupled windows take one recording per call ([n_q, 1, F]), got {tuple(codes.shape)}")
+        cp, pp, stride, n_q, B, F, keep = self._codes_args(codes, packed, bits, n_q, F)
+        if B != 1:
+            raise ValueError(f"packed: coupled windows take one recording per call ([1, bytes]), got {B} rows")
+        out, lat, cond = self._codes_outputs(1, F, want_stages)
+        p = lambda t: t.data_ptr() if t is not None else None
+        s = self._enter()
+        try:
+            L.check(call(cp, pp, stride, int(bits), n_q, F, out.data_ptr(), p(lat), p(cond), s))
+        finally:
+            self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond}
+        return out
+
+    def decode_codes_windows(self, codes=None, packed=None, n_steps: Optional[int] = None, Lw: Optional[int] = None,
+                             overlap: Optional[int] = None, t_start: int = 0, eta: float = 0.0, noise=None, want_stages: bool = False,
+                             bits: int = 10, n_q: Optional[int] = None, F: Optional[int] = None):
+        """`decode_windows` (t_start 0) / `decode_ddim_windows` (t_start > 0) started from the RVQ codes of one recording (the receiver
+        side): codes [n_q, 1, F] int64, or packed [1, >= packed bytes] uint8 with n_q and F passed in, as decode_codes takes them.
+        want_stages: {"wav", "latents", "cond"}."""
+        if n_steps is None or Lw is None or overlap is None:
+            raise ValueError("n_steps, Lw and overlap are required")
+        noise = self._f32(noise) if noise is not None else None
+        pn = noise.data_ptr() if noise is not None else None
+        return self._decode_codes_windows(codes, packed, bits, n_q, F, want_stages, lambda cp, pp, st, b, q, f, o, la, co, s:
+                                          self.lib.ldc_decode_codes_windows(self._ctx, cp, pp, st, b, q, f, int(t_start), int(n_steps), float(eta),
+                                                                            pn, int(Lw), int(overlap), o, la, co, s))
+
+    def decode_codes_dpm_windows(self, codes=None, packed=None, t_start: int = 100, n_steps: int = 10, Lw: Optional[int] = None,
+                                 overlap: Optional[int] = None, want_stages: bool = False, bits: int = 10, n_q: Optional[int] = None,
+                                 F: Optional[int] = None):
+        """`decode_dpm_windows` started from the RVQ codes of one recording; the code arguments as decode_codes_windows."""
+        if Lw is None or overlap is None:
+            raise ValueError("Lw and overlap are required")
+        return self._decode_codes_windows(codes, packed, bits, n_q, F, want_stages, lambda cp, pp, st, b, q, f, o, la, co, s:
+                                          self.lib.ldc_decode_codes_dpm_windows(self._ctx, cp, pp, st, b, q, f, int(t_start), int(n_steps),
+                                                                                int(Lw), int(overlap), o, la, co, s))
+
     def unet_forward_items(self, x, t, cond, lens=None):
         """`unet_forward` with a timestep per item (Unet1D.forward's `time[B]`): t a sequence of B timesteps; lens (optional) per-item
         latent lengths as in `unet_forward_ragged`.  eps is zero beyond an item's length."""

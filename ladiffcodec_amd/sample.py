@@ -12,7 +12,8 @@ Same flags, defaults and output naming as the reference.  What differs, by desig
   * `--ragged` batches mono files of DIFFERENT lengths (plan_ragged_batches, Engine.decode_ragged): every file is still decoded
     as if alone, but trimmed to the chunk quantum (2560 samples for `--enc_ratios 8 4`) instead of the reference's 640;
   * `--chunk_overlap_sec S` (with `--chunk_sec`) decodes a long mono recording on coupled windows that overlap by S seconds
-    (Engine.decode_windows: one shared latent, no seams) instead of as independent chunks;
+    (Engine.decode_windows: one shared latent, no seams) instead of as independent chunks -- also in `sample_ddim`, `sample_dpm`
+    and, from the container's codes, in `decompress`;
   * under `torch.distributed.run` the FILE list is sharded over the ranks (one process per GPU; all channels of a
     file stay on one rank, every output file has exactly one writer).
 Flags that are inert in the reference stay accepted and inert (`--sampling_timesteps`,
@@ -632,32 +633,54 @@ def plan_window_segments(Ltot: int, Lw: int, overlap: int, up: int, max_windows:
     return [(a, b - a) for a, b in zip(cuts, cuts[1:] + [Ltot])]
 
 
+def window_decoder(eng, sampler, Lw: int, ov: int):
+    """The coupled-windows call of `sampler` on `eng` as (piece, noise, want_stages) -> result.  DdpmSampler / DdimSampler / DpmSampler:
+    piece is the waveform [1, 1, T] (Engine.decode_windows / decode_ddim_windows / decode_dpm_windows); a CodesSampler around one of
+    them: piece is the codes [n_q, 1, F] (Engine.decode_codes_windows / decode_codes_dpm_windows).  A DPM route is never handed noise."""
+    from_codes = isinstance(sampler, CodesSampler)
+    inner = sampler.inner if from_codes else sampler
+    if not isinstance(inner, (DdpmSampler, DdimSampler, DpmSampler)):
+        raise SystemExit("--chunk_overlap_sec: coupled windows decode with DDPM, DDIM or DPM-Solver++ sampling only")
+    ddim = isinstance(inner, DdimSampler)
+
+    def one(wav, noise, stages):
+        if isinstance(inner, DpmSampler):
+            return eng.decode_dpm_windows(wav, inner.t_start, inner.n_steps, Lw, ov, want_stages=stages)
+        if ddim:
+            return eng.decode_ddim_windows(wav, inner.t_start, inner.n_steps, Lw, ov, eta=inner.eta, noise=noise, want_stages=stages)
+        return eng.decode_windows(wav, inner.n_steps, Lw, ov, noise=noise, want_stages=stages)
+
+    def one_codes(codes, noise, stages):
+        if isinstance(inner, DpmSampler):
+            return eng.decode_codes_dpm_windows(codes=codes, t_start=inner.t_start, n_steps=inner.n_steps, Lw=Lw, overlap=ov, want_stages=stages)
+        return eng.decode_codes_windows(codes=codes, n_steps=inner.n_steps, Lw=Lw, overlap=ov, t_start=inner.t_start if ddim else 0,
+                                        eta=inner.eta if ddim else 0.0, noise=noise, want_stages=stages)
+
+    return one_codes if from_codes else one
+
+
 def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: float, rank: int, world: int, local_rank: int, sampler=None) -> List[str]:
-    """--chunk_overlap_sec: every long mono recording of this rank through Engine.decode_windows / decode_ddim_windows, trimmed to
-    whole 640-sample frames as the whole-file path trims.  A recording that needs more than MAX_WINDOWS windows is cut into segments
-    that are decoded one after another and hard-joined (raw decoder outputs, normalised once over the recording)."""
+    """--chunk_overlap_sec: every long mono recording of this rank through Engine.decode_windows / decode_ddim_windows /
+    decode_dpm_windows, trimmed to whole 640-sample frames as the whole-file path trims.  With a CodesSampler (decompress) `wavs` is a
+    container source and the recording's codes go through Engine.decode_codes_windows / decode_codes_dpm_windows instead.  A recording
+    that needs more than MAX_WINDOWS windows is cut into segments (of the waveform, or of the codes: cuts fall at whole condition
+    frames) that are decoded one after another and hard-joined (raw decoder outputs, normalised once over the recording)."""
     import sys
     import torch
     from scipy.io import wavfile
     from . import lib as L, parallel
     sampler = _sampler(inp_args, sampler)
-    if not isinstance(sampler, (DdpmSampler, DdimSampler)):
-        raise SystemExit("--chunk_overlap_sec: coupled windows decode with DDPM or DDIM sampling only")
+    from_codes = isinstance(sampler, CodesSampler)
     enc_ratios = getattr(inp_args, "enc_ratios", [8, 4])
     hop, up = int(np.prod(list(enc_ratios))), int(np.prod(list(inp_args.upsampling_ratios)))
     Lw, ov = window_grid(float(inp_args.chunk_sec), overlap_sec, enc_ratios, inp_args.upsampling_ratios)
     dev = torch.device("cuda", local_rank)
     provider = getattr(inp_args, "noise_provider", None)
-
-    def one(wav, noise, stages):
-        if isinstance(sampler, DdimSampler):
-            return eng.decode_ddim_windows(wav, sampler.t_start, sampler.n_steps, Lw, ov, eta=sampler.eta, noise=noise, want_stages=stages)
-        return eng.decode_windows(wav, sampler.n_steps, Lw, ov, noise=noise, want_stages=stages)
-
+    one = window_decoder(eng, sampler, Lw, ov)   # (refuses a sampler without a windows route before anything is loaded)
     written = []
     for i in parallel.shard_utterances([sh[1] for sh in wavs.shapes], rank, world):
         n = wavs.shapes[i][1] // 640 * 640
-        x = torch.from_numpy(np.ascontiguousarray(wavs[i][:1, None, :n]))
+        x = None if from_codes else torch.from_numpy(np.ascontiguousarray(wavs[i][:1, None, :n]))
         segs = plan_window_segments(n // hop, Lw, ov, up)
         if len(segs) > 1:
             print(f"[windows] {files[i]}: {n // hop} latent frames need more than {MAX_WINDOWS} windows; decoded as {len(segs)} "
@@ -666,7 +689,11 @@ def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: floa
         for k, (f0, fl) in enumerate(segs):
             # test seam (see decode_files): keys are (file index, segment number)
             noise = provider([(i, k)], sampler.draws, fl).to(dev) if provider is not None and sampler.draws > 0 else None
-            got = one(x[:, :, f0 * hop:(f0 + fl) * hop].contiguous().to(dev), noise, len(segs) > 1)
+            if from_codes:   # the segment's codes [n_q, 1, fl / up] (a cut at latent frame f0 is condition frame f0 / up)
+                piece = wavs.chunk_batch([(i, k, f0 * hop)], fl * hop).codes
+            else:
+                piece = x[:, :, f0 * hop:(f0 + fl) * hop].contiguous()
+            got = one(piece.to(dev), noise, len(segs) > 1)
             raw.append(got if len(segs) == 1 else eng.decode_latents(L.MODEL_MAIN, got["latents"]))
         whole = raw[0] if len(segs) == 1 else eng.output_normalise(torch.cat(raw, dim=-1), per_item=False)
         if not bool(torch.isfinite(whole).all()):
@@ -675,7 +702,8 @@ def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: floa
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         wavfile.write(path, 16000, np.ascontiguousarray(whole.cpu().numpy()[0, 0]))
         written.append(path)
-        wavs.drop(i)
+        if not from_codes:
+            wavs.drop(i)
     return written
 
 
@@ -693,8 +721,8 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
     files, wavs = [files[i] for i in keep], wavs.subset(keep)
     chunk_sec = float(getattr(inp_args, "chunk_sec", 0.0) or 0.0)
     overlap_sec = windows_options(inp_args)
-    if overlap_sec is not None and source is not None:
-        raise SystemExit("--chunk_overlap_sec decodes waveforms only (coupled windows have no code-driven variant)")
+    if overlap_sec is not None and source is not None and not isinstance(sampler, CodesSampler):
+        raise SystemExit("--chunk_overlap_sec: a batch source other than waveforms needs a CodesSampler (decompress)")
     if chunk_sec > 0:
         # recordings longer than a chunk (mono) take the long-form path, everything else the reference's whole-file path
         is_long = [sh[0] == 1 and sh[1] > int(round(chunk_sec * 16000)) for sh in wavs.shapes]

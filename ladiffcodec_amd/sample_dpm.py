@@ -4,7 +4,8 @@ Every flag of `srcs.sample` plus `--dpm_steps` (default 10).  The decode starts 
 condition, as the DDPM and DDIM decodes do, and runs `--dpm_steps` iterations of the second-order multistep solver in its
 data-prediction form (Lu et al. 2022) over the timesteps of `sample_ddim`,
 reversed(linspace(-1, midway_t - 1, steps + 1)), with the same clipped x0.  The sampler is deterministic: `--seed` changes nothing.
-Output naming, batching, `--in_flight`, `--chunk_sec`, `--ragged` and rank sharding are those of `srcs.sample`;
+Output naming, batching, `--in_flight`, `--chunk_sec`, `--chunk_overlap_sec` (Engine.decode_dpm_windows), `--ragged` and rank sharding
+are those of `srcs.sample`;
 `--sampling_timesteps` stays inert, as it is there.
 """
 from __future__ import annotations

@@ -15,7 +15,12 @@ and the launches of one step (step list + the step's first kernel + its update l
 
 `--kernels`: only a few windows calls and a few one-part denoise calls at B = 15, for a run under
 `rocprofv3 --kernel-trace --stats -- python tools/window_time.py --kernels`, whose kernel statistics then hold windows_update_kernel
-next to p_sample_update_kernel at B = 15."""
+next to p_sample_update_kernel at B = 15.
+
+`--dpm`: instead of the above, at the default split and alternated round by round in the same way,
+  ddim_windows / dpm_windows   Engine.ddim_sample_windows (eta 0) and Engine.dpm_sample_windows from t_start 100, marginal ms per step
+  decode_wav / decode_codes    one 20-step Engine.decode_windows of the 30 s waveform and one Engine.decode_codes_windows of its codes, ms
+                   per call (the code-driven call skips the cond encoder and the quantiser)."""
 import json
 import os
 import statistics
@@ -32,6 +37,7 @@ def main():
     from ladiffcodec_amd.spec import CodecConfig, UnetConfig
     argv = [a for a in sys.argv[1:] if not a.startswith("--")]
     kernels_only = "--kernels" in sys.argv[1:]
+    dpm_mode = "--dpm" in sys.argv[1:]
     rounds = int(argv[0]) if argv else 5
     Ltot, Lw, O_, up = 15000, 1200, 200, 10
     cc = CodecConfig(enc_ratios=(8, 5, 4, 2), quantization=True, bandwidth=3.0)
@@ -65,6 +71,30 @@ def main():
             assert bool(torch.isfinite(windows(20)).all())
             assert bool(torch.isfinite(items15(20)).all())
         torch.cuda.synchronize()
+        e.close()
+        return
+    if dpm_mode:
+        timed(e, torch, rounds, {"ddim_windows": lambda n: e.ddim_sample_windows(img, cond, 100, n, Lw, O_, eta=0.0),
+                                 "dpm_windows": lambda n: e.dpm_sample_windows(img, cond, 100, n, Lw, O_)}, W, Ltot, Lw, O_)
+        wav = (torch.from_numpy(synth.synthetic_wav(1, Ltot * 32, seed=7)) * 0.5).cuda()
+        codes = e.get_cond(wav, return_codes=True)[1]
+        calls = {"decode_wav": lambda: e.decode_windows(wav, 20, Lw, O_), "decode_codes": lambda: e.decode_codes_windows(codes=codes, n_steps=20, Lw=Lw, overlap=O_)}
+        for fn in calls.values():
+            fn(), fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in calls}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                out = fn()
+                b.record()
+                b.synchronize()
+                assert bool(torch.isfinite(out).all()), k
+                ms[k].append(a.elapsed_time(b))
+        for k, v in ms.items():
+            print(f"{k}: {statistics.median(v):.2f} ms per 20-step call (min {min(v):.2f}, max {max(v):.2f}, {rounds} rounds)")
+        print(json.dumps({"ms_per_call": {k: round(statistics.median(v), 3) for k, v in ms.items()}, "rounds": rounds}))
         e.close()
         return
     # launches of one step: the step list in profile mode (eager, one event pair per op) + the step's first kernel + its update launch
@@ -106,6 +136,32 @@ def main():
     print(f"launches per step: windows {launches['windows']}, one part of {W} items {launches['items15_split1']}")
     print(json.dumps({"ms_per_step": res, "launches_per_step": launches, "windows": W, "Ltot": Ltot, "Lw": Lw, "overlap": O_, "rounds": rounds}))
     e.close()
+
+
+def timed(e, torch, rounds, runs, W, Ltot, Lw, O_):
+    """marginal ms per step of every loop of `runs` (a 40-step call minus a 20-step call, over 20), warmed, alternated round by round"""
+    for fn in runs.values():
+        for n in (20, 40, 20, 40):
+            fn(n)
+    torch.cuda.synchronize()
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):
+        for k, fn in runs.items():
+            t = []
+            for n in (20, 40):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                out = fn(n)
+                b.record()
+                b.synchronize()
+                assert bool(torch.isfinite(out).all()), k
+                t.append(a.elapsed_time(b))
+            ms[k].append((t[1] - t[0]) / 20.0)
+    res = {k: round(statistics.median(v), 4) for k, v in ms.items()}
+    for k, v in ms.items():
+        print(f"{k}: {res[k]:.3f} ms per step (min {min(v):.3f}, max {max(v):.3f}, {rounds} rounds)")
+    print(json.dumps({"ms_per_step": res, "windows": W, "Ltot": Ltot, "Lw": Lw, "overlap": O_, "rounds": rounds}))
+    return res
 
 
 if __name__ == "__main__":
