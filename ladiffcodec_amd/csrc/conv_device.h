@@ -834,6 +834,7 @@ __device__ __forceinline__ void epilogue_rows_dispatch(const KA& a, f32x16 (&acc
 }
 
 // conv_fast_{bf16,f32}.hip
+extern long long g_lean_launches[8];        // test hook (ldc_debug_lean_launches): conv_lean_kernel launches of this process by unit kind
 extern unsigned long long* g_conv_stamps;   // tuning aid, set by ldc_conv_microbench when LDC_CONV_STAMPS is on
 bool conv_fast_eligible(const ConvLayer& ly);
 hipError_t launch_conv_fast(const ConvLayer& ly, const ConvKArgs& a, int M, int span_rows, hipStream_t s, bool* launched);

@@ -8,6 +8,7 @@
 namespace ldc {
 
 unsigned long long* g_conv_stamps = nullptr;
+long long g_lean_launches[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 hipError_t launch_conv_fast_bf16(const ConvLayer& ly, const ConvKArgs& a_in, int M, int span_rows, hipStream_t s, bool* launched);
 int conv_wgs_per_cu_bf16();

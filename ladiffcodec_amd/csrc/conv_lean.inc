@@ -16,8 +16,12 @@
 //   * the weight slabs of a unit lie [16-column group][slab][16 rows] in LDS, so that a wave's slab copies are contiguous too;
 //   * epilogue kind, folded second conv, folded LayerNorm and split-K are template parameters chosen by the launcher: an
 //     instantiation carries only its own path.
-// Not here (the launcher keeps conv_fast_kernel for them): k = 4 / 7 tap groups, fp8 weights / activations, 128 x 128 and 4 x 1-wave tiles,
-// post-activations and the unfused GroupNorm statistics.
+// Not here (the launcher keeps conv_fast_kernel for them): fp8 weights / activations, 128 x 128 and 4 x 1-wave tiles, post-activations and
+// the unfused GroupNorm statistics; k = 4 / 7 in f32, k = 8.
+// Round 7: the bf16 step's last conv_fast_kernel launches -- the four stride-2 downsamples (k = 4) and init_conv (k = 7) -- as two more
+// unit kinds (ConvTune::lean_all).  Same window, slabs, swizzle and MFMA order again; what differs from LEAN_K3 is the plane's height
+// (LEAN_K4S2: 2 BM + 2 rows, up to five pieces per wave, copied as two runs) and, for k = 7, that a chunk makes TWO units (taps 0-3 | 4-6
+// and the zero row against a valid slab, as conv_fast_body multiplies it): the loop's two stages are the two tap groups.
 
 struct LeanTile { int m0, n0, sk_k, sk_tile, R_lo, nrows, u_begin, u_end; };   // one per workgroup, dispatch order
 struct LeanGeom {
@@ -28,21 +32,26 @@ struct LeanGeom {
   int grid;
 };
 
-enum { LEAN_K3 = 0, LEAN_K1 = 1, LEAN_K1_LN = 2 };            // unit kinds: 3 taps x 1 chunk | 1 tap x 2 chunks | the same with the folded PreNorm
+// unit kinds: 3 taps x 1 chunk | 1 tap x 2 chunks | the same with the folded PreNorm | 4 taps x 1 chunk, stride 2 | (4 + 3) taps: two units per chunk
+enum { LEAN_K3 = 0, LEAN_K1 = 1, LEAN_K1_LN = 2, LEAN_K4S2 = 3, LEAN_K7 = 4 };
 enum { LEAN_EPI_PLAIN = 0, LEAN_EPI_RES = 1, LEAN_EPI_GN = 2, LEAN_EPI_GN_RES = 3, LEAN_EPI_QKV = 4 };
 
 template <int TM, int KIND, bool RF>
 struct LeanShape {
-  static constexpr bool K3 = KIND == LEAN_K3;
-  static constexpr int TG = K3 ? 3 : 1, KC = K3 ? 1 : 2, NS = TG * KC, NSB = NS + (RF ? 1 : 0);
+  static constexpr bool K3 = KIND == LEAN_K3, K4 = KIND == LEAN_K4S2, K7 = KIND == LEAN_K7;
+  static constexpr bool TAPS = K3 || K4 || K7;                             // a unit is the tap slabs of ONE chunk
+  static constexpr int TG = K3 ? 3 : (TAPS ? 4 : 1), KC = TAPS ? 1 : 2, NS = TG * KC, NSB = NS + (RF ? 1 : 0);
+  static constexpr int NTAP = K7 ? 8 : TG;                                 // fragment address sets per row block (k = 7: both tap groups; tap 7 is the zero row)
   static constexpr int BM = TM * 64, BN = 64;
-  static constexpr int PLANE_ROWS = K3 ? (TM == 2 ? 144 : 80) : BM;       // window rows a plane holds (stride 1: BM + 2 rounded up to 16)
+  // window rows a plane holds (stride 1: BM + taps - 1, stride 2: 2 BM + 2, rounded up to 16)
+  static constexpr int PLANE_ROWS = K4 ? (TM == 2 ? 272 : 144) : (TAPS ? (TM == 2 ? 144 : 80) : BM);
   static constexpr int NAW = (PLANE_ROWS / 16 + 3) / 4;                    // 1 KiB window pieces per wave and plane (wave w: pieces w NAW ..)
+  static constexpr int NAW0 = NAW > 3 ? 3 : NAW, NAW1 = NAW - NAW0;        // ... copied as one or two runs
   static constexpr int PLANE_BYTES = PLANE_ROWS * kRowBytes + kRowBytes;   // + the zero row behind the plane
   static constexpr int ZERO_OFF = PLANE_ROWS * kRowBytes;
   static constexpr int B_OFF = KC * PLANE_BYTES;
   static constexpr int STAGE_BYTES = B_OFF + NSB * BN * kRowBytes;
-  static_assert(NAW >= 1 && NAW <= 3 && NSB >= 2 && NSB <= 4, "runs of at most four copies per M0 write (13-bit immediate)");
+  static_assert(NAW >= 1 && NAW <= 5 && NAW1 <= 2 && NSB >= 2 && NSB <= 4, "runs of at most four copies per M0 write (13-bit immediate)");
 };
 
 // a run of up to N copies of 1 KiB behind ONE M0 write: copy i lands at m0v + 1024 i and reads (base + voff_i + 1024 i); only the first
@@ -523,6 +532,7 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
   constexpr bool LN = KIND == LEAN_K1_LN;
   constexpr unsigned kBias = 3072u;   // the copies' immediates (0 / 1024 / 2048 / 3072) also move the global address: offsets are pre-biased, the base is lowered
   static_assert(!RF || SH::K3, "the folded 1x1 conv rides on a k = 3 unit");
+  static_assert((!SH::K4 && !SH::K7) || (EPI <= LEAN_EPI_RES && (!SK || SH::K4)), "k = 4 / 7: plain and residual epilogues; k = 7 is never split");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __attribute__((address_space(3))) void* lptr_t;
   const unsigned lds_base = (unsigned)(size_t)(lptr_t)smem;
@@ -558,7 +568,7 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
     for (int i = 0; i < NAW; ++i) {
       int r = (wave * NAW + i) * 16 + r16;
       if (r >= nrows) r = 0;
-      vw[i] = (unsigned)(R_lo + r) * ldb + gslot + kBias - (unsigned)i * 1024u;
+      vw[i] = (unsigned)(R_lo + r) * ldb + gslot + kBias - (unsigned)(i < SH::NAW0 ? i : i - SH::NAW0) * 1024u;   // (the immediate of its place in its run)
     }
   };
   const unsigned wcnt = (unsigned)__builtin_amdgcn_readfirstlane(max(0, min(NAW, (nrows - wave * NAW * 16 + 15) >> 4)));
@@ -566,12 +576,12 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
   unsigned vb[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int q = 0; q < NSB; ++q) {
-    // slab q of a unit: tap q of the chunk (k = 3; q = 3: the folded 1x1 conv's slab) | chunk q of the unit (1x1 convs)
-    const unsigned slab = SH::K3 ? (unsigned)q * slab_bytes : (unsigned)q * (unsigned)a.wtaps * slab_bytes;
+    // slab q of a unit: tap q of the chunk (k = 3 / 4 / 7; k = 3, q = 3: the folded 1x1 conv's slab) | chunk q of the unit (1x1 convs)
+    const unsigned slab = SH::TAPS ? (unsigned)q * slab_bytes : (unsigned)q * (unsigned)a.wtaps * slab_bytes;
     vb[q] = slab + (unsigned)(n0 + wave * 16 + r16) * kRowBytes + gslot + kBias - (unsigned)q * 1024u;
   }
   const int csw = a.C1 / BKE;                                // first chunk that comes from x2
-  const int pc0 = tl.u_begin * KC;
+  const int pc0 = SH::K7 ? tl.u_begin >> 1 : tl.u_begin * KC;   // (k = 7: never split, u_begin = 0)
   int pc = pc0;                                              // producer cursor: next chunk to copy
   const char* xb;                                            // window source of chunk pc, lowered by the bias
   if (pc0 >= csw && a.C2 > 0) {
@@ -587,13 +597,29 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
   const unsigned m0_b = lds_base + (unsigned)(SH::B_OFF + wave * NSB * 1024);
   if (g.stamps) t_tab = __builtin_amdgcn_s_memtime();
 
+  const unsigned wcnt0 = SH::NAW1 ? min(wcnt, (unsigned)SH::NAW0) : wcnt, wcnt1 = wcnt - wcnt0;
   auto issue = [&](const int st) {   // (st is a literal at every call site)
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) lean_dma_run<NAW>(xb + kc * kRowBytes, m0_win + (unsigned)(st * STAGE + kc * PLANE), wcnt, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
-    lean_dma_all<NSB>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3]);
+    for (int kc = 0; kc < KC; ++kc) {
+      lean_dma_run<SH::NAW0>(xb + kc * kRowBytes, m0_win + (unsigned)(st * STAGE + kc * PLANE), wcnt0, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
+      if constexpr (SH::NAW1 > 0)
+        lean_dma_run<SH::NAW1>(xb + kc * kRowBytes, m0_win + (unsigned)(st * STAGE + kc * PLANE + SH::NAW0 * 1024), wcnt1, vw[NAW > 3 ? 3 : 0], vw[NAW > 4 ? 4 : 0], 0u);
+    }
+    if constexpr (SH::K7) {
+      // taps 0-3 of the chunk into stage 0, taps 4-6 into stage 1 with the chunk's window once more; the fourth slab of the second group
+      // is tap 4 again (conv_fast_body: "pointed at a valid one"): it meets the zero row
+      if (st == 0) {
+        lean_dma_all<4>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3]);
+        wb += (size_t)4 * slab_bytes;
+        return;
+      }
+      lean_dma_all<4>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3] - 3u * slab_bytes);
+    } else {
+      lean_dma_all<NSB>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3]);
+    }
     pc += KC;
     xb += KC * kRowBytes;
-    wb += (size_t)KC * chunk_w;
+    wb += SH::K7 ? (size_t)3 * slab_bytes : (size_t)KC * chunk_w;
     if (pc == csw) {   // the concatenated input's second tensor from here on
       xb = a.x2 - kBias;
       window_offsets(ldb2);
@@ -705,7 +731,7 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
   // fragment addresses of this lane (stage 0, plane 0): A[i][tap][k-half], B[k-half]; stage / plane / slab offsets are immediates
   const int kh = lane >> 5;
   const int leff = a.L_in << a.ups;
-  unsigned a_ad[TM][TG][2];
+  unsigned a_ad[TM][SH::NTAP][2];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int m = m0 + (wm * TM + i) * 32 + (lane & 31);
@@ -718,9 +744,9 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
     const int u0 = rl * a.stride - a.pad_left;
     const int rowb = rb * a.L_in - R_lo;
 #pragma unroll
-    for (int t = 0; t < TG; ++t) {
+    for (int t = 0; t < SH::NTAP; ++t) {
       const int u = u0 + t * a.dil;
-      const bool ok = rb >= 0 && (unsigned)u < (unsigned)leff;
+      const bool ok = rb >= 0 && (unsigned)u < (unsigned)leff && (!SH::K7 || t < 7);
       const int row = rowb + (u >> a.ups);
       const int sw = (row >> 2) & 3;
       a_ad[i][t][0] = lds_base + (unsigned)(ok ? row * kRowBytes + ((kh ^ sw) << 4) : SH::ZERO_OFF);
@@ -755,7 +781,7 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
   auto compute = [&](const int st) {   // the MFMA chain of one unit: straight-line code, every LDS offset an immediate
 #pragma unroll
     for (int q = 0; q < NS; ++q) {
-      const int kc = q / TG, t = q % TG;
+      const int kc = q / TG, t = SH::K7 ? st * TG + q : q % TG;   // (k = 7: stage = tap group)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         uint4 af[TM];
@@ -875,7 +901,7 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
         lean_epilogue_gn<T, TM, true>(a, acc, wl, mw, cw, M, m0, BM, wm, cl, gst, g.stamps != nullptr, second_out);
       } else {
         // (the launcher sends post-activations and the unfused GroupNorm statistics to conv_fast_kernel; the k column max rides on 1x1 convs only)
-        if constexpr (!SH::K3) {
+        if constexpr (!SH::TAPS) {
           if (a.colmax) epilogue_colmax<T, TM, TN>(a, acc, mw + 4 * (lane >> 5), cw + (lane & 31), m0, BM, M);
         }
         lean_epilogue_plain<T, TM, EPI == LEAN_EPI_RES>(a, acc, wl, mw, cw, M, cl.bias);
@@ -906,7 +932,7 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
 // host side: the tile table of a launch geometry (the dispatch order of conv_fast_body, evaluated once) and the launcher
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct LeanKey {
-  int v[26];
+  int v[27];
   bool operator<(const LeanKey& o) const { return memcmp(v, o.v, sizeof(v)) < 0; }
 };
 
@@ -1033,27 +1059,11 @@ static bool lean_xcd_order(const ConvKArgs& a, const FastGeom& gm, size_t esz, s
   return true;
 }
 
-// device copy of the tile table of this geometry (built on first use, kept for the life of the process: ~20 KB per geometry);
-// *max_rows = the largest window of any tile.  nullptr on allocation failure.
-static const LeanTile* lean_tile_table(const ConvKArgs& a, const FastGeom& gm, int BM, int BN, int KC, int M, int bke, int* max_rows) {
-  struct Entry { LeanTile* dev; int max_rows; };
-  static std::map<LeanKey, Entry> cache;
-  static std::mutex mu;
-  LeanKey k;
-  memset(&k, 0, sizeof(k));
-  const int vals[24] = {gm.grid, gm.ntiles, gm.ntn, gm.ntm, a.ksplit, gm.sk_xcd, gm.item_major, gm.m_fastest, BM, BN, KC, M, a.B, a.L_rows, a.L_in,
-                        a.stride, a.taps, a.dil, a.pad_left, a.ups, a.reflect_back, a.reflect_fwd, a.C1 + a.C2, bke};
-  memcpy(k.v, vals, sizeof(vals));
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  k.v[23] = bke | (dev_id << 8);
-  k.v[24] = a.wtaps * 65536 + a.n_pad;   // (with the order option: what lean_xcd_order decides on)
-  k.v[25] = a.tune ? a.tune->xcd_order : 0;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(k);
-  if (it != cache.end()) { *max_rows = it->second.max_rows; return it->second.dev; }
-  std::vector<LeanTile> h((size_t)gm.grid);
-  const int nunits_all = ((a.C1 + a.C2) / bke) / KC;
+// the tile table of a launch geometry, on the host: entry b = what workgroup b does.  Returns the largest window of any tile.
+// upc = units per chunk group (2 for k = 7: its two tap groups)
+static int lean_build_tiles(const ConvKArgs& a, const FastGeom& gm, int BM, int BN, int KC, int M, int bke, int upc, std::vector<LeanTile>& h) {
+  h.assign((size_t)gm.grid, LeanTile());
+  const int nunits_all = ((a.C1 + a.C2) / bke) / KC * upc;
   int mx = 0;
   std::vector<int> tile_of;
   int xn = 0;
@@ -1077,6 +1087,31 @@ static const LeanTile* lean_tile_table(const ConvKArgs& a, const FastGeom& gm, i
     t.u_begin = a.ksplit > 1 ? (int)(((long long)nunits_all * t.sk_k) / a.ksplit) : 0;
     t.u_end = a.ksplit > 1 ? (int)(((long long)nunits_all * (t.sk_k + 1)) / a.ksplit) : nunits_all;
   }
+  return mx;
+}
+
+// device copy of the tile table of this geometry (built on first use, kept for the life of the process: ~20 KB per geometry);
+// *max_rows = the largest window of any tile.  nullptr on allocation failure.
+static const LeanTile* lean_tile_table(const ConvKArgs& a, const FastGeom& gm, int BM, int BN, int KC, int M, int bke, int* max_rows, int upc = 1) {
+  struct Entry { LeanTile* dev; int max_rows; };
+  static std::map<LeanKey, Entry> cache;
+  static std::mutex mu;
+  LeanKey k;
+  memset(&k, 0, sizeof(k));
+  const int vals[24] = {gm.grid, gm.ntiles, gm.ntn, gm.ntm, a.ksplit, gm.sk_xcd, gm.item_major, gm.m_fastest, BM, BN, KC, M, a.B, a.L_rows, a.L_in,
+                        a.stride, a.taps, a.dil, a.pad_left, a.ups, a.reflect_back, a.reflect_fwd, a.C1 + a.C2, bke};
+  memcpy(k.v, vals, sizeof(vals));
+  int dev_id = 0;
+  (void)hipGetDevice(&dev_id);
+  k.v[23] = bke | (dev_id << 8);
+  k.v[24] = a.wtaps * 65536 + a.n_pad;   // (with the order option: what lean_xcd_order decides on)
+  k.v[25] = a.tune ? a.tune->xcd_order : 0;
+  k.v[26] = upc;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(k);
+  if (it != cache.end()) { *max_rows = it->second.max_rows; return it->second.dev; }
+  std::vector<LeanTile> h;
+  const int mx = lean_build_tiles(a, gm, BM, BN, KC, M, bke, upc, h);
   void* d = nullptr;
   if (hipMalloc(&d, h.size() * sizeof(LeanTile)) != hipSuccess) return nullptr;
   if (hipMemcpy(d, h.data(), h.size() * sizeof(LeanTile), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
@@ -1095,6 +1130,7 @@ static hipError_t launch_lean_kernel(const ConvKArgs& a, const LeanGeom& g, size
     lds_opt_in = true;
   }
   hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), lds, s, a, g);
+  __atomic_fetch_add(&g_lean_launches[KIND], 1ll, __ATOMIC_RELAXED);
   return hipGetLastError();
 }
 
@@ -1103,8 +1139,37 @@ static hipError_t launch_lean_kernel(const ConvKArgs& a, const LeanGeom& g, size
 template <typename T, int TM, int TG, int KC, bool RF>
 static hipError_t launch_lean(const ConvKArgs& a, const FastGeom& gm, int M, hipStream_t s, bool* launched) {
   *launched = false;
-  if constexpr (kW8 || kFp8 || !((TG == 3 && KC == 1) || (TG == 1 && KC == 2)) || (RF && TG != 3)) {
+  if constexpr (kW8 || kFp8 || !((TG == 3 && KC == 1) || (TG == 1 && KC == 2) || (TG == 4 && KC == 1 && sizeof(T) == 2)) || (RF && TG != 3)) {
     return hipSuccess;
+  } else if constexpr (TG == 4) {
+    // round 7 (bf16): the stride-2 downsamples (k = 4, pad 1) and init_conv (k = 7, two tap groups per chunk), plain or residual epilogue
+    const ConvTune* tn = a.tune;
+    if (tn && (!tn->lean || !tn->lean_all)) return hipSuccess;
+    const bool k4 = a.taps == 4 && a.stride == 2 && gm.ngroups == 1, k7 = a.taps == 7 && a.stride == 1 && gm.ngroups == 2;
+    if (!(k4 || k7) || a.dil != 1 || a.ups || a.wtaps != a.taps) return hipSuccess;
+    if (a.pad_mode != PAD_ZERO || a.post_act != ACT_NONE || a.gn_sum || a.gn_part || a.colmax || a.wscale || a.ln_s || a.qkv_ctx_ws || a.y2) return hipSuccess;
+    constexpr int bke = kRowBytes / (int)sizeof(T);
+    if ((a.C1 % bke) || (a.C2 % bke)) return hipSuccess;
+    const bool sk = a.ksplit > 1, res = a.residual != nullptr;
+    if (sk && (res || k7)) return hipSuccess;
+    using SH4 = LeanShape<TM, LEAN_K4S2, false>;
+    using SH7 = LeanShape<TM, LEAN_K7, false>;
+    int max_rows = 0;
+    const LeanTile* tiles = lean_tile_table(a, gm, SH4::BM, SH4::BN, 1, M, bke, &max_rows, k7 ? 2 : 1);
+    if (!tiles) return hipErrorOutOfMemory;
+    if (max_rows > (k4 ? SH4::PLANE_ROWS : SH7::PLANE_ROWS)) return hipSuccess;   // (odd input lengths: conv_fast_kernel)
+    LeanGeom g;
+    g.tiles = tiles; g.stamps = gm.stamps; g.debug = gm.debug; g.grid = gm.grid; g.ln_off = 0;
+    const size_t epi_bytes = (size_t)4 * TM * 32 * (32 * (res ? 4 : sizeof(T)) + 16);
+    const size_t lds = std::max((size_t)2 * (k4 ? SH4::STAGE_BYTES : SH7::STAGE_BYTES), epi_bytes);
+    *launched = true;
+    if (k4) {
+      if (res) return launch_lean_kernel<T, TM, LEAN_K4S2, false, LEAN_EPI_RES, false>(a, g, lds, s);
+      if (sk) return launch_lean_kernel<T, TM, LEAN_K4S2, false, LEAN_EPI_PLAIN, true>(a, g, lds, s);
+      return launch_lean_kernel<T, TM, LEAN_K4S2, false, LEAN_EPI_PLAIN, false>(a, g, lds, s);
+    }
+    if (res) return launch_lean_kernel<T, TM, LEAN_K7, false, LEAN_EPI_RES, false>(a, g, lds, s);
+    return launch_lean_kernel<T, TM, LEAN_K7, false, LEAN_EPI_PLAIN, false>(a, g, lds, s);
   } else {
     constexpr bool K3 = TG == 3;
     const ConvTune* tn = a.tune;

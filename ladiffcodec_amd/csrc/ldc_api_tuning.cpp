@@ -473,7 +473,11 @@ extern "C" int ldc_profile_read(ldc_ctx* c, double* conv_ms_total, int64_t* conv
   return LDC_OK;
 }
 
-namespace ldc { extern unsigned long long* g_conv_stamps; }
+namespace ldc { extern unsigned long long* g_conv_stamps; extern long long g_lean_launches[8]; }
+
+extern "C" long long ldc_debug_lean_launches(int kind) {
+  return kind >= 0 && kind < 8 ? __atomic_load_n(&ldc::g_lean_launches[kind], __ATOMIC_RELAXED) : -1;
+}
 
 // uniform [-1, 1) values of the given dtype (host LCG, uploaded)
 static int fill_random(void* dev, size_t n, int dt, unsigned seed) {

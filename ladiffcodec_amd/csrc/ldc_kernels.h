@@ -67,6 +67,7 @@ struct ConvTune {
   int force_tile = -1;          // self-check / tuning: 0 = 64x64, 1 = 128x64 tiles wherever the layer's N allows
   int xcd_order = 1;            // round 6: lean kernel's dispatch order as an xm x xn arrangement of the XCDs chosen by operand bytes (conv_lean.inc: lean_xcd_order); 0 = conv_fast_body's order; 2 / 4 / 8 = xn forced
   int lean = 1;                 // round 6: the instruction-diet kernel (conv_lean.inc) where its shapes allow; 0 = conv_fast_kernel everywhere (LDC_CONV_LEAN)
+  int lean_all = 1;             // round 7: also the stride-2 downsamples (k = 4) and init_conv (k = 7) of the bf16 engine on it; 0 = conv_fast_kernel for those (A/B)
 };
 
 struct ConvCall {

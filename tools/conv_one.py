@@ -1,4 +1,6 @@
-"""Launch one conv-GEMM shape repeatedly (for rocprofv3 --pmc).  Usage: python tools/conv_one.py L cin1 cin2 cout k stride ups [iters] [dtype]"""
+"""Launch one conv-GEMM shape repeatedly (for rocprofv3 --pmc).  Usage: python tools/conv_one.py L cin1 cin2 cout k stride ups [iters] [dtype]
+or python tools/conv_one.py NAME [iters] [dtype] for a launch of the bench grid by name (NAMED below: the stride-2 downsamples, init_conv's x half
+and the folded-upsampling convs; LDC_OPTIONS=lean_all=0 keeps the k = 4 / k = 7 ones on conv_fast_kernel, conv_lean=0 all of them)."""
 import ctypes as C
 import os
 import sys
@@ -7,9 +9,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from ladiffcodec_amd import lib as L  # noqa: E402
 
-Lx, c1, c2, co, k, st, ups = (int(v) for v in sys.argv[1:8])
-iters = int(sys.argv[8]) if len(sys.argv) > 8 else 10
-dtype = sys.argv[9] if len(sys.argv) > 9 else "bf16"
+# name -> (input L, cin1, cin2, cout, k, stride, ups)
+NAMED = {
+    "down_256_600": (1200, 256, 0, 256, 4, 2, 0), "down_512_300": (600, 256, 0, 512, 4, 2, 0), "down_512_150": (300, 512, 0, 512, 4, 2, 0),
+    "down_1024_75": (150, 512, 0, 1024, 4, 2, 0), "init_x": (1200, 128, 0, 256, 7, 1, 0),
+    "up_1024_150": (75, 1024, 0, 1024, 3, 1, 1), "up_512_300": (150, 1024, 0, 512, 3, 1, 1), "up_512_600": (300, 512, 0, 512, 3, 1, 1),
+    "up_256_1200": (600, 512, 0, 256, 3, 1, 1),
+}
+args = sys.argv[1:]
+if args and args[0] in NAMED:
+    args = [str(v) for v in NAMED[args[0]]] + args[1:]
+Lx, c1, c2, co, k, st, ups = (int(v) for v in args[:7])
+iters = int(args[7]) if len(args) > 7 else 10
+dtype = args[8] if len(args) > 8 else "bf16"
 Bn = int(os.environ.get("LDC_B", "32"))
 lib = L.load()
 cfg = L.LdcConfig()
