@@ -345,6 +345,10 @@ int ldc_pool_evict(ldc_pool* pool, int slot);                                 /*
  * the latent chunk quantum lcm(up, 2^halvings), the fp8 engine, and what ldc_denoise / ldc_ddim_sample / ldc_decode refuse.
  * A windows plan is one batch part on one stream whatever `split` says; its cache key holds (Ltot, Lw, overlap), so its step graphs are
  * its own.  Warm calls allocate nothing and never synchronise the device.
+ * ldc_window_layout_n: ldc_window_layout for up to max_windows (<= 128) windows, starts_out [max_windows]; bit-identical to it for
+ * W <= 32.  ldc_window_parts: P_eff = min(parts, W) and the range starts first_out [parts + 1] of W windows (W <= 32 parts) cut into
+ * `parts` (<= 4) contiguous batch parts, part p holding [floor(p W / P_eff), floor((p + 1) W / P_eff)).  Both host-only; they lay the
+ * ground for a windows call in batch parts, which no call with a context offers yet.
  * DPM-Solver++(2M) on windows (ldc_dpm_sample_windows, ldc_decode_dpm_windows, ldc_decode_codes_dpm_windows): iteration j blends the
  * windows' eps as above and applies the update documented at ldc_dpm_schedule to the ONE state with ONE history x0_{j-1} [1,C,Ltot] (not
  * one per window), which lives with the windows plan.  Nothing is drawn and the noise epoch stays where it is; the steps replay graphs
@@ -357,6 +361,8 @@ int ldc_pool_evict(ldc_pool* pool, int slot);                                 /*
  * Not available: decode pools, batch parts, more than 32 windows or several recordings per call, ragged variants.  Nothing here is a
  * claim about perceived quality. */
 int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out /*[32]*/, float* weights_out /*[W*Lw] or NULL*/);
+int ldc_window_layout_n(int Ltot, int Lw, int overlap, int up, int max_windows, int* starts_out /*[max_windows]*/, float* weights_out /*[W*Lw] or NULL*/);
+int ldc_window_parts(int W, int parts, int* first_out /*[parts + 1]*/);
 /* the blended eps of one UNet pass at timestep t: x [1,C,Ltot], cond [1,Cc,Ftot] (raw), eps_out [1,C,Ltot] */
 int ldc_unet_forward_windows(ldc_ctx* ctx, const float* x, int t, const float* cond, int Ltot, int Ftot, int Lw, int overlap,
                              float* eps_out, void* stream);

@@ -3411,61 +3411,43 @@ extern "C" int ldc_decode_codes_dpm(ldc_ctx* c, const int64_t* codes, const uint
 // ---- coupled windows: a recording longer than the UNet's window, decoded on ONE shared latent ---------------------
 // The W overlapping windows of the recording are the items of an ordinary equal-length batch; after every UNet pass their eps are blended
 // per global frame and the recording's single fp32 state is updated from the blend (windows_update_kernel, in place of the update launch).
-struct WinLayout {
-  int Ltot = 0, Lw = 0, O = 0, W = 0;
-  std::vector<int> start, cover;   // cover[g] = first covering window | count << 8
-  std::vector<float> weight;       // [W][Lw]
-};
-static constexpr int kMaxWindows = 32;
-
+// (the builders are the pure functions of ldc_windows.h: WinLayout, win_layout_build, win_parts_split, win_ptr_tables)
 // the layout, the cover table and the weights (double, rounded once to float) of (Ltot, Lw, overlap); every refusal names its value
-static int window_layout(int Ltot, int Lw, int O, int up, WinLayout* out) {
-  if (up < 1) return fail(LDC_E_INVALID, "up %d: the latent frames per condition frame must be >= 1", up);
-  if (Ltot <= 0 || Ltot % up) return fail(LDC_E_INVALID, "Ltot %d: must be a positive multiple of up = %d", Ltot, up);
-  if (Lw <= 0 || Lw % up) return fail(LDC_E_INVALID, "Lw %d: must be a positive multiple of up = %d", Lw, up);
-  if (O < 0 || O % up || O > Lw / 2) return fail(LDC_E_INVALID, "overlap %d: must be a multiple of up = %d in [0, Lw / 2 = %d]", O, up, Lw / 2);
-  if (Ltot <= Lw) Lw = Ltot;   // one window: the recording itself
-  const int H = Lw - O;
-  const long long W = Ltot <= Lw ? 1 : 1 + ((long long)(Ltot - Lw) + H - 1) / H;
-  if (W > kMaxWindows) return fail(LDC_E_INVALID, "Ltot %d needs %lld windows of %d frames at overlap %d: at most %d per call", Ltot, W, Lw, O, kMaxWindows);
-  out->Ltot = Ltot; out->Lw = Lw; out->O = O; out->W = (int)W;
-  out->start.assign((size_t)W, 0);
-  for (int k = 0; k < W; ++k) out->start[k] = (int)std::min<long long>((long long)k * H, Ltot - Lw);   // the last window is right-aligned
-  std::vector<double> u((size_t)W * Lw);
-  for (int k = 0; k < W; ++k) {
-    const int Rl = k > 0 ? out->start[k - 1] + Lw - out->start[k] : 0, Rr = k + 1 < W ? out->start[k] + Lw - out->start[k + 1] : 0;
-    for (int l = 0; l < Lw; ++l) {
-      double v = 1.0;
-      if (Rl > 0) v = std::min(v, (l + 0.5) / Rl);
-      if (Rr > 0) v = std::min(v, (Lw - l - 0.5) / Rr);
-      u[(size_t)k * Lw + l] = v;
-    }
-  }
-  out->cover.assign((size_t)Ltot, 0);
-  out->weight.assign((size_t)W * Lw, 0.f);
-  int first = 0;
-  for (int g = 0; g < Ltot; ++g) {
-    while (out->start[first] + Lw <= g) ++first;   // (starts ascend, so the covering windows are consecutive from here)
-    int n = 0;
-    double sum = 0.0;
-    while (first + n < W && out->start[first + n] <= g) { sum += u[(size_t)(first + n) * Lw + (g - out->start[first + n])]; ++n; }
-    if (n < 1 || n > 3) return fail(LDC_E_STATE, "internal: frame %d is covered by %d windows", g, n);
-    out->cover[g] = first | (n << 8);
-    for (int j = 0; j < n; ++j) {
-      const size_t i = (size_t)(first + j) * Lw + (g - out->start[first + j]);
-      out->weight[i] = (float)(u[i] / sum);
-    }
-  }
+static int window_layout(int Ltot, int Lw, int O, int up, int max_windows, WinLayout* out) {
+  std::string err;
+  const int rc = win_layout_build(Ltot, Lw, O, up, max_windows, out, &err);
+  if (rc) return fail(rc == 1 ? LDC_E_INVALID : LDC_E_STATE, "%s", err.c_str());
   return LDC_OK;
 }
 
 extern "C" int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out, float* weights_out) {
   WinLayout lay;
-  LDCCHK(window_layout(Ltot, Lw, overlap, up, &lay));
+  LDCCHK(window_layout(Ltot, Lw, overlap, up, kWinPerPart, &lay));
   if (starts_out)
-    for (int k = 0; k < kMaxWindows; ++k) starts_out[k] = k < lay.W ? lay.start[k] : 0;
+    for (int k = 0; k < kWinPerPart; ++k) starts_out[k] = k < lay.W ? lay.start[k] : 0;
   if (weights_out) std::copy(lay.weight.begin(), lay.weight.end(), weights_out);
   return lay.W;
+}
+
+// ldc_window_layout for up to max_windows (<= 128) windows: starts_out [max_windows], zero behind W.  For W <= 32 it is
+// ldc_window_layout bit for bit -- one builder serves both.  Host-only: needs no context.  (The calls with a context take 32 windows.)
+extern "C" int ldc_window_layout_n(int Ltot, int Lw, int overlap, int up, int max_windows, int* starts_out, float* weights_out) {
+  WinLayout lay;
+  LDCCHK(window_layout(Ltot, Lw, overlap, up, max_windows, &lay));
+  if (starts_out)
+    for (int k = 0; k < max_windows; ++k) starts_out[k] = k < lay.W ? lay.start[k] : 0;
+  if (weights_out) std::copy(lay.weight.begin(), lay.weight.end(), weights_out);
+  return lay.W;
+}
+
+// The partition of W windows into `parts` batch parts of contiguous windows: returns P_eff = min(parts, W) and writes first_out
+// [parts + 1], the range starts (part p holds the windows [first_out[p], first_out[p + 1]); entries behind P_eff are W).  Host-only.
+extern "C" int ldc_window_parts(int W, int parts, int* first_out) {
+  if (!first_out) return fail(LDC_E_INVALID, "null output");
+  if (W < 1 || W > kMaxWindows) return fail(LDC_E_INVALID, "W %d: must be in [1, %d]", W, kMaxWindows);
+  if (parts < 1 || parts > kMaxParts) return fail(LDC_E_INVALID, "parts %d: must be in [1, %d]", parts, kMaxParts);
+  if (W > kWinPerPart * parts) return fail(LDC_E_INVALID, "W %d: %d part(s) hold at most %d windows", W, parts, kWinPerPart * parts);
+  return win_parts_split(W, parts, first_out);
 }
 
 // everything a windows call refuses, before any GPU work; then the plan of the layout (made on its first use: the recording's state and
@@ -3477,7 +3459,7 @@ static int windows_prepare(ldc_ctx* c, int Ltot, int Ftot, int Lw, int O, hipStr
     return fail(LDC_E_INVALID, "Ltot (%d) must equal Ftot (%d) x prod(upsampling_ratios) (%d)", Ltot, Ftot, up);
   if (Ltot > Lw && (Lw <= 0 || Lw % q)) return fail(LDC_E_INVALID, "Lw %d: a window must be a positive multiple of %d latent frames (the chunk quantum)", Lw, q);
   WinLayout lay;
-  LDCCHK(window_layout(Ltot, Lw, O, up, &lay));
+  LDCCHK(window_layout(Ltot, Lw, O, up, kWinPerPart, &lay));
   *h = Halves();
   c->call_tick = c->use_tick;
   Plan* pl = nullptr;

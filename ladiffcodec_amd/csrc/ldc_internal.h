@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "ldc_kernels.h"
+#include "ldc_windows.h"
 
 // Every device-wide synchronisation of the library goes through this counter (ldc_debug_sync_count): the steady state of the
 // decode path -- plans built, graphs captured -- must issue none (tests/test_gpu_parity.py: test_warm_decode_never_waits_for_the_device)
@@ -235,6 +236,7 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
 // A batch is decoded as (up to) two independent halves on two streams: utterances do not interact inside
 // the UNet, so the halves' kernels overlap and fill each other's tails and launch gaps.
 static constexpr int kMaxParts = 4;
+static_assert(kMaxParts == kWinMaxParts, "ldc_windows.h sizes the windows cap by the number of batch parts");
 struct Halves {                // (the name dates from the two-way split; n parts, n <= kMaxParts)
   int n = 0;
   Plan* p[kMaxParts] = {nullptr, nullptr, nullptr, nullptr};

@@ -24,7 +24,7 @@ EXPORTS = [
     "ldc_seanet_encode", "ldc_seanet_decode", "ldc_rvq_encode", "ldc_rvq_decode", "ldc_get_cond",
     "ldc_cond_upsample", "ldc_unet_forward", "ldc_p_sample", "ldc_denoise", "ldc_p_sample_loop", "ldc_infilling", "ldc_output_normalise", "ldc_decode", "ldc_ddim_times", "ldc_ddim_sample", "ldc_decode_ddim", "ldc_decode_codes", "ldc_decode_codes_ddim",
     "ldc_dpm_schedule", "ldc_dpm_sample", "ldc_decode_dpm", "ldc_decode_codes_dpm", "ldc_decode_ragged_dpm",
-    "ldc_window_layout", "ldc_unet_forward_windows", "ldc_denoise_windows", "ldc_ddim_sample_windows", "ldc_decode_windows", "ldc_decode_ddim_windows",
+    "ldc_window_layout", "ldc_window_layout_n", "ldc_window_parts", "ldc_unet_forward_windows", "ldc_denoise_windows", "ldc_ddim_sample_windows", "ldc_decode_windows", "ldc_decode_ddim_windows",
     "ldc_dpm_sample_windows", "ldc_decode_dpm_windows", "ldc_decode_codes_windows", "ldc_decode_codes_dpm_windows",
     "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
     "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
@@ -121,6 +121,8 @@ def load() -> C.CDLL:
     lib.ldc_decode_codes_dpm.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp]
     lib.ldc_decode_ragged_dpm.argtypes = [vp, fp, C.POINTER(C.c_int32), i32, i32, i32, i32, fp, fp, fp, vp, vp]
     lib.ldc_window_layout.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.ldc_window_layout_n.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.ldc_window_parts.argtypes = [i32, i32, C.POINTER(C.c_int)]
     lib.ldc_unet_forward_windows.argtypes = [vp, fp, i32, fp, i32, i32, i32, i32, fp, vp]
     lib.ldc_denoise_windows.argtypes = [vp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
     lib.ldc_ddim_sample_windows.argtypes = [vp, fp, fp, fp, i32, i32, C.c_float, i32, i32, i32, i32, vp]
@@ -240,17 +242,37 @@ def ddim_times(t_start: int, n_steps: int):
     return list(out)
 
 
-def window_layout(Ltot: int, Lw: int, overlap: int, up: int):
-    """The coupled-windows layout of ldc_window_layout (host-only): -> (starts [W] list, weights [W, Lw'] float32), Lw' = min(Lw, Ltot)."""
+def window_layout(Ltot: int, Lw: int, overlap: int, up: int, max_windows: int = 32):
+    """The coupled-windows layout of ldc_window_layout (host-only): -> (starts [W] list, weights [W, Lw'] float32), Lw' = min(Lw, Ltot).
+    max_windows other than 32 (up to 128: the layouts of a call in batch parts, 32 windows per part) goes through ldc_window_layout_n;
+    the engine's own calls take 32 windows."""
     import numpy as np
-    starts = (C.c_int * 32)()
-    W = load().ldc_window_layout(int(Ltot), int(Lw), int(overlap), int(up), starts, None)
+    lib = load()
+    max_windows = int(max_windows)
+    if max_windows == 32:
+        def call(starts, weights):
+            return lib.ldc_window_layout(int(Ltot), int(Lw), int(overlap), int(up), starts, weights)
+    else:
+        def call(starts, weights):
+            return lib.ldc_window_layout_n(int(Ltot), int(Lw), int(overlap), int(up), max_windows, starts, weights)
+    starts = (C.c_int * max(32, max_windows))()
+    W = call(starts, None)
     if W < 0:
         check(W)
     lw = min(int(Lw), int(Ltot))
     weights = (C.c_float * (W * lw))()
-    check(min(0, load().ldc_window_layout(int(Ltot), int(Lw), int(overlap), int(up), starts, weights)))
+    check(min(0, call(starts, weights)))
     return list(starts)[:W], np.array(weights, dtype=np.float32).reshape(W, lw)
+
+
+def window_parts(W: int, parts: int):
+    """W windows cut into min(parts, W) contiguous batch parts (ldc_window_parts, host-only): -> the P_eff + 1 range starts;
+    part p holds the windows [first[p], first[p + 1])."""
+    first = (C.c_int * (max(1, int(parts)) + 1))()
+    p_eff = load().ldc_window_parts(int(W), int(parts), first)
+    if p_eff < 0:
+        check(p_eff)
+    return list(first)[:p_eff + 1]
 
 
 def dpm_schedule(sqrt_recip, sqrt_recipm1, t_start: int, n_steps: int):
