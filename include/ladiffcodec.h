@@ -358,8 +358,23 @@ int ldc_pool_evict(ldc_pool* pool, int slot);                                 /*
  * condition frames -- quantizer.decode(codes), the start image normalised over the whole recording, per-window condition slices, the
  * coupled loop, the decoder over the whole latent.  For the codes ldc_decode_windows returns, cond_out is bit-identical to its cond_out.
  * Sources, packed layout and the "[bad_code]" refusal are those of ldc_decode_codes at B = 1, F = Ftot.
- * Not available: decode pools, batch parts, more than 32 windows or several recordings per call, ragged variants.  Nothing here is a
- * claim about perceived quality. */
+ * Window groups (the *_windows_group entries): R >= 1 recordings in one call, the windows of all of them -- W_sum = sum W_r <= 32 -- the
+ * items of ONE equal-length batch at (B = W_sum, L = Lw, F = Lw / up).  Recording r keeps the layout ldc_window_layout(Ltot_r, Lw,
+ * overlap, up) gives it alone, its windows take the batch items w0_r .. w0_r + W_r - 1 (w0_r = sum_{q<r} W_q) in recording order, its own
+ * fp32 state, noise and (DPM) x0 history, and its eps are blended from its own windows only; the timestep and the schedule are the
+ * call's.  Each recording comes out as the single-recording call gives it alone.  Packed tensors: with off_r = sum_{q<r} Ltot_q and Lsum
+ * = sum Ltot_r, the state, eps_out and every step of a tape [n_steps][C * Lsum] hold recording r's [C][Ltot_r] block at float offset
+ * C * off_r (inside a block: the B = 1, L = Ltot_r layout); the raw condition holds [Cc][Ftot_r] at Cc * off_r / up; waveforms lie one
+ * behind the other, codes_out holds [n_q][Ftot_r] blocks.  Ltot, Ftot, T and seeds are HOST arrays of R entries.  Noise: a tape, or Philox
+ * with seeds[R] -- recording r draws what ldc_denoise_windows / ldc_ddim_sample_windows draws for it alone right after
+ * ldc_reseed(seeds[r]) (key seeds[r], epoch 0).  A group call never reads or advances the context's noise epoch; a sampler that draws with
+ * neither a tape nor seeds is refused; DPM takes neither.  Refused besides what the single-recording calls refuse: R outside [1, 32], a
+ * recording shorter than Lw (index and value named: it would shrink the window and break the equal-length batch), W_sum > 32 (the sum
+ * named).  An R = 1 group is the single-recording call, a group of R one-window recordings an ordinary B = R batch.  The group's plan and
+ * step graphs are keyed by the ORDERED list of lengths, Lw and overlap: neither a single-recording call nor a group of other lengths
+ * replays them.  One part on one stream whatever `split` says; warm calls allocate nothing and never synchronise the device.
+ * Not available: decode pools, batch parts, more than 32 windows per call, ragged window lengths; for window groups also the receiver
+ * (decoding from codes) and the fp8 engine.  Nothing here is a claim about perceived quality. */
 int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out /*[32]*/, float* weights_out /*[W*Lw] or NULL*/);
 int ldc_window_layout_n(int Ltot, int Lw, int overlap, int up, int max_windows, int* starts_out /*[max_windows]*/, float* weights_out /*[W*Lw] or NULL*/);
 int ldc_window_parts(int W, int parts, int* first_out /*[parts + 1]*/);
@@ -394,6 +409,23 @@ int ldc_decode_codes_windows(ldc_ctx* ctx, const int64_t* codes, const uint8_t* 
 int ldc_decode_codes_dpm_windows(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
                                  int Ftot, int t_start, int n_steps, int Lw, int overlap, float* wav_out, float* latents_out,
                                  float* cond_out, void* stream);
+/* Window groups.  ldc_window_group_layout (host-only): w0_out [R + 1], starts_out [32] in each recording's own frames (zero behind
+ * W_sum), weights_out [W_sum][Lw] or NULL; returns W_sum. */
+int ldc_window_group_layout(int R, const int* Ltot /*[R]*/, int Lw, int overlap, int up, int* w0_out /*[R + 1]*/, int* starts_out /*[32]*/,
+                            float* weights_out /*[W_sum*Lw] or NULL*/);
+/* ldc_unet_forward_windows of every recording in one UNet pass: x, eps_out packed [C][Ltot_r] blocks, cond packed [Cc][Ftot_r] blocks */
+int ldc_unet_forward_windows_group(ldc_ctx* ctx, const float* x, int t, const float* cond, int R, const int* Ltot /*[R]*/,
+                                   const int* Ftot /*[R]*/, int Lw, int overlap, float* eps_out, void* stream);
+/* sampler 0: ldc_denoise_windows (t_start, eta unused); 1: ldc_ddim_sample_windows; 2: ldc_dpm_sample_windows (eta, noise, seeds unused)
+ * of every recording in one loop; refusals of that call in its order.  img_inout, cond and noise [n_steps][C * Lsum] packed. */
+int ldc_sample_windows_group(ldc_ctx* ctx, float* img_inout, const float* cond, int sampler, int t_start, int n_steps, float eta,
+                             const float* noise, const uint64_t* seeds /*[R] or NULL*/, int R, const int* Ltot /*[R]*/,
+                             const int* Ftot /*[R]*/, int Lw, int overlap, void* stream);
+/* ldc_decode_windows / _ddim_windows / _dpm_windows of every recording with ONE loop; the codec ends run per recording (get_cond, the
+ * start image normalised over that recording, the decoder, output normalisation).  wav, wav_out: T[r] samples each, one behind the other. */
+int ldc_decode_windows_group(ldc_ctx* ctx, const float* wav, int R, const int* T /*[R]*/, int sampler, int t_start, int n_steps, float eta,
+                             const float* noise, const uint64_t* seeds /*[R] or NULL*/, int Lw, int overlap, float* wav_out,
+                             float* latents_out, float* cond_out, int64_t* codes_out, void* stream);
 
 /* The decode of ldc_decode / ldc_decode_ddim started from RVQ codes instead of a waveform (the receiver side):
  * quantizer.decode(codes) -> upsample, /= max|.| -> sampling -> decoder -> output normalisation.

@@ -767,6 +767,288 @@ hipError_t launch_windows_dpm_update(int dt, float* x, const void* eps_cl, float
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Window groups ("Several recordings per call"): the windows of R recordings are the items of ONE batch, every
+// recording keeps its own fp32 state block, cover rows, noise and Philox key.  Sibling kernels of windows_update_kernel /
+// windows_dpm_update_kernel (whose instantiations stay as they are): the same 32 x 32 tiling, walked over a host-built TILE TABLE --
+// blockIdx.x -> {recording, l0}, a recording owns ceil(Ltot_r / 32) tiles, so the recording of a tile is uniform over the workgroup
+// and its table entry arrives through scalar loads.  Inside its recording a tile does what the single-recording kernel does at
+// (Ltot_r, the recording's cover rows): the cover entry counts windows WITHIN the recording, the kernel adds w0_r; x, the eps output,
+// the history and the tape are packed, recording r's [C][Ltot_r] block at C * off_r floats, so the tape index and the Philox block
+// of an element are those of the B = 1, L = Ltot_r call.  Frames of a recording's last tile at or behind Ltot_r have count 0: they
+// blend nothing and are stored nowhere.  One writer per element of every window row, no atomics.
+// Load order: tile entry -> recording entry -> cover -> (start, weight, eps) and x do not depend on the step and are issued before the
+// step state -> coefficient-table chain.  LDS: tile[32][33] fp32, conflict-free as above.  All offsets size_t.
+// ---------------------------------------------------------------------------------------------
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void windows_group_update_kernel(float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
+                                                                   void* x_cl, float* ebar, int C, WinGroupTables gt, StepTables tb,
+                                                                   const DdimStep* sched, const int* st) {
+  __shared__ float tile[32][33];
+  const WinGroupTile te = gt.tile[blockIdx.x];
+  const WinGroupRec rc = gt.rec[te.rec];
+  const int c0 = blockIdx.y * 32, l0 = te.l0;
+  const int Ltot = rc.Ltot, Lw = gt.Lw, w0 = rc.w0;
+  const size_t xo = (size_t)C * rc.off;   // the recording's block of x / ebar / the tape
+  const int* cover = gt.cover + rc.cover_off;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  int cov[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int g = l0 + ty + ii * 8;
+    cov[ii] = g < Ltot ? cover[g] : 0;   // (count 0: a frame behind the recording's end blends nothing and is stored nowhere)
+  }
+  float ev[4], xin[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = w0 + (cov[ii] & 255), n = cov[ii] >> 8;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < n && c < C) {
+        const int k = first + j, l = g - gt.start[k];
+        const float we = gt.weight[(size_t)k * Lw + l] * dld<T>(eps_cl, ((size_t)k * Lw + l) * C + c);
+        acc = j == 0 ? we : acc + we;
+      }
+    ev[ii] = acc;
+    const int cc = c0 + i, ll = l0 + tx;
+    xin[ii] = (KIND != WIN_BLEND && cc < C && ll < Ltot) ? x[xo + (size_t)cc * Ltot + ll] : 0.f;
+  }
+  int t = 0, j = 0;
+  float recip = 0.f, recipm1 = 0.f, c1 = 0.f, c2 = 0.f, sigma = 0.f;
+  DdimStep sp{};
+  bool draw = false;
+  if (KIND != WIN_BLEND) {
+    t = st[0]; j = st[1];
+    if (KIND == WIN_DDIM) { sp = sched[j]; t = sp.t; }
+    recip = tb.sqrt_recip_alphas_cumprod[t]; recipm1 = tb.sqrt_recipm1_alphas_cumprod[t];
+    if (KIND == WIN_DDPM) {
+      c1 = tb.posterior_mean_coef1[t]; c2 = tb.posterior_mean_coef2[t];
+      sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
+      draw = t > 0;
+    } else {
+      sigma = sp.sigma;
+      draw = !sp.last && sp.sigma > 0.f;
+    }
+  }
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
+  __syncthreads();
+  if (KIND == WIN_BLEND) {
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+      const int i = ty + ii * 8;
+      const int c = c0 + i, g = l0 + tx;
+      if (c < C && g < Ltot) ebar[xo + (size_t)c * Ltot + g] = tile[tx][i];
+    }
+    return;
+  }
+  float newv[4];
+  // one Philox block per thread under the RECORDING's key at the index of its first element in the B = 1, L = Ltot_r layout
+  float zz[4] = {0.f, 0.f, 0.f, 0.f};
+  if (draw && !noise) philox_normal4(((uint64_t)rc.key_hi << 32) | (uint64_t)rc.key_lo, (unsigned)j, (uint64_t)(c0 + ty) * Ltot + l0 + tx, zz);
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int c = c0 + i, g = l0 + tx;
+    newv[ii] = 0.f;
+    if (c < C && g < Ltot) {
+      const size_t idx = xo + (size_t)c * Ltot + g;
+      const float e = tile[tx][i];
+      float v = KIND == WIN_DDPM ? p_sample_mean(recip, recipm1, c1, c2, xin[ii], e) : ddim_mean(sp, recip, recipm1, xin[ii], e);
+      if (draw) v += sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);
+      x[idx] = v;
+      newv[ii] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][g]
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = w0 + (cov[ii] & 255), n = cov[ii] >> 8;
+    const float v = tile[tx][i];
+#pragma unroll
+    for (int jj = 0; jj < 3; ++jj)
+      if (jj < n && c < C) {
+        const int k = first + jj, l = g - gt.start[k];
+        dst<T>(x_cl, ((size_t)k * Lw + l) * C + c, v);
+      }
+  }
+}
+
+static bool win_group_tables_ok(const WinGroupTables& gt) {
+  return gt.n_tiles > 0 && gt.R > 0 && gt.Lw > 0 && gt.tile && gt.rec && gt.cover && gt.weight && gt.start && gt.wrec;
+}
+
+template <typename T>
+static hipError_t launch_windows_group_update_t(int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
+                                                float* ebar, int C, WinGroupTables gt, StepTables tb, const DdimStep* sched, const int* st,
+                                                hipStream_t s) {
+  dim3 grid(gt.n_tiles, (C + 31) / 32, 1);
+  if (kind == WIN_BLEND)
+    hipLaunchKernelGGL((windows_group_update_kernel<T, WIN_BLEND>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, gt, tb, sched, st);
+  else if (kind == WIN_DDPM)
+    hipLaunchKernelGGL((windows_group_update_kernel<T, WIN_DDPM>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, gt, tb, sched, st);
+  else
+    hipLaunchKernelGGL((windows_group_update_kernel<T, WIN_DDIM>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, gt, tb, sched, st);
+  return hipGetLastError();
+}
+hipError_t launch_windows_group_update(int dt, int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
+                                       float* ebar, int C, WinGroupTables gt, StepTables tb, const DdimStep* sched, const int* st, hipStream_t s) {
+  if (kind != WIN_BLEND && kind != WIN_DDPM && kind != WIN_DDIM) return hipErrorInvalidValue;
+  if (!win_group_tables_ok(gt) || !eps_cl || C <= 0 || (kind == WIN_DDIM && !sched)) return hipErrorInvalidValue;
+  if (kind == WIN_BLEND ? !ebar : (!x || !x_cl || !st)) return hipErrorInvalidValue;
+  if (dt == DT_F32) return launch_windows_group_update_t<float>(kind, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, gt, tb, sched, st, s);
+  return launch_windows_group_update_t<__bf16>(kind, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, gt, tb, sched, st, s);
+}
+
+// WIN_DPM of a window group: windows_dpm_update_kernel over the tile table, the history x0_prev packed like x.  The history's load
+// follows st -> row (has_prev) and is issued in front of the row -> coefficient-table loads, as in the single-recording kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void windows_group_dpm_update_kernel(float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C,
+                                                                       WinGroupTables gt, StepTables tb, const DpmStep* sched, const int* st) {
+  __shared__ float tile[32][33];
+  const WinGroupTile te = gt.tile[blockIdx.x];
+  const WinGroupRec rc = gt.rec[te.rec];
+  const int c0 = blockIdx.y * 32, l0 = te.l0;
+  const int Ltot = rc.Ltot, Lw = gt.Lw, w0 = rc.w0;
+  const size_t xo = (size_t)C * rc.off;
+  const int* cover = gt.cover + rc.cover_off;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  int cov[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int g = l0 + ty + ii * 8;
+    cov[ii] = g < Ltot ? cover[g] : 0;
+  }
+  float ev[4], xin[4], pv[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = w0 + (cov[ii] & 255), n = cov[ii] >> 8;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < n && c < C) {
+        const int k = first + j, l = g - gt.start[k];
+        const float we = gt.weight[(size_t)k * Lw + l] * dld<T>(eps_cl, ((size_t)k * Lw + l) * C + c);
+        acc = j == 0 ? we : acc + we;
+      }
+    ev[ii] = acc;
+    const int cc = c0 + i, ll = l0 + tx;
+    xin[ii] = (cc < C && ll < Ltot) ? x[xo + (size_t)cc * Ltot + ll] : 0.f;
+  }
+  const DpmStep sp = sched[st[1]];
+  const bool hist = !sp.last && sp.has_prev;   // (uniform over the grid) the only case in which the history is read
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int cc = c0 + ty + ii * 8, ll = l0 + tx;
+    pv[ii] = (hist && cc < C && ll < Ltot) ? x0_prev[xo + (size_t)cc * Ltot + ll] : 0.f;
+  }
+  const float recip = tb.sqrt_recip_alphas_cumprod[sp.t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[sp.t];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
+  __syncthreads();
+  float newv[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int c = c0 + i, g = l0 + tx;
+    newv[ii] = 0.f;
+    if (c < C && g < Ltot) {
+      const size_t idx = xo + (size_t)c * Ltot + g;
+      const float x0 = clipped_x0(recip, recipm1, xin[ii], tile[tx][i]);
+      float v = x0;
+      if (!sp.last) {
+        v = sp.a * xin[ii] + sp.b0 * x0;
+        if (hist) v += sp.b1 * pv[ii];
+        x0_prev[idx] = x0;
+      }
+      x[idx] = v;
+      newv[ii] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][g]
+  __syncthreads();
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const int i = ty + ii * 8;
+    const int g = l0 + i, c = c0 + tx;
+    const int first = w0 + (cov[ii] & 255), n = cov[ii] >> 8;
+    const float v = tile[tx][i];
+#pragma unroll
+    for (int jj = 0; jj < 3; ++jj)
+      if (jj < n && c < C) {
+        const int k = first + jj, l = g - gt.start[k];
+        dst<T>(x_cl, ((size_t)k * Lw + l) * C + c, v);
+      }
+  }
+}
+
+hipError_t launch_windows_group_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WinGroupTables gt, StepTables tb,
+                                           const DpmStep* sched, const int* st, hipStream_t s) {
+  if (!win_group_tables_ok(gt)) return hipErrorInvalidValue;
+  if (!x || !eps_cl || !x0_prev || !x_cl || !sched || !st || C <= 0) return hipErrorInvalidValue;
+  dim3 grid(gt.n_tiles, (C + 31) / 32, 1);
+  if (dt == DT_F32) hipLaunchKernelGGL(windows_group_dpm_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, gt, tb, sched, st);
+  else hipLaunchKernelGGL(windows_group_dpm_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, gt, tb, sched, st);
+  return hipGetLastError();
+}
+
+// windows_gather_kernel with a per-item source: window k of the batch reads the block of ITS recording r = wrec[k] of a packed
+// [C][Ltot_r] sequence -- the block at C * (off_r / div) floats, rows of Ltot_r / div frames -- from start[k] / div
+// (div = up for the raw condition: its blocks are [Cc][Ftot_r] at Cc * off_r / up)
+template <typename T>
+__global__ __launch_bounds__(256) void windows_group_gather_kernel(const float* x, void* y, int C, int Lw, WinGroupTables gt, int div) {
+  __shared__ float tile[32][33];
+  const int k = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const WinGroupRec rc = gt.rec[gt.wrec[k]];
+  const int Lr = rc.Ltot / div, s0 = gt.start[k] / div;
+  const float* xr = x + (size_t)C * (rc.off / div);
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, l = l0 + tx;
+    tile[i][tx] = (c < C && l < Lw && s0 + l < Lr) ? xr[(size_t)c * Lr + s0 + l] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int l = l0 + i, c = c0 + tx;
+    if (l < Lw && c < C) dst<T>(y, ((size_t)k * Lw + l) * C + c, tile[tx][i]);
+  }
+}
+// y [W][Lw][C] dt <- the windows' slices of the packed x; Lw: the frames of a window of THIS sequence (the group's Lw / div)
+hipError_t launch_windows_group_gather(int dt, const float* x, void* y, int W, int C, int Lw, WinGroupTables gt, int div, hipStream_t s) {
+  if (W <= 0 || Lw <= 0 || C <= 0 || div < 1 || !x || !y || !win_group_tables_ok(gt)) return hipErrorInvalidValue;
+  dim3 grid((Lw + 31) / 32, (C + 31) / 32, W);
+  if (dt == DT_F32) hipLaunchKernelGGL(windows_group_gather_kernel<float>, grid, dim3(256), 0, s, x, y, C, Lw, gt, div);
+  else hipLaunchKernelGGL(windows_group_gather_kernel<__bf16>, grid, dim3(256), 0, s, x, y, C, Lw, gt, div);
+  return hipGetLastError();
+}
+
+// the recordings' Philox keys written on the stream (kernel arguments carry them, as launch_ddim_table_write's entries: no host buffer
+// outlives the call, a captured step graph takes the keys from memory)
+struct WinGroupKeys { uint64_t k[32]; };
+__global__ void windows_group_keys_kernel(WinGroupRec* rec, WinGroupKeys keys, int R) {
+  const int r = threadIdx.x;
+  if (r < R) { rec[r].key_lo = (unsigned)keys.k[r]; rec[r].key_hi = (unsigned)(keys.k[r] >> 32); }
+}
+hipError_t launch_windows_group_keys(WinGroupRec* rec, const uint64_t* keys_host, int R, hipStream_t s) {
+  if (!rec || R < 1 || R > 32) return hipErrorInvalidValue;
+  WinGroupKeys ks{};
+  for (int r = 0; r < R; ++r) ks.k[r] = keys_host ? keys_host[r] : 0;
+  hipLaunchKernelGGL(windows_group_keys_kernel, dim3(1), dim3(32), 0, s, rec, ks, R);
+  return hipGetLastError();
+}
+
 // the DPM schedule table written on the stream, as launch_ddim_table_write writes its table
 struct DpmChunk { DpmStep e[kDdimChunk]; };
 __global__ void dpm_table_write_kernel(DpmStep* dst, DpmChunk src, int n) {

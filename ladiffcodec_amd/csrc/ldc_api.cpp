@@ -1981,10 +1981,13 @@ static void evict_plan(ldc_ctx* c, size_t idx) {
   c->plans.erase(c->plans.begin() + idx);
 }
 
-int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id, int win_Ltot, int win_O) {
+int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id, int win_Ltot, int win_O,
+             const std::vector<int>* win_group) {
+  static const std::vector<int> no_group;
+  const std::vector<int>& wgl = win_group ? *win_group : no_group;   // a window group: the ORDERED list of its recordings' lengths is part of the key
   for (auto& p : c->plans)
     if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged && p->items == items && p->pool_id == pool_id &&
-        p->win_Ltot == win_Ltot && p->win_O == win_O) {
+        p->win_Ltot == win_Ltot && p->win_O == win_O && p->win_group.Ltot == wgl) {
       p->last_use = ++c->use_tick;
       *out = p.get();
       return LDC_OK;
@@ -1995,6 +1998,8 @@ int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** ou
   pl->pool_id = pool_id;
   pl->win_Ltot = win_Ltot;
   pl->win_O = win_O;
+  pl->win_group.Ltot = wgl;   // (the rest of the group's tables: windows_group_prepare)
+  if (win_group) pl->win_group_id = c->next_win_group_id++;
   {   // pass 1: what do the convs of this plan need as split-K workspace?
     Arena dry;
     LDCCHK(build_plan(c, pl.get(), dry, B, L, F));
@@ -2394,7 +2399,14 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
                              sm.kind == SAMPLER_DDIM ? sm.ddim : nullptr));
   }
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
-  if (pl->win_Ltot) {   // coupled windows: x is the recording's one state, the blend and the update are one launch (noise: the B = 1, L = Ltot tape)
+  if (pl->win_group_id) {   // a window group: the windows plan over R recordings -- x, the tape and the DPM history are packed, the keys are in the recording table
+    if (h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part");
+    if (sm.kind == SAMPLER_DPM)
+      HIPCHK(launch_windows_group_dpm_update(c->dt, x, pl->eps_cl, pl->x0_prev, pl->x_cl, c->unet.channels, pl->wg, c->sched, sm.dpm, pl->step_state, s));
+    else
+      HIPCHK(launch_windows_group_update(c->dt, sm.kind == SAMPLER_DDIM ? WIN_DDIM : WIN_DDPM, x, pl->eps_cl, noise, noise_stride, pl->x_cl, nullptr,
+                                         c->unet.channels, pl->wg, c->sched, sm.ddim, pl->step_state, s));
+  } else if (pl->win_Ltot) {   // coupled windows: x is the recording's one state, the blend and the update are one launch (noise: the B = 1, L = Ltot tape)
     if (h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part");
     if (sm.kind == SAMPLER_DPM)   // WIN_DPM: x0_prev is the recording's ONE history [C][Ltot] (ensure_windows_history)
       HIPCHK(launch_windows_dpm_update(c->dt, x, pl->eps_cl, pl->x0_prev, pl->x_cl, c->unet.channels, pl->win, c->sched, sm.dpm, pl->step_state, s));
@@ -2519,6 +2531,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   const bool strided = sm.kind != SAMPLER_DDPM;   // a strided schedule, DDIM or DPM: the graph lengths below are theirs alike
   const int L = h.p[0]->L, F = h.p[0]->F;
   const int wl = h.p[0]->win_Ltot, wo = h.p[0]->win_O;   // a coupled-windows plan: its own graphs, the noise tape of ONE item of wl frames
+  const int wg = h.p[0]->win_group_id;   // a window-group plan (wl: the frames of all its recordings): graphs of that plan alone
   const int64_t stride = wl ? (int64_t)c->unet.channels * wl : (int64_t)B * c->unet.channels * L;
   LDCCHK(set_steps(c, h, n_steps - 1, 0, s));   // (DDIM: t is overwritten from the table in every step's first kernel)
   if (c->profile || c->serial_parts || n_steps < 3) {
@@ -2531,7 +2544,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   const int rag = h.p[0]->ragged ? 1 : 0;   // the steps of ragged plans are graphs of their own, replayed for any set of lengths
   const int kind = sm.kind;   // a loop never replays another sampler's graph (DDPM, DDIM, DPM); all stay cached side by side
   for (auto& g : c->graphs)
-    if (g.B == B && g.L == L && g.F == F && g.sampler == kind && g.ragged == rag && g.pool_id == 0 && g.win_Ltot == wl && g.win_O == wo) sg = &g;
+    if (g.B == B && g.L == L && g.F == F && g.sampler == kind && g.ragged == rag && g.pool_id == 0 && g.win_Ltot == wl && g.win_O == wo && g.win_group == wg) sg = &g;
   if (!sg) {
     // graphs of shapes whose plans are gone were dropped with them (evict_plan); additionally keep at most 16 alive
     if (c->graphs.size() >= 16) {
@@ -2546,7 +2559,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     }
     c->graphs.push_back(StepGraph());
     sg = &c->graphs.back();
-    sg->B = B; sg->L = L; sg->F = F; sg->sampler = kind; sg->ragged = rag; sg->win_Ltot = wl; sg->win_O = wo;
+    sg->B = B; sg->L = L; sg->F = F; sg->sampler = kind; sg->ragged = rag; sg->win_Ltot = wl; sg->win_O = wo; sg->win_group = wg;
   }
   sg->last_use = ++c->use_tick;
   const bool par = parts_parallel(c, h);
@@ -3726,6 +3739,248 @@ extern "C" int ldc_decode_codes_dpm_windows(ldc_ctx* c, const int64_t* codes, co
   LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Ftot, &src, &T));
   LDCCHK(dpm_schedule(c, t_start, n_steps));
   return decode_windows_body(c, src, T, n_steps, SAMPLER_DPM, false, nullptr, Lw, overlap, wav_out, latents_out, cond_out, nullptr, stream);
+}
+
+// ---- window groups ("Several recordings per call"): R recordings, the windows of all of them in ONE batch -----------
+// Every recording keeps its own layout, fp32 state block, noise and (DPM) x0 history; its eps are blended from its own windows only.  The
+// timestep and the schedule are the call's.  x, eps, the history and every step of a tape are packed: recording r's [C][Ltot_r] block at
+// C * off_r floats (off_r: the frames of the recordings in front), the raw condition's [Cc][Ftot_r] block at Cc * off_r / up.
+static int window_group(int R, const int* Ltot, int Lw, int O, int up, WinGroup* out) {
+  std::string err;
+  const int rc = win_group_build(R, Ltot, Lw, O, up, out, &err);
+  if (rc) return fail(rc == 1 ? LDC_E_INVALID : LDC_E_STATE, "%s", err.c_str());
+  return LDC_OK;
+}
+
+// Host-only: w0_out [R + 1] (recording r's windows are the batch items w0_out[r] .. w0_out[r + 1] - 1), starts_out [32] in each
+// recording's own frames (zero behind W_sum), weights_out [W_sum][Lw] or null.  Returns W_sum.
+extern "C" int ldc_window_group_layout(int R, const int* Ltot, int Lw, int overlap, int up, int* w0_out, int* starts_out, float* weights_out) {
+  WinGroup g;
+  LDCCHK(window_group(R, Ltot, Lw, overlap, up, &g));
+  if (w0_out) std::copy(g.w0.begin(), g.w0.end(), w0_out);
+  if (starts_out)
+    for (int k = 0; k < kWinPerPart; ++k) starts_out[k] = k < g.W_sum ? g.start[k] : 0;
+  if (weights_out) std::copy(g.weight.begin(), g.weight.end(), weights_out);
+  return g.W_sum;
+}
+
+// what windows_prepare is to one recording: every refusal before any GPU work, then the group's plan -- the windows plan at B = W_sum with
+// the packed state, the tables, the recording table and the tile table in its one allocation (made and uploaded on its first use)
+static int windows_group_prepare(ldc_ctx* c, int R, const int* Ltot, const int* Ftot, int Lw, int O, hipStream_t s, Halves* h) {
+  if (c->w8) return fail(LDC_E_INVALID, "coupled windows are not available on the fp8 engine: use dtype bf16 or f32");
+  if (R < 1 || R > kWinPerPart) return fail(LDC_E_INVALID, "R %d: a window group holds 1 to %d recordings", R, kWinPerPart);
+  if (!Ltot || !Ftot) return fail(LDC_E_INVALID, "null list of lengths");
+  const int up = upsample_factor(c), q = ragged_latent_quantum(c);
+  bool longer = false;
+  for (int r = 0; r < R; ++r) {
+    if (Ltot[r] <= 0 || Ftot[r] <= 0 || (long long)Ftot[r] * up != Ltot[r])
+      return fail(LDC_E_INVALID, "recording %d: Ltot (%d) must equal Ftot (%d) x prod(upsampling_ratios) (%d)", r, Ltot[r], Ftot[r], up);
+    longer = longer || Ltot[r] > Lw;
+  }
+  if (longer && (Lw <= 0 || Lw % q)) return fail(LDC_E_INVALID, "Lw %d: a window must be a positive multiple of %d latent frames (the chunk quantum)", Lw, q);
+  WinGroup g;
+  LDCCHK(window_group(R, Ltot, Lw, O, up, &g));
+  *h = Halves();
+  c->call_tick = c->use_tick;
+  Plan* pl = nullptr;
+  LDCCHK(get_plan(c, g.W_sum, Lw, Lw / up, 0, s, &pl, false, false, 0, g.Lsum, O, &g.Ltot));
+  if (!pl->win_base) {
+    const int C = c->unet.channels;
+    auto pad = [](size_t n) { return (n + 255) / 256 * 256; };
+    const size_t nx = pad((size_t)C * g.Lsum * 4), nc = pad((size_t)g.Lsum * 4), nw = pad((size_t)g.W_sum * Lw * 4), ns = pad((size_t)g.W_sum * 4);
+    const size_t nr = pad((size_t)R * sizeof(WinGroupRec)), nt = pad(g.tile.size() * sizeof(WinGroupTile));
+    const size_t total = nx + nc + nw + 2 * ns + nr + nt;
+    void* base = nullptr;
+    hipError_t e = hipMalloc(&base, total);
+    if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the window group's state failed: %s", total, hipGetErrorString(e));
+    pl->win_base = base;
+    pl->win_x = (float*)base;
+    char* p = (char*)base + nx;
+    int* cover = (int*)p; p += nc;
+    float* weight = (float*)p; p += nw;
+    int* start = (int*)p; p += ns;
+    int* wrec = (int*)p; p += ns;
+    WinGroupRec* rec = (WinGroupRec*)p; p += nr;
+    WinGroupTile* tile = (WinGroupTile*)p;
+    pl->win_group = std::move(g);   // (the host copies stay alive with the plan: the upload is asynchronous)
+    const WinGroup& wg = pl->win_group;
+    HIPCHK(hipMemcpyAsync(cover, wg.cover.data(), wg.cover.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(weight, wg.weight.data(), wg.weight.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(start, wg.start.data(), wg.start.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(wrec, wg.wrec.data(), wg.wrec.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(rec, wg.rec.data(), wg.rec.size() * sizeof(WinGroupRec), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(tile, wg.tile.data(), wg.tile.size() * sizeof(WinGroupTile), hipMemcpyHostToDevice, s));
+    pl->wg = WinGroupTables{tile, rec, cover, weight, start, wrec, (int)wg.tile.size(), R, Lw};
+    pl->wg_rec = rec;
+  }
+  h->n = 1;
+  h->p[0] = pl;
+  h->b0[0] = 0;
+  c->last_halves = *h;
+  return LDC_OK;
+}
+
+static int windows_group_load_cond(ldc_ctx* c, Plan* pl, const float* cond, hipStream_t s) {
+  HIPCHK(launch_windows_group_gather(DT_F32, cond, pl->cond_in_cl, pl->B, c->unet.cond_channels, pl->F, pl->wg, upsample_factor(c), s));
+  return run_ops(c, pl, pl->cond_ops, false, s);
+}
+static int windows_group_load_x(ldc_ctx* c, Plan* pl, const float* x, hipStream_t s) {
+  HIPCHK(launch_windows_group_gather(c->dt, x, pl->x_cl, pl->B, c->unet.channels, pl->L, pl->wg, 1, s));
+  return LDC_OK;
+}
+
+// ldc_unet_forward_windows of R recordings in one batch: x, eps_out packed [C][Ltot_r] blocks, cond packed [Cc][Ftot_r] blocks
+extern "C" int ldc_unet_forward_windows_group(ldc_ctx* c, const float* x, int t, const float* cond, int R, const int* Ltot, const int* Ftot, int Lw,
+                                              int overlap, float* eps_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!x || !cond || !eps_out) return fail(LDC_E_INVALID, "null tensor");
+  if (t < 0 || t >= c->unet.timesteps) return fail(LDC_E_INVALID, "t %d: out of range [0, %d)", t, c->unet.timesteps);
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_group_prepare(c, R, Ltot, Ftot, Lw, overlap, s, &h));
+  Plan* pl = h.p[0];
+  LDCCHK(windows_group_load_cond(c, pl, cond, s));
+  LDCCHK(windows_group_load_x(c, pl, x, s));
+  HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
+  HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
+  LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+  HIPCHK(launch_windows_group_update(c->dt, WIN_BLEND, nullptr, pl->eps_cl, nullptr, 0, nullptr, eps_out, c->unet.channels, pl->wg, c->sched, nullptr,
+                                     nullptr, s));
+  return finish_stream(c, stream);
+}
+
+// The front of a group sampler call, the refusals of ldc_denoise_windows / ldc_ddim_sample_windows / ldc_dpm_sample_windows in their order
+// (sampler 0 DDPM: t_start and eta are not used; 1 DDIM; 2 DPM: eta, noise and seeds are not used).  Leaves the schedule in c->ddim_host /
+// c->dpm_host.  A sampler that draws needs a tape or the recordings' seeds.
+static int windows_group_front(ldc_ctx* c, int sampler, int t_start, int n_steps, float eta, const float* noise, const uint64_t* seeds, bool tensors,
+                               bool codec, bool* draws) {
+  if (sampler != SAMPLER_DDPM && sampler != SAMPLER_DDIM && sampler != SAMPLER_DPM)
+    return fail(LDC_E_INVALID, "sampler %d: must be 0 (DDPM), 1 (DDIM) or 2 (DPM-Solver++)", sampler);
+  *draws = false;
+  if (sampler == SAMPLER_DPM) {
+    LDCCHK(dpm_front_args(t_start, n_steps));
+    if (!tensors) return fail(LDC_E_INVALID, codec ? "bad arguments" : "null tensor");
+    LDCCHK(check_ready(c, LDC_MODEL_MAIN, codec));
+    LDCCHK(dpm_schedule(c, t_start, n_steps));
+    return LDC_OK;
+  }
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, codec));
+  if (!tensors) return fail(LDC_E_INVALID, codec ? "bad arguments" : "null tensor");
+  if (sampler == SAMPLER_DDPM) {
+    if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+    *draws = true;
+  } else {
+    LDCCHK(ddim_schedule(c, t_start, n_steps, eta, draws));
+  }
+  if (*draws && !noise && !seeds)
+    return fail(LDC_E_INVALID, "seeds NULL: a group call that draws takes a noise tape or one seed per recording (it never reads the context's epoch)");
+  return LDC_OK;
+}
+
+// the coupled loop of the group on the plan's packed state; the keys go to the recording table on the stream, in front of the loop.  The
+// context's Philox epoch is neither read nor advanced (as in decode pools, section 5e): recording r draws under seeds[r] at epoch 0.
+static int windows_group_loop(ldc_ctx* c, const Halves& h, const StepSampler& sm, const float* noise, const uint64_t* seeds, int n_steps, hipStream_t s) {
+  Plan* pl = h.p[0];
+  HIPCHK(launch_windows_group_keys(pl->wg_rec, noise ? nullptr : seeds, pl->wg.R, s));
+  return denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm);
+}
+
+extern "C" int ldc_sample_windows_group(ldc_ctx* c, float* img, const float* cond, int sampler, int t_start, int n_steps, float eta, const float* noise,
+                                        const uint64_t* seeds, int R, const int* Ltot, const int* Ftot, int Lw, int overlap, void* stream) {
+  bool draws = false;
+  LDCCHK(windows_group_front(c, sampler, t_start, n_steps, eta, noise, seeds, img && cond, false, &draws));
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_group_prepare(c, R, Ltot, Ftot, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
+  Plan* pl = h.p[0];
+  StepSampler sm;
+  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));
+  LDCCHK(windows_group_load_cond(c, pl, cond, s));
+  const size_t nbytes = (size_t)c->unet.channels * pl->win_Ltot * 4;
+  HIPCHK(hipMemcpyAsync(pl->win_x, img, nbytes, hipMemcpyDeviceToDevice, s));
+  LDCCHK(windows_group_load_x(c, pl, pl->win_x, s));
+  LDCCHK(windows_group_loop(c, h, sm, sampler == SAMPLER_DPM ? nullptr : noise, seeds, n_steps, s));
+  HIPCHK(hipMemcpyAsync(img, pl->win_x, nbytes, hipMemcpyDeviceToDevice, s));
+  return finish_stream(c, stream);
+}
+
+// ldc_decode_windows / _ddim_windows / _dpm_windows of R recordings with ONE loop: wav packed (recording r's T[r] samples behind those in
+// front), the codec ends per recording with the code of decode_windows_body -- get_cond_rows at B = 1, the start image normalised over that
+// recording, the decoder over that recording's latent, output_normalise for that recording.  Outputs packed: wav_out like wav, latents_out
+// [D][Ltot_r] blocks, cond_out [D][Ftot_r] blocks, codes_out [n_q][Ftot_r] blocks.
+extern "C" int ldc_decode_windows_group(ldc_ctx* c, const float* wav, int R, const int* T, int sampler, int t_start, int n_steps, float eta,
+                                        const float* noise, const uint64_t* seeds, int Lw, int overlap, float* wav_out, float* latents_out,
+                                        float* cond_out, int64_t* codes_out, void* stream) {
+  bool draws = false;
+  LDCCHK(windows_group_front(c, sampler, t_start, n_steps, eta, noise, seeds, wav && wav_out && T && R >= 1, true, &draws));
+  if (R > kWinPerPart) return fail(LDC_E_INVALID, "R %d: a window group holds 1 to %d recordings", R, kWinPerPart);
+  const Codec& cc = c->codec[LDC_MODEL_COND];
+  const Codec& mc = c->codec[LDC_MODEL_MAIN];
+  const int D = c->cfg.rep_dims;
+  std::vector<int> Lr((size_t)R), Fr((size_t)R);
+  std::vector<size_t> toff((size_t)R + 1, 0);
+  for (int r = 0; r < R; ++r) {
+    if (T[r] <= 0 || T[r] % cc.hop || T[r] % mc.hop)
+      return fail(LDC_E_INVALID, "recording %d: T %d: must be a positive multiple of %d and %d (sample.py:87 trims to 640)", r, T[r], cc.hop, mc.hop);
+    Fr[r] = T[r] / cc.hop; Lr[r] = T[r] / mc.hop;
+    LDCCHK(check_unet_args(c, 1, Lr[r], Fr[r]));
+    toff[r + 1] = toff[r] + (size_t)T[r];
+  }
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_group_prepare(c, R, Lr.data(), Fr.data(), Lw, overlap, s, &h));   // (every refusal, before any GPU work)
+  LDCCHK(ensure_outnorm(c, 1));
+  Plan* pl = h.p[0];
+  StepSampler sm;
+  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));
+  const WinGroup& g = pl->win_group;
+  const int n_q = n_q_for_bandwidth(c, 0.f);
+  LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
+    float* mx = (float*)ar.alloc((size_t)R * 4);
+    const int Fw = pl->F, upf = upsample_factor(c);
+    for (int r = 0; r < R; ++r) {
+      const int F = Fr[r], L = Lr[r];
+      const size_t foff = (size_t)g.off[r] / upf;
+      float* qr = nullptr;
+      int Fq = 0;
+      LDCCHK(get_cond_rows(c, wav + toff[r], 1, T[r], 0.f, ar, dry, s, &qr, &Fq, codes_out ? codes_out + (size_t)n_q * foff : nullptr, 1));
+      if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
+      void* up = nullptr;
+      int Lu = 0;
+      LDCCHK(upsample_rows(c, qr, 1, F, ar, dry, s, &up, &Lu));
+      if (!dry) {
+        if (cond_out) HIPCHK(launch_from_cl(DT_F32, qr, cond_out + (size_t)D * foff, 1, D, F, nullptr, 0, 0.f, s));
+        HIPCHK(hipMemsetAsync(mx + r, 0, 4, s));
+        HIPCHK(launch_maxabs(DT_F32, up, 1, (int64_t)L * D, 0, mx + r, s));
+        HIPCHK(launch_from_cl(DT_F32, up, pl->win_x + (size_t)D * g.off[r], 1, D, L, mx + r, 0, 1e-8f, s));
+        for (int k = g.w0[r]; k < g.w0[r + 1]; ++k)   // process_cond per window: a window's slice is one contiguous run of the recording's rows
+          HIPCHK(hipMemcpyAsync((float*)pl->cond_in_cl + (size_t)k * Fw * D, qr + (size_t)(g.start[k] / upf) * D, (size_t)Fw * D * 4,
+                                hipMemcpyDeviceToDevice, s));
+      }
+    }
+    if (!dry) {
+      LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
+      LDCCHK(windows_group_load_x(c, pl, pl->win_x, s));
+      LDCCHK(windows_group_loop(c, h, sm, sampler == SAMPLER_DPM ? nullptr : noise, seeds, n_steps, s));
+      if (latents_out) HIPCHK(hipMemcpyAsync(latents_out, pl->win_x, (size_t)D * g.Lsum * 4, hipMemcpyDeviceToDevice, s));
+    }
+    for (int r = 0; r < R; ++r) {   // decoder over each recording's latent (quirk Q3: no x18 un-scaling on this path, sample.py:131)
+      const int L = Lr[r];
+      SeaRun Rn{c, &ar, s, dry, 1};
+      void* zc = ar.alloc((size_t)L * D * 4);
+      if (!dry) HIPCHK(launch_to_cl(DT_F32, pl->win_x + (size_t)D * g.off[r], zc, 1, D, L, nullptr, 0, 0.f, s));
+      void* y = nullptr;
+      int Lo = 0, Cd = 0;
+      LDCCHK(run_seanet(Rn, mc.dec, zc, L, &y, &Lo, &Cd));
+      if (!dry) {
+        if (Lo != T[r]) return fail(LDC_E_STATE, "internal: the decoder gave %d samples for recording %d of %d", Lo, r, T[r]);
+        HIPCHK(hipMemcpyAsync(wav_out + toff[r], y, (size_t)Lo * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(launch_output_normalise(wav_out + toff[r], 1, Lo, 0, c->outnorm_ws, s, nullptr, mc.hop));
+      }
+    }
+    return LDC_OK;
+  }));
+  return finish_stream(c, stream);
 }
 
 int check_dev(ldc_ctx* c) {

@@ -218,6 +218,15 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
   WindowTables win{};           // cover [win_Ltot], weight [B][L], start [B] (device)
   std::vector<int> win_cover_h, win_start_h;
   std::vector<float> win_weight_h;
+  // Window-group plan (ldc_*_windows_group; section 5g, "Several recordings per call"): the windows plan at B = W_sum of R recordings.
+  // win_Ltot is Lsum, the frames of all of them -- the packed state, the packed DPM history and the step stride of a tape are sized by it
+  // as a single recording's are by its Ltot.  win_group holds the host side of the tables (the ordered list of lengths is part of the
+  // cache key: empty on every other plan), win_group_id the plan's identity for its step graphs, wg the device tables, which live in
+  // win_base behind the state with the recording table and the tile table.
+  WinGroup win_group;
+  int win_group_id = 0;
+  WinGroupTables wg{};
+  WinGroupRec* wg_rec = nullptr;   // == wg.rec, writable: the keys of a call go in on the stream
   std::vector<std::function<hipError_t(hipStream_t)>> cond_ops;   // process_cond (once per denoise)
   std::vector<std::function<hipError_t(hipStream_t)>> step_ops;   // Unet1D.forward after process_cond
   std::vector<int> step_is_conv;                                   // 1 where step_ops[i] is a conv-GEMM launch
@@ -258,6 +267,7 @@ struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sa
   int ragged = 0;    // (part of the cache key) the steps of ragged plans
   int pool_id = 0;   // (part of the cache key) != 0: the step graphs of that decode pool's plans
   int win_Ltot = 0, win_O = 0;   // (part of the cache key) != 0: the steps of that coupled-windows plan (B windows of L frames)
+  int win_group = 0;             // (part of the cache key) != 0: the steps of that window-group plan (Plan::win_group_id)
   int sampler = SAMPLER_DDPM;   // sampler kind (part of the cache key): a loop never replays another kind's graph (DDIM, DPM: the schedule table's address is captured, not its contents)
   const float* noise = nullptr;
   float* x = nullptr;
@@ -374,6 +384,7 @@ struct ldc_ctx {
   size_t plan_bytes = 0, plan_bytes_cap = (size_t)48 << 30;   // LDC_PLAN_CACHE_GB
   int plan_count_cap = 24;                                     // LDC_PLAN_CACHE_N
   int live_pools = 0, next_pool_id = 1;                        // decode pools (ldc_pool_create): their plans are pinned in the cache
+  int next_win_group_id = 1;                                   // window-group plans (Plan::win_group_id): the identity of their step graphs
   // device-drawn noise: every sampler call that draws advances the epoch, so no two calls share a realisation
   uint64_t noise_epoch = 0, cur_key = 0;
   // asynchronous device-side failure flag, host-mapped: word 0 = 1 cooperative LSTM timeout, 2 fused GroupNorm wait timeout,
@@ -552,7 +563,7 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F);
 int check_dev(ldc_ctx* c);   // hipSetDevice only: calls that need no weights
 // what ldc_api_pool.cpp shares with the samplers of ldc_api.cpp
 int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false, bool items = false, int pool_id = 0,
-             int win_Ltot = 0, int win_O = 0);
+             int win_Ltot = 0, int win_O = 0, const std::vector<int>* win_group = nullptr);
 int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step, hipStream_t s);
 int calibrate_part_streams(ldc_ctx* c, hipStream_t s);
 bool parts_parallel(ldc_ctx* c, const Halves& h);

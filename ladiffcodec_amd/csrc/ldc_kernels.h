@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ldc_windows.h"   // WinGroupRec, WinGroupTile: what the window-group kernels read, as the host builder writes it
+
 namespace ldc {
 
 enum { DT_F32 = 0, DT_BF16 = 1, DT_FP8 = 2 };   // DT_FP8: OCP e4m3 conv INPUTS of the fp8 x fp8 MFMA path (conv_fast_fp8.hip); outputs stay bf16
@@ -319,6 +321,29 @@ hipError_t launch_dpm_update(int dt, float* x, const void* eps_cl, float* x0_pre
 // state goes into x and into every covering window's row of x_cl [W][Lw][C] dt.  Nothing is drawn.
 hipError_t launch_windows_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WindowTables wt, StepTables tb,
                                      const DpmStep* sched, const int* st, hipStream_t s);
+// Window groups ("Several recordings per call"): the host-built tables of R recordings whose windows share one
+// batch (ldc_windows.h: win_group_build), in device memory.
+struct WinGroupTables {
+  const WinGroupTile* tile;   // [n_tiles] {recording, l0}: one entry per workgroup column of the update launch
+  const WinGroupRec* rec;     // [R] {Ltot_r, w0_r, off_r, cover_off_r, Philox key}
+  const int* cover;           // [Lsum] the recordings' cover rows, concatenated; first window counted WITHIN the recording | count << 8
+  const float* weight;        // [W_sum][Lw]
+  const int* start;           // [W_sum] first frame of each window in its recording's own frames
+  const int* wrec;            // [W_sum] window -> recording
+  int n_tiles, R, Lw;
+};
+// launch_windows_update / launch_windows_dpm_update of a window group: x, ebar, x0_prev and every step of the tape are packed, recording
+// r's [C][Ltot_r] block at C * off_r floats (noise_step_stride = C * Lsum); Philox draws under the recording's own key.  Grid
+// (n_tiles, ceil(C / 32)).
+hipError_t launch_windows_group_update(int dt, int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
+                                       float* ebar, int C, WinGroupTables gt, StepTables tb, const DdimStep* sched, const int* st, hipStream_t s);
+hipError_t launch_windows_group_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WinGroupTables gt, StepTables tb,
+                                           const DpmStep* sched, const int* st, hipStream_t s);
+// y [W_sum][Lw][C] dt <- the windows' slices of a packed fp32 sequence whose blocks are [C][Ltot_r / div] at C * off_r / div floats
+// (Lw: the frames of a window of this sequence)
+hipError_t launch_windows_group_gather(int dt, const float* x, void* y, int W, int C, int Lw, WinGroupTables gt, int div, hipStream_t s);
+// rec[r].key = keys_host[r] (null: 0), stream-ordered; the keys travel as kernel arguments
+hipError_t launch_windows_group_keys(WinGroupRec* rec, const uint64_t* keys_host, int R, hipStream_t s);
 // x /= (maxabs[b or 0] + eps) in place on a raw element stream (n_per_item elements per item)
 hipError_t launch_scale_by_maxabs(int dt, void* x, int B, int64_t n_per_item, const float* maxabs, int per_item,
                                   float eps, hipStream_t s);

@@ -1,6 +1,7 @@
 // Coupled windows: the host-only builders of a windows call -- the layout with its cover and weight tables, the
-// partition of the windows into batch parts, and the per-window base-pointer tables of a call in parts.  Pure functions of their
-// arguments (no context, no HIP, no globals): ldc_api.cpp wraps them, tools/window_layout_check.cpp runs them under the host sanitizers.
+// partition of the windows into batch parts, the per-window base-pointer tables of a call in parts, and the tables of a window group
+// (several recordings whose windows share one batch).  Pure functions of their arguments (no context, no HIP, no globals): ldc_api.cpp
+// wraps them, tools/window_layout_check.cpp and tools/window_group_check.cpp run them under the host sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -101,6 +102,84 @@ inline bool win_ptr_tables(int W, int P, const int* first, const void* const* ep
     }
   }
   return true;
+}
+
+// ---- window groups ("Several recordings per call"): R recordings, the windows of all of them in ONE batch ----------
+// Recording r keeps its own layout win_layout_build(Ltot_r, Lw, O, up); its windows take the batch indices w0[r] .. w0[r] + W_r - 1 in
+// recording order, its [C][Ltot_r] blocks of the packed tensors begin at C * off[r] floats (off[r] = the frames of the recordings in
+// front), its cover rows at off[r] of the concatenated table.  The update kernels walk a tile table: one entry per workgroup column,
+// recording r owns ceil(Ltot_r / 32) tiles, so no tile spans two recordings.
+struct WinGroupRec {    // one recording, as the kernels read it (device memory; 32 bytes)
+  int Ltot;             // its latent frames
+  int w0;               // batch index of its first window
+  int off;              // frames in front of it on the packed axis: its state block begins at C * off floats
+  int cover_off;        // its rows of the concatenated cover table begin here
+  unsigned key_lo, key_hi;   // its Philox key (written on the stream in front of every loop, launch_windows_group_keys)
+  int W, pad;
+};
+struct WinGroupTile { int rec, l0; };   // a workgroup column: 32 frames of recording rec from l0 (in the recording's own frames)
+
+static constexpr int kWinGroupTile = 32;
+
+struct WinGroup {
+  int R = 0, Lw = 0, O = 0, W_sum = 0, Lsum = 0;
+  std::vector<int> Ltot, w0, off;        // [R], [R + 1], [R + 1]
+  std::vector<int> start, cover, wrec;   // [W_sum] in the recording's own frames; [Lsum] first window WITHIN the recording | count << 8; [W_sum] window -> recording
+  std::vector<float> weight;             // [W_sum][Lw]
+  std::vector<WinGroupRec> rec;          // [R] (keys zero)
+  std::vector<WinGroupTile> tile;        // [sum ceil(Ltot_r / 32)]
+};
+
+// The group of R recordings of Ltot[r] frames at (Lw, overlap).  0: ok; 1: refused (*err names the value, and the recording where it is
+// one's own); 2: internal.  Every recording must be at least one window long: a shorter one would shrink the window (win_layout_build's
+// Ltot <= Lw case) and break the equal-length batch.
+inline int win_group_build(int R, const int* Ltot, int Lw, int O, int up, WinGroup* out, std::string* err) {
+  char msg[320];
+  auto refuse = [&](int code) { *err = msg; return code; };
+  if (R < 1 || R > kWinPerPart) { snprintf(msg, sizeof msg, "R %d: a window group holds 1 to %d recordings", R, kWinPerPart); return refuse(1); }
+  if (!Ltot) { snprintf(msg, sizeof msg, "null list of lengths"); return refuse(1); }
+  *out = WinGroup();
+  out->R = R; out->Lw = Lw; out->O = O;
+  out->Ltot.assign(Ltot, Ltot + R);
+  out->w0.assign((size_t)R + 1, 0);
+  out->off.assign((size_t)R + 1, 0);
+  std::vector<WinLayout> lay((size_t)R);
+  long long wsum = 0, lsum = 0;
+  for (int r = 0; r < R; ++r) {
+    std::string e1;
+    const int rc = win_layout_build(Ltot[r], Lw, O, up, kWinPerPart, &lay[r], &e1);
+    if (rc) { snprintf(msg, sizeof msg, "recording %d: %s", r, e1.c_str()); return refuse(rc); }
+    if (Ltot[r] < Lw) {
+      snprintf(msg, sizeof msg, "recording %d: Ltot %d is shorter than the window Lw = %d (every recording of a group is at least one window long)", r,
+               Ltot[r], Lw);
+      return refuse(1);
+    }
+    wsum += lay[r].W;
+    lsum += Ltot[r];
+    out->w0[r + 1] = (int)wsum;
+    out->off[r + 1] = (int)lsum;   // (<= 32 recordings of <= 32 windows of Lw frames: far from 2^31 for every Lw the UNet takes; checked below)
+  }
+  if (wsum > kWinPerPart) {
+    snprintf(msg, sizeof msg, "the %d recordings need %lld windows of %d frames at overlap %d in all: at most %d per call", R, wsum, Lw, O, kWinPerPart);
+    return refuse(1);
+  }
+  if (lsum > 0x3fffffff) { snprintf(msg, sizeof msg, "the recordings hold %lld frames in all: too many for one call", lsum); return refuse(1); }
+  out->W_sum = (int)wsum; out->Lsum = (int)lsum;
+  out->start.reserve((size_t)wsum); out->wrec.reserve((size_t)wsum);
+  out->cover.reserve((size_t)lsum); out->weight.reserve((size_t)wsum * Lw);
+  out->rec.assign((size_t)R, WinGroupRec());
+  for (int r = 0; r < R; ++r) {
+    const WinLayout& l = lay[r];
+    if (l.Lw != Lw) { snprintf(msg, sizeof msg, "internal: recording %d got windows of %d frames", r, l.Lw); return refuse(2); }
+    out->start.insert(out->start.end(), l.start.begin(), l.start.end());
+    out->cover.insert(out->cover.end(), l.cover.begin(), l.cover.end());
+    out->weight.insert(out->weight.end(), l.weight.begin(), l.weight.end());
+    out->wrec.insert(out->wrec.end(), (size_t)l.W, r);
+    WinGroupRec& g = out->rec[r];
+    g.Ltot = Ltot[r]; g.w0 = out->w0[r]; g.off = out->off[r]; g.cover_off = out->off[r]; g.W = l.W;
+    for (int l0 = 0; l0 < Ltot[r]; l0 += kWinGroupTile) out->tile.push_back(WinGroupTile{r, l0});
+  }
+  return 0;
 }
 
 }  // namespace ldc

@@ -26,6 +26,7 @@ EXPORTS = [
     "ldc_dpm_schedule", "ldc_dpm_sample", "ldc_decode_dpm", "ldc_decode_codes_dpm", "ldc_decode_ragged_dpm",
     "ldc_window_layout", "ldc_window_layout_n", "ldc_window_parts", "ldc_unet_forward_windows", "ldc_denoise_windows", "ldc_ddim_sample_windows", "ldc_decode_windows", "ldc_decode_ddim_windows",
     "ldc_dpm_sample_windows", "ldc_decode_dpm_windows", "ldc_decode_codes_windows", "ldc_decode_codes_dpm_windows",
+    "ldc_window_group_layout", "ldc_unet_forward_windows_group", "ldc_sample_windows_group", "ldc_decode_windows_group",
     "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
     "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
     "ldc_stream_min_first", "ldc_stream_create", "ldc_stream_reset", "ldc_stream_destroy", "ldc_seanet_encode_stream", "ldc_seanet_decode_stream", "ldc_get_cond_stream",
@@ -132,6 +133,11 @@ def load() -> C.CDLL:
     lib.ldc_decode_dpm_windows.argtypes = [vp, fp, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp]
     lib.ldc_decode_codes_windows.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, C.c_float, fp, i32, i32, fp, fp, fp, vp]
     lib.ldc_decode_codes_dpm_windows.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp]
+    ip, u64p = C.POINTER(C.c_int), C.POINTER(C.c_uint64)
+    lib.ldc_window_group_layout.argtypes = [i32, ip, i32, i32, i32, ip, ip, C.POINTER(C.c_float)]
+    lib.ldc_unet_forward_windows_group.argtypes = [vp, fp, i32, fp, i32, ip, ip, i32, i32, fp, vp]
+    lib.ldc_sample_windows_group.argtypes = [vp, fp, fp, i32, i32, i32, C.c_float, fp, u64p, i32, ip, ip, i32, i32, vp]
+    lib.ldc_decode_windows_group.argtypes = [vp, fp, i32, ip, i32, i32, i32, C.c_float, fp, u64p, i32, i32, fp, fp, fp, vp, vp]
     lib.ldc_ac_encode_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
     lib.ldc_ac_decode_ragged.argtypes = [vp, vp, C.c_int64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldc_unet_forward_ragged.argtypes = [vp, fp, i32, fp, C.POINTER(C.c_int32), i32, i32, i32, fp, vp]
@@ -263,6 +269,25 @@ def window_layout(Ltot: int, Lw: int, overlap: int, up: int, max_windows: int = 
     weights = (C.c_float * (W * lw))()
     check(min(0, call(starts, weights)))
     return list(starts)[:W], np.array(weights, dtype=np.float32).reshape(W, lw)
+
+
+def window_group_layout(Ltot, Lw: int, overlap: int, up: int):
+    """The layout of a window group (ldc_window_group_layout, host-only): R recordings of Ltot[r] latent frames whose windows share one
+    batch -> (w0 [R + 1] list: recording r's windows are the batch items w0[r] .. w0[r + 1] - 1, starts [W_sum] list in each recording's
+    own frames, weights [W_sum, Lw] float32)."""
+    import numpy as np
+    lib = load()
+    lens = [int(v) for v in Ltot]
+    R = len(lens)
+    arr = (C.c_int * max(1, R))(*lens)
+    w0 = (C.c_int * (R + 1))()
+    starts = (C.c_int * 32)()
+    W = lib.ldc_window_group_layout(R, arr, int(Lw), int(overlap), int(up), w0, starts, None)
+    if W < 0:
+        check(W)
+    weights = (C.c_float * (W * int(Lw)))()
+    check(min(0, lib.ldc_window_group_layout(R, arr, int(Lw), int(overlap), int(up), w0, starts, weights)))
+    return list(w0), list(starts)[:W], np.array(weights, dtype=np.float32).reshape(W, int(Lw))
 
 
 def window_parts(W: int, parts: int):

@@ -695,6 +695,115 @@ class Engine:
         return self._decode_windows(wav, want_stages, lambda w, T, o, la, co, cd, s: self.lib.ldc_decode_dpm_windows(
             self._ctx, w, T, int(t_start), int(n_steps), int(Lw), int(overlap), o, la, co, cd, s))
 
+    # ---- window groups ("Several recordings per call"): lists of recordings in, lists out ----------
+    SAMPLERS = {"ddpm": 0, "ddim": 1, "dpm": 2}
+
+    def window_group_layout(self, Ltot, Lw: int, overlap: int):
+        """ldc_window_group_layout for this engine's `up`: -> (w0 [R + 1], starts [W_sum], weights [W_sum, Lw] float32)."""
+        return L.window_group_layout(Ltot, Lw, overlap, int(np.prod(self.unet.upsampling_ratios or ())))
+
+    def _pack(self, xs, what: str):
+        """a list of [1, C, n_r] tensors as one packed float32 buffer of [C][n_r] blocks, and the n_r"""
+        xs = [self._one_recording(x, what) for x in xs]
+        if not xs:
+            raise ValueError(f"{what}: a window group holds at least one recording")
+        return self.torch.cat([x.reshape(-1) for x in xs]).contiguous(), [int(x.shape[2]) for x in xs]
+
+    def _unpack(self, flat, C_: int, lens):
+        out, o = [], 0
+        for n in lens:
+            out.append(flat[o:o + C_ * n].reshape(1, C_, n).clone())
+            o += C_ * n
+        return out
+
+    @staticmethod
+    def _ints(v):
+        return (C.c_int * len(v))(*[int(a) for a in v])
+
+    def _group_noise(self, noise, seeds, lens, n_rows):
+        """a list of per-recording tapes [n, 1, C, Ltot_r] -> one packed tape [n][C * Lsum]; seeds -> uint64 [R]"""
+        pn = ps = None
+        if noise is not None:
+            if len(noise) != len(lens):
+                raise ValueError("noise: one tape per recording")
+            tapes = [self._f32(t) for t in noise]
+            n = tapes[0].shape[0]
+            if any(t.dim() != 4 or t.shape[0] != n or t.shape[1] != 1 or t.shape[3] != l for t, l in zip(tapes, lens)) or n < n_rows:
+                raise ValueError("noise: tapes of [n_steps, 1, C, Ltot_r], the same n_steps for every recording")
+            pn = self.torch.cat([t.reshape(n, -1) for t in tapes], dim=1).contiguous()
+        if seeds is not None:
+            if len(seeds) != len(lens):
+                raise ValueError("seeds: one per recording")
+            ps = (C.c_uint64 * len(lens))(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
+        return pn, ps
+
+    def unet_forward_windows_group(self, xs, t: int, conds, Lw: int, overlap: int):
+        """The blended eps of ONE UNet pass over the windows of every recording: xs [1, C, Ltot_r], conds [1, C, Ftot_r] (raw) -> a list
+        of [1, C, Ltot_r]."""
+        x, lens = self._pack(xs, "x")
+        cond, flens = self._pack(conds, "cond")
+        if len(lens) != len(flens):
+            raise ValueError("one condition per recording")
+        eps = self.torch.empty_like(x)
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_unet_forward_windows_group(self._ctx, x.data_ptr(), int(t), cond.data_ptr(), len(lens), self._ints(lens),
+                                                            self._ints(flens), int(Lw), int(overlap), eps.data_ptr(), s))
+        finally:
+            self._exit()
+        return self._unpack(eps, xs[0].shape[1], lens)
+
+    def sample_windows_group(self, imgs, conds, n_steps: int, Lw: int, overlap: int, sampler: str = "ddpm", t_start: int = 0,
+                             eta: float = 0.0, noise=None, seeds=None):
+        """`denoise_windows` ("ddpm"), `ddim_sample_windows` ("ddim") or `dpm_sample_windows` ("dpm") of every recording in ONE loop whose
+        batch holds the windows of all of them (at most 32).  imgs [1, C, Ltot_r], conds [1, C, Ftot_r]; noise: a list of tapes
+        [n_steps, 1, C, Ltot_r], or seeds: one per recording -- recording r then draws what the single call draws right after
+        reseed(seeds[r]); the engine's own noise epoch is neither read nor advanced.  -> a list of [1, C, Ltot_r]."""
+        img, lens = self._pack(imgs, "img")
+        cond, flens = self._pack(conds, "cond")
+        if len(lens) != len(flens):
+            raise ValueError("one condition per recording")
+        pn, ps = self._group_noise(noise, seeds, lens, int(n_steps))
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_sample_windows_group(self._ctx, img.data_ptr(), cond.data_ptr(), self.SAMPLERS[sampler], int(t_start),
+                                                      int(n_steps), float(eta), pn.data_ptr() if pn is not None else None, ps, len(lens),
+                                                      self._ints(lens), self._ints(flens), int(Lw), int(overlap), s))
+        finally:
+            self._exit()
+        return self._unpack(img, imgs[0].shape[1], lens)
+
+    def decode_windows_group(self, wavs, n_steps: int, Lw: int, overlap: int, sampler: str = "ddpm", t_start: int = 0, eta: float = 0.0,
+                             noise=None, seeds=None, want_stages: bool = False):
+        """`decode_windows` / `decode_ddim_windows` / `decode_dpm_windows` of every recording wavs[r] [1, 1, T_r] with ONE denoise loop; the
+        codec ends run per recording.  -> a list of waveforms [1, 1, T_r], or of the stage dicts of `decode_windows`."""
+        wav, Ts = self._pack(wavs, "wav")
+        hop_c, hop_m, D = self.cond_codec.hop_length, self.main_codec.hop_length, self.main_codec.rep_dims
+        Fs, Ls = [T // hop_c for T in Ts], [T // hop_m for T in Ts]
+        pn, ps = self._group_noise(noise, seeds, Ls, int(n_steps))
+        n_q = self.cond_codec.n_q_for_bandwidth(None)
+        out = self._empty(sum(Ts))
+        lat = self._empty(D * sum(Ls)) if want_stages else None
+        cond = self._empty(D * sum(Fs)) if want_stages else None
+        codes = self._empty(n_q * sum(Fs), dtype=self.torch.int64) if want_stages else None
+        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_decode_windows_group(self._ctx, wav.data_ptr(), len(Ts), self._ints(Ts), self.SAMPLERS[sampler], int(t_start),
+                                                      int(n_steps), float(eta), p(pn), ps, int(Lw), int(overlap), out.data_ptr(), p(lat),
+                                                      p(cond), p(codes), s))
+        finally:
+            self._exit()
+        outs = self._unpack(out, 1, Ts)
+        if not want_stages:
+            return outs
+        lats, conds = self._unpack(lat, D, Ls), self._unpack(cond, D, Fs)
+        cds, o = [], 0
+        for F in Fs:
+            cds.append(codes[o:o + n_q * F].reshape(n_q, 1, F).clone())
+            o += n_q * F
+        return [{"wav": w, "latents": a, "cond": b, "codes": cd} for w, a, b, cd in zip(outs, lats, conds, cds)]
+
     def _decode_codes_windows(self, codes, packed, bits, n_q, F, want_stages: bool, call):
         if codes is not None and (codes.dim() != 3 or codes.shape[1] != 1):
             raise ValueError(f"codes: coupled windows take one recording per call ([n_q, 1, F]), got {tuple(codes.shape)}")

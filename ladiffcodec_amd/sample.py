@@ -14,6 +14,9 @@ Same flags, defaults and output naming as the reference.  What differs, by desig
   * `--chunk_overlap_sec S` (with `--chunk_sec`) decodes a long mono recording on coupled windows that overlap by S seconds
     (Engine.decode_windows: one shared latent, no seams) instead of as independent chunks -- also in `sample_ddim`, `sample_dpm`
     and, from the container's codes, in `decompress`;
+  * `--window_group` (with `--chunk_overlap_sec`; `sample`, `sample_ddim`, `sample_dpm`) decodes SEVERAL such recordings per call
+    (Engine.decode_windows_group: the windows of a group, at most 32 in all, share one batch; file order, first fit).  Recording i of
+    the run's file list draws under seed (`--seed` + i) mod 2^64, whatever group or rank it lands in;
   * under `torch.distributed.run` the FILE list is sharded over the ranks (one process per GPU; all channels of a
     file stay on one rank, every output file has exactly one writer).
 Flags that are inert in the reference stay accepted and inert (`--sampling_timesteps`,
@@ -24,7 +27,7 @@ from __future__ import annotations
 import argparse
 import glob
 import os
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -93,6 +96,10 @@ _EXTRA: List[Tuple[str, dict]] = [
                                  help="--chunk_sec > 0: decode a long mono recording on COUPLED windows of --chunk_sec that overlap by this "
                                       "much (Engine.decode_windows: one shared latent, the windows' predictions are cross-faded at every "
                                       "step, so there are no seams) instead of as independent chunks; at most half of --chunk_sec, 0 allowed")),
+    ("--window_group", dict(dest="window_group", action="store_true", default=argparse.SUPPRESS,
+                            help="--chunk_overlap_sec: decode SEVERAL long mono recordings per call (Engine.decode_windows_group): their "
+                                 "windows, at most 32 in all, share one batch; recording i of the run is seeded (--seed + i) mod 2^64, so its "
+                                 "audio depends neither on the grouping nor on the number of ranks")),
 ]
 
 
@@ -119,6 +126,15 @@ def windows_options(a):
     if not 0.0 <= ov <= chunk_sec / 2:
         raise SystemExit(f"--chunk_overlap_sec {ov}: must be in [0, --chunk_sec / 2 = {chunk_sec / 2}]")
     return ov
+
+
+def window_group_option(a) -> bool:
+    """--window_group of a parsed namespace (off without the flag); it needs --chunk_overlap_sec."""
+    if not getattr(a, "window_group", False):
+        return False
+    if not hasattr(a, "chunk_overlap_sec"):
+        raise SystemExit("--window_group needs --chunk_overlap_sec (it groups the recordings that are decoded on coupled windows)")
+    return True
 
 
 def _unsupported(a) -> None:
@@ -659,12 +675,44 @@ def window_decoder(eng, sampler, Lw: int, ov: int):
     return one_codes if from_codes else one
 
 
-def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: float, rank: int, world: int, local_rank: int, sampler=None) -> List[str]:
+def plan_window_groups(windows: List[int], max_windows: int = MAX_WINDOWS) -> List[List[int]]:
+    """--window_group: recordings of windows[k] windows each packed into groups of at most max_windows windows in all -- in order, first
+    fit; -> the groups as lists of positions (ascending inside a group).  Every group is one Engine.decode_windows_group call."""
+    groups, room = [], []
+    for k, w in enumerate(windows):
+        if not 1 <= w <= max_windows:
+            raise ValueError(f"recording {k}: {w} windows do not fit a group of {max_windows}")
+        g = next((j for j, r in enumerate(room) if w <= r), None)
+        if g is None:
+            groups.append([])
+            room.append(max_windows)
+            g = len(groups) - 1
+        groups[g].append(k)
+        room[g] -= w
+    return groups
+
+
+def decode_window_group(eng, wavs_dev, sampler, Lw: int, ov: int, noise=None, seeds=None):
+    """One Engine.decode_windows_group call of `sampler` (DdpmSampler / DdimSampler / DpmSampler) -> the list of waveforms."""
+    if isinstance(sampler, DpmSampler):
+        return eng.decode_windows_group(wavs_dev, sampler.n_steps, Lw, ov, sampler="dpm", t_start=sampler.t_start)
+    if isinstance(sampler, DdimSampler):
+        return eng.decode_windows_group(wavs_dev, sampler.n_steps, Lw, ov, sampler="ddim", t_start=sampler.t_start, eta=sampler.eta,
+                                        noise=noise, seeds=seeds)
+    return eng.decode_windows_group(wavs_dev, sampler.n_steps, Lw, ov, noise=noise, seeds=seeds)
+
+
+def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: float, rank: int, world: int, local_rank: int, sampler=None,
+                        run_index: Optional[List[int]] = None) -> List[str]:
     """--chunk_overlap_sec: every long mono recording of this rank through Engine.decode_windows / decode_ddim_windows /
     decode_dpm_windows, trimmed to whole 640-sample frames as the whole-file path trims.  With a CodesSampler (decompress) `wavs` is a
     container source and the recording's codes go through Engine.decode_codes_windows / decode_codes_dpm_windows instead.  A recording
     that needs more than MAX_WINDOWS windows is cut into segments (of the waveform, or of the codes: cuts fall at whole condition
-    frames) that are decoded one after another and hard-joined (raw decoder outputs, normalised once over the recording)."""
+    frames) that are decoded one after another and hard-joined (raw decoder outputs, normalised once over the recording).
+    --window_group (waveforms only): the rank's recordings that fit one call are packed into groups of at most MAX_WINDOWS windows
+    (plan_window_groups: file order, first fit), every group one Engine.decode_windows_group call.  Without a noise provider recording i
+    is seeded (--seed + run_index[i]) mod 2^64 -- run_index[i]: its index in the run's file list (default: i) --, so its audio depends
+    neither on the grouping nor on the number of ranks; the provider is asked per recording as without the flag, key (i, 0)."""
     import sys
     import torch
     from scipy.io import wavfile
@@ -678,7 +726,41 @@ def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: floa
     provider = getattr(inp_args, "noise_provider", None)
     one = window_decoder(eng, sampler, Lw, ov)   # (refuses a sampler without a windows route before anything is loaded)
     written = []
-    for i in parallel.shard_utterances([sh[1] for sh in wavs.shapes], rank, world):
+    mine = list(parallel.shard_utterances([sh[1] for sh in wavs.shapes], rank, world))
+    grouped = set()
+    if window_group_option(inp_args):
+        if from_codes:
+            raise SystemExit("--window_group: decoding from codes has no group call (Engine.decode_windows_group takes waveforms); drop the flag")
+
+        def n_windows(i):   # 0: the recording keeps the route below (more than MAX_WINDOWS windows: segments)
+            Ltot = wavs.shapes[i][1] // 640 * 640 // hop
+            if Ltot < Lw or len(plan_window_segments(Ltot, Lw, ov, up)) > 1:
+                return 0
+            return 1 + -(-(Ltot - Lw) // (Lw - ov))
+        cand = [i for i in mine if n_windows(i)]
+        inner_draws = sampler.draws
+        for g in plan_window_groups([n_windows(i) for i in cand]):
+            idx = [cand[k] for k in g]
+            ns = [wavs.shapes[i][1] // 640 * 640 for i in idx]
+            xs = [torch.from_numpy(np.ascontiguousarray(wavs[i][:1, None, :n])).to(dev) for i, n in zip(idx, ns)]
+            noise = seeds = None
+            if inner_draws > 0 and provider is not None:   # test seam (see decode_files): asked per recording, key (file index, 0)
+                noise = [provider([(i, 0)], inner_draws, n // hop).to(dev) for i, n in zip(idx, ns)]
+            elif inner_draws > 0:
+                seeds = [(int(inp_args.seed) + (run_index[i] if run_index is not None else i)) % (1 << 64) for i in idx]
+            outs = decode_window_group(eng, xs, sampler, Lw, ov, noise=noise, seeds=seeds)
+            for i, whole in zip(idx, outs):
+                if not bool(torch.isfinite(whole).all()):
+                    raise RuntimeError(f"non-finite audio decoded for {files[i]}")
+                path = output_path(files[i], inp_args.input_dir, inp_args.output_dir, wavs.in_ext)
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                wavfile.write(path, 16000, np.ascontiguousarray(whole.cpu().numpy()[0, 0]))
+                written.append(path)
+                wavs.drop(i)
+        grouped = set(cand)
+    for i in mine:
+        if i in grouped:
+            continue
         n = wavs.shapes[i][1] // 640 * 640
         x = None if from_codes else torch.from_numpy(np.ascontiguousarray(wavs[i][:1, None, :n]))
         segs = plan_window_segments(n // hop, Lw, ov, up)
@@ -721,6 +803,7 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
     files, wavs = [files[i] for i in keep], wavs.subset(keep)
     chunk_sec = float(getattr(inp_args, "chunk_sec", 0.0) or 0.0)
     overlap_sec = windows_options(inp_args)
+    window_group_option(inp_args)   # (--window_group without --chunk_overlap_sec is refused before anything is decoded)
     if overlap_sec is not None and source is not None and not isinstance(sampler, CodesSampler):
         raise SystemExit("--chunk_overlap_sec: a batch source other than waveforms needs a CodesSampler (decompress)")
     if chunk_sec > 0:
@@ -731,7 +814,8 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
         long_f, long_w = [files[i] for i in long_i], wavs.subset(long_i)
         files, wavs = [files[i] for i in short_i], wavs.subset(short_i)
         if overlap_sec is not None:
-            written_long = decode_window_files(eng, long_f, long_w, inp_args, overlap_sec, rank, world, local_rank, sampler=sampler) if long_f else []
+            written_long = decode_window_files(eng, long_f, long_w, inp_args, overlap_sec, rank, world, local_rank, sampler=sampler,
+                                               run_index=[keep[i] for i in long_i]) if long_f else []
         else:
             written_long = decode_long_files(eng, long_f, long_w, inp_args, rank, world, local_rank, sampler=sampler) if long_f else []
     else:

@@ -20,7 +20,13 @@ next to p_sample_update_kernel at B = 15.
 `--dpm`: instead of the above, at the default split and alternated round by round in the same way,
   ddim_windows / dpm_windows   Engine.ddim_sample_windows (eta 0) and Engine.dpm_sample_windows from t_start 100, marginal ms per step
   decode_wav / decode_codes    one 20-step Engine.decode_windows of the 30 s waveform and one Engine.decode_codes_windows of its codes, ms
-                   per call (the code-driven call skips the cond encoder and the quantiser)."""
+                   per call (the code-driven call skips the cond encoder and the quantiser).
+
+`--group`: instead of the above, at `split` 1 and alternated round by round in the same way, marginal ms per step of
+  group_2x15       Engine.sample_windows_group of TWO such recordings: 30 windows in one batch ("Several
+                   recordings per call")
+  two_single_calls Engine.denoise_windows of the one and then of the other (the figure is per step of BOTH: two steps of 15 windows)
+  items30_split1   Engine.denoise of the 30 windows as independent items: the same batch without the blend"""
 import json
 import os
 import statistics
@@ -71,6 +77,22 @@ def main():
             assert bool(torch.isfinite(windows(20)).all())
             assert bool(torch.isfinite(items15(20)).all())
         torch.cuda.synchronize()
+        e.close()
+        return
+    if "--group" in sys.argv[1:]:
+        # a second recording of the same length; everything at `split` 1 (a windows plan is one part anyway)
+        cond2 = torch.randn(1, 128, Ltot // up, generator=g).cuda()
+        img2 = e.cond_upsample(cond2, 1)
+        wimg2, wcond2 = cut(img2, starts, Lw), cut(cond2, [a // up for a in starts], Lw // up)
+        iimg, icond = torch.cat([wimg, wimg2]).contiguous(), torch.cat([wcond, wcond2]).contiguous()
+        e.set_option("split", 1)
+
+        def two_singles(n):
+            e.denoise_windows(img, cond, n, Lw, O_)
+            return e.denoise_windows(img2, cond2, n, Lw, O_)
+        timed(e, torch, rounds, {"group_2x15": lambda n: e.sample_windows_group([img, img2], [cond, cond2], n, Lw, O_, seeds=[11, 12])[1],
+                                 "two_single_calls": two_singles,
+                                 "items30_split1": lambda n: e.denoise(iimg, icond, n)}, 2 * W, 2 * Ltot, Lw, O_)
         e.close()
         return
     if dpm_mode:
