@@ -416,166 +416,6 @@ hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float*
   return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------
-// Coupled windows: W overlapping windows of one recording are the batch items of the UNet, ONE fp32 state
-// x [C][Ltot] is what they all read.  This kernel takes the place of the update launch of a step: the 32 x 32 tiling of
-// p_sample_update_kernel over GLOBAL frames.  A tile reads the cover entry (first window | count << 8, count <= 3, consecutive
-// windows) of each of its 32 frames, blends the covering windows' eps rows (channels-last, coalesced over c) with the host-built
-// weights in fp32 and in window order -- a singly covered frame is 1.0f * eps --, applies the sampler's arithmetic to x as the
-// B = 1, L = Ltot kernels above do (same tape index, same Philox block), and stores the new state channels-last into the row of
-// EVERY covering window of the UNet's input buffer.  Each element of that buffer has one writer: the tile that owns its global frame.
-// KIND WIN_BLEND stores the blended eps as [C][Ltot] fp32 and nothing else (ldc_unet_forward_windows).
-// LDS: tile[32][33] fp32 as above -- rows written by 32 consecutive lanes, read transposed at stride 33 dwords: conflict-free.
-// ---------------------------------------------------------------------------------------------
-template <typename T, int KIND>
-__global__ __launch_bounds__(256) void windows_update_kernel(float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
-                                                             void* x_cl, float* ebar, int C, WindowTables wt, StepTables tb,
-                                                             const DdimStep* sched, const int* st) {
-  __shared__ float tile[32][33];
-  const int c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
-  const int Ltot = wt.Ltot, Lw = wt.Lw;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  // the tensor loads do not depend on the step: cover -> (start, weight, eps) and x are issued before the step-state -> table chain
-  int cov[4];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int g = l0 + ty + ii * 8;
-    cov[ii] = g < Ltot ? wt.cover[g] : 0;   // (count 0: a frame behind the recording's end blends nothing and is stored nowhere)
-  }
-  float ev[4], xin[4];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int i = ty + ii * 8;
-    const int g = l0 + i, c = c0 + tx;
-    const int first = cov[ii] & 255, n = cov[ii] >> 8;
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (j < n && c < C) {
-        const int k = first + j, l = g - wt.start[k];
-        const float we = wt.weight[(size_t)k * Lw + l] * dld<T>(eps_cl, ((size_t)k * Lw + l) * C + c);
-        acc = j == 0 ? we : acc + we;
-      }
-    ev[ii] = acc;
-    const int cc = c0 + i, ll = l0 + tx;
-    xin[ii] = (KIND != WIN_BLEND && cc < C && ll < Ltot) ? x[(size_t)cc * Ltot + ll] : 0.f;
-  }
-  int t = 0, j = 0;
-  uint64_t seed = 0;
-  float recip = 0.f, recipm1 = 0.f, c1 = 0.f, c2 = 0.f, sigma = 0.f;
-  DdimStep sp{};
-  bool draw = false;
-  if (KIND != WIN_BLEND) {
-    t = st[0]; j = st[1];
-    seed = ((uint64_t)(unsigned)st[3] << 32) | (uint64_t)(unsigned)st[2];
-    if (KIND == WIN_DDIM) { sp = sched[j]; t = sp.t; }
-    recip = tb.sqrt_recip_alphas_cumprod[t]; recipm1 = tb.sqrt_recipm1_alphas_cumprod[t];
-    if (KIND == WIN_DDPM) {
-      c1 = tb.posterior_mean_coef1[t]; c2 = tb.posterior_mean_coef2[t];
-      sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
-      draw = t > 0;
-    } else {
-      sigma = sp.sigma;
-      draw = !sp.last && sp.sigma > 0.f;
-    }
-  }
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
-  __syncthreads();
-  if (KIND == WIN_BLEND) {
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      const int i = ty + ii * 8;
-      const int c = c0 + i, g = l0 + tx;
-      if (c < C && g < Ltot) ebar[(size_t)c * Ltot + g] = tile[tx][i];
-    }
-    return;
-  }
-  float newv[4];
-  // one Philox block per thread at the index of its first element in the B = 1, L = Ltot layout: what ldc_denoise draws there
-  float zz[4] = {0.f, 0.f, 0.f, 0.f};
-  if (draw && !noise) philox_normal4(seed, (unsigned)j, (uint64_t)(c0 + ty) * Ltot + l0 + tx, zz);
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int i = ty + ii * 8;
-    const int c = c0 + i, g = l0 + tx;
-    newv[ii] = 0.f;
-    if (c < C && g < Ltot) {
-      const size_t idx = (size_t)c * Ltot + g;
-      const float e = tile[tx][i];
-      float v = KIND == WIN_DDPM ? p_sample_mean(recip, recipm1, c1, c2, xin[ii], e) : ddim_mean(sp, recip, recipm1, xin[ii], e);
-      if (draw) v += sigma * (noise ? noise[(size_t)j * noise_step_stride + idx] : zz[ii]);
-      x[idx] = v;
-      newv[ii] = v;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][g]
-  __syncthreads();
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int i = ty + ii * 8;
-    const int g = l0 + i, c = c0 + tx;
-    const int first = cov[ii] & 255, n = cov[ii] >> 8;
-    const float v = tile[tx][i];
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj)
-      if (jj < n && c < C) {
-        const int k = first + jj, l = g - wt.start[k];
-        dst<T>(x_cl, ((size_t)k * Lw + l) * C + c, v);
-      }
-  }
-}
-
-template <typename T>
-static hipError_t launch_windows_update_t(int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
-                                          float* ebar, int C, WindowTables wt, StepTables tb, const DdimStep* sched, const int* st,
-                                          hipStream_t s) {
-  dim3 grid((wt.Ltot + 31) / 32, (C + 31) / 32, 1);
-  if (kind == WIN_BLEND)
-    hipLaunchKernelGGL((windows_update_kernel<T, WIN_BLEND>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st);
-  else if (kind == WIN_DDPM)
-    hipLaunchKernelGGL((windows_update_kernel<T, WIN_DDPM>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st);
-  else
-    hipLaunchKernelGGL((windows_update_kernel<T, WIN_DDIM>), grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st);
-  return hipGetLastError();
-}
-hipError_t launch_windows_update(int dt, int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
-                                 float* ebar, int C, WindowTables wt, StepTables tb, const DdimStep* sched, const int* st, hipStream_t s) {
-  if (kind != WIN_BLEND && kind != WIN_DDPM && kind != WIN_DDIM) return hipErrorInvalidValue;
-  if (wt.Ltot <= 0 || wt.Lw <= 0 || !wt.cover || !wt.weight || !wt.start || (kind == WIN_DDIM && !sched)) return hipErrorInvalidValue;
-  if (kind == WIN_BLEND ? !ebar : (!x || !x_cl || !st)) return hipErrorInvalidValue;
-  if (dt == DT_F32) return launch_windows_update_t<float>(kind, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st, s);
-  return launch_windows_update_t<__bf16>(kind, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, wt, tb, sched, st, s);
-}
-
-// the windows' slices of a [C][Ltot] fp32 sequence as the items of a channels-last batch: y[k][l][c] = x[c][start[k] / div + l]
-// (the to_cl_kernel tiling; div = up for the raw condition, whose windows start at start[k] / up condition frames)
-template <typename T>
-__global__ __launch_bounds__(256) void windows_gather_kernel(const float* x, void* y, int C, int Lw, int Ltot, const int* start, int div) {
-  __shared__ float tile[32][33];
-  const int k = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int s0 = start[k] / div;
-  for (int i = ty; i < 32; i += 8) {
-    const int c = c0 + i, l = l0 + tx;
-    tile[i][tx] = (c < C && l < Lw && s0 + l < Ltot) ? x[(size_t)c * Ltot + s0 + l] : 0.f;
-  }
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8) {
-    const int l = l0 + i, c = c0 + tx;
-    if (l < Lw && c < C) dst<T>(y, ((size_t)k * Lw + l) * C + c, tile[tx][i]);
-  }
-}
-hipError_t launch_windows_gather(int dt, const float* x, void* y, int W, int C, int Lw, int Ltot, const int* start, int div, hipStream_t s) {
-  if (W <= 0 || Lw <= 0 || Ltot < Lw || div < 1 || !start) return hipErrorInvalidValue;
-  dim3 grid((Lw + 31) / 32, (C + 31) / 32, W);
-  if (dt == DT_F32) hipLaunchKernelGGL(windows_gather_kernel<float>, grid, dim3(256), 0, s, x, y, C, Lw, Ltot, start, div);
-  else hipLaunchKernelGGL(windows_gather_kernel<__bf16>, grid, dim3(256), 0, s, x, y, C, Lw, Ltot, start, div);
-  return hipGetLastError();
-}
-
 // the DDIM schedule table written on the stream (kernel arguments carry the entries: no host buffer outlives the call)
 constexpr int kDdimChunk = 64;
 struct DdimChunk { DdimStep e[kDdimChunk]; };
@@ -667,118 +507,23 @@ hipError_t launch_dpm_update(int dt, float* x, const void* eps_cl, float* x0_pre
 }
 
 // ---------------------------------------------------------------------------------------------
-// Coupled windows, kind WIN_DPM ("DPM-Solver++ windows"): the DPM-Solver++(2M) update of dpm_update_kernel on the
-// recording's ONE state x [C][Ltot] with its ONE history x0_prev [C][Ltot], from the blended eps of windows_update_kernel -- a sibling
-// of that template (its instantiations stay as they are): same tiling over GLOBAL frames, same cover / weight / start tables, same
-// blend (w * eps in fp32, window order, the first term assigned), same stores into x and into the row of every covering window of x_cl.
-// The history is loaded only where the entry says has_prev (and is not the last) and written on every iteration but the last; an entry
-// without has_prev never reads it, so it is never cleared.  Nothing is drawn.
-// Load order: cover -> (start, weight, eps) and x do not depend on the step and go first; the history's load depends on the table row
-// (has_prev), so it follows st -> row and is issued in front of the row -> coefficient-table loads and of everything that consumes them.
-// LDS: tile[32][33] fp32, rows written by 32 consecutive lanes, read transposed at stride 33 dwords: conflict-free.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void windows_dpm_update_kernel(float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WindowTables wt,
-                                                                 StepTables tb, const DpmStep* sched, const int* st) {
-  __shared__ float tile[32][33];
-  const int c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
-  const int Ltot = wt.Ltot, Lw = wt.Lw;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  int cov[4];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int g = l0 + ty + ii * 8;
-    cov[ii] = g < Ltot ? wt.cover[g] : 0;   // (count 0: a frame behind the recording's end blends nothing and is stored nowhere)
-  }
-  float ev[4], xin[4], pv[4];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int i = ty + ii * 8;
-    const int g = l0 + i, c = c0 + tx;
-    const int first = cov[ii] & 255, n = cov[ii] >> 8;
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (j < n && c < C) {
-        const int k = first + j, l = g - wt.start[k];
-        const float we = wt.weight[(size_t)k * Lw + l] * dld<T>(eps_cl, ((size_t)k * Lw + l) * C + c);
-        acc = j == 0 ? we : acc + we;
-      }
-    ev[ii] = acc;
-    const int cc = c0 + i, ll = l0 + tx;
-    xin[ii] = (cc < C && ll < Ltot) ? x[(size_t)cc * Ltot + ll] : 0.f;
-  }
-  const DpmStep sp = sched[st[1]];
-  const bool hist = !sp.last && sp.has_prev;   // (uniform over the grid) the only case in which the history is read
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int cc = c0 + ty + ii * 8, ll = l0 + tx;
-    pv[ii] = (hist && cc < C && ll < Ltot) ? x0_prev[(size_t)cc * Ltot + ll] : 0.f;
-  }
-  const float recip = tb.sqrt_recip_alphas_cumprod[sp.t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[sp.t];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
-  __syncthreads();
-  float newv[4];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int i = ty + ii * 8;
-    const int c = c0 + i, g = l0 + tx;
-    newv[ii] = 0.f;
-    if (c < C && g < Ltot) {
-      const size_t idx = (size_t)c * Ltot + g;
-      const float x0 = clipped_x0(recip, recipm1, xin[ii], tile[tx][i]);
-      float v = x0;
-      if (!sp.last) {
-        v = sp.a * xin[ii] + sp.b0 * x0;
-        if (hist) v += sp.b1 * pv[ii];
-        x0_prev[idx] = x0;
-      }
-      x[idx] = v;
-      newv[ii] = v;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = newv[ii];   // tile[c][g]
-  __syncthreads();
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-    const int i = ty + ii * 8;
-    const int g = l0 + i, c = c0 + tx;
-    const int first = cov[ii] & 255, n = cov[ii] >> 8;
-    const float v = tile[tx][i];
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj)
-      if (jj < n && c < C) {
-        const int k = first + jj, l = g - wt.start[k];
-        dst<T>(x_cl, ((size_t)k * Lw + l) * C + c, v);
-      }
-  }
-}
-
-hipError_t launch_windows_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WindowTables wt, StepTables tb,
-                                     const DpmStep* sched, const int* st, hipStream_t s) {
-  if (wt.Ltot <= 0 || wt.Lw <= 0 || !wt.cover || !wt.weight || !wt.start) return hipErrorInvalidValue;
-  if (!x || !eps_cl || !x0_prev || !x_cl || !sched || !st || C <= 0) return hipErrorInvalidValue;
-  dim3 grid((wt.Ltot + 31) / 32, (C + 31) / 32, 1);
-  if (dt == DT_F32) hipLaunchKernelGGL(windows_dpm_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, wt, tb, sched, st);
-  else hipLaunchKernelGGL(windows_dpm_update_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, x0_prev, x_cl, C, wt, tb, sched, st);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Window groups ("Several recordings per call"): the windows of R recordings are the items of ONE batch, every
-// recording keeps its own fp32 state block, cover rows, noise and Philox key.  Sibling kernels of windows_update_kernel /
-// windows_dpm_update_kernel (whose instantiations stay as they are): the same 32 x 32 tiling, walked over a host-built TILE TABLE --
-// blockIdx.x -> {recording, l0}, a recording owns ceil(Ltot_r / 32) tiles, so the recording of a tile is uniform over the workgroup
-// and its table entry arrives through scalar loads.  Inside its recording a tile does what the single-recording kernel does at
-// (Ltot_r, the recording's cover rows): the cover entry counts windows WITHIN the recording, the kernel adds w0_r; x, the eps output,
-// the history and the tape are packed, recording r's [C][Ltot_r] block at C * off_r floats, so the tape index and the Philox block
-// of an element are those of the B = 1, L = Ltot_r call.  Frames of a recording's last tile at or behind Ltot_r have count 0: they
-// blend nothing and are stored nowhere.  One writer per element of every window row, no atomics.
+// Coupled windows: the overlapping windows of R recordings (a single-recording call is R = 1) are the items of
+// ONE batch of the UNet; every recording keeps ONE fp32 state block that all its windows read, its own cover rows, noise and Philox
+// key.  This kernel takes the place of the update launch of a step: the 32 x 32 tiling of p_sample_update_kernel over a recording's
+// GLOBAL frames, walked over a host-built TILE TABLE -- blockIdx.x -> {recording, l0}, a recording owns ceil(Ltot_r / 32) tiles, so the
+// recording of a tile is uniform over the workgroup and its table entry arrives through scalar loads.  A tile reads the cover entry
+// (first window WITHIN the recording | count << 8, count <= 3, consecutive windows; the kernel adds w0_r) of each of its 32 frames,
+// blends the covering windows' eps rows (channels-last, coalesced over c) with the host-built weights in fp32 and in window order -- a
+// singly covered frame is 1.0f * eps --, applies the sampler's arithmetic to x as the B = 1, L = Ltot_r kernels above do, and stores
+// the new state channels-last into the row of EVERY covering window of the UNet's input buffer.  x, the eps output, the history and
+// the tape are packed, recording r's [C][Ltot_r] block at C * off_r floats, so the tape index and the Philox block of an element are
+// those of the B = 1, L = Ltot_r call; the Philox key is the recording table's (launch_windows_group_keys), never the step state's.
+// Frames of a recording's last tile at or behind Ltot_r have count 0: they blend nothing and are stored nowhere.  One writer per
+// element of every window row (the tile that owns its global frame), no atomics.
+// KIND WIN_BLEND stores the blended eps as packed [C][Ltot_r] fp32 and nothing else (ldc_unet_forward_windows / _windows_group).
 // Load order: tile entry -> recording entry -> cover -> (start, weight, eps) and x do not depend on the step and are issued before the
-// step state -> coefficient-table chain.  LDS: tile[32][33] fp32, conflict-free as above.  All offsets size_t.
+// step state -> coefficient-table chain.  LDS: tile[32][33] fp32 -- rows written by 32 consecutive lanes, read transposed at stride
+// 33 dwords: conflict-free.  All offsets size_t.
 // ---------------------------------------------------------------------------------------------
 template <typename T, int KIND>
 __global__ __launch_bounds__(256) void windows_group_update_kernel(float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
@@ -908,8 +653,13 @@ hipError_t launch_windows_group_update(int dt, int kind, float* x, const void* e
   return launch_windows_group_update_t<__bf16>(kind, x, eps_cl, noise, noise_step_stride, x_cl, ebar, C, gt, tb, sched, st, s);
 }
 
-// WIN_DPM of a window group: windows_dpm_update_kernel over the tile table, the history x0_prev packed like x.  The history's load
-// follows st -> row (has_prev) and is issued in front of the row -> coefficient-table loads, as in the single-recording kernel.
+// Kind WIN_DPM ("DPM-Solver++ windows"): the DPM-Solver++(2M) update of dpm_update_kernel on the recordings' states
+// with ONE history block x0_prev [C][Ltot_r] per recording, packed like x, from the blend of windows_group_update_kernel -- same tile
+// table, same cover / weight / start tables, same blend (w * eps in fp32, window order, the first term assigned), same stores into x
+// and into the row of every covering window of x_cl.  The history is loaded only where the entry says has_prev (and is not the last)
+// and written on every iteration but the last; an entry without has_prev never reads it, so it is never cleared.  Nothing is drawn.
+// Load order: as above; the history's load depends on the table row (has_prev), so it follows st -> row and is issued in front of the
+// row -> coefficient-table loads and of everything that consumes them.
 template <typename T>
 __global__ __launch_bounds__(256) void windows_group_dpm_update_kernel(float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C,
                                                                        WinGroupTables gt, StepTables tb, const DpmStep* sched, const int* st) {
@@ -1004,8 +754,8 @@ hipError_t launch_windows_group_dpm_update(int dt, float* x, const void* eps_cl,
   return hipGetLastError();
 }
 
-// windows_gather_kernel with a per-item source: window k of the batch reads the block of ITS recording r = wrec[k] of a packed
-// [C][Ltot_r] sequence -- the block at C * (off_r / div) floats, rows of Ltot_r / div frames -- from start[k] / div
+// the windows' slices of a packed fp32 sequence as the items of a channels-last batch (the to_cl_kernel tiling): window k reads the
+// block of ITS recording r = wrec[k] -- [C][Ltot_r / div] at C * (off_r / div) floats -- from start[k] / div: y[k][l][c] = x_r[c][start[k] / div + l]
 // (div = up for the raw condition: its blocks are [Cc][Ftot_r] at Cc * off_r / up)
 template <typename T>
 __global__ __launch_bounds__(256) void windows_group_gather_kernel(const float* x, void* y, int C, int Lw, WinGroupTables gt, int div) {

@@ -1981,13 +1981,13 @@ static void evict_plan(ldc_ctx* c, size_t idx) {
   c->plans.erase(c->plans.begin() + idx);
 }
 
-int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id, int win_Ltot, int win_O,
-             const std::vector<int>* win_group) {
+int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id, const std::vector<int>* win_lens,
+             int win_O) {
   static const std::vector<int> no_group;
-  const std::vector<int>& wgl = win_group ? *win_group : no_group;   // a window group: the ORDERED list of its recordings' lengths is part of the key
+  const std::vector<int>& wgl = win_lens ? *win_lens : no_group;   // a windows plan: the ORDERED list of its recordings' lengths is part of the key (with L, its effective Lw)
   for (auto& p : c->plans)
     if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged && p->items == items && p->pool_id == pool_id &&
-        p->win_Ltot == win_Ltot && p->win_O == win_O && p->win_group.Ltot == wgl) {
+        p->win_O == win_O && p->win_group.Ltot == wgl) {
       p->last_use = ++c->use_tick;
       *out = p.get();
       return LDC_OK;
@@ -1996,10 +1996,10 @@ int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** ou
   pl->ragged = ragged;
   pl->items = items;
   pl->pool_id = pool_id;
-  pl->win_Ltot = win_Ltot;
   pl->win_O = win_O;
-  pl->win_group.Ltot = wgl;   // (the rest of the group's tables: windows_group_prepare)
-  if (win_group) pl->win_group_id = c->next_win_group_id++;
+  pl->win_group.Ltot = wgl;   // (the rest of the group's tables: windows_prepare)
+  for (int l : wgl) pl->win_Ltot += l;
+  if (win_lens) pl->win_id = c->next_win_id++;
   {   // pass 1: what do the convs of this plan need as split-K workspace?
     Arena dry;
     LDCCHK(build_plan(c, pl.get(), dry, B, L, F));
@@ -2399,20 +2399,13 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
                              sm.kind == SAMPLER_DDIM ? sm.ddim : nullptr));
   }
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
-  if (pl->win_group_id) {   // a window group: the windows plan over R recordings -- x, the tape and the DPM history are packed, the keys are in the recording table
+  if (pl->win_id) {   // coupled windows: x is the recordings' packed state, the blend and the update are one launch (the tape and the DPM history are packed like x, the keys are in the recording table)
     if (h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part");
     if (sm.kind == SAMPLER_DPM)
       HIPCHK(launch_windows_group_dpm_update(c->dt, x, pl->eps_cl, pl->x0_prev, pl->x_cl, c->unet.channels, pl->wg, c->sched, sm.dpm, pl->step_state, s));
     else
       HIPCHK(launch_windows_group_update(c->dt, sm.kind == SAMPLER_DDIM ? WIN_DDIM : WIN_DDPM, x, pl->eps_cl, noise, noise_stride, pl->x_cl, nullptr,
                                          c->unet.channels, pl->wg, c->sched, sm.ddim, pl->step_state, s));
-  } else if (pl->win_Ltot) {   // coupled windows: x is the recording's one state, the blend and the update are one launch (noise: the B = 1, L = Ltot tape)
-    if (h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part");
-    if (sm.kind == SAMPLER_DPM)   // WIN_DPM: x0_prev is the recording's ONE history [C][Ltot] (ensure_windows_history)
-      HIPCHK(launch_windows_dpm_update(c->dt, x, pl->eps_cl, pl->x0_prev, pl->x_cl, c->unet.channels, pl->win, c->sched, sm.dpm, pl->step_state, s));
-    else
-      HIPCHK(launch_windows_update(c->dt, sm.kind == SAMPLER_DDIM ? WIN_DDIM : WIN_DDPM, x, pl->eps_cl, noise, noise_stride, pl->x_cl, nullptr,
-                                   c->unet.channels, pl->win, c->sched, sm.ddim, pl->step_state, s));
   } else if (sm.kind == SAMPLER_DPM)
     HIPCHK(launch_dpm_update(c->dt, x + off, pl->eps_cl, pl->x0_prev, pl->x_cl, pl->B, c->unet.channels, pl->L, c->sched, sm.dpm,
                              pl->step_state, s, pl->ragged ? pl->lens : nullptr));
@@ -2530,8 +2523,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   if (left_forked) *left_forked = false;
   const bool strided = sm.kind != SAMPLER_DDPM;   // a strided schedule, DDIM or DPM: the graph lengths below are theirs alike
   const int L = h.p[0]->L, F = h.p[0]->F;
-  const int wl = h.p[0]->win_Ltot, wo = h.p[0]->win_O;   // a coupled-windows plan: its own graphs, the noise tape of ONE item of wl frames
-  const int wg = h.p[0]->win_group_id;   // a window-group plan (wl: the frames of all its recordings): graphs of that plan alone
+  const int wl = h.p[0]->win_Ltot, wid = h.p[0]->win_id;   // a coupled-windows plan: graphs of that plan alone, the packed noise tape of wl frames (all its recordings')
   const int64_t stride = wl ? (int64_t)c->unet.channels * wl : (int64_t)B * c->unet.channels * L;
   LDCCHK(set_steps(c, h, n_steps - 1, 0, s));   // (DDIM: t is overwritten from the table in every step's first kernel)
   if (c->profile || c->serial_parts || n_steps < 3) {
@@ -2544,7 +2536,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
   const int rag = h.p[0]->ragged ? 1 : 0;   // the steps of ragged plans are graphs of their own, replayed for any set of lengths
   const int kind = sm.kind;   // a loop never replays another sampler's graph (DDPM, DDIM, DPM); all stay cached side by side
   for (auto& g : c->graphs)
-    if (g.B == B && g.L == L && g.F == F && g.sampler == kind && g.ragged == rag && g.pool_id == 0 && g.win_Ltot == wl && g.win_O == wo && g.win_group == wg) sg = &g;
+    if (g.B == B && g.L == L && g.F == F && g.sampler == kind && g.ragged == rag && g.pool_id == 0 && g.win_id == wid) sg = &g;
   if (!sg) {
     // graphs of shapes whose plans are gone were dropped with them (evict_plan); additionally keep at most 16 alive
     if (c->graphs.size() >= 16) {
@@ -2559,7 +2551,7 @@ static int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const floa
     }
     c->graphs.push_back(StepGraph());
     sg = &c->graphs.back();
-    sg->B = B; sg->L = L; sg->F = F; sg->sampler = kind; sg->ragged = rag; sg->win_Ltot = wl; sg->win_O = wo; sg->win_group = wg;
+    sg->B = B; sg->L = L; sg->F = F; sg->sampler = kind; sg->ragged = rag; sg->win_id = wid;
   }
   sg->last_use = ++c->use_tick;
   const bool par = parts_parallel(c, h);
@@ -3420,11 +3412,14 @@ extern "C" int ldc_decode_codes_dpm(ldc_ctx* c, const int64_t* codes, const uint
 }
 
 
-// calls that need no weights (bit-stream layer, resampler, tuning aids): any context of the device will do
-// ---- coupled windows: a recording longer than the UNet's window, decoded on ONE shared latent ---------------------
-// The W overlapping windows of the recording are the items of an ordinary equal-length batch; after every UNet pass their eps are blended
-// per global frame and the recording's single fp32 state is updated from the blend (windows_update_kernel, in place of the update launch).
-// (the builders are the pure functions of ldc_windows.h: WinLayout, win_layout_build, win_parts_split, win_ptr_tables)
+// ---- coupled windows: recordings longer than the UNet's window, each decoded on ONE shared latent -----------------
+// The overlapping windows of R recordings are the items of an ordinary equal-length batch; after every UNet pass their eps are blended per
+// global frame of their recording and the recording's single fp32 state is updated from the blend (windows_group_update_kernel, in place of
+// the update launch).  Every recording keeps its own layout, state block, noise and (DPM) x0 history; the timestep and the schedule are the
+// call's.  x, eps, the history and every step of a tape are packed: recording r's [C][Ltot_r] block at C * off_r floats (off_r: the frames
+// of the recordings in front), the raw condition's [Cc][Ftot_r] block at Cc * off_r / up.  A single-recording call (ldc_*_windows) is the
+// group of one: it differs in its refusals' words, in its one-window case (Ltot <= Lw) and in drawing under the context's Philox epoch.
+// (the builders are the pure functions of ldc_windows.h: WinLayout, win_layout_build, win_parts_split, win_ptr_tables, win_group_build)
 // the layout, the cover table and the weights (double, rounded once to float) of (Ltot, Lw, overlap); every refusal names its value
 static int window_layout(int Ltot, int Lw, int O, int up, int max_windows, WinLayout* out) {
   std::string err;
@@ -3433,17 +3428,8 @@ static int window_layout(int Ltot, int Lw, int O, int up, int max_windows, WinLa
   return LDC_OK;
 }
 
-extern "C" int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out, float* weights_out) {
-  WinLayout lay;
-  LDCCHK(window_layout(Ltot, Lw, overlap, up, kWinPerPart, &lay));
-  if (starts_out)
-    for (int k = 0; k < kWinPerPart; ++k) starts_out[k] = k < lay.W ? lay.start[k] : 0;
-  if (weights_out) std::copy(lay.weight.begin(), lay.weight.end(), weights_out);
-  return lay.W;
-}
-
-// ldc_window_layout for up to max_windows (<= 128) windows: starts_out [max_windows], zero behind W.  For W <= 32 it is
-// ldc_window_layout bit for bit -- one builder serves both.  Host-only: needs no context.  (The calls with a context take 32 windows.)
+// The layout for up to max_windows (<= 128) windows: starts_out [max_windows], zero behind W.  Host-only: needs no context.  (The calls
+// with a context take 32 windows.)
 extern "C" int ldc_window_layout_n(int Ltot, int Lw, int overlap, int up, int max_windows, int* starts_out, float* weights_out) {
   WinLayout lay;
   LDCCHK(window_layout(Ltot, Lw, overlap, up, max_windows, &lay));
@@ -3451,6 +3437,10 @@ extern "C" int ldc_window_layout_n(int Ltot, int Lw, int overlap, int up, int ma
     for (int k = 0; k < max_windows; ++k) starts_out[k] = k < lay.W ? lay.start[k] : 0;
   if (weights_out) std::copy(lay.weight.begin(), lay.weight.end(), weights_out);
   return lay.W;
+}
+
+extern "C" int ldc_window_layout(int Ltot, int Lw, int overlap, int up, int* starts_out, float* weights_out) {
+  return ldc_window_layout_n(Ltot, Lw, overlap, up, kWinPerPart, starts_out, weights_out);
 }
 
 // The partition of W windows into `parts` batch parts of contiguous windows: returns P_eff = min(parts, W) and writes first_out
@@ -3463,291 +3453,9 @@ extern "C" int ldc_window_parts(int W, int parts, int* first_out) {
   return win_parts_split(W, parts, first_out);
 }
 
-// everything a windows call refuses, before any GPU work; then the plan of the layout (made on its first use: the recording's state and
-// the tables in one allocation, uploaded on s) as a one-part Halves -- the blend couples every window at every step, whatever `split` says
-static int windows_prepare(ldc_ctx* c, int Ltot, int Ftot, int Lw, int O, hipStream_t s, Halves* h) {
-  if (c->w8) return fail(LDC_E_INVALID, "coupled windows are not available on the fp8 engine: use dtype bf16 or f32");
-  const int up = upsample_factor(c), q = ragged_latent_quantum(c);
-  if (Ltot <= 0 || Ftot <= 0 || (long long)Ftot * up != Ltot)
-    return fail(LDC_E_INVALID, "Ltot (%d) must equal Ftot (%d) x prod(upsampling_ratios) (%d)", Ltot, Ftot, up);
-  if (Ltot > Lw && (Lw <= 0 || Lw % q)) return fail(LDC_E_INVALID, "Lw %d: a window must be a positive multiple of %d latent frames (the chunk quantum)", Lw, q);
-  WinLayout lay;
-  LDCCHK(window_layout(Ltot, Lw, O, up, kWinPerPart, &lay));
-  *h = Halves();
-  c->call_tick = c->use_tick;
-  Plan* pl = nullptr;
-  LDCCHK(get_plan(c, lay.W, lay.Lw, lay.Lw / up, 0, s, &pl, false, false, 0, Ltot, O));
-  if (!pl->win_base) {
-    const int C = c->unet.channels;
-    const size_t nx = ((size_t)C * Ltot * 4 + 255) / 256 * 256, nc = ((size_t)Ltot * 4 + 255) / 256 * 256;
-    const size_t nw = ((size_t)lay.W * lay.Lw * 4 + 255) / 256 * 256, ns = 256;
-    void* base = nullptr;
-    hipError_t e = hipMalloc(&base, nx + nc + nw + ns);
-    if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the windows state failed: %s", nx + nc + nw + ns, hipGetErrorString(e));
-    pl->win_base = base;
-    pl->win_x = (float*)base;
-    int* cover = (int*)((char*)base + nx);
-    float* weight = (float*)((char*)base + nx + nc);
-    int* start = (int*)((char*)base + nx + nc + nw);
-    pl->win_cover_h = lay.cover; pl->win_weight_h = lay.weight; pl->win_start_h = lay.start;
-    HIPCHK(hipMemcpyAsync(cover, pl->win_cover_h.data(), (size_t)Ltot * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(weight, pl->win_weight_h.data(), (size_t)lay.W * lay.Lw * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(start, pl->win_start_h.data(), (size_t)lay.W * 4, hipMemcpyHostToDevice, s));
-    pl->win = WindowTables{cover, weight, start, Ltot, lay.Lw};
-  }
-  h->n = 1;
-  h->p[0] = pl;
-  h->b0[0] = 0;
-  c->last_halves = *h;
-  return LDC_OK;
-}
-
-// The DPM-Solver++(2M) history of a windows plan: ONE x0_prev [channels][Ltot] fp32 for the recording, in the layout of win_x (not one per
-// window).  Like the parts' histories (ensure_history) it is made by the first DPM call on the plan, outside of any capture, kept in
-// pl->x0_prev until the plan goes -- behind the plan's graphs (evict_plan, drop_plans) -- and never cleared: the first iteration does not load it.
-static int ensure_windows_history(ldc_ctx* c, Plan* pl) {
-  if (pl->x0_prev) return LDC_OK;
-  void* p = nullptr;
-  const size_t bytes = (size_t)c->unet.channels * pl->win_Ltot * 4;
-  hipError_t e = hipMalloc(&p, bytes);
-  if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the windows DPM history failed: %s", bytes, hipGetErrorString(e));
-  pl->x0_prev = (float*)p;
-  return LDC_OK;
-}
-
-// the sampler of a windows loop: the schedule the caller left in c->ddim_host / c->dpm_host goes to the device in front of everything else
-// (before any capture), a DPM loop gets the plan's history
-static int windows_sampler(ldc_ctx* c, Plan* pl, int sampler, hipStream_t s, StepSampler* sm) {
-  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));
-  if (sampler == SAMPLER_DPM) {
-    LDCCHK(dpm_upload(c, s));
-    LDCCHK(ensure_windows_history(c, pl));
-  }
-  sm->kind = sampler;
-  sm->ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
-  sm->dpm = sampler == SAMPLER_DPM ? c->dpm_table : nullptr;
-  return LDC_OK;
-}
-
-// the windows' condition slices from cond [Cc][Ftot] through process_cond, as ldc_unet_forward does at B = W
-static int windows_load_cond(ldc_ctx* c, Plan* pl, const float* cond, int Ftot, hipStream_t s) {
-  HIPCHK(launch_windows_gather(DT_F32, cond, pl->cond_in_cl, pl->B, c->unet.cond_channels, pl->F, Ftot, pl->win.start, upsample_factor(c), s));
-  return run_ops(c, pl, pl->cond_ops, false, s);
-}
-// the windows' input rows from the recording's state
-static int windows_load_x(ldc_ctx* c, Plan* pl, const float* x, hipStream_t s) {
-  HIPCHK(launch_windows_gather(c->dt, x, pl->x_cl, pl->B, c->unet.channels, pl->L, pl->win.Ltot, pl->win.start, 1, s));
-  return LDC_OK;
-}
-
-extern "C" int ldc_unet_forward_windows(ldc_ctx* c, const float* x, int t, const float* cond, int Ltot, int Ftot, int Lw, int overlap,
-                                        float* eps_out, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
-  if (!x || !cond || !eps_out) return fail(LDC_E_INVALID, "null tensor");
-  if (t < 0 || t >= c->unet.timesteps) return fail(LDC_E_INVALID, "t %d: out of range [0, %d)", t, c->unet.timesteps);
-  hipStream_t s = pick_stream(c, stream);
-  Halves h;
-  LDCCHK(windows_prepare(c, Ltot, Ftot, Lw, overlap, s, &h));
-  Plan* pl = h.p[0];
-  LDCCHK(windows_load_cond(c, pl, cond, Ftot, s));
-  LDCCHK(windows_load_x(c, pl, x, s));
-  HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
-  HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
-  LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
-  HIPCHK(launch_windows_update(c->dt, WIN_BLEND, nullptr, pl->eps_cl, nullptr, 0, nullptr, eps_out, c->unet.channels, pl->win, c->sched, nullptr,
-                               nullptr, s));
-  return finish_stream(c, stream);
-}
-
-// the coupled loop on the plan's own state: img [1][C][Ltot] in, the loop, img out
-static int windows_sample(ldc_ctx* c, float* img, const float* cond, const float* noise, int n_steps, int sampler, bool draws, int Ltot,
-                          int Ftot, int Lw, int overlap, void* stream) {
-  hipStream_t s = pick_stream(c, stream);
-  Halves h;
-  LDCCHK(windows_prepare(c, Ltot, Ftot, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
-  Plan* pl = h.p[0];
-  StepSampler sm;
-  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));   // c->ddim_host / c->dpm_host, filled by the caller
-  LDCCHK(windows_load_cond(c, pl, cond, Ftot, s));
-  const size_t nbytes = (size_t)c->unet.channels * Ltot * 4;
-  HIPCHK(hipMemcpyAsync(pl->win_x, img, nbytes, hipMemcpyDeviceToDevice, s));
-  LDCCHK(windows_load_x(c, pl, pl->win_x, s));
-  next_noise_key(c, noise == nullptr && draws);
-  LDCCHK(denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm));
-  HIPCHK(hipMemcpyAsync(img, pl->win_x, nbytes, hipMemcpyDeviceToDevice, s));
-  return finish_stream(c, stream);
-}
-
-extern "C" int ldc_denoise_windows(ldc_ctx* c, float* img, const float* cond, const float* noise, int n_steps, int Ltot, int Ftot, int Lw,
-                                   int overlap, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
-  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
-  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
-  return windows_sample(c, img, cond, noise, n_steps, SAMPLER_DDPM, true, Ltot, Ftot, Lw, overlap, stream);
-}
-
-extern "C" int ldc_ddim_sample_windows(ldc_ctx* c, float* img, const float* cond, const float* noise, int t_start, int n_steps, float eta,
-                                       int Ltot, int Ftot, int Lw, int overlap, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
-  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
-  bool draws = false;
-  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
-  return windows_sample(c, img, cond, noise, n_steps, SAMPLER_DDIM, draws, Ltot, Ftot, Lw, overlap, stream);
-}
-
-// DPM-Solver++(2M) on coupled windows, as ldc_dpm_sample at B = 1: deterministic, nothing is drawn, the Philox epoch stays where it is
-extern "C" int ldc_dpm_sample_windows(ldc_ctx* c, float* img, const float* cond, int t_start, int n_steps, int Ltot, int Ftot, int Lw, int overlap,
-                                      void* stream) {
-  LDCCHK(dpm_front_args(t_start, n_steps));
-  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
-  LDCCHK(dpm_schedule(c, t_start, n_steps));
-  return windows_sample(c, img, cond, nullptr, n_steps, SAMPLER_DPM, false, Ltot, Ftot, Lw, overlap, stream);
-}
-
-// ldc_decode / ldc_decode_ddim / ldc_decode_dpm (src.wav) or ldc_decode_codes / _ddim / _dpm (src.codes | src.packed) at B = 1 with the
-// denoise loop replaced by the coupled loop: the condition rows (get_cond, or the dequantised codes) and the normalised start image over
-// the whole recording, the windows' loop on the shared latent, the SEANet decoder over the whole latent, output_normalise
-static int decode_windows_body(ldc_ctx* c, const FrontSrc& src, int T, int n_steps, int sampler, bool draws, const float* noise, int Lw, int overlap,
-                               float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
-  const Codec& cc = c->codec[LDC_MODEL_COND];
-  const Codec& mc = c->codec[LDC_MODEL_MAIN];
-  if (T % cc.hop || T % mc.hop) return fail(LDC_E_INVALID, "T %d: must be a multiple of %d and %d (sample.py:87 trims to 640)", T, cc.hop, mc.hop);
-  const int F = T / cc.hop, L = T / mc.hop, D = c->cfg.rep_dims;
-  LDCCHK(check_unet_args(c, 1, L, F));
-  hipStream_t s = pick_stream(c, stream);
-  Halves h;
-  LDCCHK(windows_prepare(c, L, F, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
-  LDCCHK(ensure_outnorm(c, 1));
-  Plan* pl = h.p[0];
-  StepSampler sm;
-  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));
-  LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
-    float* mx = (float*)ar.alloc(4);
-    float* qr = nullptr;
-    int Fq = 0;
-    if (src.wav) {
-      LDCCHK(get_cond_rows(c, src.wav, 1, T, 0.f, ar, dry, s, &qr, &Fq, codes_out, 1));
-    } else {   // the receiver: quantizer.decode(codes) over the whole recording, as decode_body at B = 1 (bad code values raise the device flag)
-      qr = (float*)ar.alloc((size_t)F * D * 4);
-      Fq = F;
-      if (!dry)
-        HIPCHK(launch_rvq_dequant(src.codes, src.packed, src.packed_stride, src.bits, src.n_q, 1, 0, 1, F, cc.codebooks, cc.bins, D, qr,
-                                  c->dev_flag_dev, s, nullptr));
-    }
-    if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
-    void* up = nullptr;
-    int Lu = 0;
-    LDCCHK(upsample_rows(c, qr, 1, F, ar, dry, s, &up, &Lu));
-    if (!dry) {
-      if (cond_out) HIPCHK(launch_from_cl(DT_F32, qr, cond_out, 1, D, F, nullptr, 0, 0.f, s));
-      // start image: upsample, /= max|.|+1e-8 over the whole recording (sample.py:125-129), straight into the plan's state
-      HIPCHK(hipMemsetAsync(mx, 0, 4, s));
-      HIPCHK(launch_maxabs(DT_F32, up, 1, (int64_t)L * D, 0, mx, s));
-      HIPCHK(launch_from_cl(DT_F32, up, pl->win_x, 1, D, L, mx, 0, 1e-8f, s));
-      // process_cond per window: the rows are channels-last fp32 already, a window's slice is one contiguous run of them
-      const int Fw = pl->F, upf = upsample_factor(c);
-      for (int k = 0; k < pl->B; ++k)
-        HIPCHK(hipMemcpyAsync((float*)pl->cond_in_cl + (size_t)k * Fw * D, qr + (size_t)(pl->win_start_h[k] / upf) * D, (size_t)Fw * D * 4,
-                              hipMemcpyDeviceToDevice, s));
-      LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
-      LDCCHK(windows_load_x(c, pl, pl->win_x, s));
-      next_noise_key(c, noise == nullptr && draws);
-      LDCCHK(denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm));
-      if (latents_out) HIPCHK(hipMemcpyAsync(latents_out, pl->win_x, (size_t)D * L * 4, hipMemcpyDeviceToDevice, s));
-    }
-    // decoder over the whole latent (quirk Q3: no x18 un-scaling on this path, sample.py:131)
-    SeaRun R{c, &ar, s, dry, 1};
-    void* zc = ar.alloc((size_t)L * D * 4);
-    if (!dry) HIPCHK(launch_to_cl(DT_F32, pl->win_x, zc, 1, D, L, nullptr, 0, 0.f, s));
-    void* y = nullptr;
-    int Lo = 0, Cd = 0;
-    LDCCHK(run_seanet(R, mc.dec, zc, L, &y, &Lo, &Cd));
-    if (!dry) {
-      HIPCHK(hipMemcpyAsync(wav_out, y, (size_t)Lo * 4, hipMemcpyDeviceToDevice, s));
-      HIPCHK(launch_output_normalise(wav_out, 1, Lo, 0, c->outnorm_ws, s, nullptr, mc.hop));
-    }
-    return LDC_OK;
-  }));
-  return finish_stream(c, stream);
-}
-
-extern "C" int ldc_decode_windows(ldc_ctx* c, const float* wav, int T, int n_steps, const float* noise, int Lw, int overlap, float* wav_out,
-                                  float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
-  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
-  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
-  FrontSrc src;
-  src.wav = wav;
-  return decode_windows_body(c, src, T, n_steps, SAMPLER_DDPM, true, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
-}
-
-extern "C" int ldc_decode_ddim_windows(ldc_ctx* c, const float* wav, int T, int t_start, int n_steps, float eta, const float* noise, int Lw,
-                                       int overlap, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
-  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
-  bool draws = false;
-  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
-  FrontSrc src;
-  src.wav = wav;
-  return decode_windows_body(c, src, T, n_steps, SAMPLER_DDIM, draws, noise, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
-}
-
-// ldc_decode_dpm of one recording with the loop on coupled windows: no eta, no noise, the Philox epoch stays where it is
-extern "C" int ldc_decode_dpm_windows(ldc_ctx* c, const float* wav, int T, int t_start, int n_steps, int Lw, int overlap, float* wav_out,
-                                      float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
-  LDCCHK(dpm_front_args(t_start, n_steps));
-  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
-  LDCCHK(dpm_schedule(c, t_start, n_steps));
-  FrontSrc src;
-  src.wav = wav;
-  return decode_windows_body(c, src, T, n_steps, SAMPLER_DPM, false, nullptr, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream);
-}
-
-// The receiver on coupled windows: ldc_decode_windows / ldc_decode_ddim_windows from the RVQ codes of ONE recording of Ftot condition
-// frames (int64 codes [n_q][1][Ftot] or the packed payload, as ldc_decode_codes).  t_start 0: DDPM halfway sampling of n_steps (eta is not
-// used); > 0: DDIM -- the convention of ldc_decode_codes_ragged.  The context-free refusals come first (a NULL context sees them too).
-extern "C" int ldc_decode_codes_windows(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int Ftot,
-                                        int t_start, int n_steps, float eta, const float* noise, int Lw, int overlap, float* wav_out,
-                                        float* latents_out, float* cond_out, void* stream) {
-  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, 1, Ftot, wav_out));
-  if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "eta %g: must be a finite value in [0, 1]", (double)eta);
-  if (t_start < 0) return fail(LDC_E_INVALID, "t_start %d: must be >= 0 (0: DDPM halfway sampling)", t_start);
-  if (n_steps < 1) return fail(LDC_E_INVALID, "n_steps %d: must be >= 1", n_steps);
-  if (t_start > 0 && n_steps > t_start)
-    return fail(LDC_E_INVALID, "n_steps %d: must be in [1, t_start = %d] (more would repeat timesteps)", n_steps, t_start);
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
-  FrontSrc src;
-  int T = 0;
-  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Ftot, &src, &T));
-  bool draws = true;
-  if (t_start > 0) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
-  else if (n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
-  return decode_windows_body(c, src, T, n_steps, t_start > 0 ? SAMPLER_DDIM : SAMPLER_DDPM, draws, noise, Lw, overlap, wav_out, latents_out, cond_out,
-                             nullptr, stream);
-}
-
-extern "C" int ldc_decode_codes_dpm_windows(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
-                                            int Ftot, int t_start, int n_steps, int Lw, int overlap, float* wav_out, float* latents_out,
-                                            float* cond_out, void* stream) {
-  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, 1, Ftot, wav_out));
-  LDCCHK(dpm_front_args(t_start, n_steps));
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
-  FrontSrc src;
-  int T = 0;
-  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Ftot, &src, &T));
-  LDCCHK(dpm_schedule(c, t_start, n_steps));
-  return decode_windows_body(c, src, T, n_steps, SAMPLER_DPM, false, nullptr, Lw, overlap, wav_out, latents_out, cond_out, nullptr, stream);
-}
-
-// ---- window groups ("Several recordings per call"): R recordings, the windows of all of them in ONE batch -----------
-// Every recording keeps its own layout, fp32 state block, noise and (DPM) x0 history; its eps are blended from its own windows only.  The
-// timestep and the schedule are the call's.  x, eps, the history and every step of a tape are packed: recording r's [C][Ltot_r] block at
-// C * off_r floats (off_r: the frames of the recordings in front), the raw condition's [Cc][Ftot_r] block at Cc * off_r / up.
-static int window_group(int R, const int* Ltot, int Lw, int O, int up, WinGroup* out) {
+static int window_group(int R, const int* Ltot, int Lw, int O, int up, WinGroup* out, bool single = false) {
   std::string err;
-  const int rc = win_group_build(R, Ltot, Lw, O, up, out, &err);
+  const int rc = win_group_build(R, Ltot, Lw, O, up, out, &err, single);
   if (rc) return fail(rc == 1 ? LDC_E_INVALID : LDC_E_STATE, "%s", err.c_str());
   return LDC_OK;
 }
@@ -3764,26 +3472,31 @@ extern "C" int ldc_window_group_layout(int R, const int* Ltot, int Lw, int overl
   return g.W_sum;
 }
 
-// what windows_prepare is to one recording: every refusal before any GPU work, then the group's plan -- the windows plan at B = W_sum with
-// the packed state, the tables, the recording table and the tile table in its one allocation (made and uploaded on its first use)
-static int windows_group_prepare(ldc_ctx* c, int R, const int* Ltot, const int* Ftot, int Lw, int O, hipStream_t s, Halves* h) {
+// everything a windows call refuses, before any GPU work (on the caller's Lw and overlap, in the words of a single-recording call where
+// `single`); then the plan of the layout -- the windows plan at B = W_sum with the packed state, the tables, the recording table and the
+// tile table in its one allocation (made and uploaded on s on its first use) -- as a one-part Halves: the blend couples every window at
+// every step, whatever `split` says
+static int windows_prepare(ldc_ctx* c, int R, const int* Ltot, const int* Ftot, int Lw, int O, hipStream_t s, Halves* h, bool single) {
   if (c->w8) return fail(LDC_E_INVALID, "coupled windows are not available on the fp8 engine: use dtype bf16 or f32");
   if (R < 1 || R > kWinPerPart) return fail(LDC_E_INVALID, "R %d: a window group holds 1 to %d recordings", R, kWinPerPart);
   if (!Ltot || !Ftot) return fail(LDC_E_INVALID, "null list of lengths");
   const int up = upsample_factor(c), q = ragged_latent_quantum(c);
   bool longer = false;
   for (int r = 0; r < R; ++r) {
-    if (Ltot[r] <= 0 || Ftot[r] <= 0 || (long long)Ftot[r] * up != Ltot[r])
+    if (Ltot[r] <= 0 || Ftot[r] <= 0 || (long long)Ftot[r] * up != Ltot[r]) {
+      if (single) return fail(LDC_E_INVALID, "Ltot (%d) must equal Ftot (%d) x prod(upsampling_ratios) (%d)", Ltot[r], Ftot[r], up);
       return fail(LDC_E_INVALID, "recording %d: Ltot (%d) must equal Ftot (%d) x prod(upsampling_ratios) (%d)", r, Ltot[r], Ftot[r], up);
+    }
     longer = longer || Ltot[r] > Lw;
   }
   if (longer && (Lw <= 0 || Lw % q)) return fail(LDC_E_INVALID, "Lw %d: a window must be a positive multiple of %d latent frames (the chunk quantum)", Lw, q);
   WinGroup g;
-  LDCCHK(window_group(R, Ltot, Lw, O, up, &g));
+  LDCCHK(window_group(R, Ltot, Lw, O, up, &g, single));
+  Lw = g.Lw;   // (a single recording no longer than the window is its one window)
   *h = Halves();
   c->call_tick = c->use_tick;
   Plan* pl = nullptr;
-  LDCCHK(get_plan(c, g.W_sum, Lw, Lw / up, 0, s, &pl, false, false, 0, g.Lsum, O, &g.Ltot));
+  LDCCHK(get_plan(c, g.W_sum, Lw, Lw / up, 0, s, &pl, false, false, 0, &g.Ltot, O));
   if (!pl->win_base) {
     const int C = c->unet.channels;
     auto pad = [](size_t n) { return (n + 255) / 256 * 256; };
@@ -3792,7 +3505,7 @@ static int windows_group_prepare(ldc_ctx* c, int R, const int* Ltot, const int* 
     const size_t total = nx + nc + nw + 2 * ns + nr + nt;
     void* base = nullptr;
     hipError_t e = hipMalloc(&base, total);
-    if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the window group's state failed: %s", total, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the windows state failed: %s", total, hipGetErrorString(e));
     pl->win_base = base;
     pl->win_x = (float*)base;
     char* p = (char*)base + nx;
@@ -3820,33 +3533,292 @@ static int windows_group_prepare(ldc_ctx* c, int R, const int* Ltot, const int* 
   return LDC_OK;
 }
 
-static int windows_group_load_cond(ldc_ctx* c, Plan* pl, const float* cond, hipStream_t s) {
+// The DPM-Solver++(2M) history of a windows plan: ONE x0_prev [channels][Ltot_r] fp32 block per recording, in the layout of win_x (not one
+// per window).  Like the parts' histories (ensure_history) it is made by the first DPM call on the plan, outside of any capture, kept in
+// pl->x0_prev until the plan goes -- behind the plan's graphs (evict_plan, drop_plans) -- and never cleared: the first iteration does not load it.
+static int ensure_windows_history(ldc_ctx* c, Plan* pl) {
+  if (pl->x0_prev) return LDC_OK;
+  void* p = nullptr;
+  const size_t bytes = (size_t)c->unet.channels * pl->win_Ltot * 4;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the windows DPM history failed: %s", bytes, hipGetErrorString(e));
+  pl->x0_prev = (float*)p;
+  return LDC_OK;
+}
+
+// the sampler of a windows loop: the schedule the caller left in c->ddim_host / c->dpm_host goes to the device in front of everything else
+// (before any capture), a DPM loop gets the plan's history
+static int windows_sampler(ldc_ctx* c, Plan* pl, int sampler, hipStream_t s, StepSampler* sm) {
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));
+  if (sampler == SAMPLER_DPM) {
+    LDCCHK(dpm_upload(c, s));
+    LDCCHK(ensure_windows_history(c, pl));
+  }
+  sm->kind = sampler;
+  sm->ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
+  sm->dpm = sampler == SAMPLER_DPM ? c->dpm_table : nullptr;
+  return LDC_OK;
+}
+
+// the windows' condition slices from the packed cond ([Cc][Ftot_r] blocks) through process_cond, as ldc_unet_forward does at B = W_sum
+static int windows_load_cond(ldc_ctx* c, Plan* pl, const float* cond, hipStream_t s) {
   HIPCHK(launch_windows_group_gather(DT_F32, cond, pl->cond_in_cl, pl->B, c->unet.cond_channels, pl->F, pl->wg, upsample_factor(c), s));
   return run_ops(c, pl, pl->cond_ops, false, s);
 }
-static int windows_group_load_x(ldc_ctx* c, Plan* pl, const float* x, hipStream_t s) {
+// the windows' input rows from the recordings' packed state
+static int windows_load_x(ldc_ctx* c, Plan* pl, const float* x, hipStream_t s) {
   HIPCHK(launch_windows_group_gather(c->dt, x, pl->x_cl, pl->B, c->unet.channels, pl->L, pl->wg, 1, s));
   return LDC_OK;
 }
 
-// ldc_unet_forward_windows of R recordings in one batch: x, eps_out packed [C][Ltot_r] blocks, cond packed [Cc][Ftot_r] blocks
-extern "C" int ldc_unet_forward_windows_group(ldc_ctx* c, const float* x, int t, const float* cond, int R, const int* Ltot, const int* Ftot, int Lw,
-                                              int overlap, float* eps_out, void* stream) {
+// one UNet pass over the windows and the blend of their eps: x, eps_out packed [C][Ltot_r] blocks, cond packed [Cc][Ftot_r] blocks
+static int unet_forward_windows(ldc_ctx* c, const float* x, int t, const float* cond, int R, const int* Ltot, const int* Ftot, int Lw, int overlap,
+                                float* eps_out, void* stream, bool single) {
   LDCCHK(check_ready(c, LDC_MODEL_MAIN));
   if (!x || !cond || !eps_out) return fail(LDC_E_INVALID, "null tensor");
   if (t < 0 || t >= c->unet.timesteps) return fail(LDC_E_INVALID, "t %d: out of range [0, %d)", t, c->unet.timesteps);
   hipStream_t s = pick_stream(c, stream);
   Halves h;
-  LDCCHK(windows_group_prepare(c, R, Ltot, Ftot, Lw, overlap, s, &h));
+  LDCCHK(windows_prepare(c, R, Ltot, Ftot, Lw, overlap, s, &h, single));
   Plan* pl = h.p[0];
-  LDCCHK(windows_group_load_cond(c, pl, cond, s));
-  LDCCHK(windows_group_load_x(c, pl, x, s));
+  LDCCHK(windows_load_cond(c, pl, cond, s));
+  LDCCHK(windows_load_x(c, pl, x, s));
   HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
   HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
   LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
   HIPCHK(launch_windows_group_update(c->dt, WIN_BLEND, nullptr, pl->eps_cl, nullptr, 0, nullptr, eps_out, c->unet.channels, pl->wg, c->sched, nullptr,
                                      nullptr, s));
   return finish_stream(c, stream);
+}
+
+extern "C" int ldc_unet_forward_windows(ldc_ctx* c, const float* x, int t, const float* cond, int Ltot, int Ftot, int Lw, int overlap,
+                                        float* eps_out, void* stream) {
+  return unet_forward_windows(c, x, t, cond, 1, &Ltot, &Ftot, Lw, overlap, eps_out, stream, true);
+}
+
+extern "C" int ldc_unet_forward_windows_group(ldc_ctx* c, const float* x, int t, const float* cond, int R, const int* Ltot, const int* Ftot, int Lw,
+                                              int overlap, float* eps_out, void* stream) {
+  return unet_forward_windows(c, x, t, cond, R, Ltot, Ftot, Lw, overlap, eps_out, stream, false);
+}
+
+// the coupled loop on the plan's packed state; the update kernels draw under the recording table's keys, which go in on the stream in
+// front of the loop.  A single-recording call (`single`) draws as ldc_denoise at B = 1 does: under the key of the context's Philox epoch,
+// which a drawing call without a tape advances (`draws`).  A group call neither reads nor advances the epoch (as decode pools, section
+// 5e): recording r draws under seeds[r] at epoch 0, and a call with a tape leaves the keys zero.
+static int windows_loop(ldc_ctx* c, const Halves& h, const StepSampler& sm, const float* noise, const uint64_t* seeds, bool single, bool draws,
+                        int n_steps, hipStream_t s) {
+  Plan* pl = h.p[0];
+  if (single) next_noise_key(c, noise == nullptr && draws);
+  HIPCHK(launch_windows_group_keys(pl->wg_rec, single ? &c->cur_key : (noise ? nullptr : seeds), pl->wg.R, s));
+  return denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm);
+}
+
+// img (packed [C][Ltot_r] blocks) in, the coupled loop on the plan's own state, img out
+static int windows_sample(ldc_ctx* c, float* img, const float* cond, const float* noise, const uint64_t* seeds, int n_steps, int sampler, bool draws,
+                          int R, const int* Ltot, const int* Ftot, int Lw, int overlap, void* stream, bool single) {
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_prepare(c, R, Ltot, Ftot, Lw, overlap, s, &h, single));   // (every refusal, before any GPU work)
+  Plan* pl = h.p[0];
+  StepSampler sm;
+  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));   // c->ddim_host / c->dpm_host, filled by the caller
+  LDCCHK(windows_load_cond(c, pl, cond, s));
+  const size_t nbytes = (size_t)c->unet.channels * pl->win_Ltot * 4;
+  HIPCHK(hipMemcpyAsync(pl->win_x, img, nbytes, hipMemcpyDeviceToDevice, s));
+  LDCCHK(windows_load_x(c, pl, pl->win_x, s));
+  LDCCHK(windows_loop(c, h, sm, noise, seeds, single, draws, n_steps, s));
+  HIPCHK(hipMemcpyAsync(img, pl->win_x, nbytes, hipMemcpyDeviceToDevice, s));
+  return finish_stream(c, stream);
+}
+
+extern "C" int ldc_denoise_windows(ldc_ctx* c, float* img, const float* cond, const float* noise, int n_steps, int Ltot, int Ftot, int Lw,
+                                   int overlap, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+  return windows_sample(c, img, cond, noise, nullptr, n_steps, SAMPLER_DDPM, true, 1, &Ltot, &Ftot, Lw, overlap, stream, true);
+}
+
+extern "C" int ldc_ddim_sample_windows(ldc_ctx* c, float* img, const float* cond, const float* noise, int t_start, int n_steps, float eta,
+                                       int Ltot, int Ftot, int Lw, int overlap, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  bool draws = false;
+  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  return windows_sample(c, img, cond, noise, nullptr, n_steps, SAMPLER_DDIM, draws, 1, &Ltot, &Ftot, Lw, overlap, stream, true);
+}
+
+// DPM-Solver++(2M) on coupled windows, as ldc_dpm_sample at B = 1: deterministic, nothing is drawn, the Philox epoch stays where it is
+extern "C" int ldc_dpm_sample_windows(ldc_ctx* c, float* img, const float* cond, int t_start, int n_steps, int Ltot, int Ftot, int Lw, int overlap,
+                                      void* stream) {
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  return windows_sample(c, img, cond, nullptr, nullptr, n_steps, SAMPLER_DPM, false, 1, &Ltot, &Ftot, Lw, overlap, stream, true);
+}
+
+// ldc_decode / ldc_decode_ddim / ldc_decode_dpm (src.wav) or ldc_decode_codes / _ddim / _dpm (src.codes | src.packed; R = 1 only) with the
+// denoise loop replaced by ONE coupled loop over the windows of R recordings.  The codec ends run per recording: the condition rows
+// (get_cond_rows at B = 1, or the dequantised codes) and the start image normalised over that recording, the SEANet decoder over that
+// recording's latent, output_normalise for that recording.  src.wav and wav_out are packed (recording r's T[r] samples behind those in
+// front), latents_out [D][Ltot_r] blocks, cond_out [D][Ftot_r] blocks, codes_out [n_q][Ftot_r] blocks.
+static int decode_windows_body(ldc_ctx* c, const FrontSrc& src, int R, const int* T, int n_steps, int sampler, bool draws, const float* noise,
+                               const uint64_t* seeds, int Lw, int overlap, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out,
+                               void* stream, bool single) {
+  const Codec& cc = c->codec[LDC_MODEL_COND];
+  const Codec& mc = c->codec[LDC_MODEL_MAIN];
+  const int D = c->cfg.rep_dims;
+  if (!src.wav && R != 1) return fail(LDC_E_STATE, "internal: the receiver's windows decode one recording");
+  std::vector<int> Lr((size_t)R), Fr((size_t)R);
+  std::vector<size_t> toff((size_t)R + 1, 0);
+  for (int r = 0; r < R; ++r) {
+    if (T[r] <= 0 || T[r] % cc.hop || T[r] % mc.hop) {
+      if (single) return fail(LDC_E_INVALID, "T %d: must be a multiple of %d and %d (sample.py:87 trims to 640)", T[r], cc.hop, mc.hop);
+      return fail(LDC_E_INVALID, "recording %d: T %d: must be a positive multiple of %d and %d (sample.py:87 trims to 640)", r, T[r], cc.hop, mc.hop);
+    }
+    Fr[r] = T[r] / cc.hop; Lr[r] = T[r] / mc.hop;
+    LDCCHK(check_unet_args(c, 1, Lr[r], Fr[r]));
+    toff[r + 1] = toff[r] + (size_t)T[r];
+  }
+  hipStream_t s = pick_stream(c, stream);
+  Halves h;
+  LDCCHK(windows_prepare(c, R, Lr.data(), Fr.data(), Lw, overlap, s, &h, single));   // (every refusal, before any GPU work)
+  LDCCHK(ensure_outnorm(c, 1));
+  Plan* pl = h.p[0];
+  StepSampler sm;
+  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));
+  const WinGroup& g = pl->win_group;
+  const int n_q = n_q_for_bandwidth(c, 0.f);
+  LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
+    float* mx = (float*)ar.alloc((size_t)R * 4);
+    const int Fw = pl->F, upf = upsample_factor(c);
+    for (int r = 0; r < R; ++r) {
+      const int F = Fr[r], L = Lr[r];
+      const size_t foff = (size_t)g.off[r] / upf;
+      float* qr = nullptr;
+      int Fq = 0;
+      if (src.wav) {
+        LDCCHK(get_cond_rows(c, src.wav + toff[r], 1, T[r], 0.f, ar, dry, s, &qr, &Fq, codes_out ? codes_out + (size_t)n_q * foff : nullptr, 1));
+      } else {   // the receiver: quantizer.decode(codes) over the whole recording, as decode_body at B = 1 (bad code values raise the device flag)
+        qr = (float*)ar.alloc((size_t)F * D * 4);
+        Fq = F;
+        if (!dry)
+          HIPCHK(launch_rvq_dequant(src.codes, src.packed, src.packed_stride, src.bits, src.n_q, 1, 0, 1, F, cc.codebooks, cc.bins, D, qr,
+                                    c->dev_flag_dev, s, nullptr));
+      }
+      if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
+      void* up = nullptr;
+      int Lu = 0;
+      LDCCHK(upsample_rows(c, qr, 1, F, ar, dry, s, &up, &Lu));
+      if (!dry) {
+        if (cond_out) HIPCHK(launch_from_cl(DT_F32, qr, cond_out + (size_t)D * foff, 1, D, F, nullptr, 0, 0.f, s));
+        // start image: upsample, /= max|.|+1e-8 over the whole recording (sample.py:125-129), straight into the plan's state
+        HIPCHK(hipMemsetAsync(mx + r, 0, 4, s));
+        HIPCHK(launch_maxabs(DT_F32, up, 1, (int64_t)L * D, 0, mx + r, s));
+        HIPCHK(launch_from_cl(DT_F32, up, pl->win_x + (size_t)D * g.off[r], 1, D, L, mx + r, 0, 1e-8f, s));
+        // process_cond per window: the rows are channels-last fp32 already, a window's slice is one contiguous run of its recording's rows
+        for (int k = g.w0[r]; k < g.w0[r + 1]; ++k)
+          HIPCHK(hipMemcpyAsync((float*)pl->cond_in_cl + (size_t)k * Fw * D, qr + (size_t)(g.start[k] / upf) * D, (size_t)Fw * D * 4,
+                                hipMemcpyDeviceToDevice, s));
+      }
+    }
+    if (!dry) {
+      LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
+      LDCCHK(windows_load_x(c, pl, pl->win_x, s));
+      LDCCHK(windows_loop(c, h, sm, noise, seeds, single, draws, n_steps, s));
+      if (latents_out) HIPCHK(hipMemcpyAsync(latents_out, pl->win_x, (size_t)D * g.Lsum * 4, hipMemcpyDeviceToDevice, s));
+    }
+    for (int r = 0; r < R; ++r) {   // decoder over each recording's latent (quirk Q3: no x18 un-scaling on this path, sample.py:131)
+      const int L = Lr[r];
+      SeaRun Rn{c, &ar, s, dry, 1};
+      void* zc = ar.alloc((size_t)L * D * 4);
+      if (!dry) HIPCHK(launch_to_cl(DT_F32, pl->win_x + (size_t)D * g.off[r], zc, 1, D, L, nullptr, 0, 0.f, s));
+      void* y = nullptr;
+      int Lo = 0, Cd = 0;
+      LDCCHK(run_seanet(Rn, mc.dec, zc, L, &y, &Lo, &Cd));
+      if (!dry) {
+        if (Lo != T[r]) return fail(LDC_E_STATE, "internal: the decoder gave %d samples for recording %d of %d", Lo, r, T[r]);
+        HIPCHK(hipMemcpyAsync(wav_out + toff[r], y, (size_t)Lo * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(launch_output_normalise(wav_out + toff[r], 1, Lo, 0, c->outnorm_ws, s, nullptr, mc.hop));
+      }
+    }
+    return LDC_OK;
+  }));
+  return finish_stream(c, stream);
+}
+
+extern "C" int ldc_decode_windows(ldc_ctx* c, const float* wav, int T, int n_steps, const float* noise, int Lw, int overlap, float* wav_out,
+                                  float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_windows_body(c, src, 1, &T, n_steps, SAMPLER_DDPM, true, noise, nullptr, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream,
+                             true);
+}
+
+extern "C" int ldc_decode_ddim_windows(ldc_ctx* c, const float* wav, int T, int t_start, int n_steps, float eta, const float* noise, int Lw,
+                                       int overlap, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  bool draws = false;
+  LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  FrontSrc src;
+  src.wav = wav;
+  return decode_windows_body(c, src, 1, &T, n_steps, SAMPLER_DDIM, draws, noise, nullptr, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream,
+                             true);
+}
+
+// ldc_decode_dpm of one recording with the loop on coupled windows: no eta, no noise, the Philox epoch stays where it is
+extern "C" int ldc_decode_dpm_windows(ldc_ctx* c, const float* wav, int T, int t_start, int n_steps, int Lw, int overlap, float* wav_out,
+                                      float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  if (!wav || !wav_out || T <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  FrontSrc src;
+  src.wav = wav;
+  return decode_windows_body(c, src, 1, &T, n_steps, SAMPLER_DPM, false, nullptr, nullptr, Lw, overlap, wav_out, latents_out, cond_out, codes_out, stream,
+                             true);
+}
+
+// The receiver on coupled windows: ldc_decode_windows / ldc_decode_ddim_windows from the RVQ codes of ONE recording of Ftot condition
+// frames (int64 codes [n_q][1][Ftot] or the packed payload, as ldc_decode_codes).  t_start 0: DDPM halfway sampling of n_steps (eta is not
+// used); > 0: DDIM -- the convention of ldc_decode_codes_ragged.  The context-free refusals come first (a NULL context sees them too).
+extern "C" int ldc_decode_codes_windows(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int Ftot,
+                                        int t_start, int n_steps, float eta, const float* noise, int Lw, int overlap, float* wav_out,
+                                        float* latents_out, float* cond_out, void* stream) {
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, 1, Ftot, wav_out));
+  if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "eta %g: must be a finite value in [0, 1]", (double)eta);
+  if (t_start < 0) return fail(LDC_E_INVALID, "t_start %d: must be >= 0 (0: DDPM halfway sampling)", t_start);
+  if (n_steps < 1) return fail(LDC_E_INVALID, "n_steps %d: must be >= 1", n_steps);
+  if (t_start > 0 && n_steps > t_start)
+    return fail(LDC_E_INVALID, "n_steps %d: must be in [1, t_start = %d] (more would repeat timesteps)", n_steps, t_start);
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Ftot, &src, &T));
+  bool draws = true;
+  if (t_start > 0) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  else if (n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+  return decode_windows_body(c, src, 1, &T, n_steps, t_start > 0 ? SAMPLER_DDIM : SAMPLER_DDPM, draws, noise, nullptr, Lw, overlap, wav_out, latents_out,
+                             cond_out, nullptr, stream, true);
+}
+
+extern "C" int ldc_decode_codes_dpm_windows(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q,
+                                            int Ftot, int t_start, int n_steps, int Lw, int overlap, float* wav_out, float* latents_out,
+                                            float* cond_out, void* stream) {
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, 1, Ftot, wav_out));
+  LDCCHK(dpm_front_args(t_start, n_steps));
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Ftot, &src, &T));
+  LDCCHK(dpm_schedule(c, t_start, n_steps));
+  return decode_windows_body(c, src, 1, &T, n_steps, SAMPLER_DPM, false, nullptr, nullptr, Lw, overlap, wav_out, latents_out, cond_out, nullptr, stream,
+                             true);
 }
 
 // The front of a group sampler call, the refusals of ldc_denoise_windows / ldc_ddim_sample_windows / ldc_dpm_sample_windows in their order
@@ -3877,110 +3849,24 @@ static int windows_group_front(ldc_ctx* c, int sampler, int t_start, int n_steps
   return LDC_OK;
 }
 
-// the coupled loop of the group on the plan's packed state; the keys go to the recording table on the stream, in front of the loop.  The
-// context's Philox epoch is neither read nor advanced (as in decode pools, section 5e): recording r draws under seeds[r] at epoch 0.
-static int windows_group_loop(ldc_ctx* c, const Halves& h, const StepSampler& sm, const float* noise, const uint64_t* seeds, int n_steps, hipStream_t s) {
-  Plan* pl = h.p[0];
-  HIPCHK(launch_windows_group_keys(pl->wg_rec, noise ? nullptr : seeds, pl->wg.R, s));
-  return denoise_loop(c, h, pl->B, pl->win_x, noise, n_steps, s, nullptr, sm);
-}
-
 extern "C" int ldc_sample_windows_group(ldc_ctx* c, float* img, const float* cond, int sampler, int t_start, int n_steps, float eta, const float* noise,
                                         const uint64_t* seeds, int R, const int* Ltot, const int* Ftot, int Lw, int overlap, void* stream) {
   bool draws = false;
   LDCCHK(windows_group_front(c, sampler, t_start, n_steps, eta, noise, seeds, img && cond, false, &draws));
-  hipStream_t s = pick_stream(c, stream);
-  Halves h;
-  LDCCHK(windows_group_prepare(c, R, Ltot, Ftot, Lw, overlap, s, &h));   // (every refusal, before any GPU work)
-  Plan* pl = h.p[0];
-  StepSampler sm;
-  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));
-  LDCCHK(windows_group_load_cond(c, pl, cond, s));
-  const size_t nbytes = (size_t)c->unet.channels * pl->win_Ltot * 4;
-  HIPCHK(hipMemcpyAsync(pl->win_x, img, nbytes, hipMemcpyDeviceToDevice, s));
-  LDCCHK(windows_group_load_x(c, pl, pl->win_x, s));
-  LDCCHK(windows_group_loop(c, h, sm, sampler == SAMPLER_DPM ? nullptr : noise, seeds, n_steps, s));
-  HIPCHK(hipMemcpyAsync(img, pl->win_x, nbytes, hipMemcpyDeviceToDevice, s));
-  return finish_stream(c, stream);
+  return windows_sample(c, img, cond, sampler == SAMPLER_DPM ? nullptr : noise, seeds, n_steps, sampler, draws, R, Ltot, Ftot, Lw, overlap, stream, false);
 }
 
-// ldc_decode_windows / _ddim_windows / _dpm_windows of R recordings with ONE loop: wav packed (recording r's T[r] samples behind those in
-// front), the codec ends per recording with the code of decode_windows_body -- get_cond_rows at B = 1, the start image normalised over that
-// recording, the decoder over that recording's latent, output_normalise for that recording.  Outputs packed: wav_out like wav, latents_out
-// [D][Ltot_r] blocks, cond_out [D][Ftot_r] blocks, codes_out [n_q][Ftot_r] blocks.
+// ldc_decode_windows / _ddim_windows / _dpm_windows of R recordings with ONE loop (decode_windows_body's packed layouts)
 extern "C" int ldc_decode_windows_group(ldc_ctx* c, const float* wav, int R, const int* T, int sampler, int t_start, int n_steps, float eta,
                                         const float* noise, const uint64_t* seeds, int Lw, int overlap, float* wav_out, float* latents_out,
                                         float* cond_out, int64_t* codes_out, void* stream) {
   bool draws = false;
   LDCCHK(windows_group_front(c, sampler, t_start, n_steps, eta, noise, seeds, wav && wav_out && T && R >= 1, true, &draws));
   if (R > kWinPerPart) return fail(LDC_E_INVALID, "R %d: a window group holds 1 to %d recordings", R, kWinPerPart);
-  const Codec& cc = c->codec[LDC_MODEL_COND];
-  const Codec& mc = c->codec[LDC_MODEL_MAIN];
-  const int D = c->cfg.rep_dims;
-  std::vector<int> Lr((size_t)R), Fr((size_t)R);
-  std::vector<size_t> toff((size_t)R + 1, 0);
-  for (int r = 0; r < R; ++r) {
-    if (T[r] <= 0 || T[r] % cc.hop || T[r] % mc.hop)
-      return fail(LDC_E_INVALID, "recording %d: T %d: must be a positive multiple of %d and %d (sample.py:87 trims to 640)", r, T[r], cc.hop, mc.hop);
-    Fr[r] = T[r] / cc.hop; Lr[r] = T[r] / mc.hop;
-    LDCCHK(check_unet_args(c, 1, Lr[r], Fr[r]));
-    toff[r + 1] = toff[r] + (size_t)T[r];
-  }
-  hipStream_t s = pick_stream(c, stream);
-  Halves h;
-  LDCCHK(windows_group_prepare(c, R, Lr.data(), Fr.data(), Lw, overlap, s, &h));   // (every refusal, before any GPU work)
-  LDCCHK(ensure_outnorm(c, 1));
-  Plan* pl = h.p[0];
-  StepSampler sm;
-  LDCCHK(windows_sampler(c, pl, sampler, s, &sm));
-  const WinGroup& g = pl->win_group;
-  const int n_q = n_q_for_bandwidth(c, 0.f);
-  LDCCHK(with_scratch(c, s, [&](Arena& ar, bool dry) -> int {
-    float* mx = (float*)ar.alloc((size_t)R * 4);
-    const int Fw = pl->F, upf = upsample_factor(c);
-    for (int r = 0; r < R; ++r) {
-      const int F = Fr[r], L = Lr[r];
-      const size_t foff = (size_t)g.off[r] / upf;
-      float* qr = nullptr;
-      int Fq = 0;
-      LDCCHK(get_cond_rows(c, wav + toff[r], 1, T[r], 0.f, ar, dry, s, &qr, &Fq, codes_out ? codes_out + (size_t)n_q * foff : nullptr, 1));
-      if (!dry && Fq != F) return fail(LDC_E_INVALID, "internal: encoder produced %d frames, expected %d", Fq, F);
-      void* up = nullptr;
-      int Lu = 0;
-      LDCCHK(upsample_rows(c, qr, 1, F, ar, dry, s, &up, &Lu));
-      if (!dry) {
-        if (cond_out) HIPCHK(launch_from_cl(DT_F32, qr, cond_out + (size_t)D * foff, 1, D, F, nullptr, 0, 0.f, s));
-        HIPCHK(hipMemsetAsync(mx + r, 0, 4, s));
-        HIPCHK(launch_maxabs(DT_F32, up, 1, (int64_t)L * D, 0, mx + r, s));
-        HIPCHK(launch_from_cl(DT_F32, up, pl->win_x + (size_t)D * g.off[r], 1, D, L, mx + r, 0, 1e-8f, s));
-        for (int k = g.w0[r]; k < g.w0[r + 1]; ++k)   // process_cond per window: a window's slice is one contiguous run of the recording's rows
-          HIPCHK(hipMemcpyAsync((float*)pl->cond_in_cl + (size_t)k * Fw * D, qr + (size_t)(g.start[k] / upf) * D, (size_t)Fw * D * 4,
-                                hipMemcpyDeviceToDevice, s));
-      }
-    }
-    if (!dry) {
-      LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
-      LDCCHK(windows_group_load_x(c, pl, pl->win_x, s));
-      LDCCHK(windows_group_loop(c, h, sm, sampler == SAMPLER_DPM ? nullptr : noise, seeds, n_steps, s));
-      if (latents_out) HIPCHK(hipMemcpyAsync(latents_out, pl->win_x, (size_t)D * g.Lsum * 4, hipMemcpyDeviceToDevice, s));
-    }
-    for (int r = 0; r < R; ++r) {   // decoder over each recording's latent (quirk Q3: no x18 un-scaling on this path, sample.py:131)
-      const int L = Lr[r];
-      SeaRun Rn{c, &ar, s, dry, 1};
-      void* zc = ar.alloc((size_t)L * D * 4);
-      if (!dry) HIPCHK(launch_to_cl(DT_F32, pl->win_x + (size_t)D * g.off[r], zc, 1, D, L, nullptr, 0, 0.f, s));
-      void* y = nullptr;
-      int Lo = 0, Cd = 0;
-      LDCCHK(run_seanet(Rn, mc.dec, zc, L, &y, &Lo, &Cd));
-      if (!dry) {
-        if (Lo != T[r]) return fail(LDC_E_STATE, "internal: the decoder gave %d samples for recording %d of %d", Lo, r, T[r]);
-        HIPCHK(hipMemcpyAsync(wav_out + toff[r], y, (size_t)Lo * 4, hipMemcpyDeviceToDevice, s));
-        HIPCHK(launch_output_normalise(wav_out + toff[r], 1, Lo, 0, c->outnorm_ws, s, nullptr, mc.hop));
-      }
-    }
-    return LDC_OK;
-  }));
-  return finish_stream(c, stream);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_windows_body(c, src, R, T, n_steps, sampler, draws, sampler == SAMPLER_DPM ? nullptr : noise, seeds, Lw, overlap, wav_out, latents_out,
+                             cond_out, codes_out, stream, false);
 }
 
 int check_dev(ldc_ctx* c) {

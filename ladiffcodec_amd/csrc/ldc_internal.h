@@ -206,25 +206,19 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
   float* cur_ss = nullptr;      // [ss_stride] timestep-MLP row of the step this part is executing
   float* x0_prev = nullptr;     // DPM-Solver++(2M) history of this part: x0 of the previous iteration, [B][channels][L] fp32.  An allocation of
                                 // its own, made by the first DPM call on the plan (before any capture) and freed with the plan: captured DPM
-                                // graphs keep its address.  On a coupled-windows plan (below) it is the recording's ONE history instead,
-                                // [channels][win_Ltot] fp32 in win_x's layout (ensure_windows_history), with the same lifetime
-  // Coupled-windows plan (ldc_*_windows): the ordinary equal-length plan at (B = W windows, L = Lw, F = Lw / up) of ONE
-  // recording of win_Ltot latent frames cut with overlap win_O -- both part of the cache key, 0 on every other plan.  One allocation of its
-  // own (win_base, made before any capture, freed with the plan) holds the recording's fp32 state and the layout's tables; the host copies
-  // stay alive with the plan because the upload is asynchronous.
-  int win_Ltot = 0, win_O = 0;
+                                // graphs keep its address.  On a coupled-windows plan (below) it is the recordings' history instead,
+                                // one [channels][Ltot_r] fp32 block per recording in win_x's layout (ensure_windows_history), with the same lifetime
+  // Coupled-windows plan (ldc_*_windows, ldc_*_windows_group): the ordinary equal-length plan at (B = W_sum windows,
+  // L = Lw, F = Lw / up) of R recordings cut with overlap win_O; a single-recording call is R = 1 (and L its effective window: Ltot where
+  // the recording is shorter than Lw).  The ORDERED list of the recordings' lengths (win_group.Ltot) and win_O are part of the cache key
+  // with (B, L, F): empty / 0 on every other plan.  win_Ltot is Lsum, the frames of all the recordings: the packed state, the packed DPM
+  // history and the step stride of a tape are sized by it.  One allocation of its own (win_base, made before any capture, freed with the
+  // plan) holds the fp32 state and, behind it, the device tables wg with the recording table and the tile table; win_group keeps the
+  // host side alive with the plan because the upload is asynchronous.  win_id is the plan's identity for its step graphs.
+  int win_Ltot = 0, win_O = 0, win_id = 0;
   void* win_base = nullptr;
-  float* win_x = nullptr;       // [channels][win_Ltot] fp32: the one latent every window reads (captured step graphs keep its address)
-  WindowTables win{};           // cover [win_Ltot], weight [B][L], start [B] (device)
-  std::vector<int> win_cover_h, win_start_h;
-  std::vector<float> win_weight_h;
-  // Window-group plan (ldc_*_windows_group; section 5g, "Several recordings per call"): the windows plan at B = W_sum of R recordings.
-  // win_Ltot is Lsum, the frames of all of them -- the packed state, the packed DPM history and the step stride of a tape are sized by it
-  // as a single recording's are by its Ltot.  win_group holds the host side of the tables (the ordered list of lengths is part of the
-  // cache key: empty on every other plan), win_group_id the plan's identity for its step graphs, wg the device tables, which live in
-  // win_base behind the state with the recording table and the tile table.
+  float* win_x = nullptr;       // packed [channels][Ltot_r] fp32 blocks: the one latent every window of a recording reads (captured step graphs keep its address)
   WinGroup win_group;
-  int win_group_id = 0;
   WinGroupTables wg{};
   WinGroupRec* wg_rec = nullptr;   // == wg.rec, writable: the keys of a call go in on the stream
   std::vector<std::function<hipError_t(hipStream_t)>> cond_ops;   // process_cond (once per denoise)
@@ -259,15 +253,14 @@ enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_DPM = 2 };
 struct StepSampler {
   int kind = SAMPLER_DDPM;
   const DdimStep* ddim = nullptr;   // SAMPLER_DDIM: c->ddim_table (step_begin takes t from it, ddim_update the coefficients)
-  const DpmStep* dpm = nullptr;     // SAMPLER_DPM: c->dpm_table (likewise; dpm_update / windows_dpm_update also read and write the plan's x0_prev)
+  const DpmStep* dpm = nullptr;     // SAMPLER_DPM: c->dpm_table (likewise; dpm_update / windows_group_dpm_update also read and write the plan's x0_prev)
 };
 
 struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update | dpm_update, step_advance}
   int B = 0, L = 0, F = 0, n = 0;
   int ragged = 0;    // (part of the cache key) the steps of ragged plans
   int pool_id = 0;   // (part of the cache key) != 0: the step graphs of that decode pool's plans
-  int win_Ltot = 0, win_O = 0;   // (part of the cache key) != 0: the steps of that coupled-windows plan (B windows of L frames)
-  int win_group = 0;             // (part of the cache key) != 0: the steps of that window-group plan (Plan::win_group_id)
+  int win_id = 0;    // (part of the cache key) != 0: the steps of that coupled-windows plan (Plan::win_id)
   int sampler = SAMPLER_DDPM;   // sampler kind (part of the cache key): a loop never replays another kind's graph (DDIM, DPM: the schedule table's address is captured, not its contents)
   const float* noise = nullptr;
   float* x = nullptr;
@@ -384,7 +377,7 @@ struct ldc_ctx {
   size_t plan_bytes = 0, plan_bytes_cap = (size_t)48 << 30;   // LDC_PLAN_CACHE_GB
   int plan_count_cap = 24;                                     // LDC_PLAN_CACHE_N
   int live_pools = 0, next_pool_id = 1;                        // decode pools (ldc_pool_create): their plans are pinned in the cache
-  int next_win_group_id = 1;                                   // window-group plans (Plan::win_group_id): the identity of their step graphs
+  int next_win_id = 1;                                         // coupled-windows plans (Plan::win_id): the identity of their step graphs
   // device-drawn noise: every sampler call that draws advances the epoch, so no two calls share a realisation
   uint64_t noise_epoch = 0, cur_key = 0;
   // asynchronous device-side failure flag, host-mapped: word 0 = 1 cooperative LSTM timeout, 2 fused GroupNorm wait timeout,
@@ -563,7 +556,7 @@ int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F);
 int check_dev(ldc_ctx* c);   // hipSetDevice only: calls that need no weights
 // what ldc_api_pool.cpp shares with the samplers of ldc_api.cpp
 int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false, bool items = false, int pool_id = 0,
-             int win_Ltot = 0, int win_O = 0, const std::vector<int>* win_group = nullptr);
+             const std::vector<int>* win_lens = nullptr, int win_O = 0);
 int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step, hipStream_t s);
 int calibrate_part_streams(ldc_ctx* c, hipStream_t s);
 bool parts_parallel(ldc_ctx* c, const Halves& h);

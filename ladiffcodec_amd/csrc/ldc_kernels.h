@@ -282,22 +282,6 @@ hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src_host, int 
 hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                               void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
                               uint64_t elem_base, hipStream_t s, const int* lens = nullptr);
-// Coupled windows: the host-built tables of one layout (Ltot, Lw, overlap), in device memory.
-struct WindowTables {
-  const int* cover;      // [Ltot]: first covering window | count << 8 (count <= 3, the covering windows have consecutive indices)
-  const float* weight;   // [W][Lw]: w_k(start[k] + l); the weights of the windows that cover a frame sum to 1, a lone window has 1.0f
-  const int* start;      // [W] first global frame of each window
-  int Ltot, Lw;
-};
-enum { WIN_BLEND = 0, WIN_DDPM = 1, WIN_DDIM = 2, WIN_DPM = 3 };   // WIN_DPM: launch_windows_dpm_update below (DpmStep follows)
-// The update launch of a coupled-windows step: blends eps_cl [W][Lw][C] dt into the eps of the global frames, applies p_sample
-// (WIN_DDPM) or the DDIM entry sched[st[1]] (WIN_DDIM) to x [C][Ltot] fp32 exactly as the B = 1, L = Ltot kernels above (noise:
-// [.. j ..][C][Ltot] or null for Philox at elem_base 0) and stores the new state into every covering window's row of x_cl [W][Lw][C] dt.
-// WIN_BLEND: the blended eps into ebar [C][Ltot] fp32, nothing else is read or written.
-hipError_t launch_windows_update(int dt, int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
-                                 float* ebar, int C, WindowTables wt, StepTables tb, const DdimStep* sched, const int* st, hipStream_t s);
-// y [W][Lw][C] dt <- x [C][Ltot] fp32 at frames start[k] / div + l
-hipError_t launch_windows_gather(int dt, const float* x, void* y, int W, int C, int Lw, int Ltot, const int* start, int div, hipStream_t s);
 // One iteration of DPM-Solver++(2M) in its data-prediction form: the host fills one entry per iteration j
 // (ldc_api.cpp: ldc_dpm_schedule, double arithmetic rounded once to float) into a device table that the step state indexes.
 struct DpmStep {
@@ -315,26 +299,26 @@ struct DpmStep {
 hipError_t launch_dpm_table_write(DpmStep* dst, const DpmStep* src_host, int n, hipStream_t s);   // dst[0..n) = src_host[0..n), stream-ordered
 hipError_t launch_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int B, int C, int L, StepTables tb,
                              const DpmStep* sched, const int* st, hipStream_t s, const int* lens = nullptr);
-// The fourth kind of the coupled-windows update launch (WIN_DPM; a sibling kernel of the WIN_BLEND / WIN_DDPM / WIN_DDIM template): the
-// blend of launch_windows_update, then the update of launch_dpm_update on x [C][Ltot] fp32 with the recording's ONE history x0_prev
-// [C][Ltot] fp32 (loaded only where the entry sched[st[1]] says has_prev, written on every iteration but the last, never cleared); the new
-// state goes into x and into every covering window's row of x_cl [W][Lw][C] dt.  Nothing is drawn.
-hipError_t launch_windows_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WindowTables wt, StepTables tb,
-                                     const DpmStep* sched, const int* st, hipStream_t s);
-// Window groups ("Several recordings per call"): the host-built tables of R recordings whose windows share one
-// batch (ldc_windows.h: win_group_build), in device memory.
+// Coupled windows: the host-built tables of R recordings whose windows share one batch (ldc_windows.h:
+// win_group_build; a single-recording call is R = 1), in device memory.
 struct WinGroupTables {
   const WinGroupTile* tile;   // [n_tiles] {recording, l0}: one entry per workgroup column of the update launch
   const WinGroupRec* rec;     // [R] {Ltot_r, w0_r, off_r, cover_off_r, Philox key}
   const int* cover;           // [Lsum] the recordings' cover rows, concatenated; first window counted WITHIN the recording | count << 8
-  const float* weight;        // [W_sum][Lw]
+  const float* weight;        // [W_sum][Lw]: the weights of the windows that cover a frame sum to 1, a lone window has 1.0f
   const int* start;           // [W_sum] first frame of each window in its recording's own frames
   const int* wrec;            // [W_sum] window -> recording
   int n_tiles, R, Lw;
 };
-// launch_windows_update / launch_windows_dpm_update of a window group: x, ebar, x0_prev and every step of the tape are packed, recording
-// r's [C][Ltot_r] block at C * off_r floats (noise_step_stride = C * Lsum); Philox draws under the recording's own key.  Grid
-// (n_tiles, ceil(C / 32)).
+enum { WIN_BLEND = 0, WIN_DDPM = 1, WIN_DDIM = 2, WIN_DPM = 3 };   // WIN_DPM: launch_windows_group_dpm_update
+// The update launch of a coupled-windows step: blends eps_cl [W_sum][Lw][C] dt into the eps of each recording's global frames, applies
+// p_sample (WIN_DDPM) or the DDIM entry sched[st[1]] (WIN_DDIM) to the recording's state exactly as the B = 1, L = Ltot_r kernels above
+// and stores the new state into every covering window's row of x_cl [W_sum][Lw][C] dt.  x, ebar, x0_prev and every step of the tape are
+// packed, recording r's [C][Ltot_r] block at C * off_r floats (noise_step_stride = C * Lsum; noise null: Philox at elem_base 0 under
+// the recording table's key).  WIN_BLEND: the blended eps into ebar, nothing else is read or written.  Grid (n_tiles, ceil(C / 32)).
+// WIN_DPM is a kernel of its own (it takes the history and a DpmStep table): the same blend, then the update of launch_dpm_update with
+// ONE history block per recording (loaded only where sched[st[1]] says has_prev, written on every iteration but the last, never
+// cleared).  Nothing is drawn.
 hipError_t launch_windows_group_update(int dt, int kind, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
                                        float* ebar, int C, WinGroupTables gt, StepTables tb, const DdimStep* sched, const int* st, hipStream_t s);
 hipError_t launch_windows_group_dpm_update(int dt, float* x, const void* eps_cl, float* x0_prev, void* x_cl, int C, WinGroupTables gt, StepTables tb,

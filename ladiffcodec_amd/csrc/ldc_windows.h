@@ -133,11 +133,14 @@ struct WinGroup {
 // The group of R recordings of Ltot[r] frames at (Lw, overlap).  0: ok; 1: refused (*err names the value, and the recording where it is
 // one's own); 2: internal.  Every recording must be at least one window long: a shorter one would shrink the window (win_layout_build's
 // Ltot <= Lw case) and break the equal-length batch.
-inline int win_group_build(int R, const int* Ltot, int Lw, int O, int up, WinGroup* out, std::string* err) {
+// single (R == 1 only): the group of a single-recording call -- win_layout_build's refusals in its own words (no "recording 0:"), and a
+// recording shorter than Lw is its one window: out->Lw is then Ltot[0], the layout's effective window.
+inline int win_group_build(int R, const int* Ltot, int Lw, int O, int up, WinGroup* out, std::string* err, bool single = false) {
   char msg[320];
   auto refuse = [&](int code) { *err = msg; return code; };
   if (R < 1 || R > kWinPerPart) { snprintf(msg, sizeof msg, "R %d: a window group holds 1 to %d recordings", R, kWinPerPart); return refuse(1); }
   if (!Ltot) { snprintf(msg, sizeof msg, "null list of lengths"); return refuse(1); }
+  if (single && R != 1) { snprintf(msg, sizeof msg, "internal: a single-recording group of %d recordings", R); return refuse(2); }
   *out = WinGroup();
   out->R = R; out->Lw = Lw; out->O = O;
   out->Ltot.assign(Ltot, Ltot + R);
@@ -148,7 +151,9 @@ inline int win_group_build(int R, const int* Ltot, int Lw, int O, int up, WinGro
   for (int r = 0; r < R; ++r) {
     std::string e1;
     const int rc = win_layout_build(Ltot[r], Lw, O, up, kWinPerPart, &lay[r], &e1);
+    if (rc && single) { *err = e1; return rc; }
     if (rc) { snprintf(msg, sizeof msg, "recording %d: %s", r, e1.c_str()); return refuse(rc); }
+    if (single) Lw = out->Lw = lay[r].Lw;
     if (Ltot[r] < Lw) {
       snprintf(msg, sizeof msg, "recording %d: Ltot %d is shorter than the window Lw = %d (every recording of a group is at least one window long)", r,
                Ltot[r], Lw);

@@ -133,6 +133,30 @@ def test_denoise_windows_draws_the_noise_of_one_item_of_Ltot_frames(tag, Ltot, L
     assert rel(again, e.denoise_windows(img, cond, 6, Lw, O_, noise=tape0).cpu().numpy()) > 10 * TOL[dtype]["chain_small"]
 
 
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_a_drawing_windows_call_advances_the_epoch_once(dtype):
+    """The windows call draws under the key of the context's epoch (it travels through the recording table) and moves the epoch on by
+    one, as ldc_denoise does: the call and a plain decode behind it repeat after another reseed, and the decode draws at epoch 1."""
+    tag, Ltot, Lw, O_ = MAIN[0]
+    s = R.inputs(tag, Ltot, N)
+    e = engine(tag, dtype)
+    img, cond = s["img"].cuda(), s["cond"].cuda()
+    wav = (torch.from_numpy(synth.synthetic_wav(1, Lw * CASES[tag][0].hop_length, seed=83)) * 0.5).cuda()
+
+    def pair():
+        e.reseed(SEED)
+        return e.denoise_windows(img, cond, 6, Lw, O_).cpu().numpy(), e.decode(wav, 6, None).cpu().numpy()
+    win0, dec0 = pair()
+    win1, dec1 = pair()
+    close(dtype, "repeat", rel(win1, win0), "the drawing windows call after another reseed", ("repeat", tag, 4))
+    close(dtype, "repeat", rel(dec1, dec0), "the decode behind it after another reseed", ("repeat", tag, 1))
+    e.reseed(SEED)
+    at0 = e.decode(wav, 6, None).cpu().numpy()
+    at1 = e.decode(wav, 6, None).cpu().numpy()
+    close(dtype, "repeat", rel(dec0, at1), "the decode behind it against a decode at epoch 1", ("repeat", tag, 1))
+    assert rel(dec0, at0) > 10 * bar(dtype, "repeat", ("repeat", tag, 1))       # (epoch 0 draws other noise)
+
+
 # ------------------------------------------------------------------------------------------------------------ 4. the identities
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("tag,Lw", [("r84", 80), ("r8", 160)])
@@ -301,6 +325,8 @@ def test_refusals_leave_the_engine_usable():
     calls = [
         (lambda: e.denoise_windows(img, cond, 3, Lw, 45, noise=noise), "overlap 45"),
         (lambda: e.denoise_windows(img, cond, 3, Lw, 50, noise=noise), "overlap 50"),
+        # Ltot < Lw, Lw / 2 < overlap <= Ltot: refused on the caller's Lw, not on the one window of Ltot frames the call would run as
+        (lambda: e.denoise_windows(img, cond, 3, 200, 110, noise=noise), "overlap 110: must be a multiple of up = 10 in [0, Lw / 2 = 100]"),
         (lambda: e.denoise_windows(img, cond, 3, 90, 40, noise=noise), "Lw 90"),                     # a multiple of up, not of the quantum
         (lambda: e.denoise_windows(img, cond[..., :17].contiguous(), 3, Lw, O_, noise=noise), "Ftot (17)"),
         (lambda: e.denoise_windows(img, cond, 0, Lw, O_, noise=noise), "n_steps 0"),

@@ -263,10 +263,29 @@ def test_a_group_of_one_is_the_single_call(tag, dtype, sampler):
     s = G.inputs(tag, N)[:1]
     e = engine(tag, dtype)
     got = npy(run_group(e, s, sampler, Lw, O_))[0]
+    # A single-recording call IS the group of one (one plan, one kernel): this compares a code path with itself and guards against the
+    # two ever splitting again.  What pins the arithmetic are the tests against the restatements (test_sample_windows_group, tests/test_gpu_windows.py).
     # the same batch, the same sampler, another call: the run-to-run constant of THIS sampler on a batch of this recording's W windows
     # (tests/test_gpu_windows_receiver.py; a DDIM eta 1 chain scatters twice as far run to run as a DDPM one, 8.1e-4 against 4.4e-4 on r8)
     m = TR.PARENT_MEASURED[("rerun_lat", tag, TR.W_OF[tag], sampler)]
     close(dtype, "repeat", rel(got, run_alone(e, s[0], sampler, Lw, O_).cpu().numpy()), f"{tag} {sampler} R = 1 against the single call", m)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_a_single_call_and_a_group_of_one_alternate_on_their_shared_plan(dtype):
+    """The two calls of one (Ltot, Lw, O) share a plan, its recording table and its step graphs.  The single call runs on a tape, the group
+    call draws under its seed: a key or a tape left behind by the other call would move the second result of either off its first."""
+    tag, sampler = "r84", "ddpm"
+    Lw, O_, _ = G.GROUPS[tag]
+    s = G.inputs(tag, N)[:1]
+    e = engine(tag, dtype)
+    m = TR.PARENT_MEASURED[("rerun_lat", tag, TR.W_OF[tag], sampler)]
+    single = lambda: run_alone(e, s[0], sampler, Lw, O_).cpu().numpy()                                       # noqa: E731
+    group = lambda: npy(run_group(e, s, sampler, Lw, O_, noise=False, seeds=SEEDS[:1]))[0]                    # noqa: E731
+    single0, group0, single1, group1 = single(), group(), single(), group()
+    close(dtype, "repeat", rel(single1, single0), "the single call on its tape, behind the group call, against its first result", m)
+    close(dtype, "repeat", rel(group1, group0), "the group call under its seed, behind the single call, against its first result", m)
+    assert rel(group0, single0) > 10 * bar(dtype, "repeat", m)                                                # (the seed's noise is not the tape's)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])

@@ -155,6 +155,26 @@ int main() {
   refused({180, 80}, 2, 85, 40, 10, "Lw 85");
   refused({180, 80}, 2, 80, 40, 0, "up 0");
   refused({80, len(33, 80, 40, 40)}, 2, 80, 40, 10, "recording 1");       // one recording alone beyond the cap
+  // `single`, the group of a single-recording call: the same tables as the plain group of one; a recording shorter than the window is its
+  // one window (the plain group at Lw = Ltot); refusals in win_layout_build's own words, on the caller's Lw
+  for (int Ltot : {180, 80, 70}) {
+    WinGroup a, b;
+    std::string err;
+    const int one[1] = {Ltot}, lw = std::min(80, Ltot);
+    EXPECT(win_group_build(1, one, 80, 40, 10, &a, &err, true) == 0 && win_group_build(1, one, lw, 40 <= lw / 2 ? 40 : 0, 10, &b, &err) == 0,
+           "single Ltot %d: refused: %s", Ltot, err.c_str());
+    EXPECT(a.Lw == lw && a.W_sum == b.W_sum && a.Lsum == b.Lsum && a.w0 == b.w0 && a.off == b.off && a.start == b.start && a.cover == b.cover &&
+               a.wrec == b.wrec && a.weight == b.weight && a.tile.size() == b.tile.size() && a.rec[0].Ltot == Ltot && a.rec[0].W == b.rec[0].W,
+           "single Ltot %d: not the plain group of one", Ltot);
+  }
+  {
+    WinGroup g;
+    std::string err;
+    const int one[1] = {180}, two[2] = {180, 80};
+    EXPECT(win_group_build(1, one, 200, 110, 10, &g, &err, true) == 1 && err.rfind("overlap 110", 0) == 0 && err.find("Lw / 2 = 100") != std::string::npos,
+           "single: expected the overlap refusal on the caller's Lw, got '%s'", err.c_str());
+    EXPECT(win_group_build(2, two, 80, 40, 10, &g, &err, true) == 2, "single with R = 2 is an internal error, got '%s'", err.c_str());
+  }
   printf(bad ? "FAILED (%d)\n" : "%d window groups ok (R = 1..%d, the cap, the refusals)\n", bad ? bad : groups, kWinPerPart);
   return bad ? 1 : 0;
 }

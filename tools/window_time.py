@@ -14,7 +14,7 @@ and the launches of one step (step list + the step's first kernel + its update l
     python tools/window_time.py [rounds]
 
 `--kernels`: only a few windows calls and a few one-part denoise calls at B = 15, for a run under
-`rocprofv3 --kernel-trace --stats -- python tools/window_time.py --kernels`, whose kernel statistics then hold windows_update_kernel
+`rocprofv3 --kernel-trace --stats -- python tools/window_time.py --kernels`, whose kernel statistics then hold windows_group_update_kernel
 next to p_sample_update_kernel at B = 15.
 
 `--dpm`: instead of the above, at the default split and alternated round by round in the same way,
