@@ -670,6 +670,30 @@ int ldc_debug_attn_core(ldc_ctx* ctx, int kind, const float* qkv, int B, int L, 
  * (fold_ctx, fuse_attn_tail, fuse_kmax, fold_ln, conv_lean) routes as in a decode.  Synchronous; honours the device-side failure
  * flag (LDC_E_HIP, "device-side failure [ctx_range]" when the context fold met k values outside its valid range). */
 int ldc_debug_attention_block(ldc_ctx* ctx, const char* name, const float* x, int B, int L, float* out, void* stream);
+/* Test hook: one ResnetBlock of the loaded UNet on caller data, launched by the plan builder itself, so every option (fuse_gn_epi,
+ * fuse_gn_stats, fold_res, fold_ln, fuse_ln, conv_lean) routes as in a decode.  name: "down<i>.1", "down<i>.2", "mid.1", "mid.2",
+ * "up<i>.1", "up<i>.2" or "final" (which runs with the output mode of a step: tanh included).  x1 [B, cin1, L] and, for the blocks that
+ * read a concatenation (the up levels and "final"), x2 [B, cin2, L]: fp32 on the device; x2 is NULL otherwise (a mismatch is
+ * LDC_E_INVALID).  t: the timestep, set as a step sets it (which also clears the GroupNorm sums, the split-K counters and the granule
+ * regions of the fused exchange in front of the run).  lens (host, NULL: equal lengths) with shift: a ragged plan of B items whose
+ * lengths are given in rows of level 0, this block sitting `shift` halvings below it (an item has lens[b] >> shift of the L rows); x1
+ * and x2 are masked to zero behind each item's length first, the invariant a ragged plan gives its convs.  t_items (host, NULL; needs
+ * lens): a per-item plan, one timestep per item, t is ignored.  with_attention (only "down<i>.2", "mid.1", "up<i>.2"): the block and the
+ * attention block behind it are built as a step pairs them (the PreNorm folded into to_qkv on the block's row partials, or written by
+ * the block's last kernel), and attn_out [B, cout, L] receives the attention block's output.
+ * out [B, cout, L]; mid [B, cout, L]: block1's stored output (so fp8 contexts are refused: LDC_E_INVALID); stats float [2][B][groups][2]:
+ * (sum, sum of squares) of conv 1 and conv 2 per (item, group) as the kernels themselves accumulated them -- the atomic /
+ * launch_gn_stats buffers, or, for a conv with the fused GroupNorm epilogue, the tagged granules of its in-launch exchange read back
+ * and summed on the host.  pre (device, NULL: not wanted) [2][B][cout][L] fp32: the outputs of conv 1 and conv 2 as stored, which is
+ * what launch_gn_stats and gn_apply read on the unfused route (a conv with the fused epilogue stores none: zeros).  info (int[12], host): [0] [1] conv 1 / conv 2 took the fused epilogue, [2] res_conv folded into conv 1,
+ * [3] fused (atomic) statistics rather than launch_gn_stats on the unfused path, [4] the PreNorm output (y_ln) was produced, [5] the
+ * row partials for a folded PreNorm were produced, [6] [7] tile rows and wave rows of conv 1, [8] [9] of conv 2, [10] every granule the
+ * exchange reads carried both tags, [11] a granule outside those was written.  Synchronous; honours the device-side failure flag
+ * ("[gn_wait]").  Allocates and frees its workspace: not for the decode path.  out, mid and stats all NULL: planning only, on the
+ * host -- info[0..9] of the run these arguments would make; nothing is launched and the tensors are not read. */
+int ldc_debug_resnet_block(ldc_ctx* ctx, const char* name, const float* x1, const float* x2, int B, int L, int t, const int32_t* lens,
+                           int shift, const int32_t* t_items, int with_attention, float* out, float* mid, float* stats, float* attn_out,
+                           float* pre, int* info, void* stream);
 
 /* Test hook: one SEANet conv on caller-supplied host weights (already weight-norm folded) through the conv path an encode / decode
  * takes (sea_conv: its ConvCall, its split-K workspace under option "sea_splitk").  Plain (transposed = 0; w [Cout, Cin, k], reflect padding

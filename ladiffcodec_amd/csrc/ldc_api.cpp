@@ -1435,7 +1435,10 @@ struct PlanBuilder {
     return ar->alloc((size_t)rows * C * es);
   }
   // ragged plan: the device lengths and the level of a tensor of L rows per item (a level's lengths are lens[b] >> level)
-  const int* lens() const { return pl->ragged ? pl->lens : nullptr; }
+  // (a planning pass on a measuring arena has no device memory: the lengths' address is a placeholder there, never dereferenced -- a null
+  // one made those passes plan the equal-length forms, so that a ragged plan of a model whose ResnetBlocks fuse their GroupNorm apply
+  // was measured WITHOUT the conv outputs its unfused forms store, and built past the end of its arena)
+  const int* lens() const { return pl->ragged ? (pl->lens ? pl->lens : reinterpret_cast<const int*>(16)) : nullptr; }
   int level(int L) const {
     int sh = 0;
     while ((L << sh) < pl->L) ++sh;
@@ -1479,6 +1482,18 @@ struct PlanBuilder {
   const float* ln_rowstat_next = nullptr;   // row-statistics partials of the next (LayerNorm-folded) conv's input
   bool want_rowstat = false;                // the next resnet()'s fused block2 conv leaves those partials of its output ...
   float* last_rowstat = nullptr;            // ... here (null when it could not)
+  // what the last resnet() built, for ldc_debug_resnet_block (null on every plan of a decode): the route it took and where its
+  // intermediate tensors and GroupNorm statistics live
+  struct ResnetTrace {
+    int epi1 = 0, epi2 = 0, folded = 0, fuse_stats = 0, xn = 0, rowstat = 0;
+    int t1[4] = {0, 0, 1, 0}, t2[4] = {0, 0, 1, 0};   // conv_bm of the two launched convs
+    void* b = nullptr;                                  // block1's stored output
+    void *a = nullptr, *d = nullptr;                    // unfused: the conv outputs as stored (what launch_gn_stats and gn_apply read)
+    float *st1 = nullptr, *st2 = nullptr;               // unfused: [B][groups][kGnPad]
+    char *part1 = nullptr, *part2 = nullptr;            // fused: the convs' granule regions
+    int mslots1 = 0, mslots2 = 0;
+  };
+  ResnetTrace* trace = nullptr;
   // fused GroupNorm apply of a conv (see ConvCall::gn_cnt)
   struct GnEpi {
     void* part = nullptr;          // granule region of this conv
@@ -1662,9 +1677,20 @@ struct PlanBuilder {
       }, false, 0, LDC_CLASS_GN_APPLY, (f8 ? 1.5 : 2.0) * Bn * L * rp->cout * es);
     }
     void* xn = nullptr;
-    if (ln_g && xn_out && c->fuse_ln && !ln && gn_apply_ln_fusable(r.cout)) {
+    const bool xn_made = ln_g && xn_out && c->fuse_ln && !ln && gn_apply_ln_fusable(r.cout);
+    if (xn_made) {
       xn = xn_fp8 ? ar->alloc((size_t)rows * r.cout) : act(rows, r.cout);
       *xn_out = xn;
+    }
+    if (trace) {
+      ResnetTrace& tr = *trace;
+      tr = ResnetTrace();
+      tr.epi1 = epi1; tr.epi2 = epi2; tr.folded = folded; tr.fuse_stats = fuse_stats; tr.xn = xn_made;
+      tr.rowstat = epi2 && rowstat_wanted && !f8;
+      conv_bm(c1, L, L, false, tr.t1);   // (as the gate above asks: the tile shape of the launched layer)
+      conv_bm(f8 ? r.c2_f8 : r.c2, L, L, false, tr.t2);
+      tr.b = b; tr.a = a; tr.d = d; tr.st1 = st1; tr.st2 = st2;
+      tr.part1 = (char*)ge1.part; tr.part2 = (char*)ge2.part; tr.mslots1 = ge1.mslots; tr.mslots2 = ge2.mslots;
     }
     if (epi2) {   // block2: conv -> GroupNorm -> SiLU -> + res (-> tanh), one launch; the PreNorm LayerNorm of a following attention block reads `out`
       ge2.gamma = r.g2; ge2.beta = r.b2; ge2.ss = nullptr; ge2.out = out_mode & 5;
@@ -2032,6 +2058,7 @@ int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** ou
   real.base = (char*)base;
   real.cap = want;
   int rc = build_plan(c, pl.get(), real, B, L, F);
+  if (rc == LDC_OK && real.off > want) rc = fail(LDC_E_STATE, "internal: the plan needs %zu bytes, its planning pass measured %zu", real.off, want);
   if (rc != LDC_OK) { (void)hipFree(base); return rc; }
   for (const auto& z : pl->zero_once) {   // the step state's epoch word: cleared once, before the plan's first use
     hipError_t ez = hipMemsetAsync(z.first, 0, z.second, s);
@@ -2378,6 +2405,208 @@ extern "C" int ldc_debug_attention_block(ldc_ctx* c, const char* name, const flo
   HIPCHK(launch_from_cl(dt, y_cl, out, B, C, L, nullptr, 0, 0.f, s));
   HIPCHK(hipStreamSynchronize(s));
   return check_dev_flag(c);
+}
+
+// One ResnetBlock of the loaded UNet on caller data (tests), optionally with the attention block that follows it in a step.  As
+// ldc_debug_attention_block: a private plan that is never cached, the launches from PlanBuilder::resnet() (and attention()) themselves, so
+// fuse_gn_epi, fuse_gn_stats, fold_res, fold_ln, fuse_ln and conv_lean route as in a decode.  The timestep is set as a step sets it
+// (launch_step_set + launch_step_begin on the plan's zero region, or the item records + launch_step_begin_items), which also clears the
+// GroupNorm sums, the split-K counters and the granule regions of the fused convs in front of the run.  `stats` are the sums the kernels
+// themselves accumulated: the atomic / launch_gn_stats buffers, or the granules of the fused exchange read back and summed on the host.
+namespace {
+struct PlanEvents {   // run_ops creates the fork / join events of a plan on first use; a cached plan frees them when it is evicted
+  Plan* pl;
+  ~PlanEvents() {
+    for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
+    pl->marker_events.clear();
+  }
+};
+}   // namespace
+extern "C" int ldc_debug_resnet_block(ldc_ctx* c, const char* name, const float* x1, const float* x2, int B, int L, int t, const int32_t* lens,
+                                      int shift, const int32_t* t_items, int with_attention, float* out, float* mid, float* stats, float* attn_out,
+                                      float* pre, int* info, void* stream) {
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  const bool route_only = !out && !mid && !stats;   // planning on the host alone: info[0..9] of the run these arguments would make
+  if (!name || !info || B <= 0 || L <= 0 || (!route_only && (!x1 || !out || !mid || !stats))) return fail(LDC_E_INVALID, "bad arguments");
+  if (c->w8) return fail(LDC_E_INVALID, "ldc_debug_resnet_block does not support fp8 contexts (block1's output is stored in fp8 there)");
+  const UnetW& u = c->unet;
+  if (!t_items && (t < 0 || t >= u.timesteps)) return fail(LDC_E_INVALID, "t out of range");
+  if (t_items && !lens) return fail(LDC_E_INVALID, "per-item timesteps need lengths (a per-item plan is a ragged plan)");
+  if (!lens && shift != 0) return fail(LDC_E_INVALID, "shift without lengths");
+  if (shift < 0 || shift > 8 || ((long long)L << shift) > (1ll << 30)) return fail(LDC_E_INVALID, "bad shift");
+  for (int b = 0; lens && b < B; ++b) {
+    if (lens[b] > (L << shift) || (lens[b] >> shift) < 1) return fail(LDC_E_INVALID, "length %d of item %d must leave 1..%d rows at shift %d", (int)lens[b], b, L, shift);
+    if (t_items && (t_items[b] < 0 || t_items[b] >= u.timesteps)) return fail(LDC_E_INVALID, "t of item %d out of range", b);
+  }
+  // ---- which block ----
+  const ResnetW* r = nullptr;
+  const LinAttnW* a = nullptr;   // the attention block that follows it in a step (down<i>.2, mid.1, up<i>.2)
+  bool linear = true, is_final = false;
+  const std::string n = name;
+  auto level = [&](const char* pre, const std::vector<LevelW>& lv) {
+    const size_t pl = strlen(pre), dot = n.find('.');
+    if (n.compare(0, pl, pre) != 0 || dot == std::string::npos || dot == pl || n.find_first_not_of("0123456789", pl) != dot) return;
+    const size_t i = (size_t)atoi(n.c_str() + pl);
+    const std::string which = n.substr(dot + 1);
+    if (i >= lv.size() || (which != "1" && which != "2")) return;
+    r = which == "1" ? &lv[i].b1 : &lv[i].b2;
+    a = which == "2" ? &lv[i].attn : nullptr;
+  };
+  if (n == "mid.1") { r = &u.mid1; a = &u.mid_attn; linear = false; }
+  else if (n == "mid.2") r = &u.mid2;
+  else if (n == "final") { r = &u.fin; is_final = true; }
+  else { level("down", u.downs); level("up", u.ups); }
+  if (!r) return fail(LDC_E_INVALID, "unknown ResnetBlock '%s' (down<i>.1, down<i>.2, mid.1, mid.2, up<i>.1, up<i>.2, final)", name);
+  if (!route_only && (r->cin2 > 0) != (x2 != nullptr)) return fail(LDC_E_INVALID, "block '%s' reads %s", name, r->cin2 > 0 ? "a concatenation: x2 is missing" : "one tensor: x2 must be null");
+  if (with_attention && (!a || (!route_only && !attn_out))) return fail(LDC_E_INVALID, "with_attention: block '%s' has no attention block behind it, or attn_out is null", name);
+  hipStream_t s = pick_stream(c, stream);
+  const int dt = c->dt, g = u.groups, cout = r->cout;
+  const size_t es = dt_size(dt);
+  const size_t gn_bytes = (size_t)2 * B * g * kGnPad * 4;
+  const size_t lin_bytes = (size_t)B * linattn_ws_floats_per_item(u.heads, u.dim_head) * 4;
+  const int sk_tiles_cap = 1024;
+  Plan pl;
+  PlanEvents events{&pl};
+  pl.B = B; pl.L = lens ? L << shift : L;
+  pl.ragged = lens != nullptr; pl.items = t_items != nullptr;
+  PlanBuilder::ResnetTrace tr;
+  void *x1_cl = nullptr, *x2_cl = nullptr, *y_cl = nullptr, *ya_cl = nullptr;
+  auto build = [&](Arena& ar) {
+    pl.step_ops.clear(); pl.step_is_conv.clear(); pl.step_where.clear(); pl.step_flops.clear(); pl.step_class.clear(); pl.step_bytes.clear(); pl.step_info.clear();
+    pl.sk_need_max = 0; pl.part_need = 0;
+    PlanBuilder pb{c, &pl, &ar, B, es};
+    pb.trace = &tr;
+    // GroupNorm sums | split-K arrival counters | granule regions | LinearAttention workspace: what a step's first kernel clears
+    const size_t part_bytes = (pl.part_bytes + 63) / 64 * 64;
+    const size_t zero_bytes = gn_bytes + (size_t)sk_tiles_cap * 4 + part_bytes + lin_bytes;
+    pb.stats_pool = (float*)ar.alloc(zero_bytes + 64);
+    pb.sk_count = reinterpret_cast<unsigned*>(pb.stats_pool + gn_bytes / 4);
+    pb.part_pool = reinterpret_cast<char*>(pb.sk_count + sk_tiles_cap);
+    pb.part_cap = part_bytes;
+    pb.sk_count_cap = sk_tiles_cap;
+    pb.linattn_ws = reinterpret_cast<float*>(pb.part_pool + part_bytes);
+    pl.zero_ptr = pb.stats_pool; pl.zero_bytes = zero_bytes;
+    pb.sk_part_cap = pl.sk_floats;
+    pb.sk_part = (float*)ar.alloc((size_t)std::max<long long>(pb.sk_part_cap, 4) * 4);
+    pl.step_state = (int*)ar.alloc(64);
+    pl.cur_ss = (float*)ar.alloc((size_t)std::max(1, u.ss_stride) * 4);
+    pl.item_state = pl.items ? (ItemState*)ar.alloc((size_t)B * sizeof(ItemState)) : nullptr;
+    pl.lens = pl.ragged ? (int*)ar.alloc((size_t)B * 4) : nullptr;
+    pl.flens = nullptr;
+    x1_cl = pb.act(B * L, r->cin1);
+    x2_cl = r->cin2 > 0 ? pb.act(B * L, r->cin2) : nullptr;
+    ya_cl = nullptr;
+    if (with_attention) {   // the block and the attention block behind it, as build_plan pairs them
+      void* xn = nullptr;
+      if (pb.ln_foldable(*a, L)) { pb.want_rowstat = true; y_cl = pb.resnet(*r, x1_cl, x2_cl, L); }
+      else y_cl = pb.resnet(*r, x1_cl, x2_cl, L, a->norm_g, &xn, pb.qkv_fp8(*a));
+      ya_cl = pb.attention(*a, y_cl, L, linear, xn);
+    } else if (is_final) {   // the final block's tanh, as build_plan applies it
+      if (gn_apply_fp8_ok(u.dim)) {
+        y_cl = pb.resnet(*r, x1_cl, x2_cl, L, nullptr, nullptr, false, 4);
+      } else {
+        const void* xin = pb.resnet(*r, x1_cl, x2_cl, L);
+        void* tb = pb.act(B * L, u.dim);
+        const int64_t ne = (int64_t)B * L * u.dim;
+        pb.add([=](hipStream_t q) { return launch_act(dt, xin, tb, ne, ACT_TANH, q, 0); }, false, 0, LDC_CLASS_ELEMENTWISE, 2.0 * ne * es);
+        y_cl = tb;
+      }
+    } else {
+      y_cl = pb.resnet(*r, x1_cl, x2_cl, L);
+    }
+  };
+  for (int pass = 0; pass < 2; ++pass) {   // split-K workspace and granule pool from the convs' own dry runs, as get_plan sizes them
+    Arena dry;
+    build(dry);
+    pl.sk_floats = std::max(pl.sk_floats, pl.sk_need_max);
+    pl.part_bytes = std::max(pl.part_bytes, pl.part_need);
+  }
+  Arena measure;
+  build(measure);
+  auto route = [&]() {
+    info[0] = tr.epi1; info[1] = tr.epi2; info[2] = tr.folded; info[3] = tr.fuse_stats; info[4] = tr.xn; info[5] = tr.rowstat;
+    info[6] = tr.t1[0]; info[7] = tr.t1[1]; info[8] = tr.t2[0]; info[9] = tr.t2[1];
+    info[10] = info[11] = 0;
+  };
+  if (route_only) { route(); return LDC_OK; }
+  DevMem keep;
+  void* base = nullptr;
+  LDCCHK(keep.alloc(&base, measure.off + 4096));
+  Arena real;
+  real.base = (char*)base; real.cap = measure.off + 4096;
+  build(real);
+  if (real.off > real.cap) return fail(LDC_E_STATE, "internal: the plan needs %zu bytes, its planning pass measured %zu", real.off, real.cap);
+  HIPCHK(hipMemsetAsync(pl.step_state, 0, 64, s));   // (the epoch word)
+  if (lens) HIPCHK(launch_lens_write(pl.lens, lens, B, s));
+  HIPCHK(launch_to_cl(dt, x1, x1_cl, B, r->cin1, L, nullptr, 0, 0.f, s));
+  if (x2_cl) HIPCHK(launch_to_cl(dt, x2, x2_cl, B, r->cin2, L, nullptr, 0, 0.f, s));
+  if (lens) {   // the invariant a ragged plan gives its convs: zero behind every item's length
+    HIPCHK(launch_mask_rows(dt, x1_cl, B, L, r->cin1, pl.lens, shift, s));
+    if (x2_cl) HIPCHK(launch_mask_rows(dt, x2_cl, B, L, r->cin2, pl.lens, shift, s));
+  }
+  if (t_items) {
+    std::vector<ItemState> recs(B);
+    for (int b = 0; b < B; ++b) {
+      ItemState it{};
+      it.t = t_items[b]; it.remaining = 1; it.len = lens[b];
+      recs[b] = it;
+    }
+    HIPCHK(launch_items_write(pl.item_state, recs.data(), B, pl.lens, nullptr, upsample_factor(c), s));
+    HIPCHK(launch_step_begin_items(pl.item_state, B, pl.step_state, pl.zero_ptr, pl.zero_bytes, 0, s));
+  } else {
+    HIPCHK(launch_step_set(pl.step_state, t, 0, c->cur_key, s));
+    HIPCHK(launch_step_begin(u.ss_table, u.ss_stride, pl.step_state, pl.cur_ss, nullptr, s, pl.zero_ptr, pl.zero_bytes));
+  }
+  LDCCHK(run_ops(c, &pl, pl.step_ops, true, s));
+  HIPCHK(launch_from_cl(dt, y_cl, out, B, cout, L, nullptr, 0, 0.f, s));
+  HIPCHK(launch_from_cl(dt, tr.b, mid, B, cout, L, nullptr, 0, 0.f, s));
+  if (ya_cl) HIPCHK(launch_from_cl(dt, ya_cl, attn_out, B, a->dim, L, nullptr, 0, 0.f, s));
+  for (int k = 0; pre && k < 2; ++k) {   // the conv outputs as stored, where the route stores them
+    float* dst = pre + (size_t)k * B * cout * L;
+    const void* src = k == 0 ? tr.a : tr.d;
+    if (src) HIPCHK(launch_from_cl(dt, src, dst, B, cout, L, nullptr, 0, 0.f, s));
+    else HIPCHK(hipMemsetAsync(dst, 0, (size_t)B * cout * L * 4, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  LDCCHK(check_dev_flag(c));
+  // ---- the statistics as the kernels accumulated them ----
+  int tags_ok = 1, stray = 0;
+  const int cpg = cout / g;
+  for (int k = 0; k < 2; ++k) {
+    float* dst = stats + (size_t)k * B * g * 2;
+    const bool fused = k == 0 ? tr.epi1 : tr.epi2;
+    if (!fused) {
+      std::vector<float> h((size_t)B * g * kGnPad);
+      HIPCHK(hipMemcpy(h.data(), k == 0 ? tr.st1 : tr.st2, h.size() * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < B * g; ++i) { dst[2 * i] = h[(size_t)i * kGnPad]; dst[2 * i + 1] = h[(size_t)i * kGnPad + 1]; }
+      continue;
+    }
+    // gn_part[item][M-tile slot][wave row][32-column block] x {tag, sum, tag, sumsq} (conv_device.h: epilogue_gn_fused)
+    const int bm = (k == 0 ? tr.t1 : tr.t2)[0], wm = (k == 0 ? tr.t1 : tr.t2)[1], mslots = k == 0 ? tr.mslots1 : tr.mslots2;
+    const int nc32 = cout / 32, sub_n = cpg / 32;
+    if (bm <= 0 || wm <= 0 || sub_n <= 0) return fail(LDC_E_STATE, "internal: a fused conv without its tile shape");
+    std::vector<uint32_t> h((size_t)B * mslots * wm * nc32 * 4);
+    HIPCHK(hipMemcpy(h.data(), k == 0 ? tr.part1 : tr.part2, h.size() * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) {
+      const int lo = b * L, hi = lo + L;
+      const int used = (hi - 1) / bm - lo / bm + 1;   // the M-tile slots `gather` reads for this item
+      for (int gi = 0; gi < g; ++gi) { dst[((size_t)b * g + gi) * 2] = 0.f; dst[((size_t)b * g + gi) * 2 + 1] = 0.f; }
+      for (int ms = 0; ms < mslots; ++ms)
+        for (int w = 0; w < wm; ++w)
+          for (int c32 = 0; c32 < nc32; ++c32) {
+            const uint32_t* v = &h[((((size_t)b * mslots + ms) * wm + w) * nc32 + c32) * 4];
+            if (ms >= used) { stray |= (v[0] | v[1] | v[2] | v[3]) != 0u; continue; }
+            if (v[0] != 1u || v[2] != 1u) { tags_ok = 0; continue; }
+            float sv, qv;
+            memcpy(&sv, &v[1], 4); memcpy(&qv, &v[3], 4);
+            dst[((size_t)b * g + c32 / sub_n) * 2] += sv;
+            dst[((size_t)b * g + c32 / sub_n) * 2 + 1] += qv;
+          }
+    }
+  }
+  route();
+  info[10] = tags_ok; info[11] = stray;
+  return LDC_OK;
 }
 
 // one reverse-diffusion step of batch part k on stream s: select the timestep row, run the UNet, update the state,

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import lib as L
-from .spec import CodecConfig, UnetConfig
+from .spec import CodecConfig, UnetConfig, unet_graph
 
 
 @dataclass
@@ -310,6 +310,54 @@ class Engine:
         finally:
             self._exit()
         return out
+
+    RESNET_INFO = ("epi1", "epi2", "folded", "fuse_stats", "y_ln", "rowstat", "bm1", "wm1", "bm2", "wm2", "tags_complete", "stray_slots")
+
+    def debug_resnet_block(self, name: str, x1, x2=None, t: int = 0, lens=None, shift: int = 0, t_items=None, with_attention=False):
+        """ldc_debug_resnet_block: the ResnetBlock 'down<i>.1' / 'down<i>.2' / 'mid.1' / 'mid.2' / 'up<i>.1' / 'up<i>.2' / 'final' of the
+        loaded UNet on x1 [B, cin1, L] (and x2 [B, cin2, L] where the block reads a concatenation), routed by the plan builder under
+        the engine's current options.  lens (rows of level 0) with shift: a ragged plan; t_items: a per-item plan.  Returns a dict:
+        out, mid (block1's stored output) [B, cout, L], stats [2, B, groups, 2] (sum, sum of squares of conv 1 / conv 2 as the kernels
+        accumulated them), attn_out (with_attention: the attention block behind it), pre [2, B, cout, L] (the conv outputs as stored,
+        zeros for a conv with the fused epilogue) and info (RESNET_INFO -> int)."""
+        x1 = self._f32(x1)
+        x2 = self._f32(x2) if x2 is not None else None
+        B, _, Lx = x1.shape
+        cout = self.resnet_cout(name)
+        out, mid = self._empty(B, cout, Lx), self._empty(B, cout, Lx)
+        attn = self._empty(B, cout, Lx) if with_attention else None
+        pre = self._empty(2, B, cout, Lx)
+        stats = np.zeros((2, B, self.unet.groups, 2), np.float32)
+        info = (C.c_int * 12)()
+        arr = lambda v: (C.c_int * B)(*[int(i) for i in v]) if v is not None else None   # noqa: E731
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_debug_resnet_block(self._ctx, name.encode(), x1.data_ptr(), x2.data_ptr() if x2 is not None else None, B, Lx,
+                                                    int(t), arr(lens), int(shift), arr(t_items), int(bool(with_attention)), out.data_ptr(),
+                                                    mid.data_ptr(), stats.ctypes.data_as(C.c_void_p), attn.data_ptr() if attn is not None else None,
+                                                    pre.data_ptr(), info, s))
+        finally:
+            self._exit()
+        return dict(out=out, mid=mid, stats=stats, attn_out=attn, pre=pre, info=dict(zip(self.RESNET_INFO, info)))
+
+    def debug_resnet_route(self, name: str, B: int, Lx: int, lens=None, shift: int = 0, per_item=False, with_attention=False):
+        """the info dict of the debug_resnet_block call with these arguments, from the planner alone (nothing is launched)"""
+        info = (C.c_int * 12)()
+        arr = lambda v: (C.c_int * B)(*[int(i) for i in v]) if v is not None else None   # noqa: E731
+        L.check(self.lib.ldc_debug_resnet_block(self._ctx, name.encode(), None, None, int(B), int(Lx), 0, arr(lens), int(shift),
+                                                arr([0] * B) if per_item else None, int(bool(with_attention)), None, None, None, None, None, info, None))
+        return dict(zip(self.RESNET_INFO[:10], info))
+
+    def resnet_cout(self, name: str) -> int:
+        """output channels of the ResnetBlock `name` (debug_resnet_block's names)"""
+        g = unet_graph(self.unet)
+        if name == "final":
+            return g.final.cout
+        lvl, which = name.split(".")
+        if lvl == "mid":
+            return (g.mid1 if which == "1" else g.mid2).cout
+        lv = (g.downs if lvl.startswith("down") else g.ups)[int(lvl.lstrip("downup"))]
+        return (lv.block1 if which == "1" else lv.block2).cout
 
     SEA_ROUTES = {1: "cin1_rows", 2: "cin1_generic", 3: "pipelined", 4: "generic"}
     SEA_OP_KINDS = ("conv_cin1", "conv", "convtr", "res", "lstm")
