@@ -727,6 +727,17 @@ long long ldc_debug_lean_launches(int kind);
 /* Host-side cost of the step-graph replays since the last reset: milliseconds spent inside hipGraphLaunch, milliseconds spent
  * waiting for the bounded look-ahead window (LDC_FLOW_DEPTH), number of replays. */
 int ldc_host_stats(ldc_ctx* ctx, int reset, double* graph_launch_ms, double* lookahead_wait_ms, int64_t* graph_launches);
+/* The graph-length rule of the sampler loops; host-only, needs no context or GPU (like ldc_ddim_times).  A loop of n_steps steps over
+ * `parts` batch parts replays captured graphs of K steps and, for the remainder, of one step.  strided != 0: a DDIM / DPM loop.
+ * graph_steps_option: the value of the "graph_steps" option (0: the default).
+ *   want = option, if > 0; else 5 for a strided loop or several parts, 10 for one part of a DDPM loop.
+ *   DDPM with option 0: among the lengths that divide n_steps -- 8..25 for one part, 3..7 for several -- the one nearest to want, the
+ *   smaller of two equally near, replaces it.  K = want for a strided loop (every step count replays the same graphs), else
+ *   min(want, max(1, n_steps - 1)).
+ * n_big = n_steps / K replays of the K-step graph and n_single = n_steps - n_big K of the one-step graph: the counts of a loop whose
+ * graphs exist (a loop that captures runs its first step eagerly and replays the counts of n_steps - 1, with the same K).  Each output
+ * may be NULL.  Refused with LDC_E_INVALID: n_steps < 1, parts outside [1, 4], a negative option. */
+int ldc_graph_schedule(int n_steps, int parts, int strided, int graph_steps_option, int* K_out, int* n_big_out, int* n_single_out);
 /* Preconditions of the timed mode (round 6): what the part-stream calibration measured -- streams of the context that overlap with the
  * caller's stream and each other / candidates (good = -1: none has run), wall ms of one 150 us spin alone and of all accepted streams
  * spinning together, parts a batch is decoded as. */

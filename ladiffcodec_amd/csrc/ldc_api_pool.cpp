@@ -52,23 +52,10 @@ ItemState idle_record(int len) {
 
 // the pool's graphs and pinned plans leave the caches (nothing of them may be running)
 void drop_pool_plans(ldc_ctx* c, int id) {
-  for (size_t g = 0; g < c->graphs.size();) {
-    if (c->graphs[g].pool_id == id) {
-      c->graphs[g].destroy();
-      c->graphs.erase(c->graphs.begin() + g);
-    } else {
-      ++g;
-    }
-  }
+  drop_step_graphs(c, [id](const StepGraph& g) { return g.key.pool_id == id; });
   for (size_t i = 0; i < c->plans.size();) {
-    Plan* pl = c->plans[i].get();
-    if (pl->pool_id != id) { ++i; continue; }
-    for (int k = 0; k < c->last_halves.n; ++k)
-      if (c->last_halves.p[k] == pl) c->last_halves = Halves();
-    for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
-    if (pl->arena_base) (void)hipFree(pl->arena_base);
-    c->plan_bytes -= pl->arena_bytes;
-    c->plans.erase(c->plans.begin() + i);
+    if (c->plans[i]->pool_id == id) release_plan(c, i);
+    else ++i;
   }
 }
 
@@ -97,15 +84,12 @@ int pool_eager_step(ldc_ctx* c, ldc_pool* p, hipStream_t s) {
   return LDC_OK;
 }
 
-constexpr int kPoolGraphSteps = 5;   // steps per replayed graph, as the two-part denoise loop (ldc_api.cpp: denoise_loop); single steps for the remainder
+constexpr int kPoolGraphSteps = 5;   // steps per replayed graph, as the two-part denoise loop (ldc_api_sample.cpp: denoise_loop); single steps for the remainder
 
-StepGraph* pool_graph(ldc_ctx* c, const ldc_pool* p) {
-  for (auto& g : c->graphs)
-    if (g.pool_id == p->id) return &g;
-  c->graphs.push_back(StepGraph());
-  StepGraph* sg = &c->graphs.back();
-  sg->B = p->slots; sg->L = p->Lmax; sg->F = p->Fmax; sg->ragged = 1; sg->pool_id = p->id;
-  return sg;
+int pool_graph(ldc_ctx* c, const ldc_pool* p, StepGraph** out) {
+  StepGraphKey key;
+  key.B = p->slots; key.L = p->Lmax; key.F = p->Fmax; key.ragged = 1; key.pool_id = p->id;
+  return step_graph_for(c, key, out);
 }
 
 // n steps of every running slot.  ONE single-stream graph per batch part (5 steps, and 1 step for the remainder), captured once and
@@ -121,31 +105,12 @@ int pool_steps(ldc_ctx* c, ldc_pool* p, int n, hipStream_t s) {
     p->warm = true;
     if (done == n) return LDC_OK;
   }
-  StepGraph* sg = pool_graph(c, p);
-  sg->last_use = ++c->use_tick;
+  StepGraph* sg = nullptr;
+  LDCCHK(pool_graph(c, p, &sg));
   const int K = kPoolGraphSteps;
-  if (!sg->any()) {
-    for (int k = 0; k < h.n; ++k) {
-      hipStream_t sk = k == 0 ? s : c->aux_stream[k];
-      for (int which = 0; which < 2; ++which) {
-        const int steps = which == 0 ? K : 1;
-        hipGraph_t g = nullptr;
-        HIPCHK(hipStreamBeginCapture(sk, hipStreamCaptureModeRelaxed));
-        int r = LDC_OK;
-        for (int i = 0; i < steps && r == LDC_OK; ++i) r = pool_half_step(c, p, k, sk);
-        hipError_t e = hipStreamEndCapture(sk, &g);
-        // (a capture that fails midway drops the executables it has made: the entry stays unbuilt and the next call captures afresh)
-        if (r != LDC_OK) { if (g) (void)hipGraphDestroy(g); sg->destroy(); return r; }
-        if (e != hipSuccess) { sg->destroy(); return fail(LDC_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e)); }
-        e = hipGraphInstantiate(&sg->pexec[k][which], g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) { sg->pexec[k][which] = nullptr; sg->destroy(); return fail(LDC_E_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e)); }
-      }
-    }
-    sg->exec[0] = sg->pexec[0][0];   // marks the entry as built (StepGraph::any, destroy)
-    sg->per_part = true;
-    sg->n = h.n * 100 + K + 100000;
-    sg->stream = s;
+  if (!sg->built) {
+    LDCCHK(build_step_graphs(c, h, sg, K, true, h.n >= 2, s, [&](int k, hipStream_t sk) { return pool_half_step(c, p, k, sk); }));
+    sg->bound = StepGraphBinding{p->x, nullptr, s, h.n, K, true};
   }
   const int left = n - done, n_big = left / K, n_rep = n_big + (left - n_big * K);
   if (h.n >= 2) LDCCHK(fork_parts(c, h, s));

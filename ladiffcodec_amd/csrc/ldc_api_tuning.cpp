@@ -345,8 +345,7 @@ extern "C" int ldc_timeline_enable(ldc_ctx* c, int on) {
   if (!c) return fail(LDC_E_INVALID, "null ctx");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(counted_device_sync());
-  for (auto& g : c->graphs) g.destroy();
-  c->graphs.clear();
+  drop_step_graphs(c, [](const StepGraph&) { return true; });
   if (on && !c->tl_buf) {
     void* p = nullptr;
     HIPCHK(hipMalloc(&p, (size_t)kMaxParts * 2048 * 2 * sizeof(unsigned long long)));

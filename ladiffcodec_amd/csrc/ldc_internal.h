@@ -1,5 +1,6 @@
 // ldc_internal.h -- what the translation units of the C ABI share: the context and plan structures, error handling, the few
-// helpers of ldc_api.cpp (core: context, weights, codec stages, UNet plans, step graphs, samplers, ldc_decode) that
+// helpers of ldc_api.cpp (core: context, weights, codec stages, UNet plans, ldc_decode), ldc_api_sample.cpp (the denoise step, the denoise
+// loop, the sampler entry points) and step_graphs.cpp (the step-graph cache: step_graphs.h) that
 // ldc_api_ext.cpp (bit-stream, resampler and training entry points) and ldc_api_tuning.cpp (primitive KATs, cost / census / host
 // statistics, timeline and per-kernel stamps, profiling, microbenchmarks, self-checks) call.  Host-side C++ only.
 #pragma once
@@ -256,30 +257,7 @@ struct StepSampler {
   const DpmStep* dpm = nullptr;     // SAMPLER_DPM: c->dpm_table (likewise; dpm_update / windows_group_dpm_update also read and write the plan's x0_prev)
 };
 
-struct StepGraph {   // per batch part: hipGraph of {step_begin, unet step, p_sample_update | ddim_update | dpm_update, step_advance}
-  int B = 0, L = 0, F = 0, n = 0;
-  int ragged = 0;    // (part of the cache key) the steps of ragged plans
-  int pool_id = 0;   // (part of the cache key) != 0: the step graphs of that decode pool's plans
-  int win_id = 0;    // (part of the cache key) != 0: the steps of that coupled-windows plan (Plan::win_id)
-  int sampler = SAMPLER_DDPM;   // sampler kind (part of the cache key): a loop never replays another kind's graph (DDIM, DPM: the schedule table's address is captured, not its contents)
-  const float* noise = nullptr;
-  float* x = nullptr;
-  hipStream_t stream = nullptr;
-  hipGraphExec_t exec[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipGraphExec_t pexec[kMaxParts][2] = {};   // per-part single-stream graphs ([part][0] = K steps, [1] = one step)
-  bool per_part = false;
-  std::vector<hipEvent_t> part_ev;            // per-part mode: look-ahead events [part][depth]
-  uint64_t last_use = 0;
-  bool any() const { return exec[0] != nullptr; }
-  void destroy() {   // exec[0] aliases pexec[0][0] in per-part mode
-    if (per_part) exec[0] = nullptr;
-    for (hipEvent_t e : part_ev) (void)hipEventDestroy(e);
-    part_ev.clear();
-    for (auto& e : exec) { if (e) (void)hipGraphExecDestroy(e); e = nullptr; }
-    for (auto& pe : pexec) for (auto& e : pe) { if (e) (void)hipGraphExecDestroy(e); e = nullptr; }
-    per_part = false;
-  }
-};
+#include "step_graphs.h"
 
 struct ldc_ctx {
   ldc_config cfg;
@@ -371,7 +349,7 @@ struct ldc_ctx {
   ConvTune tune;
   int lstm_stream_only = 0;     // LDC_LSTM_STREAM: never use the cooperative LSTM
   int serial_parts = 0;         // LDC_SERIAL: batch parts back to back, eager (diagnostics)
-  int graph_steps = 0;          // option "graph_steps": denoise steps per replayed graph (0: by chain count, denoise_loop)
+  int graph_steps = 0;          // option "graph_steps": denoise steps per replayed graph (0: by chain count, ldc_graph_schedule)
   // plan / graph cache (LRU): a corpus with many distinct lengths must not grow device memory without bound
   uint64_t use_tick = 0, call_tick = 0;
   size_t plan_bytes = 0, plan_bytes_cap = (size_t)48 << 30;   // LDC_PLAN_CACHE_GB
@@ -543,6 +521,8 @@ int make_convtr(ldc_ctx* c, int dt, int cin, int cout, int stride, int trim_left
                 ConvLayer* out);
 int build_lstm(ldc_ctx* c, WeightReader& wr, const std::string& p, int H, int layers, std::vector<LstmLayer>* out);
 void drop_plans(ldc_ctx* c);
+void free_plan_resources(Plan* pl);        // what a plan owns on the device besides its cache entry: marker events, arena, DPM history, windows state
+void release_plan(ldc_ctx* c, size_t idx);   // plan `idx` leaves the cache (its step graphs have gone, nothing of it is running)
 int ensure_scratch(ldc_ctx* c, size_t bytes, hipStream_t s);
 int conv_out_len(const ConvLayer& ly, int L);
 int sea_conv(SeaRun& R, const ConvLayer& ly, const void* x, const void* residual, int L_in, void** y, int* L_out, int cout);
@@ -562,11 +542,19 @@ int calibrate_part_streams(ldc_ctx* c, hipStream_t s);
 bool parts_parallel(ldc_ctx* c, const Halves& h);
 int fork_parts(ldc_ctx* c, const Halves& h, hipStream_t s);
 int join_parts(ldc_ctx* c, const Halves& h, hipStream_t s);
-hipError_t replay_parts(ldc_ctx* c, const Halves& h, StepGraph* sg, int n_big, int n_rep, bool single_len, hipStream_t s, const char** what);
 int ragged_latent_quantum(const ldc_ctx* c);
 int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool ragged = false, bool items = false, int pool_id = 0);
 int load_cond(ldc_ctx* c, const Halves& h, const float* cond, hipStream_t s);
+int load_x(ldc_ctx* c, const Halves& h, const float* x, hipStream_t s);
+// ldc_api_sample.cpp: the denoise loop and the schedules, for ldc_decode, the windows front ends and the decode pools
+int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const float* noise, int n_steps, hipStream_t s, bool* left_forked = nullptr,
+                 const StepSampler& sm = StepSampler());
 int ddim_schedule_fill(ldc_ctx* c, int t_start, int n_steps, float eta, std::vector<DdimStep>* out, bool* draws);
+int ddim_schedule(ldc_ctx* c, int t_start, int n_steps, float eta, bool* draws);
+int ddim_upload(ldc_ctx* c, hipStream_t s);
+int dpm_schedule(ldc_ctx* c, int t_start, int n_steps);
+int dpm_upload(ldc_ctx* c, hipStream_t s);
+int ensure_history(ldc_ctx* c, const Halves& h);
 
 // runs `body` twice: once against a measuring arena, then (after sizing the scratch) for real
 template <typename F>

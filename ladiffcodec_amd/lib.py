@@ -31,7 +31,7 @@ EXPORTS = [
     "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
     "ldc_stream_min_first", "ldc_stream_create", "ldc_stream_reset", "ldc_stream_destroy", "ldc_seanet_encode_stream", "ldc_seanet_decode_stream", "ldc_get_cond_stream",
     "ldc_sconv1d", "ldc_sconvtr1d", "ldc_slstm", "ldc_unet_debug_tap", "ldc_unet_step_cost", "ldc_profile_enable",
-    "ldc_profile_read", "ldc_profile_read_classes", "ldc_conv_microbench", "ldc_conv_compare", "ldc_conv_compare_fp8", "ldc_ln_fold_compare", "ldc_gn_microbench", "ldc_host_stats", "ldc_stream_info", "ldc_clock_sample", "ldc_debug_raise_failure", "ldc_debug_attn_core", "ldc_debug_attention_block", "ldc_debug_resnet_block", "ldc_debug_sea_conv", "ldc_debug_sea_op", "ldc_debug_sync_count", "ldc_debug_lean_launches", "ldc_xcc_census", "ldc_timeline_enable", "ldc_timeline_read", "ldc_kstamps_enable", "ldc_kstamps_reset", "ldc_kstamps_read", "ldc_packed_bytes", "ldc_pack_codes", "ldc_unpack_codes",
+    "ldc_profile_read", "ldc_profile_read_classes", "ldc_conv_microbench", "ldc_conv_compare", "ldc_conv_compare_fp8", "ldc_ln_fold_compare", "ldc_gn_microbench", "ldc_host_stats", "ldc_graph_schedule", "ldc_stream_info", "ldc_clock_sample", "ldc_debug_raise_failure", "ldc_debug_attn_core", "ldc_debug_attention_block", "ldc_debug_resnet_block", "ldc_debug_sea_conv", "ldc_debug_sea_op", "ldc_debug_sync_count", "ldc_debug_lean_launches", "ldc_xcc_census", "ldc_timeline_enable", "ldc_timeline_read", "ldc_kstamps_enable", "ldc_kstamps_reset", "ldc_kstamps_read", "ldc_packed_bytes", "ldc_pack_codes", "ldc_unpack_codes",
     "ldc_ac_build_cdf", "ldc_ac_encode", "ldc_ac_decode", "ldc_train_q_sample", "ldc_train_num_timesteps", "ldc_train_predict_x_start", "ldc_train_neg_sdsdr", "ldc_train_l1_loss", "ldc_train_block_ws_floats",
     "ldc_train_block_forward", "ldc_train_block_backward", "ldc_train_layernorm_forward", "ldc_train_layernorm_backward", "ldc_train_adam_step", "ldc_train_adam_step_dev", "ldc_train_pointwise_forward", "ldc_train_pointwise_backward", "ldc_train_linattn_ws_floats", "ldc_train_linattn_forward", "ldc_train_linattn_backward", "ldc_train_conv_forward", "ldc_train_conv_backward", "ldc_train_join", "ldc_train_side_stream", "ldc_train_upsample2", "ldc_train_activation", "ldc_train_attn_ws_floats", "ldc_train_attn_forward", "ldc_train_attn_backward", "ldc_train_convtr_forward", "ldc_train_convtr_backward", "ldc_train_maxscale", "ldc_resample_out_len", "ldc_resample",
 ]
@@ -109,6 +109,7 @@ def load() -> C.CDLL:
     lib.ldc_output_normalise.argtypes = [vp, fp, i32, i32, i32, vp]
     lib.ldc_decode.argtypes = [vp, fp, i32, i32, i32, fp, i32, fp, fp, fp, vp, vp]
     lib.ldc_ddim_times.argtypes = [i32, i32, C.POINTER(C.c_int)]
+    lib.ldc_graph_schedule.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.ldc_ddim_sample.argtypes = [vp, fp, fp, fp, i32, i32, i32, C.c_float, i32, i32, i32, vp]
     lib.ldc_decode_ddim.argtypes = [vp, fp, i32, i32, i32, i32, C.c_float, fp, i32, fp, fp, fp, vp, vp]
     lib.ldc_decode_codes.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, fp, i32, fp, fp, fp, vp]
