@@ -1,4 +1,4 @@
-// ldc_api.cpp -- context, weight folding/packing, execution plans, hipGraph capture and the C ABI
+// ldc_api.cpp -- context, weight folding/packing, codec stages, the decode front ends and the C ABI (UNet plans: unet_plan.cpp)
 // declared in include/ladiffcodec.h.  Host-side C++ only; every kernel lives in the .hip files.
 //
 // Mapping to the reference (haiciyang/LaDiffCodec):
@@ -66,7 +66,6 @@ static std::vector<float> fold_weight_std(const HostTensor& wt) {
 
 
 // the column form of gn_apply (norm_act.hip) is the one that can write fp8
-static bool gn_apply_fp8_ok(int C) { return C % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0 && C <= 2048; }
 
 int make_conv(ldc_ctx* c, const ConvSpec& sp, const float* w_oik, const float* bias, ConvLayer* out) {
   ConvLayer ly;
@@ -1420,657 +1419,6 @@ extern "C" int ldc_cond_upsample(ldc_ctx* c, const float* cond, int B, int F, in
   return finish_stream(c, stream);
 }
 
-// ------------------------------------------------------------------------------------------------
-// UNet plan
-// ------------------------------------------------------------------------------------------------
-struct PlanBuilder {
-  ldc_ctx* c;
-  Plan* pl;
-  Arena* ar;
-  int B;
-  size_t es;   // element size of the UNet dtype
-  float* stats_pool = nullptr;   // [n_gn][B][groups][2]
-  int stats_used = 0;
-  char* part_pool = nullptr;     // granule regions of the fused GroupNorm applies (inside the region the step's first kernel clears)
-  size_t part_used = 0, part_cap = 0;
-  float* linattn_ws = nullptr;
-  int linattn_used = 0;
-  float* sk_part = nullptr;        // split-K workspace shared by the plan's convs (they run one after another)
-  unsigned* sk_count = nullptr;    // arrival counters, inside the region the step's memset clears
-  long long sk_part_cap = 0;
-  int sk_count_cap = 0;
-
-  void* act(int rows, int C) {
-    pl->act_bytes += (double)rows * C * es;
-    return ar->alloc((size_t)rows * C * es);
-  }
-  // ragged plan: the device lengths and the level of a tensor of L rows per item (a level's lengths are lens[b] >> level)
-  // (a planning pass on a measuring arena has no device memory: the lengths' address is a placeholder there, never dereferenced -- a null
-  // one made those passes plan the equal-length forms, so that a ragged plan of a model whose ResnetBlocks fuse their GroupNorm apply
-  // was measured WITHOUT the conv outputs its unfused forms store, and built past the end of its arena)
-  const int* lens() const { return pl->ragged ? (pl->lens ? pl->lens : reinterpret_cast<const int*>(16)) : nullptr; }
-  int level(int L) const {
-    int sh = 0;
-    while ((L << sh) < pl->L) ++sh;
-    return sh;
-  }
-  // the padding rows of y [B*L][C] written as zero: behind every plain conv whose output another conv reads (its bias and the taps that
-  // reach back over the item's edge leave values there)
-  void mask(void* y, int L, int C) {
-    if (!pl->ragged) return;
-    const int dt = c->dt, Bn = B, sh = level(L);
-    const int* ln = pl->lens;
-    info = "mask_rows_c" + std::to_string(C) + "_L" + std::to_string(L);
-    add([=](hipStream_t s) { return launch_mask_rows(dt, y, Bn, L, C, ln, sh, s); }, false, 0, LDC_CLASS_ELEMENTWISE, 0);
-  }
-  int where = 0;   // stream selector for the ops being added (0 main, 1 side)
-  void mark(int kind) {   // 2 = fork (side waits for main), 3 = join (main waits for side)
-    pl->step_ops.push_back([](hipStream_t) { return hipSuccess; });
-    pl->step_is_conv.push_back(0);
-    pl->step_where.push_back(kind);
-    pl->step_flops.push_back(0);
-    pl->step_class.push_back(LDC_CLASS_OTHER);
-    pl->step_bytes.push_back(0);
-    pl->step_info.push_back("-");
-  }
-  void add(std::function<hipError_t(hipStream_t)> f, bool is_conv = false, double flops = 0, int cls = LDC_CLASS_OTHER,
-           double bytes = 0) {
-    pl->step_ops.push_back(std::move(f));
-    pl->step_where.push_back(where);
-    pl->step_is_conv.push_back(is_conv ? 1 : 0);
-    pl->step_flops.push_back(flops);
-    pl->step_class.push_back(is_conv ? LDC_CLASS_CONV : cls);
-    pl->step_bytes.push_back(bytes);
-    pl->step_info.push_back(info.empty() ? std::string("-") : info);
-    info.clear();
-    pl->flops += flops;
-  }
-  std::string info;   // description of the next op added
-  void* y2_next = nullptr;   // second output of the next conv added (a layer with a folded 1x1 conv)
-  float* qkv_ctx_next = nullptr;   // context workspace of the next conv added (to_qkv with the context fold)
-  int qkv_ctx_stride_next = 0;
-  const float* ln_rowstat_next = nullptr;   // row-statistics partials of the next (LayerNorm-folded) conv's input
-  bool want_rowstat = false;                // the next resnet()'s fused block2 conv leaves those partials of its output ...
-  float* last_rowstat = nullptr;            // ... here (null when it could not)
-  // what the last resnet() built, for ldc_debug_resnet_block (null on every plan of a decode): the route it took and where its
-  // intermediate tensors and GroupNorm statistics live
-  struct ResnetTrace {
-    int epi1 = 0, epi2 = 0, folded = 0, fuse_stats = 0, xn = 0, rowstat = 0;
-    int t1[4] = {0, 0, 1, 0}, t2[4] = {0, 0, 1, 0};   // conv_bm of the two launched convs
-    void* b = nullptr;                                  // block1's stored output
-    void *a = nullptr, *d = nullptr;                    // unfused: the conv outputs as stored (what launch_gn_stats and gn_apply read)
-    float *st1 = nullptr, *st2 = nullptr;               // unfused: [B][groups][kGnPad]
-    char *part1 = nullptr, *part2 = nullptr;            // fused: the convs' granule regions
-    int mslots1 = 0, mslots2 = 0;
-  };
-  ResnetTrace* trace = nullptr;
-  // fused GroupNorm apply of a conv (see ConvCall::gn_cnt)
-  struct GnEpi {
-    void* part = nullptr;          // granule region of this conv
-    int mslots = 0;
-    float* rowstat = nullptr;      // with a residual: per-row (sum, sumsq) partials of the output for a LayerNorm folded into the consumer
-    const float* gamma = nullptr; const float* beta = nullptr; const float* ss = nullptr;
-    int out = 0;
-  };
-  // rows per tile the pipelined kernel would use for this conv (0: generic kernel) -- the fused apply needs L_out >= that
-  // (out[0] = rows per tile, out[1] = wave rows, out[2] = split-K factor)
-  void conv_bm(const ConvLayer& ly, int L_in, int L_out, bool with_stats, int* out) {   // out: int[4]
-    ConvCall d;
-    d.B = B; d.L_in = L_in; d.L_rows = L_out; d.y_ld = ly.n; d.tune = &c->tune;
-    d.sk_part = sk_part; d.sk_count = sk_count; d.sk_part_cap = sk_part_cap; d.sk_count_cap = sk_count_cap;
-    if (with_stats) { d.gn_sum = stats_pool; d.gn_groups = c->unet.groups; }
-    long long need = 0;
-    out[0] = out[1] = 0; out[2] = 1; out[3] = 0;
-    d.sk_need = &need; d.bm_out = out;
-    // (a layer with a folded second conv is refused without its second output -- conv_kargs -- and the refusal reads as "generic kernel, no
-    // fused epilogue": since round 5 asked for the folded layer's own tile shape, the nine folded block1 convs of a step had silently gone
-    // back to conv + gn_apply pairs.  Nothing is written in a dry run.)
-    if (ly.wtaps) d.y2 = reinterpret_cast<void*>(16);
-    (void)launch_conv(ly, d, nullptr);
-  }
-  // a granule region for a fused conv with tile height bm and wm wave rows; null when the pool is exhausted (first planning pass: sizes only)
-  bool take_part(GnEpi* ge, int L, int bm, int wm, int n) {
-    ge->mslots = (L + bm - 1) / bm + 1;
-    const size_t bytes = (size_t)B * ge->mslots * wm * (n / 32) * 16;
-    pl->part_need += bytes;
-    if (!part_pool || part_used + bytes > part_cap) return false;
-    ge->part = part_pool + part_used;
-    part_used += bytes;
-    return true;
-  }
-  void conv(const ConvLayer& ly, const void* x1, const void* x2, void* y, const void* residual, int L_in, int L_out,
-            float* gn_sum = nullptr, unsigned* colmax = nullptr, int cm_lo = 0, int cm_hi = 0, int cm_stride = 0,
-            const GnEpi* ge = nullptr) {
-    ConvCall cc;
-    cc.B = B; cc.L_in = L_in; cc.L_rows = L_out; cc.x1 = x1; cc.x2 = x2; cc.y = y; cc.residual = residual; cc.y_ld = ly.n;
-    cc.gn_sum = gn_sum; cc.gn_groups = gn_sum ? c->unet.groups : 0;
-    cc.y2 = y2_next; y2_next = nullptr;
-    cc.qkv_ctx_ws = qkv_ctx_next; cc.qkv_ctx_stride = qkv_ctx_stride_next; qkv_ctx_next = nullptr; qkv_ctx_stride_next = 0;
-    cc.ln_rowstat = ly.ln_s ? ln_rowstat_next : nullptr; ln_rowstat_next = nullptr;
-    if (pl->kst && pl->step_ops.size() < (size_t)kKstOps) {
-      cc.kst = pl->kst + pl->step_ops.size() * 2; cc.kst_stride = kKstOps * 2; cc.kst_step = pl->step_state;
-    }
-    if (ge && ge->part) {
-      cc.gn_groups = c->unet.groups;
-      cc.rowstat_out = residual ? ge->rowstat : nullptr;
-      cc.gn_part = ge->part; cc.gn_mslots = ge->mslots; cc.gn_gamma = ge->gamma; cc.gn_beta = ge->beta; cc.gn_ss = ge->ss; cc.gn_out = ge->out;
-      cc.fail_flag = c->dev_flag_dev;
-    }
-    cc.colmax = colmax; cc.colmax_lo = cm_lo; cc.colmax_hi = cm_hi; cc.colmax_stride = cm_stride;
-    cc.sk_part = sk_part; cc.sk_count = sk_count; cc.sk_part_cap = sk_part_cap; cc.sk_count_cap = sk_count_cap;
-    cc.tune = &c->tune;
-    {   // dry run of the launcher: how much split-K workspace would this conv use?
-      ConvCall d = cc;
-      long long need = 0;
-      d.sk_need = &need;
-      (void)launch_conv(ly, d, nullptr);
-      pl->sk_need_max = std::max(pl->sk_need_max, need);
-    }
-    const ConvLayer* lp = &ly;
-    {
-      char buf[96];
-      snprintf(buf, sizeof(buf), "k%d%s_s%d_u%d_c%d+%d->%d_L%d%s%s", ly.taps, ly.wtaps ? "+res" : "", ly.stride, ly.ups, ly.cin1, ly.cin2, ly.n, L_out,
-               (ge && ge->part) ? (residual ? "_gnapply+res" : "_gnapply") : (gn_sum ? "_gn" : ""), colmax ? "_kmax" : (cc.qkv_ctx_ws ? "_ctx" : ""));
-      info = buf;
-    }
-    const double cbytes = ((double)B * L_in * (ly.cin1 + ly.cin2) + (double)B * L_out * ly.n * (((ge && ge->part && residual) ? 2 : 1) + (ly.wtaps ? 1 : 0))) * es + (double)conv_packed_weight_bytes(ly);
-    pl->conv_bytes += cbytes;
-    add([lp, cc](hipStream_t s) { return launch_conv(*lp, cc, s); }, true, ly.flops_per_row * (double)B * L_out, LDC_CLASS_CONV, cbytes);
-  }
-  // zeroed-every-step bytes from the granule pool (nullptr while the pool is being sized)
-  void* take_raw(size_t bytes) {
-    bytes = (bytes + 63) / 64 * 64;
-    pl->part_need += bytes;
-    if (!part_pool || part_used + bytes > part_cap) return nullptr;
-    void* p = part_pool + part_used;
-    part_used += bytes;
-    return p;
-  }
-  float* next_stats() {
-    const int g = c->unet.groups;
-    return stats_pool + (size_t)(stats_used++) * B * g * kGnPad;
-  }
-  // ResnetBlock.forward (unet.py:176-192)
-  // ln_g != null: the block's last kernel also writes LayerNorm(out) * ln_g to *xn_out (the PreNorm of the attention
-  // block that consumes `out`)
-  // out_mode (final ResnetBlock only): bit 2 = write tanh(out) (unet.py:467), bit 0 = in fp8 (its only consumer is final_conv)
-  void* resnet(const ResnetW& r, const void* x1, const void* x2, int L, const float* ln_g = nullptr, void** xn_out = nullptr,
-               bool xn_fp8 = false, int out_mode = 0) {
-    const int rows = B * L, dt = c->dt, g = c->unet.groups, Bn = B;
-    const UnetW* u = &c->unet;
-    const float* cur_ss = pl->cur_ss;
-    // per-item plan: block1's gn_apply takes the (scale | shift) row of each item's own t from the table
-    const int* item_t = pl->items ? &pl->item_state->t : nullptr;
-    const float* ss_tab = u->ss_table + r.ss_off;
-    const int ss_stride = u->ss_stride, n_t = u->timesteps;
-    // fp8-weight context: block1's output feeds block2's conv alone, so it is produced in fp8 and that conv runs fp8 x fp8
-    const bool f8 = c->w8 && c->fp8_act && r.c2_f8.w != nullptr;
-    const int* ln = lens();   // ragged plan: conv -> gn_stats -> gn_apply, statistics over the valid rows, padding rows written as zero
-    const int sh = ln ? level(L) : 0;
-    void* b = f8 ? ar->alloc((size_t)rows * r.cout) : act(rows, r.cout);
-    void* out = (out_mode & 1) ? ar->alloc((size_t)rows * r.cout) : act(rows, r.cout);
-    float* st1 = next_stats();
-    float* st2 = next_stats();
-    const int cpg = r.cout / g;
-    const bool fuse_stats = !ln && c->fuse_gn_stats && cpg >= 4 && (cpg & (cpg - 1)) == 0;   // (a conv's own sums run over every row)
-    const bool rowstat_wanted = want_rowstat;
-    want_rowstat = false;
-    last_rowstat = nullptr;
-    // GroupNorm apply inside the conv epilogue (in-launch per-item wait): the tile height must not exceed twice an item's rows
-    // (a tile then straddles at most three items), and the output must be in the UNet dtype (fp8 outputs keep gn_apply)
-    const bool epi_ok = !ln && c->fuse_gn_epi && cpg % 32 == 0 && r.cout % 32 == 0 && L >= c->gn_epi_min_l;
-    bool epi1 = false, epi2 = false;
-    GnEpi ge1, ge2;
-    if (epi_ok) {
-      int t1[4], t2[4];
-      conv_bm(r.c1, L, L, false, t1);
-      // (the tile shape of the layer that will be LAUNCHED: with res_conv folded in -- decided below by the same rule -- that is c1r,
-      // which the 256 x 64 tiles do not take)
-      if (r.has_res && c->fold_res && r.c1r.w && t1[0] > 0 && t1[2] == 1) conv_bm(r.c1r, L, L, false, t1);
-      // Two gates on the tiles the dry run reports (BM x BN): (i) the launch as a whole stays within gn_epi_max_tiles (a performance gate:
-      // beyond two rounds of workgroups the waiting tiles cost more than the gn_apply launch they replace); (ii) a SAFETY gate per item --
-      // every tile spins until all tiles of its item(s) have published, and the dispatch order interleaves the items of a group of 8 M tiles,
-      // so an item's tiles plus two dispatch groups (the one it sits in, the one a straddling tile reaches into) must be resident together
-      // even while the other batch parts' launches hold their share of the chip (three workgroups of these kernels fit a CU: 41-51 KB of
-      // ring, <= 168 registers; the parts run concurrently).  A long single file (sample.py's whole-file mode: B = 1, L = samples / hop)
-      // fails (ii) and takes the conv + gn_apply pair instead of stalling every fused launch for its time-out.
-      // The slots come from the occupancy query of the kernels these convs land on x the device's CUs (round 6; before: a constant 3 x 256).
-      const int concurrent = std::max(2, c->split_batch);
-      const long resident_slots = (long)(c->w8 ? std::min(conv_fused_gn_wgs_per_cu(DT_BF16, true), conv_fused_gn_wgs_per_cu(DT_FP8, false)) : conv_fused_gn_wgs_per_cu(dt, false)) *
-                                  c->num_cus / concurrent * 8 / 10;
-      auto few_tiles = [&](const int* t) {
-        if (t[0] <= 0 || t[3] <= 0) return false;
-        const long ntn = (r.cout + t[3] - 1) / t[3];
-        const long launch_tiles = (long)((rows + t[0] - 1) / t[0]) * ntn;
-        const long item_tiles = (long)((L + t[0] - 1) / t[0] + 1) * ntn;
-        return launch_tiles <= c->gn_epi_max_tiles && (launch_tiles <= resident_slots || item_tiles + 16 * ntn <= resident_slots);
-      };
-      epi1 = (!f8 || dt == DT_BF16) && few_tiles(t1) && t1[0] <= 2 * L && take_part(&ge1, L, t1[0], t1[1], r.cout);   // f8: block1's output in fp8
-      conv_bm(f8 ? r.c2_f8 : r.c2, L, L, false, t2);
-      epi2 = (!(out_mode & 1) || dt == DT_BF16) && few_tiles(t2) && t2[0] <= 2 * L && take_part(&ge2, L, t2[0], t2[1], r.cout);
-    }
-    void* a = epi1 ? nullptr : act(rows, r.cout);   // un-normalised conv outputs exist only on the unfused path
-    void* d = epi2 ? nullptr : act(rows, r.cout);
-    // res_conv: folded into block1's conv where that conv runs on the pipelined kernel with an unsplit K (one launch and one
-    // read of x less); otherwise its own launch (on the side stream when there is one: it only feeds the final add)
-    const void* res = x1;
-    bool folded = false;
-    void* rr = r.has_res ? act(rows, r.cout) : nullptr;
-    if (r.has_res && c->fold_res && r.c1r.w) {
-      int t[4];
-      conv_bm(r.c1, L, L, false, t);
-      folded = t[0] > 0 && t[2] == 1;
-    }
-    if (r.has_res && !folded) {
-      mark(2);
-      where = 1;
-      conv(r.res, x1, x2, rr, nullptr, L, L);
-      where = 0;
-    }
-    if (r.has_res) res = rr;
-    const ConvLayer& c1 = folded ? r.c1r : r.c1;
-    const ResnetW* rp = &r;
-    if (epi1) {   // block1: conv -> GroupNorm -> (scale + 1, shift) -> SiLU, one launch, one store
-      ge1.gamma = r.g1; ge1.beta = r.b1; ge1.ss = cur_ss + r.ss_off; ge1.out = f8 ? 1 : 0;
-      if (folded) y2_next = rr;
-      conv(c1, x1, x2, b, nullptr, L, L, nullptr, nullptr, 0, 0, 0, &ge1);
-    } else {
-      if (folded) y2_next = rr;
-      conv(c1, x1, x2, a, nullptr, L, L, fuse_stats ? st1 : nullptr);
-      if (!fuse_stats) add([=](hipStream_t s) { return launch_gn_stats(dt, a, Bn, L, rp->cout, g, st1, s, ln, sh); });
-      add([=](hipStream_t s) {
-        if (item_t)
-          return launch_gn_apply(dt, a, b, nullptr, Bn, L, rp->cout, g, st1, rp->g1, rp->b1, ss_tab, ss_stride, item_t, ACT_SILU, s, nullptr,
-                                 nullptr, 0, ln, sh, kItemStateInts, n_t);
-        return launch_gn_apply(dt, a, b, nullptr, Bn, L, rp->cout, g, st1, rp->g1, rp->b1, cur_ss + rp->ss_off,
-                               0, nullptr, ACT_SILU, s, nullptr, nullptr, f8 ? 1 : 0, ln, sh);
-      }, false, 0, LDC_CLASS_GN_APPLY, (f8 ? 1.5 : 2.0) * Bn * L * rp->cout * es);
-    }
-    void* xn = nullptr;
-    const bool xn_made = ln_g && xn_out && c->fuse_ln && !ln && gn_apply_ln_fusable(r.cout);
-    if (xn_made) {
-      xn = xn_fp8 ? ar->alloc((size_t)rows * r.cout) : act(rows, r.cout);
-      *xn_out = xn;
-    }
-    if (trace) {
-      ResnetTrace& tr = *trace;
-      tr = ResnetTrace();
-      tr.epi1 = epi1; tr.epi2 = epi2; tr.folded = folded; tr.fuse_stats = fuse_stats; tr.xn = xn_made;
-      tr.rowstat = epi2 && rowstat_wanted && !f8;
-      conv_bm(c1, L, L, false, tr.t1);   // (as the gate above asks: the tile shape of the launched layer)
-      conv_bm(f8 ? r.c2_f8 : r.c2, L, L, false, tr.t2);
-      tr.b = b; tr.a = a; tr.d = d; tr.st1 = st1; tr.st2 = st2;
-      tr.part1 = (char*)ge1.part; tr.part2 = (char*)ge2.part; tr.mslots1 = ge1.mslots; tr.mslots2 = ge2.mslots;
-    }
-    if (epi2) {   // block2: conv -> GroupNorm -> SiLU -> + res (-> tanh), one launch; the PreNorm LayerNorm of a following attention block reads `out`
-      ge2.gamma = r.g2; ge2.beta = r.b2; ge2.ss = nullptr; ge2.out = out_mode & 5;
-      if (rowstat_wanted && !f8) ge2.rowstat = last_rowstat = (float*)ar->alloc((size_t)rows * (r.cout / 32) * 8);
-      if (r.has_res && !folded) mark(3);
-      conv(f8 ? r.c2_f8 : r.c2, b, nullptr, out, res, L, L, nullptr, nullptr, 0, 0, 0, &ge2);
-      if (xn) {
-        const int C = r.cout;
-        add([=](hipStream_t s) { return launch_ln_rows(dt, out, xn, nullptr, ln_g, rows, C, s, xn_fp8 ? 1 : 0); }, false, 0, LDC_CLASS_LAYERNORM,
-            (xn_fp8 ? 1.5 : 2.0) * rows * C * es);
-      }
-      return out;
-    }
-    conv(f8 ? r.c2_f8 : r.c2, b, nullptr, d, nullptr, L, L, fuse_stats ? st2 : nullptr);
-    if (!fuse_stats) add([=](hipStream_t s) { return launch_gn_stats(dt, d, Bn, L, rp->cout, g, st2, s, ln, sh); });
-    if (r.has_res && !folded) mark(3);
-    const int out8_ln = ((xn && xn_fp8) ? 2 : 0) | (gn_apply_fp8_ok(r.cout) ? out_mode : 0);
-    add([=](hipStream_t s) {
-      return launch_gn_apply(dt, d, out, res, Bn, L, rp->cout, g, st2, rp->g2, rp->b2, nullptr, 0, nullptr, ACT_SILU, s, xn, ln_g, out8_ln, ln, sh);
-    }, false, 0, LDC_CLASS_GN_APPLY, (xn ? 4.0 : 3.0) * Bn * L * rp->cout * es);
-    return out;
-  }
-  bool qkv_fp8(const LinAttnW& a) const { return c->w8 && c->fp8_act && a.qkv_f8.w != nullptr; }
-  // the attention block's PreNorm can ride inside to_qkv: the folded layer exists, runs on the pipelined kernel, and the ResnetBlock
-  // in front fuses its GroupNorm apply (else its gn_apply launch writes the LayerNorm output on the way at no extra launch)
-  bool ln_foldable(const LinAttnW& a, int L) {
-    if (pl->ragged || !c->fold_ln || !c->fuse_gn_epi || c->w8 || !a.qkv_ln.w || L < c->gn_epi_min_l) return false;
-    int t[4];
-    conv_bm(a.qkv_ln, L, L, false, t);
-    return t[0] > 0;
-  }
-  // Residual(PreNorm(LinearAttention)) (unet.py:208-222) / Residual(PreNorm(Attention)) (:234-246)
-  void* attention(const LinAttnW& a, const void* x, int L, bool linear, void* xn_pre = nullptr) {
-    const int rows = B * L, dt = c->dt, Bn = B;
-    const int H = c->unet.heads, Dh = c->unet.dim_head, hid = H * Dh;
-    const bool f8 = qkv_fp8(a);
-    const bool lnf = !xn_pre && ln_foldable(a, L);     // LayerNorm inside to_qkv: the conv reads x itself
-    const float* rowstat = lnf ? last_rowstat : nullptr;   // (sum, sumsq) partials of x's rows left by the ResnetBlock in front, if it could
-    last_rowstat = nullptr;
-    void* xn = lnf ? const_cast<void*>(x) : (xn_pre ? xn_pre : (f8 ? ar->alloc((size_t)rows * a.dim) : act(rows, a.dim)));
-    const ConvLayer& qkv_ly = lnf ? a.qkv_ln : (f8 ? a.qkv_f8 : a.qkv);
-    void* qkv = act(rows, 3 * hid);
-    void* o = act(rows, hid);
-    void* out = act(rows, a.dim);
-    const LinAttnW* ap = &a;
-    const int* ln = lens();
-    const int sh = ln ? level(L) : 0;
-    // one workspace per LinearAttention layer when the k column-max is fused: all of them are zeroed by the
-    // step's single memset (they sit behind the GroupNorm statistics)
-    // (a ragged plan too: its workspaces are cleared with the step's accumulators, so that its step graphs hold kernel nodes only)
-    float* ws = (linear && (c->fuse_kmax || ln)) ? linattn_ws + (size_t)(linattn_used++) * B * linattn_ws_floats_per_item(H, Dh) : linattn_ws;
-    if (!xn_pre && !lnf)
-      add([=](hipStream_t s) { return launch_ln_rows(dt, x, xn, nullptr, ap->norm_g, rows, ap->dim, s, f8 ? 1 : 0, ln, sh, L); }, false, 0, LDC_CLASS_LAYERNORM,
-          2.0 * rows * a.dim * es);
-    if (linear) {
-      const size_t wss = linattn_ws_floats_per_item(H, Dh);
-      if (!ln && c->fuse_kmax && c->fuse_attn_tail && !a.out.w8 && linattn_tail_supported(dt, H, Dh, a.dim)) {
-        // three launches: qkv conv (+ k column max) -> context -> tail (out, to_out conv, LayerNorm, + x); round 6: TWO where to_qkv
-        // accumulates the context itself (lean kernel, bf16, folded PreNorm: ConvCall::qkv_ctx_ws)
-        ln_rowstat_next = rowstat;
-        if (lnf && c->fold_ctx && c->tune.lean && !c->tune.force_generic && dt == DT_BF16 && a.qkv_ctx.w && hid == 128 && a.dim % 64 == 0) {
-          qkv_ctx_next = ws; qkv_ctx_stride_next = (int)wss;
-          conv(a.qkv_ctx, xn, nullptr, qkv, nullptr, L, L);
-        } else {
-          conv(qkv_ly, xn, nullptr, qkv, nullptr, L, L, nullptr, reinterpret_cast<unsigned*>(ws), hid, 2 * hid, (int)wss);
-          add([=](hipStream_t s) { return launch_linattn_ctx(dt, qkv, ws, Bn, L, H, Dh, s); }, false, 0, LDC_CLASS_LINATTN, 2.0 * rows * hid * es);
-        }
-        const int dim = a.dim;
-        info = "tail_c" + std::to_string(dim) + "_L" + std::to_string(L) + "_B" + std::to_string(B);
-        unsigned* flag = c->dev_flag_dev;
-        add([=](hipStream_t s) {
-          return launch_linattn_tail(dt, qkv, ws, ap->out.w, ap->out.n_pad, ap->out.bias, ap->out_g, x, out, Bn, L, H, Dh, dim, flag, s);
-        }, false, 2.0 * rows * hid * dim, LDC_CLASS_LINATTN, (1.0 * hid + 2.0 * dim) * rows * es);
-        return out;
-      }
-      if (c->fuse_kmax && !ln) {
-        ln_rowstat_next = rowstat;
-        conv(qkv_ly, xn, nullptr, qkv, nullptr, L, L, nullptr, reinterpret_cast<unsigned*>(ws), hid, 2 * hid, (int)wss);
-        add([=](hipStream_t s) { return launch_linattn(dt, qkv, o, ws, Bn, L, H, Dh, true, s); }, false, 0, LDC_CLASS_LINATTN,
-            4.0 * rows * hid * es);
-      } else {
-        ln_rowstat_next = rowstat;
-        conv(qkv_ly, xn, nullptr, qkv, nullptr, L, L);
-        add([=](hipStream_t s) { return launch_linattn(dt, qkv, o, ws, Bn, L, H, Dh, false, s, ln, sh, ln != nullptr); }, false, 0, LDC_CLASS_LINATTN,
-            5.0 * rows * hid * es);
-      }
-      void* t = act(rows, a.dim);
-      conv(a.out, o, nullptr, t, nullptr, L, L);
-      add([=](hipStream_t s) { return launch_ln_rows(dt, t, out, x, ap->out_g, rows, ap->dim, s, 0, ln, sh, L); }, false, 0, LDC_CLASS_LAYERNORM,
-          3.0 * rows * a.dim * es);
-    } else {
-      ln_rowstat_next = rowstat;
-      conv(qkv_ly, xn, nullptr, qkv, nullptr, L, L);
-      add([=](hipStream_t s) { return launch_attn_full(dt, qkv, o, Bn, L, H, Dh, s, ln, sh); }, false, 0, LDC_CLASS_ATTN_FULL, 4.0 * rows * hid * es);
-      conv(a.out, o, nullptr, out, x, L, L);   // + x in the epilogue
-      mask(out, L, a.dim);                     // (to_out's bias)
-    }
-    return out;
-  }
-};
-
-int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F) {
-  const UnetW& u = c->unet;
-  pl->B = B; pl->L = L; pl->F = F; pl->init_pc = nullptr;
-  pl->cond_ops.clear(); pl->step_ops.clear(); pl->step_is_conv.clear(); pl->step_where.clear(); pl->step_flops.clear(); pl->step_class.clear(); pl->step_bytes.clear(); pl->step_info.clear(); pl->taps.clear();
-  pl->flops = 0; pl->act_bytes = 0; pl->conv_bytes = 0; pl->sk_need_max = 0; pl->part_need = 0;
-  const int dt = c->dt;
-  const size_t es = dt_size(dt);
-  const int Cc = u.cond_channels, Cx = u.channels;
-  PlanBuilder pb{c, pl, &ar, B, es};
-  pl->zero_once.clear();
-  const int n_gn = 2 * (int)(2 * u.downs.size() + 2 + 2 * u.ups.size() + 1);
-  const size_t gn_bytes = (size_t)n_gn * B * u.groups * kGnPad * 4;
-  const bool lin_zeroed = c->fuse_kmax || pl->ragged;   // one LinearAttention workspace per layer, inside the region the step's first kernel clears
-  const size_t n_lin = lin_zeroed ? u.downs.size() + u.ups.size() : 1;
-  const size_t lin_bytes = n_lin * B * linattn_ws_floats_per_item(u.heads, u.dim_head) * 4;
-  const int sk_tiles_cap = 1024;
-  const size_t part_bytes = (pl->part_bytes + 63) / 64 * 64;   // granule regions of the fused GroupNorm applies (sized by the dry planning pass)
-  const size_t sk_count_bytes = (size_t)sk_tiles_cap * 4 + part_bytes;
-  const size_t sx_bytes = c->cfg.unet_scale_x ? (size_t)B * 4 : 0;   // per-item max|cat(cond, x)| of --unet_scale_x
-  pb.stats_pool = (float*)ar.alloc(gn_bytes + sk_count_bytes + lin_bytes + sx_bytes + 64);
-  pb.sk_count = reinterpret_cast<unsigned*>(pb.stats_pool + gn_bytes / 4);
-  pb.part_pool = reinterpret_cast<char*>(pb.sk_count + sk_tiles_cap);
-  pb.part_cap = part_bytes;
-  pb.sk_count_cap = sk_tiles_cap;
-  pb.linattn_ws = pb.stats_pool + (gn_bytes + sk_count_bytes) / 4;
-  // the region the step's ONE memset clears: GroupNorm sums, split-K counters, fused k-max keys, scale_x maxima
-  float* sx_max = pb.linattn_ws + (lin_zeroed ? lin_bytes / 4 : 0);
-  const size_t stats_bytes = gn_bytes + sk_count_bytes + (lin_zeroed ? lin_bytes : 0) + sx_bytes;
-  pb.sk_part_cap = pl->sk_floats;   // sized from the convs' own needs by a dry planning pass (get_plan)
-  pb.sk_part = (float*)ar.alloc((size_t)std::max<long long>(pb.sk_part_cap, 4) * 4);
-  pl->maxabs = (float*)ar.alloc((size_t)B * 4);
-  pl->step_state = (int*)ar.alloc(64);
-  if (ar.base) pl->zero_once.push_back({pl->step_state, 64});   // [4] = the epoch of the UNet pass (launch_step_begin counts it up)
-  pl->kst = c->kstamps ? (unsigned long long*)ar.alloc((size_t)2048 * kKstOps * 2 * 8) : nullptr;
-  pl->cur_ss = (float*)ar.alloc((size_t)std::max(1, u.ss_stride) * 4);
-  pl->x_cl = ar.alloc((size_t)B * L * Cx * es);
-  pl->eps_cl = ar.alloc((size_t)B * L * Cx * es);
-  pl->cond_cl = ar.alloc((size_t)B * L * Cc * es);
-  if (pl->items && !pl->ragged) return fail(LDC_E_INVALID, "a per-item plan is a ragged plan");
-  pl->item_state = pl->items ? (ItemState*)ar.alloc((size_t)B * sizeof(ItemState)) : nullptr;
-  if (pl->ragged) {
-    if (c->w8) return fail(LDC_E_INVALID, "ragged batches are not available on the fp8 engine (its fused forms have no length-aware variant): use dtype bf16 or f32");
-    pl->lens = (int*)ar.alloc((size_t)B * 4);
-    pl->flens = (int*)ar.alloc((size_t)B * 4);
-  } else {
-    pl->lens = pl->flens = nullptr;
-  }
-  // ---- process_cond (unet.py:407-420): fp32 upsampler, per-item max-abs, cast to the UNet dtype ----
-  void* cond_in = ar.alloc((size_t)B * F * Cc * 4);
-  pl->cond_in_cl = cond_in;
-  {
-    const void* x = cond_in;
-    int Lc = F;
-    const int Bn0 = B;
-    const int *rl = pl->ragged ? pl->lens : nullptr, *rf = pl->ragged ? pl->flens : nullptr;
-    // ragged: the upsampler sees zeros behind an item's last frame (whatever the caller's padding holds) ...
-    if (rf) pl->cond_ops.push_back([=](hipStream_t s) { return launch_mask_rows(DT_F32, cond_in, Bn0, F, Cc, rf, 0, s); });
-    for (const ConvLayer& ly : u.upsamplers) {
-      ConvCall cc;
-      cc.B = B; cc.L_in = Lc; cc.L_rows = Lc + 1; cc.L_final = Lc * ly.tr_stride; cc.y_ld = ly.tr_cout; cc.x1 = x; cc.tune = &c->tune;
-      void* y = ar.alloc((size_t)B * cc.L_final * ly.tr_cout * 4);
-      cc.y = y;
-      const ConvLayer* lp = &ly;
-      pl->cond_ops.push_back([lp, cc](hipStream_t s) { return launch_conv(*lp, cc, s); });
-      // ... and EVERY layer's output is cut to the item's length: the upsampler's transposed convs are not causal (their trim is
-      // symmetric), so what a layer leaves behind an item's end (its bias) would reach back into the item through the next layer.
-      // An item's rows of a layer's output are F_b rows of (positions per frame x channels) values.  The per-item maximum below then
-      // runs over the item's own frames, and the condition is zero in the padding
-      if (rf) {
-        const int row = cc.L_final / F * ly.tr_cout;
-        pl->cond_ops.push_back([=](hipStream_t s) { return launch_mask_rows(DT_F32, y, Bn0, F, row, rf, 0, s); });
-      }
-      x = y;
-      Lc = cc.L_final;
-    }
-    (void)rl;
-    if (Lc != L) return fail(LDC_E_INVALID, "upsampled condition length %d != latent length %d (F=%d, upsampling product %d)", Lc, L, F, upsample_factor(c));
-    float* mx = pl->maxabs;
-    void* cond_cl = pl->cond_cl;
-    const bool scale = c->cfg.unet_scale_cond != 0;
-    const int Bn = B;
-    const int64_t npi = (int64_t)L * Cc;
-    // fp32 rows -> (scaled) rows in the UNet dtype.  A [rows][C] fp32 -> dt copy is a "transpose" of a
-    // [B][C=1][L*C] tensor: reuse to_cl with C=1 (pure cast + scale).
-    if (scale) {
-      pl->cond_ops.push_back([=](hipStream_t s) { return hipMemsetAsync(mx, 0, (size_t)Bn * 4, s); });
-      pl->cond_ops.push_back([=](hipStream_t s) { return launch_maxabs(DT_F32, x, Bn, npi, 1, mx, s); });
-      pl->cond_ops.push_back([=](hipStream_t s) { return launch_to_cl(dt, (const float*)x, cond_cl, Bn, 1, (int)npi, mx, 1, 1e-20f, s); });
-    } else {
-      pl->cond_ops.push_back([=](hipStream_t s) { return launch_to_cl(dt, (const float*)x, cond_cl, Bn, 1, (int)npi, nullptr, 0, 0.f, s); });
-    }
-  }
-  pl->taps["cond_proc"] = {pl->cond_cl, Cc, L};
-  // ---- Unet1D.forward (unet.py:430-469) ----
-  pl->zero_ptr = pb.stats_pool;            // cleared by the step's first kernel (launch_step_begin): no memset node of its own
-  pl->zero_bytes = stats_bytes;
-  const void* in_cond = pl->cond_cl;
-  const void* in_x = pl->x_cl;
-  if (c->cfg.unet_scale_x) {
-    // unet.py:432-433: x = cat(cond, x) / (max|.| per item + 1e-20).  The max runs over both halves of the concatenation;
-    // the two scaled copies feed init_conv as its two inputs.
-    void* cs = ar.alloc((size_t)B * L * Cc * es);
-    void* xs = ar.alloc((size_t)B * L * Cx * es);
-    const void* cin = pl->cond_cl; const void* xin = pl->x_cl;
-    const int Bn = B;
-    const int64_t nc = (int64_t)L * Cc, nx = (int64_t)L * Cx;
-    pb.add([=](hipStream_t s) { return launch_maxabs(dt, cin, Bn, nc, 1, sx_max, s); });
-    pb.add([=](hipStream_t s) { return launch_maxabs(dt, xin, Bn, nx, 1, sx_max, s); });
-    pb.add([=](hipStream_t s) { return launch_scale_copy(dt, cin, cs, Bn, nc, sx_max, 1e-20f, s); }, false, 0, LDC_CLASS_ELEMENTWISE, 2.0 * B * nc * es);
-    pb.add([=](hipStream_t s) { return launch_scale_copy(dt, xin, xs, Bn, nx, sx_max, 1e-20f, s); }, false, 0, LDC_CLASS_ELEMENTWISE, 2.0 * B * nx * es);
-    in_cond = cs; in_x = xs;
-  }
-  void* x0 = pb.act(B * L, u.dim);
-  if (c->split_init && !c->w8 && !c->cfg.unet_scale_x && u.init_c.w && u.init_x.w) {
-    // the condition's half of init_conv once per sampler call (behind process_cond), the x half + that tensor every step
-    void* pc = pb.act(B * L, u.dim);
-    pl->init_pc = pc;
-    {
-      ConvCall cc;
-      cc.B = B; cc.L_in = L; cc.L_rows = L; cc.x1 = pl->cond_cl; cc.y = pc; cc.y_ld = u.init_c.n; cc.tune = &c->tune;
-      const ConvLayer* lp = &u.init_c;
-      pl->cond_ops.push_back([lp, cc](hipStream_t s) { return launch_conv(*lp, cc, s); });
-    }
-    pb.conv(u.init_x, in_x, nullptr, x0, pc, L, L);
-  } else {
-    pb.conv(u.init, in_cond, in_x, x0, nullptr, L, L);
-  }
-  pb.mask(x0, L, u.dim);
-  pl->taps["init"] = {x0, u.dim, L};
-  const void* x = x0;
-  int Lc = L;
-  std::vector<std::pair<const void*, int>> hs;
-  for (size_t i = 0; i < u.downs.size(); ++i) {
-    const LevelW& lv = u.downs[i];
-    x = pb.resnet(lv.b1, x, nullptr, Lc); hs.push_back({x, Lc});
-    void* xn = nullptr;
-    if (pb.ln_foldable(lv.attn, Lc)) { pb.want_rowstat = true; x = pb.resnet(lv.b2, x, nullptr, Lc); }
-    else x = pb.resnet(lv.b2, x, nullptr, Lc, lv.attn.norm_g, &xn, pb.qkv_fp8(lv.attn));
-    x = pb.attention(lv.attn, x, Lc, true, xn); hs.push_back({x, Lc});
-    int Ln = Lc;
-    if (lv.kind == 0) Ln = (Lc + 2 - 4) / 2 + 1;
-    void* y = pb.act(B * Ln, lv.cout);
-    pb.conv(lv.resample, x, nullptr, y, nullptr, Lc, Ln);
-    pb.mask(y, Ln, lv.cout);
-    x = y; Lc = Ln;
-    pl->taps["down" + std::to_string(i)] = {y, lv.cout, Lc};
-  }
-  {
-    void* xn = nullptr;
-    if (pb.ln_foldable(u.mid_attn, Lc)) { pb.want_rowstat = true; x = pb.resnet(u.mid1, x, nullptr, Lc); }
-    else x = pb.resnet(u.mid1, x, nullptr, Lc, u.mid_attn.norm_g, &xn, pb.qkv_fp8(u.mid_attn));
-    x = pb.attention(u.mid_attn, x, Lc, false, xn);
-  }
-  x = pb.resnet(u.mid2, x, nullptr, Lc);
-  pl->taps["mid"] = {const_cast<void*>(x), u.dims.back(), Lc};
-  for (size_t i = 0; i < u.ups.size(); ++i) {
-    const LevelW& lv = u.ups[i];
-    if (hs.back().second != Lc) return fail(LDC_E_INVALID, "latent length %d is not divisible by 2^%zu", L, u.downs.size() - 1);
-    x = pb.resnet(lv.b1, x, hs.back().first, Lc); hs.pop_back();
-    void* xn = nullptr;
-    if (pb.ln_foldable(lv.attn, Lc)) { pb.want_rowstat = true; x = pb.resnet(lv.b2, x, hs.back().first, Lc); }
-    else x = pb.resnet(lv.b2, x, hs.back().first, Lc, lv.attn.norm_g, &xn, pb.qkv_fp8(lv.attn));
-    hs.pop_back();
-    x = pb.attention(lv.attn, x, Lc, true, xn);
-    const int Ln = lv.kind == 1 ? 2 * Lc : Lc;
-    void* y = pb.act(B * Ln, lv.cout);
-    pb.conv(lv.resample, x, nullptr, y, nullptr, Lc, Ln);
-    pb.mask(y, Ln, lv.cout);
-    x = y; Lc = Ln;
-    pl->taps["up" + std::to_string(i)] = {y, lv.cout, Lc};
-  }
-  if (Lc != L) return fail(LDC_E_INVALID, "latent length %d does not survive the down/up path (got %d)", L, Lc);
-  {
-    // final ResnetBlock -> tanh -> final_conv (unet.py:465-469): the tanh is applied by the block's last kernel (one launch and
-    // two passes over the tensor less), in fp8 when final_conv runs fp8 x fp8
-    const bool f8 = c->w8 && c->fp8_act && u.final_conv_f8.w != nullptr;
-    const bool fuse_tanh = gn_apply_fp8_ok(u.dim);
-    const void* th = nullptr;
-    if (fuse_tanh) {
-      th = pb.resnet(u.fin, x, x0, L, nullptr, nullptr, false, 4 | (f8 ? 1 : 0));
-    } else {
-      x = pb.resnet(u.fin, x, x0, L);
-      void* tb = f8 ? ar.alloc((size_t)B * L * u.dim) : pb.act(B * L, u.dim);
-      const void* xin = x;
-      const int64_t n = (int64_t)B * L * u.dim;
-      pb.add([=](hipStream_t s) { return launch_act(dt, xin, tb, n, ACT_TANH, s, f8 ? 1 : 0); }, false, 0, LDC_CLASS_ELEMENTWISE, (f8 ? 1.5 : 2.0) * n * es);
-      th = tb;
-    }
-    pb.conv(f8 ? u.final_conv_f8 : u.final_conv, th, nullptr, pl->eps_cl, nullptr, L, L);
-  }
-  return LDC_OK;
-}
-
-// Drop plan `idx` (and every captured graph of its (L, F)): waits for the device first, nothing of it may be running.
-static void evict_plan(ldc_ctx* c, size_t idx) {
-  (void)counted_device_sync();
-  const Plan* pl = c->plans[idx].get();   // (its DPM and windows graphs carry the plan's L and F too)
-  drop_step_graphs(c, [pl](const StepGraph& g) { return g.key.L == pl->L && g.key.F == pl->F && g.key.pool_id == pl->pool_id; });
-  release_plan(c, idx);
-}
-
-int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged, bool items, int pool_id, const std::vector<int>* win_lens,
-             int win_O) {
-  static const std::vector<int> no_group;
-  const std::vector<int>& wgl = win_lens ? *win_lens : no_group;   // a windows plan: the ORDERED list of its recordings' lengths is part of the key (with L, its effective Lw)
-  for (auto& p : c->plans)
-    if (p->B == B && p->L == L && p->F == F && p->slot == slot && p->ragged == ragged && p->items == items && p->pool_id == pool_id &&
-        p->win_O == win_O && p->win_group.Ltot == wgl) {
-      p->last_use = ++c->use_tick;
-      *out = p.get();
-      return LDC_OK;
-    }
-  std::unique_ptr<Plan> pl(new Plan());
-  pl->ragged = ragged;
-  pl->items = items;
-  pl->pool_id = pool_id;
-  pl->win_O = win_O;
-  pl->win_group.Ltot = wgl;   // (the rest of the group's tables: windows_prepare)
-  for (int l : wgl) pl->win_Ltot += l;
-  if (win_lens) pl->win_id = c->next_win_id++;
-  {   // pass 1: what do the convs of this plan need as split-K workspace?
-    Arena dry;
-    LDCCHK(build_plan(c, pl.get(), dry, B, L, F));
-    pl->sk_floats = pl->sk_need_max;
-    pl->part_bytes = pl->part_need;
-    // once more with those sizes: convs that fuse their GroupNorm apply only once the granule pool exists ask for more of it, and
-    // the split-K decisions feed back into what is folded
-    Arena dry2;
-    LDCCHK(build_plan(c, pl.get(), dry2, B, L, F));
-    pl->sk_floats = std::max(pl->sk_floats, pl->sk_need_max);
-    pl->part_bytes = std::max(pl->part_bytes, pl->part_need);
-  }
-  Arena measure;
-  LDCCHK(build_plan(c, pl.get(), measure, B, L, F));
-  const size_t want = measure.off + 4096;
-  // LRU eviction: plans of the call being served (last_use > call_tick) are never candidates
-  for (;;) {
-    const bool over = c->plan_bytes + want > c->plan_bytes_cap || (int)c->plans.size() >= c->plan_count_cap;
-    if (!over) break;
-    size_t victim = c->plans.size();
-    for (size_t i = 0; i < c->plans.size(); ++i)
-      if (c->plans[i]->pool_id == 0 && c->plans[i]->last_use <= c->call_tick && (victim == c->plans.size() || c->plans[i]->last_use < c->plans[victim]->last_use)) victim = i;
-    if (victim == c->plans.size()) break;   // everything cached belongs to this call: let hipMalloc decide
-    evict_plan(c, victim);
-  }
-  void* base = nullptr;
-  hipError_t e = hipMalloc(&base, want);
-  if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the UNet workspace failed: %s", want, hipGetErrorString(e));
-  Arena real;
-  real.base = (char*)base;
-  real.cap = want;
-  int rc = build_plan(c, pl.get(), real, B, L, F);
-  if (rc == LDC_OK && real.off > want) rc = fail(LDC_E_STATE, "internal: the plan needs %zu bytes, its planning pass measured %zu", real.off, want);
-  if (rc != LDC_OK) { (void)hipFree(base); return rc; }
-  for (const auto& z : pl->zero_once) {   // the step state's epoch word: cleared once, before the plan's first use
-    hipError_t ez = hipMemsetAsync(z.first, 0, z.second, s);
-    if (ez != hipSuccess) { (void)hipFree(base); return fail(LDC_E_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(ez)); }
-  }
-  pl->arena_base = base;
-  pl->arena_bytes = want;
-  pl->slot = slot;
-  pl->last_use = ++c->use_tick;
-  c->plan_bytes += want;
-  *out = pl.get();
-  c->plans.push_back(std::move(pl));
-  (void)s;
-  return LDC_OK;
-}
-
 // The batch parts run as chains on streams of this context next to the caller's stream s.  HIP serves a process's streams from four
 // hardware queues and two streams that share one run their graphs back to back (measured: 229 instead of 143 ms per decode with part 1 on
 // such a stream; which streams share depends on what else the process created before -- torch's pool, RCCL, other contexts).  So the part
@@ -2148,72 +1496,12 @@ int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool r
   return LDC_OK;
 }
 
-int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step,
-            hipStream_t s) {
-  const bool use_side = is_step && !c->profile && c->side_streams;
-  hipStream_t side = c->side_stream[pl->slot];
-  if (use_side && pl->marker_events.empty()) {
-    size_t nm = 0;
-    for (int w : pl->step_where) nm += (w >= 2);
-    for (size_t k = 0; k < nm; ++k) {
-      hipEvent_t e = nullptr;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      pl->marker_events.push_back(e);
-    }
-  }
-  size_t marker = 0;
-  for (size_t i = 0; i < ops.size(); ++i) {
-    const bool prof = c->profile && is_step;
-    const int where = is_step ? pl->step_where[i] : 0;
-    if (where == 2) {
-      if (use_side) {
-        hipEvent_t e = pl->marker_events[marker];
-        HIPCHK(hipEventRecord(e, s));
-        HIPCHK(hipStreamWaitEvent(side, e, 0));
-      }
-      ++marker;
-      continue;
-    }
-    if (where == 3) {
-      if (use_side) {
-        hipEvent_t e = pl->marker_events[marker];
-        HIPCHK(hipEventRecord(e, side));
-        HIPCHK(hipStreamWaitEvent(s, e, 0));
-      }
-      ++marker;
-      continue;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-      HIPCHK(hipEventCreate(&e0));
-      HIPCHK(hipEventCreate(&e1));
-      HIPCHK(hipEventRecord(e0, s));
-    }
-    {
-      const hipError_t oe = ops[i]((use_side && where == 1) ? side : s);
-      if (oe != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(LDC_E_HIP, "%s op %zu (%s) failed: %s", is_step ? "step" : "cond", i, (is_step && i < pl->step_info.size()) ? pl->step_info[i].c_str() : "-", hipGetErrorString(oe));
-      }
-    }
-    if (prof) {
-      HIPCHK(hipEventRecord(e1, s));
-      c->prof_events.push_back({e0, e1});
-      c->prof_event_flops.push_back(pl->step_flops[i]);
-      c->prof_event_class.push_back(pl->step_class[i]);
-      c->prof_event_bytes.push_back(pl->step_bytes[i]);
-      c->prof_event_info.push_back(pl->step_info[i] + "_B" + std::to_string(pl->B));
-    }
-  }
-  return LDC_OK;
-}
-
 int load_cond(ldc_ctx* c, const Halves& h, const float* cond, hipStream_t s) {
   for (int k = 0; k < h.n; ++k) {
     Plan* pl = h.p[k];
     const float* src = cond + (size_t)h.b0[k] * c->unet.cond_channels * pl->F;
     HIPCHK(launch_to_cl(DT_F32, src, pl->cond_in_cl, pl->B, c->unet.cond_channels, pl->F, nullptr, 0, 0.f, s));
-    LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
+    LDCCHK(run_ops(c, pl, false, s));
   }
   return LDC_OK;
 }
@@ -2249,7 +1537,7 @@ extern "C" int ldc_unet_forward(ldc_ctx* c, const float* x, int t, const float* 
     Plan* pl = h.p[k];
     HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
     HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
-    LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+    LDCCHK(run_ops(c, pl, true, s));
     HIPCHK(launch_from_cl(c->dt, pl->eps_cl, eps_out + (size_t)h.b0[k] * c->unet.channels * L, pl->B, c->unet.channels, L, nullptr,
                           0, 0.f, s));
   }
@@ -2311,298 +1599,12 @@ extern "C" int ldc_unet_forward_ragged(ldc_ctx* c, const float* x, int t, const 
     HIPCHK(launch_mask_rows(c->dt, pl->x_cl, pl->B, Lmax, c->unet.channels, pl->lens, 0, s));   // (whatever the caller's padding holds)
     HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
     HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
-    LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+    LDCCHK(run_ops(c, pl, true, s));
     HIPCHK(launch_mask_rows(c->dt, pl->eps_cl, pl->B, Lmax, c->unet.channels, pl->lens, 0, s));   // (final_conv's bias)
     HIPCHK(launch_from_cl(c->dt, pl->eps_cl, eps_out + (size_t)h.b0[k] * c->unet.channels * Lmax, pl->B, c->unet.channels, Lmax, nullptr,
                           0, 0.f, s));
   }
   return finish_stream(c, stream);
-}
-
-extern "C" int ldc_unet_debug_tap(ldc_ctx* c, const char* name, float* out, int64_t capacity, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
-  if (!name || !out) return fail(LDC_E_INVALID, "null argument");
-  const Halves& h = c->last_halves;
-  if (h.n == 0) return fail(LDC_E_STATE, "no UNet call has been made yet");
-  int64_t need = 0;
-  for (int k = 0; k < h.n; ++k) {
-    auto it = h.p[k]->taps.find(name);
-    if (it == h.p[k]->taps.end()) return fail(LDC_E_INVALID, "unknown tap '%s'", name);
-    need += (int64_t)h.p[k]->B * it->second.C * it->second.L;
-  }
-  if (capacity < need) return fail(LDC_E_INVALID, "tap '%s' needs %lld elements", name, (long long)need);
-  hipStream_t s = pick_stream(c, stream);
-  for (int k = 0; k < h.n; ++k) {
-    const Plan::Tap& tp = h.p[k]->taps.find(name)->second;
-    HIPCHK(launch_from_cl(c->dt, tp.p, out + (size_t)h.b0[k] * tp.C * tp.L, h.p[k]->B, tp.C, tp.L, nullptr, 0, 0.f, s));
-  }
-  return finish_stream(c, stream);
-}
-
-// Residual(PreNorm(LinearAttention | Attention)) of one block of the loaded UNet on caller data (tests).  The launches come from
-// PlanBuilder::attention() itself, on a private plan that is never cached: every option (fold_ctx, fuse_attn_tail, fuse_kmax, fold_ln,
-// conv_lean) routes as it does in a decode -- the PreNorm folded into to_qkv, the context fold, the tail.  What differs from a decode:
-// no ResnetBlock in front, so a folded PreNorm computes its row statistics itself (as ldc_ln_fold_compare's out[0]) and an unfolded one
-// is its own launch; the batch is one part.  Synchronous: the call waits for its stream and reports a device-side failure of its own
-// launches.  Allocates and frees its workspace (hipFree waits for the device): not for the decode path.
-extern "C" int ldc_debug_attention_block(ldc_ctx* c, const char* name, const float* x, int B, int L, float* out, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
-  if (!name || !x || !out || B <= 0 || L <= 0) return fail(LDC_E_INVALID, "bad arguments");
-  const UnetW& u = c->unet;
-  const LinAttnW* a = nullptr;
-  bool linear = true;
-  const std::string n = name;
-  auto level = [&](const char* pre, const std::vector<LevelW>& lv) {
-    const size_t pl = strlen(pre);
-    if (n.compare(0, pl, pre) != 0 || n.size() == pl || n.find_first_not_of("0123456789", pl) != std::string::npos) return;
-    const size_t i = (size_t)atoi(n.c_str() + pl);
-    if (i < lv.size()) a = &lv[i].attn;
-  };
-  if (n == "mid") { a = &u.mid_attn; linear = false; }
-  else { level("down", u.downs); level("up", u.ups); }
-  if (!a) return fail(LDC_E_INVALID, "unknown attention block '%s' (down0..down%zu, mid, up0..up%zu)", name, u.downs.size() - 1, u.ups.size() - 1);
-  hipStream_t s = pick_stream(c, stream);
-  const int dt = c->dt, C = a->dim;
-  const size_t es = dt_size(dt);
-  const size_t lin_bytes = (size_t)B * linattn_ws_floats_per_item(u.heads, u.dim_head) * 4;
-  const int sk_tiles_cap = 1024;
-  Plan pl;
-  pl.B = B; pl.L = L;
-  void *x_cl = nullptr, *y_cl = nullptr, *zero = nullptr;
-  auto build = [&](Arena& ar) {
-    pl.step_ops.clear(); pl.step_is_conv.clear(); pl.step_where.clear(); pl.step_flops.clear(); pl.step_class.clear(); pl.step_bytes.clear(); pl.step_info.clear();
-    pl.sk_need_max = 0; pl.part_need = 0;
-    PlanBuilder pb{c, &pl, &ar, B, es};
-    zero = ar.alloc((size_t)sk_tiles_cap * 4 + lin_bytes);   // split-K arrival counters | LinearAttention workspace: what a step clears
-    pb.sk_count = reinterpret_cast<unsigned*>(zero);
-    pb.sk_count_cap = sk_tiles_cap;
-    pb.linattn_ws = reinterpret_cast<float*>(pb.sk_count + sk_tiles_cap);
-    pb.sk_part_cap = pl.sk_floats;
-    pb.sk_part = (float*)ar.alloc((size_t)std::max<long long>(pb.sk_part_cap, 4) * 4);
-    x_cl = pb.act(B * L, C);
-    y_cl = pb.attention(*a, x_cl, L, linear);
-  };
-  for (int pass = 0; pass < 2; ++pass) {   // split-K workspace from the convs' own dry runs, as get_plan sizes it
-    Arena dry;
-    build(dry);
-    pl.sk_floats = std::max(pl.sk_floats, pl.sk_need_max);
-  }
-  Arena measure;
-  build(measure);
-  DevMem keep;
-  void* base = nullptr;
-  LDCCHK(keep.alloc(&base, measure.off + 4096));
-  Arena real;
-  real.base = (char*)base; real.cap = measure.off + 4096;
-  build(real);
-  HIPCHK(hipMemsetAsync(zero, 0, (size_t)sk_tiles_cap * 4 + lin_bytes, s));
-  HIPCHK(launch_to_cl(dt, x, x_cl, B, C, L, nullptr, 0, 0.f, s));
-  LDCCHK(run_ops(c, &pl, pl.step_ops, true, s));
-  HIPCHK(launch_from_cl(dt, y_cl, out, B, C, L, nullptr, 0, 0.f, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return check_dev_flag(c);
-}
-
-// One ResnetBlock of the loaded UNet on caller data (tests), optionally with the attention block that follows it in a step.  As
-// ldc_debug_attention_block: a private plan that is never cached, the launches from PlanBuilder::resnet() (and attention()) themselves, so
-// fuse_gn_epi, fuse_gn_stats, fold_res, fold_ln, fuse_ln and conv_lean route as in a decode.  The timestep is set as a step sets it
-// (launch_step_set + launch_step_begin on the plan's zero region, or the item records + launch_step_begin_items), which also clears the
-// GroupNorm sums, the split-K counters and the granule regions of the fused convs in front of the run.  `stats` are the sums the kernels
-// themselves accumulated: the atomic / launch_gn_stats buffers, or the granules of the fused exchange read back and summed on the host.
-namespace {
-struct PlanEvents {   // run_ops creates the fork / join events of a plan on first use; a cached plan frees them when it is evicted
-  Plan* pl;
-  ~PlanEvents() {
-    for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
-    pl->marker_events.clear();
-  }
-};
-}   // namespace
-extern "C" int ldc_debug_resnet_block(ldc_ctx* c, const char* name, const float* x1, const float* x2, int B, int L, int t, const int32_t* lens,
-                                      int shift, const int32_t* t_items, int with_attention, float* out, float* mid, float* stats, float* attn_out,
-                                      float* pre, int* info, void* stream) {
-  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
-  const bool route_only = !out && !mid && !stats;   // planning on the host alone: info[0..9] of the run these arguments would make
-  if (!name || !info || B <= 0 || L <= 0 || (!route_only && (!x1 || !out || !mid || !stats))) return fail(LDC_E_INVALID, "bad arguments");
-  if (c->w8) return fail(LDC_E_INVALID, "ldc_debug_resnet_block does not support fp8 contexts (block1's output is stored in fp8 there)");
-  const UnetW& u = c->unet;
-  if (!t_items && (t < 0 || t >= u.timesteps)) return fail(LDC_E_INVALID, "t out of range");
-  if (t_items && !lens) return fail(LDC_E_INVALID, "per-item timesteps need lengths (a per-item plan is a ragged plan)");
-  if (!lens && shift != 0) return fail(LDC_E_INVALID, "shift without lengths");
-  if (shift < 0 || shift > 8 || ((long long)L << shift) > (1ll << 30)) return fail(LDC_E_INVALID, "bad shift");
-  for (int b = 0; lens && b < B; ++b) {
-    if (lens[b] > (L << shift) || (lens[b] >> shift) < 1) return fail(LDC_E_INVALID, "length %d of item %d must leave 1..%d rows at shift %d", (int)lens[b], b, L, shift);
-    if (t_items && (t_items[b] < 0 || t_items[b] >= u.timesteps)) return fail(LDC_E_INVALID, "t of item %d out of range", b);
-  }
-  // ---- which block ----
-  const ResnetW* r = nullptr;
-  const LinAttnW* a = nullptr;   // the attention block that follows it in a step (down<i>.2, mid.1, up<i>.2)
-  bool linear = true, is_final = false;
-  const std::string n = name;
-  auto level = [&](const char* pre, const std::vector<LevelW>& lv) {
-    const size_t pl = strlen(pre), dot = n.find('.');
-    if (n.compare(0, pl, pre) != 0 || dot == std::string::npos || dot == pl || n.find_first_not_of("0123456789", pl) != dot) return;
-    const size_t i = (size_t)atoi(n.c_str() + pl);
-    const std::string which = n.substr(dot + 1);
-    if (i >= lv.size() || (which != "1" && which != "2")) return;
-    r = which == "1" ? &lv[i].b1 : &lv[i].b2;
-    a = which == "2" ? &lv[i].attn : nullptr;
-  };
-  if (n == "mid.1") { r = &u.mid1; a = &u.mid_attn; linear = false; }
-  else if (n == "mid.2") r = &u.mid2;
-  else if (n == "final") { r = &u.fin; is_final = true; }
-  else { level("down", u.downs); level("up", u.ups); }
-  if (!r) return fail(LDC_E_INVALID, "unknown ResnetBlock '%s' (down<i>.1, down<i>.2, mid.1, mid.2, up<i>.1, up<i>.2, final)", name);
-  if (!route_only && (r->cin2 > 0) != (x2 != nullptr)) return fail(LDC_E_INVALID, "block '%s' reads %s", name, r->cin2 > 0 ? "a concatenation: x2 is missing" : "one tensor: x2 must be null");
-  if (with_attention && (!a || (!route_only && !attn_out))) return fail(LDC_E_INVALID, "with_attention: block '%s' has no attention block behind it, or attn_out is null", name);
-  hipStream_t s = pick_stream(c, stream);
-  const int dt = c->dt, g = u.groups, cout = r->cout;
-  const size_t es = dt_size(dt);
-  const size_t gn_bytes = (size_t)2 * B * g * kGnPad * 4;
-  const size_t lin_bytes = (size_t)B * linattn_ws_floats_per_item(u.heads, u.dim_head) * 4;
-  const int sk_tiles_cap = 1024;
-  Plan pl;
-  PlanEvents events{&pl};
-  pl.B = B; pl.L = lens ? L << shift : L;
-  pl.ragged = lens != nullptr; pl.items = t_items != nullptr;
-  PlanBuilder::ResnetTrace tr;
-  void *x1_cl = nullptr, *x2_cl = nullptr, *y_cl = nullptr, *ya_cl = nullptr;
-  auto build = [&](Arena& ar) {
-    pl.step_ops.clear(); pl.step_is_conv.clear(); pl.step_where.clear(); pl.step_flops.clear(); pl.step_class.clear(); pl.step_bytes.clear(); pl.step_info.clear();
-    pl.sk_need_max = 0; pl.part_need = 0;
-    PlanBuilder pb{c, &pl, &ar, B, es};
-    pb.trace = &tr;
-    // GroupNorm sums | split-K arrival counters | granule regions | LinearAttention workspace: what a step's first kernel clears
-    const size_t part_bytes = (pl.part_bytes + 63) / 64 * 64;
-    const size_t zero_bytes = gn_bytes + (size_t)sk_tiles_cap * 4 + part_bytes + lin_bytes;
-    pb.stats_pool = (float*)ar.alloc(zero_bytes + 64);
-    pb.sk_count = reinterpret_cast<unsigned*>(pb.stats_pool + gn_bytes / 4);
-    pb.part_pool = reinterpret_cast<char*>(pb.sk_count + sk_tiles_cap);
-    pb.part_cap = part_bytes;
-    pb.sk_count_cap = sk_tiles_cap;
-    pb.linattn_ws = reinterpret_cast<float*>(pb.part_pool + part_bytes);
-    pl.zero_ptr = pb.stats_pool; pl.zero_bytes = zero_bytes;
-    pb.sk_part_cap = pl.sk_floats;
-    pb.sk_part = (float*)ar.alloc((size_t)std::max<long long>(pb.sk_part_cap, 4) * 4);
-    pl.step_state = (int*)ar.alloc(64);
-    pl.cur_ss = (float*)ar.alloc((size_t)std::max(1, u.ss_stride) * 4);
-    pl.item_state = pl.items ? (ItemState*)ar.alloc((size_t)B * sizeof(ItemState)) : nullptr;
-    pl.lens = pl.ragged ? (int*)ar.alloc((size_t)B * 4) : nullptr;
-    pl.flens = nullptr;
-    x1_cl = pb.act(B * L, r->cin1);
-    x2_cl = r->cin2 > 0 ? pb.act(B * L, r->cin2) : nullptr;
-    ya_cl = nullptr;
-    if (with_attention) {   // the block and the attention block behind it, as build_plan pairs them
-      void* xn = nullptr;
-      if (pb.ln_foldable(*a, L)) { pb.want_rowstat = true; y_cl = pb.resnet(*r, x1_cl, x2_cl, L); }
-      else y_cl = pb.resnet(*r, x1_cl, x2_cl, L, a->norm_g, &xn, pb.qkv_fp8(*a));
-      ya_cl = pb.attention(*a, y_cl, L, linear, xn);
-    } else if (is_final) {   // the final block's tanh, as build_plan applies it
-      if (gn_apply_fp8_ok(u.dim)) {
-        y_cl = pb.resnet(*r, x1_cl, x2_cl, L, nullptr, nullptr, false, 4);
-      } else {
-        const void* xin = pb.resnet(*r, x1_cl, x2_cl, L);
-        void* tb = pb.act(B * L, u.dim);
-        const int64_t ne = (int64_t)B * L * u.dim;
-        pb.add([=](hipStream_t q) { return launch_act(dt, xin, tb, ne, ACT_TANH, q, 0); }, false, 0, LDC_CLASS_ELEMENTWISE, 2.0 * ne * es);
-        y_cl = tb;
-      }
-    } else {
-      y_cl = pb.resnet(*r, x1_cl, x2_cl, L);
-    }
-  };
-  for (int pass = 0; pass < 2; ++pass) {   // split-K workspace and granule pool from the convs' own dry runs, as get_plan sizes them
-    Arena dry;
-    build(dry);
-    pl.sk_floats = std::max(pl.sk_floats, pl.sk_need_max);
-    pl.part_bytes = std::max(pl.part_bytes, pl.part_need);
-  }
-  Arena measure;
-  build(measure);
-  auto route = [&]() {
-    info[0] = tr.epi1; info[1] = tr.epi2; info[2] = tr.folded; info[3] = tr.fuse_stats; info[4] = tr.xn; info[5] = tr.rowstat;
-    info[6] = tr.t1[0]; info[7] = tr.t1[1]; info[8] = tr.t2[0]; info[9] = tr.t2[1];
-    info[10] = info[11] = 0;
-  };
-  if (route_only) { route(); return LDC_OK; }
-  DevMem keep;
-  void* base = nullptr;
-  LDCCHK(keep.alloc(&base, measure.off + 4096));
-  Arena real;
-  real.base = (char*)base; real.cap = measure.off + 4096;
-  build(real);
-  if (real.off > real.cap) return fail(LDC_E_STATE, "internal: the plan needs %zu bytes, its planning pass measured %zu", real.off, real.cap);
-  HIPCHK(hipMemsetAsync(pl.step_state, 0, 64, s));   // (the epoch word)
-  if (lens) HIPCHK(launch_lens_write(pl.lens, lens, B, s));
-  HIPCHK(launch_to_cl(dt, x1, x1_cl, B, r->cin1, L, nullptr, 0, 0.f, s));
-  if (x2_cl) HIPCHK(launch_to_cl(dt, x2, x2_cl, B, r->cin2, L, nullptr, 0, 0.f, s));
-  if (lens) {   // the invariant a ragged plan gives its convs: zero behind every item's length
-    HIPCHK(launch_mask_rows(dt, x1_cl, B, L, r->cin1, pl.lens, shift, s));
-    if (x2_cl) HIPCHK(launch_mask_rows(dt, x2_cl, B, L, r->cin2, pl.lens, shift, s));
-  }
-  if (t_items) {
-    std::vector<ItemState> recs(B);
-    for (int b = 0; b < B; ++b) {
-      ItemState it{};
-      it.t = t_items[b]; it.remaining = 1; it.len = lens[b];
-      recs[b] = it;
-    }
-    HIPCHK(launch_items_write(pl.item_state, recs.data(), B, pl.lens, nullptr, upsample_factor(c), s));
-    HIPCHK(launch_step_begin_items(pl.item_state, B, pl.step_state, pl.zero_ptr, pl.zero_bytes, 0, s));
-  } else {
-    HIPCHK(launch_step_set(pl.step_state, t, 0, c->cur_key, s));
-    HIPCHK(launch_step_begin(u.ss_table, u.ss_stride, pl.step_state, pl.cur_ss, nullptr, s, pl.zero_ptr, pl.zero_bytes));
-  }
-  LDCCHK(run_ops(c, &pl, pl.step_ops, true, s));
-  HIPCHK(launch_from_cl(dt, y_cl, out, B, cout, L, nullptr, 0, 0.f, s));
-  HIPCHK(launch_from_cl(dt, tr.b, mid, B, cout, L, nullptr, 0, 0.f, s));
-  if (ya_cl) HIPCHK(launch_from_cl(dt, ya_cl, attn_out, B, a->dim, L, nullptr, 0, 0.f, s));
-  for (int k = 0; pre && k < 2; ++k) {   // the conv outputs as stored, where the route stores them
-    float* dst = pre + (size_t)k * B * cout * L;
-    const void* src = k == 0 ? tr.a : tr.d;
-    if (src) HIPCHK(launch_from_cl(dt, src, dst, B, cout, L, nullptr, 0, 0.f, s));
-    else HIPCHK(hipMemsetAsync(dst, 0, (size_t)B * cout * L * 4, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  LDCCHK(check_dev_flag(c));
-  // ---- the statistics as the kernels accumulated them ----
-  int tags_ok = 1, stray = 0;
-  const int cpg = cout / g;
-  for (int k = 0; k < 2; ++k) {
-    float* dst = stats + (size_t)k * B * g * 2;
-    const bool fused = k == 0 ? tr.epi1 : tr.epi2;
-    if (!fused) {
-      std::vector<float> h((size_t)B * g * kGnPad);
-      HIPCHK(hipMemcpy(h.data(), k == 0 ? tr.st1 : tr.st2, h.size() * 4, hipMemcpyDeviceToHost));
-      for (int i = 0; i < B * g; ++i) { dst[2 * i] = h[(size_t)i * kGnPad]; dst[2 * i + 1] = h[(size_t)i * kGnPad + 1]; }
-      continue;
-    }
-    // gn_part[item][M-tile slot][wave row][32-column block] x {tag, sum, tag, sumsq} (conv_device.h: epilogue_gn_fused)
-    const int bm = (k == 0 ? tr.t1 : tr.t2)[0], wm = (k == 0 ? tr.t1 : tr.t2)[1], mslots = k == 0 ? tr.mslots1 : tr.mslots2;
-    const int nc32 = cout / 32, sub_n = cpg / 32;
-    if (bm <= 0 || wm <= 0 || sub_n <= 0) return fail(LDC_E_STATE, "internal: a fused conv without its tile shape");
-    std::vector<uint32_t> h((size_t)B * mslots * wm * nc32 * 4);
-    HIPCHK(hipMemcpy(h.data(), k == 0 ? tr.part1 : tr.part2, h.size() * 4, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b) {
-      const int lo = b * L, hi = lo + L;
-      const int used = (hi - 1) / bm - lo / bm + 1;   // the M-tile slots `gather` reads for this item
-      for (int gi = 0; gi < g; ++gi) { dst[((size_t)b * g + gi) * 2] = 0.f; dst[((size_t)b * g + gi) * 2 + 1] = 0.f; }
-      for (int ms = 0; ms < mslots; ++ms)
-        for (int w = 0; w < wm; ++w)
-          for (int c32 = 0; c32 < nc32; ++c32) {
-            const uint32_t* v = &h[((((size_t)b * mslots + ms) * wm + w) * nc32 + c32) * 4];
-            if (ms >= used) { stray |= (v[0] | v[1] | v[2] | v[3]) != 0u; continue; }
-            if (v[0] != 1u || v[2] != 1u) { tags_ok = 0; continue; }
-            float sv, qv;
-            memcpy(&sv, &v[1], 4); memcpy(&qv, &v[3], 4);
-            dst[((size_t)b * g + c32 / sub_n) * 2] += sv;
-            dst[((size_t)b * g + c32 / sub_n) * 2 + 1] += qv;
-          }
-    }
-  }
-  route();
-  info[10] = tags_ok; info[11] = stray;
-  return LDC_OK;
 }
 
 static int ensure_outnorm(ldc_ctx* c, int B) {
@@ -2767,7 +1769,7 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
         if (split_ends && kk != k) continue;
         Plan* pl = h.p[kk];
         HIPCHK(hipMemcpyAsync(pl->cond_in_cl, qr + (size_t)(h.b0[kk] - b0) * F * D, (size_t)pl->B * F * D * 4, hipMemcpyDeviceToDevice, sk));
-        LDCCHK(run_ops(c, pl, pl->cond_ops, false, sk));
+        LDCCHK(run_ops(c, pl, false, sk));
         HIPCHK(launch_to_cl(c->dt, x + (size_t)h.b0[kk] * c->unet.channels * pl->L, pl->x_cl, pl->B, c->unet.channels, pl->L, nullptr, 0, 0.f, sk));
       }
     }
@@ -3185,7 +2187,7 @@ static int windows_sampler(ldc_ctx* c, Plan* pl, int sampler, hipStream_t s, Ste
 // the windows' condition slices from the packed cond ([Cc][Ftot_r] blocks) through process_cond, as ldc_unet_forward does at B = W_sum
 static int windows_load_cond(ldc_ctx* c, Plan* pl, const float* cond, hipStream_t s) {
   HIPCHK(launch_windows_group_gather(DT_F32, cond, pl->cond_in_cl, pl->B, c->unet.cond_channels, pl->F, pl->wg, upsample_factor(c), s));
-  return run_ops(c, pl, pl->cond_ops, false, s);
+  return run_ops(c, pl, false, s);
 }
 // the windows' input rows from the recordings' packed state
 static int windows_load_x(ldc_ctx* c, Plan* pl, const float* x, hipStream_t s) {
@@ -3207,7 +2209,7 @@ static int unet_forward_windows(ldc_ctx* c, const float* x, int t, const float* 
   LDCCHK(windows_load_x(c, pl, x, s));
   HIPCHK(launch_step_set(pl->step_state, t, 0, c->cur_key, s));
   HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, nullptr, s, pl->zero_ptr, pl->zero_bytes));
-  LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+  LDCCHK(run_ops(c, pl, true, s));
   HIPCHK(launch_windows_group_update(c->dt, WIN_BLEND, nullptr, pl->eps_cl, nullptr, 0, nullptr, eps_out, c->unet.channels, pl->wg, c->sched, nullptr,
                                      nullptr, s));
   return finish_stream(c, stream);
@@ -3346,7 +2348,7 @@ static int decode_windows_body(ldc_ctx* c, const FrontSrc& src, int R, const int
       }
     }
     if (!dry) {
-      LDCCHK(run_ops(c, pl, pl->cond_ops, false, s));
+      LDCCHK(run_ops(c, pl, false, s));
       LDCCHK(windows_load_x(c, pl, pl->win_x, s));
       LDCCHK(windows_loop(c, h, sm, noise, seeds, single, draws, n_steps, s));
       if (latents_out) HIPCHK(hipMemcpyAsync(latents_out, pl->win_x, (size_t)D * g.Lsum * 4, hipMemcpyDeviceToDevice, s));

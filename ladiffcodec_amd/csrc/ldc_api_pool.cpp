@@ -1,5 +1,5 @@
 // ldc_api_pool.cpp -- a timestep per item: ldc_unet_forward_items and the decode pools (include/ladiffcodec.h, "decode pools";
-// DESIGN.md section 5d).  Host-side C++ only.  The per-item plan is the ragged plan of ldc_api.cpp (PlanBuilder under Plan::items) whose
+// DESIGN.md section 5d).  Host-side C++ only.  The per-item plan is the ragged plan of unet_plan.cpp (PlanBuilder under Plan::items) whose
 // item-state table (ItemState, ldc_kernels.h) replaces the part's step_state {t, j, key} and cur_ss row; the kernels that read the table
 // are step_begin_items, gn_apply (t_stride) and p_sample_update_items.  The sampler is part of the record too: a DDIM item's record points
 // to its schedule, a row of the pool's schedule arena (ldc_pool_admit_ddim).
@@ -65,7 +65,7 @@ int pool_half_step(ldc_ctx* c, ldc_pool* p, int k, hipStream_t sk) {
   const int C = c->unet.channels;
   const int64_t item = (int64_t)C * p->Lmax;
   HIPCHK(launch_step_begin_items(pl->item_state, pl->B, pl->step_state, pl->zero_ptr, pl->zero_bytes, 1, sk));
-  LDCCHK(run_ops(c, pl, pl->step_ops, true, sk));
+  LDCCHK(run_ops(c, pl, true, sk));
   HIPCHK(launch_p_sample_update_items(c->dt, p->x + (size_t)p->h.b0[k] * item, item, pl->eps_cl, pl->x_cl, pl->B, C, p->Lmax, c->sched,
                                       pl->item_state, c->unet.timesteps, sk));
   return LDC_OK;
@@ -161,7 +161,7 @@ extern "C" int ldc_unet_forward_items(ldc_ctx* c, const float* x, const int32_t*
     HIPCHK(launch_to_cl(c->dt, x + (size_t)h.b0[k] * C * Lmax, pl->x_cl, pl->B, C, Lmax, nullptr, 0, 0.f, s));
     HIPCHK(launch_mask_rows(c->dt, pl->x_cl, pl->B, Lmax, C, pl->lens, 0, s));   // (whatever the caller's padding holds)
     HIPCHK(launch_step_begin_items(pl->item_state, pl->B, pl->step_state, pl->zero_ptr, pl->zero_bytes, 0, s));
-    LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+    LDCCHK(run_ops(c, pl, true, s));
     HIPCHK(launch_mask_rows(c->dt, pl->eps_cl, pl->B, Lmax, C, pl->lens, 0, s));   // (final_conv's bias)
     HIPCHK(launch_from_cl(c->dt, pl->eps_cl, eps_out + (size_t)h.b0[k] * C * Lmax, pl->B, C, Lmax, nullptr, 0, 0.f, s));
   }
@@ -273,7 +273,7 @@ static int pool_admit(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const
     HIPCHK(launch_lens_write(p1->lens, &L, 1, s));
     HIPCHK(launch_lens_write(p1->flens, &F, 1, s));
     HIPCHK(launch_to_cl(DT_F32, cond, p1->cond_in_cl, 1, Cc, F, nullptr, 0, 0.f, s));   // rows [0, F) of Fmax; cond_ops zero the rest
-    LDCCHK(run_ops(c, p1, p1->cond_ops, false, s));
+    LDCCHK(run_ops(c, p1, false, s));
     const size_t crow = (size_t)Lmax * Cc * es, prow = (size_t)Lmax * c->unet.dim * es, xrow = (size_t)Lmax * C * es;
     HIPCHK(hipMemcpyAsync((char*)pk->cond_cl + sb * crow, p1->cond_cl, crow, hipMemcpyDeviceToDevice, s));
     if (pk->init_pc) HIPCHK(hipMemcpyAsync((char*)pk->init_pc + sb * prow, p1->init_pc, prow, hipMemcpyDeviceToDevice, s));

@@ -21,7 +21,7 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
     HIPCHK(launch_step_begin(c->unet.ss_table, c->unet.ss_stride, pl->step_state, pl->cur_ss, tl, s, pl->zero_ptr, pl->zero_bytes, c->merge_advance,
                              sm.kind == SAMPLER_DDIM ? sm.ddim : nullptr));
   }
-  LDCCHK(run_ops(c, pl, pl->step_ops, true, s));
+  LDCCHK(run_ops(c, pl, true, s));
   if (pl->win_id) {   // coupled windows: x is the recordings' packed state, the blend and the update are one launch (the tape and the DPM history are packed like x, the keys are in the recording table)
     if (h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part");
     if (sm.kind == SAMPLER_DPM)

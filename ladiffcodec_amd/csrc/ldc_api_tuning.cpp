@@ -381,7 +381,7 @@ extern "C" int ldc_kstamps_read(ldc_ctx* c, int idx, int n_steps, int* n_ops, ui
   if (!c || idx < 0 || idx >= (int)c->plans.size() || !n_ops) return fail(LDC_E_INVALID, "bad arguments");
   Plan* pl = c->plans[idx].get();
   if (!pl->kst) return fail(LDC_E_STATE, "ldc_kstamps_enable has not been called");
-  const int nops = (int)std::min<size_t>(pl->step_ops.size(), kKstOps);
+  const int nops = (int)std::min<size_t>(pl->step.size(), kKstOps);
   *n_ops = nops;
   if (!ticks) return LDC_OK;
   if (n_steps < 1 || n_steps > 2048) return fail(LDC_E_INVALID, "n_steps must be in [1, 2048]");
@@ -397,8 +397,8 @@ extern "C" int ldc_kstamps_read(ldc_ctx* c, int idx, int n_steps, int* n_ops, ui
       ticks[((size_t)j * nops + o) * 2 + 1] = set ? ~e : 0;
     }
   for (int o = 0; o < nops; ++o) {
-    if (infos && info_cap > 0) snprintf(infos + (size_t)o * info_cap, info_cap, "%s", pl->step_info[o].c_str());
-    if (classes) classes[o] = pl->step_class[o];
+    if (infos && info_cap > 0) snprintf(infos + (size_t)o * info_cap, info_cap, "%s", pl->step[o].info.c_str());
+    if (classes) classes[o] = pl->step[o].cls;
   }
   return LDC_OK;
 }

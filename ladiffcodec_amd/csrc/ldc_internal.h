@@ -1,6 +1,6 @@
 // ldc_internal.h -- what the translation units of the C ABI share: the context and plan structures, error handling, the few
-// helpers of ldc_api.cpp (core: context, weights, codec stages, UNet plans, ldc_decode), ldc_api_sample.cpp (the denoise step, the denoise
-// loop, the sampler entry points) and step_graphs.cpp (the step-graph cache: step_graphs.h) that
+// helpers of ldc_api.cpp (core: context, weights, codec stages, ldc_decode), unet_plan.cpp (UNet plans: unet_plan.h), ldc_api_sample.cpp (the
+// denoise step, the denoise loop, the sampler entry points) and step_graphs.cpp (the step-graph cache: step_graphs.h) that
 // ldc_api_ext.cpp (bit-stream, resampler and training entry points) and ldc_api_tuning.cpp (primitive KATs, cost / census / host
 // statistics, timeline and per-kernel stamps, profiling, microbenchmarks, self-checks) call.  Host-side C++ only.
 #pragma once
@@ -23,6 +23,8 @@
 
 #include "ldc_kernels.h"
 #include "ldc_windows.h"
+#include "plan_passes.h"   // Arena, the planning protocol, the layout of the region a step clears
+static_assert(kGnSumFloats == ldc::kGnPad, "plan_passes.h sizes the GroupNorm sums by the kernels' padding");
 
 // Every device-wide synchronisation of the library goes through this counter (ldc_debug_sync_count): the steady state of the
 // decode path -- plans built, graphs captured -- must issue none (tests/test_gpu_parity.py: test_warm_decode_never_waits_for_the_device)
@@ -34,8 +36,7 @@ inline hipError_t counted_device_sync() {
 
 using namespace ldc;
 
-// errors: one message per thread, read through ldc_last_error
-int fail(int code, const char* fmt, ...);
+// errors: one message per thread, read through ldc_last_error: fail() (declared in plan_passes.h)
 #define HIPCHK(expr)                                                                                   \
   do {                                                                                                 \
     hipError_t _e = (expr);                                                                            \
@@ -58,17 +59,6 @@ struct HostTensor {
     size_t n = 1;
     for (auto s : shape) n *= (size_t)s;
     return n;
-  }
-};
-
-struct Arena {   // bump allocator over one device buffer; base == nullptr measures only
-  char* base = nullptr;
-  size_t cap = 0, off = 0;
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
   }
 };
 
@@ -223,18 +213,23 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
   WinGroupTables wg{};
   WinGroupRec* wg_rec = nullptr;   // == wg.rec, writable: the keys of a call go in on the stream
   std::vector<std::function<hipError_t(hipStream_t)>> cond_ops;   // process_cond (once per denoise)
-  std::vector<std::function<hipError_t(hipStream_t)>> step_ops;   // Unet1D.forward after process_cond
-  std::vector<int> step_is_conv;                                   // 1 where step_ops[i] is a conv-GEMM launch
-  std::vector<int> step_where;                                     // 0 main stream, 1 side stream, 2 fork, 3 join
+  struct StepOp {
+    std::function<hipError_t(hipStream_t)> fn;
+    int where;           // 0 main stream, 1 side stream, 2 fork, 3 join
+    int cls;             // LDC_CLASS_* (profiling)
+    double flops, bytes; // bytes: algorithmic HBM bytes
+    std::string info;    // human-readable shape (profile dump)
+  };
+  std::vector<StepOp> step;                                        // Unet1D.forward after process_cond
   std::vector<hipEvent_t> marker_events;                           // one event per fork/join marker (no re-use inside a capture)
-  std::vector<double> step_flops;
-  std::vector<int> step_class;                                     // LDC_CLASS_* of each op (profiling)
-  std::vector<double> step_bytes;                                  // algorithmic HBM bytes of each op
-  std::vector<std::string> step_info;                              // human-readable shape (profile dump)
   struct Tap { void* p; int C; int L; };
   std::map<std::string, Tap> taps;
   double flops = 0, act_bytes = 0, conv_bytes = 0;   // conv_bytes: inputs + outputs + packed weights of every conv-GEMM
   std::vector<std::pair<void*, size_t>> zero_once;   // regions cleared when the plan is created (the step state's epoch word)
+  void reset_build() {   // in front of every pass that builds the plan (plan_passes.h): what a pass appends to or accumulates
+    cond_ops.clear(); step.clear(); taps.clear(); zero_once.clear();
+    flops = 0; act_bytes = 0; conv_bytes = 0; sk_need_max = 0; part_need = 0;
+  }
 };
 
 // A batch is decoded as (up to) two independent halves on two streams: utterances do not interact inside
@@ -532,12 +527,9 @@ int rvq_rows(ldc_ctx* c, const float* z_rows, int rows, int n_q, int64_t* codes,
 int n_q_for_bandwidth(ldc_ctx* c, float bandwidth);
 int check_unet_args(ldc_ctx* c, int B, int L, int F);
 int upsample_factor(const ldc_ctx* c);
-int build_plan(ldc_ctx* c, Plan* pl, Arena& ar, int B, int L, int F);
 int check_dev(ldc_ctx* c);   // hipSetDevice only: calls that need no weights
+#include "unet_plan.h"
 // what ldc_api_pool.cpp shares with the samplers of ldc_api.cpp
-int get_plan(ldc_ctx* c, int B, int L, int F, int slot, hipStream_t s, Plan** out, bool ragged = false, bool items = false, int pool_id = 0,
-             const std::vector<int>* win_lens = nullptr, int win_O = 0);
-int run_ops(ldc_ctx* c, Plan* pl, const std::vector<std::function<hipError_t(hipStream_t)>>& ops, bool is_step, hipStream_t s);
 int calibrate_part_streams(ldc_ctx* c, hipStream_t s);
 bool parts_parallel(ldc_ctx* c, const Halves& h);
 int fork_parts(ldc_ctx* c, const Halves& h, hipStream_t s);
