@@ -270,6 +270,30 @@ int ldc_decode_ddim(ldc_ctx* ctx, const float* wav, int B, int T, int t_start, i
 int ldc_decode_ragged(ldc_ctx* ctx, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps,
                       float eta, const float* noise, float* wav_out, float* latents_out, float* cond_out,
                       int64_t* codes_out, void* stream);
+/* Item seeds: the samplers and decodes above with one Philox seed per item, seeds[B] uint64 in host memory.
+ * Item b, with its own latent length len_b (L of a rectangular call, its own length in a ragged one), draws at iteration j under key
+ * (lo(seeds[b]), hi(seeds[b])), counter (lo(g), hi(g), j, 0x4c444323), g = c_first * len_b + l, output (c mod 32) div 8: what
+ * ldc_reseed(seeds[b]) followed by the unseeded entry at B = 1 on the item's own length draws.  Neither the item's position in the batch,
+ * the padded length nor the batch part it lands in enter the draw; positions behind an item's length get no noise and stay zero; the
+ * context's noise epoch is neither read nor advanced.  sampler: 0 DDPM (n_steps steps from t = n_steps - 1; t_start and eta are not read),
+ * 1 DDIM (t_start, n_steps, eta as ldc_ddim_sample; draws only where the iteration is not the last and sigma > 0; eta == 0 accepts seeds
+ * and draws nothing).  The seeds are data: a step graph captured under one set serves any other.
+ * Refused with LDC_E_INVALID before any GPU work, the value named: seeds == NULL, a sampler other than 0 / 1 (DPM-Solver++ draws nothing,
+ * so there is nothing to seed) -- both also with a NULL context --, and everything the unseeded entry refuses.
+ * ldc_sample_seeded: ldc_denoise / ldc_ddim_sample on the given start image, rectangular. */
+int ldc_sample_seeded(ldc_ctx* ctx, float* img_inout, const float* cond, int sampler, int t_start, int n_steps, float eta,
+                      const uint64_t* seeds, int B, int L, int F, void* stream);
+/* ldc_decode / ldc_decode_ddim (lengths_host NULL: rectangular, T = Tmax) or ldc_decode_ragged (lengths_host[B] samples, with all its
+ * refusals, the fp8 engine's included) under item seeds.  The normalisation is per item at both ends, always: the start image is
+ * max-normalised over the item and so is the output -- otherwise "as if alone" would be false. */
+int ldc_decode_seeded(ldc_ctx* ctx, const float* wav, const int32_t* lengths_host /*[B] or NULL*/, int B, int Tmax, int sampler, int t_start,
+                      int n_steps, float eta, const uint64_t* seeds, float* wav_out, float* latents_out, float* cond_out,
+                      int64_t* codes_out, void* stream);
+/* ldc_decode_codes / ldc_decode_codes_ddim (frames_host NULL: every item Fmax frames) or ldc_decode_codes_ragged (frames_host[B]) under
+ * item seeds; per-item normalisation, as ldc_decode_seeded. */
+int ldc_decode_codes_seeded(ldc_ctx* ctx, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                            int Fmax, const int32_t* frames_host /*[B] or NULL*/, int sampler, int t_start, int n_steps, float eta,
+                            const uint64_t* seeds, float* wav_out, float* latents_out, float* cond_out, void* stream);
 /* Unet1D.forward with per-item latent lengths (test hook and building block): x [B,C,Lmax], cond [B,C,Fmax];
  * latent_lens_host[B] in latent frames, multiples of lcm(prod(upsampling_ratios), 2^halvings).  eps_out is zero beyond
  * an item's length. */

@@ -237,10 +237,13 @@ __device__ __forceinline__ float ddim_mean(const DdimStep& sp, float recip, floa
 // p_sample update on [B][C][L] fp32 state, eps arriving channels-last; also emits the channels-last
 // copy of the new state for the next UNet call.  Tile: 32 positions x 32 channels.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const void* eps_cl, const float* noise,
-                                                              int64_t noise_step_stride, void* x_cl, int C, int L,
-                                                              StepTables tb, const int* st, uint64_t elem_base, const int* lens) {
+// ITEM (the item-seeded form, DESIGN.md section 5e "Item seeds"): the Philox key of item blockIdx.z is item_keys[blockIdx.z] (the part's
+// key table, launch_item_keys_write) instead of the step state's, and the block index is the one of the item ALONE on its own length,
+// (c0 + ty) * Lv + l -- what p_sample_update_items_kernel draws -- so neither elem_base, the item's position nor the padded length enter.
+template <typename T, bool ITEM>
+__device__ __forceinline__ void p_sample_update_body(float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl,
+                                                     int C, int L, const StepTables& tb, const int* st, uint64_t elem_base, const int* lens,
+                                                     const uint64_t* item_keys) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
   const int Lv = valid_rows(lens, 0, b, L);   // ragged batch: positions [Lv, L) are padding -- x stays zero there, their noise is not read
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const vo
     xin[ii] = (cc < C && ll < L) ? x[((size_t)b * C + cc) * L + ll] : 0.f;
   }
   const int t = st[0], j = st[1];
-  const uint64_t seed = ((uint64_t)(unsigned)st[3] << 32) | (uint64_t)(unsigned)st[2];
+  const uint64_t seed = ITEM ? item_keys[b] : ((uint64_t)(unsigned)st[3] << 32) | (uint64_t)(unsigned)st[2];   // (the key rides with the step words, in front of the table chain)
   const float recip = tb.sqrt_recip_alphas_cumprod[t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[t];
   const float c1 = tb.posterior_mean_coef1[t], c2 = tb.posterior_mean_coef2[t];
   const float sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
@@ -268,7 +271,8 @@ __global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const vo
   // the thread's four elements (channels c0+ty+{0,8,16,24}, one position) share one Philox block; the block index is
   // the global index of the first of them, so the draws do not depend on how the batch is split
   float zz[4] = {0.f, 0.f, 0.f, 0.f};
-  if (t > 0 && !noise) philox_normal4(seed, (unsigned)j, elem_base + ((size_t)b * C + c0 + ty) * L + l0 + tx, zz);
+  if (t > 0 && !noise)
+    philox_normal4(seed, (unsigned)j, ITEM ? (uint64_t)(c0 + ty) * Lv + l0 + tx : elem_base + ((size_t)b * C + c0 + ty) * L + l0 + tx, zz);
 #pragma unroll
   for (int ii = 0; ii < 4; ++ii) {
     const int i = ty + ii * 8;
@@ -296,6 +300,18 @@ __global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const vo
     const int l = l0 + i, c = c0 + tx;
     if (l < L && c < C) dst<T>(x_cl, ((size_t)b * L + l) * C + c, tile[tx][i]);
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void p_sample_update_kernel(float* x, const void* eps_cl, const float* noise,
+                                                              int64_t noise_step_stride, void* x_cl, int C, int L,
+                                                              StepTables tb, const int* st, uint64_t elem_base, const int* lens) {
+  p_sample_update_body<T, false>(x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, st, elem_base, lens, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void p_sample_update_seeded_kernel(float* x, const void* eps_cl, const float* noise,
+                                                                     int64_t noise_step_stride, void* x_cl, int C, int L, StepTables tb,
+                                                                     const int* st, const int* lens, const uint64_t* item_keys) {
+  p_sample_update_body<T, true>(x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, st, 0, lens, item_keys);
 }
 
 // start images of the alternative samplers: standard normal (p_sample_loop, ddpm_loss.py:257) or uniform [0,1)
@@ -332,8 +348,17 @@ hipError_t launch_axpby(float* x, const float* y, float a, float b, int64_t n, h
 
 hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                                   void* x_cl, int B, int C, int L, StepTables tb, const int* st,
-                                  uint64_t elem_base, hipStream_t s, const int* lens) {
+                                  uint64_t elem_base, hipStream_t s, const int* lens, const uint64_t* item_keys) {
   dim3 grid((L + 31) / 32, (C + 31) / 32, B);
+  if (item_keys) {   // the item-seeded form: keys from the part's table, block indices of the item alone (elem_base does not enter)
+    if (dt == DT_F32)
+      hipLaunchKernelGGL(p_sample_update_seeded_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, st,
+                         lens, item_keys);
+    else
+      hipLaunchKernelGGL(p_sample_update_seeded_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, st,
+                         lens, item_keys);
+    return hipGetLastError();
+  }
   if (dt == DT_F32)
     hipLaunchKernelGGL(p_sample_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L,
                        tb, st, elem_base, lens);
@@ -348,11 +373,11 @@ hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const fl
 // j = st[1] from the host-written schedule table.  x0 uses eps as the UNet returned it (the reference does not
 // re-derive pred_noise from the clipped x0).
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* eps_cl, const float* noise,
-                                                          int64_t noise_step_stride, void* x_cl, int C, int L,
-                                                          StepTables tb, const DdimStep* sched, const int* st,
-                                                          uint64_t elem_base, const int* lens) {
+// ITEM: the item-seeded form, as p_sample_update_body's
+template <typename T, bool ITEM>
+__device__ __forceinline__ void ddim_update_body(float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride, void* x_cl, int C,
+                                                 int L, const StepTables& tb, const DdimStep* sched, const int* st, uint64_t elem_base,
+                                                 const int* lens, const uint64_t* item_keys) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
   const int Lv = valid_rows(lens, 0, b, L);   // as p_sample_update_kernel
@@ -367,7 +392,7 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* 
     xin[ii] = (cc < C && ll < L) ? x[((size_t)b * C + cc) * L + ll] : 0.f;
   }
   const int j = st[1];
-  const uint64_t seed = ((uint64_t)(unsigned)st[3] << 32) | (uint64_t)(unsigned)st[2];
+  const uint64_t seed = ITEM ? item_keys[b] : ((uint64_t)(unsigned)st[3] << 32) | (uint64_t)(unsigned)st[2];
   const DdimStep sp = sched[j];
   const float recip = tb.sqrt_recip_alphas_cumprod[sp.t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[sp.t];
   const bool draw = !sp.last && sp.sigma > 0.f;
@@ -377,7 +402,8 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* 
   float newv[4];
   // one Philox block per thread at the global index of its first element, as in p_sample_update_kernel
   float zz[4] = {0.f, 0.f, 0.f, 0.f};
-  if (draw && !noise) philox_normal4(seed, (unsigned)j, elem_base + ((size_t)b * C + c0 + ty) * L + l0 + tx, zz);
+  if (draw && !noise)
+    philox_normal4(seed, (unsigned)j, ITEM ? (uint64_t)(c0 + ty) * Lv + l0 + tx : elem_base + ((size_t)b * C + c0 + ty) * L + l0 + tx, zz);
 #pragma unroll
   for (int ii = 0; ii < 4; ++ii) {
     const int i = ty + ii * 8;
@@ -402,11 +428,33 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* 
     if (l < L && c < C) dst<T>(x_cl, ((size_t)b * L + l) * C + c, tile[tx][i]);
   }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void ddim_update_kernel(float* x, const void* eps_cl, const float* noise,
+                                                          int64_t noise_step_stride, void* x_cl, int C, int L,
+                                                          StepTables tb, const DdimStep* sched, const int* st,
+                                                          uint64_t elem_base, const int* lens) {
+  ddim_update_body<T, false>(x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, sched, st, elem_base, lens, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void ddim_update_seeded_kernel(float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
+                                                                 void* x_cl, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
+                                                                 const int* lens, const uint64_t* item_keys) {
+  ddim_update_body<T, true>(x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, sched, st, 0, lens, item_keys);
+}
 
 hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                               void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
-                              uint64_t elem_base, hipStream_t s, const int* lens) {
+                              uint64_t elem_base, hipStream_t s, const int* lens, const uint64_t* item_keys) {
   dim3 grid((L + 31) / 32, (C + 31) / 32, B);
+  if (item_keys) {   // the item-seeded form, as launch_p_sample_update's
+    if (dt == DT_F32)
+      hipLaunchKernelGGL(ddim_update_seeded_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, sched, st,
+                         lens, item_keys);
+    else
+      hipLaunchKernelGGL(ddim_update_seeded_kernel<__bf16>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L, tb, sched,
+                         st, lens, item_keys);
+    return hipGetLastError();
+  }
   if (dt == DT_F32)
     hipLaunchKernelGGL(ddim_update_kernel<float>, grid, dim3(256), 0, s, x, eps_cl, noise, noise_step_stride, x_cl, C, L,
                        tb, sched, st, elem_base, lens);
@@ -796,6 +844,24 @@ hipError_t launch_windows_group_keys(WinGroupRec* rec, const uint64_t* keys_host
   WinGroupKeys ks{};
   for (int r = 0; r < R; ++r) ks.k[r] = keys_host ? keys_host[r] : 0;
   hipLaunchKernelGGL(windows_group_keys_kernel, dim3(1), dim3(32), 0, s, rec, ks, R);
+  return hipGetLastError();
+}
+
+// the item keys of a seeded call's batch part written on the stream, as launch_windows_group_keys writes the recordings' (kernel arguments
+// carry them: no host buffer outlives the call, a captured step graph takes the keys from memory)
+constexpr int kItemKeyChunk = 32;
+struct ItemKeyChunk { uint64_t k[kItemKeyChunk]; };
+__global__ void item_keys_write_kernel(uint64_t* dst, ItemKeyChunk src, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = src.k[threadIdx.x];
+}
+hipError_t launch_item_keys_write(uint64_t* dst, const uint64_t* keys_host, int n, hipStream_t s) {
+  if (!dst || !keys_host || n < 1) return hipErrorInvalidValue;
+  for (int i0 = 0; i0 < n; i0 += kItemKeyChunk) {
+    ItemKeyChunk ch{};
+    const int m = std::min(kItemKeyChunk, n - i0);
+    for (int i = 0; i < m; ++i) ch.k[i] = keys_host[i0 + i];
+    hipLaunchKernelGGL(item_keys_write_kernel, dim3(1), dim3(kItemKeyChunk), 0, s, dst + i0, ch, m);
+  }
   return hipGetLastError();
 }
 

@@ -777,6 +777,7 @@ void free_plan_resources(Plan* pl) {
   for (hipEvent_t e : pl->marker_events) (void)hipEventDestroy(e);
   if (pl->arena_base) (void)hipFree(pl->arena_base);
   if (pl->x0_prev) (void)hipFree(pl->x0_prev);     // (every captured DPM graph of the plan has gone before)
+  if (pl->item_keys) (void)hipFree(pl->item_keys); // (likewise every seeded graph)
   if (pl->win_base) (void)hipFree(pl->win_base);   // (likewise every windows graph)
 }
 
@@ -1679,9 +1680,12 @@ static int ragged_cond_rows(ldc_ctx* c, const float* wav, int B, int b0, int Bk,
 }
 
 // rag (ldc_decode_ragged, ldc_decode_codes_ragged): the items' own lengths in samples (host, validated); T is then the padded length
+// seeds (ldc_decode_seeded, ldc_decode_codes_seeded; [B], host): item b draws under seeds[b] as if alone ("Item seeds");
+// noise is null and per_item 1, the context's noise epoch is neither read nor advanced
 // sampler: SAMPLER_DDPM, SAMPLER_DDIM (the schedule in c->ddim_host) or SAMPLER_DPM (c->dpm_host; draws false, noise null)
 static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_steps, int sampler, bool draws, const float* noise, int per_item,
-                       float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream, const int32_t* rag = nullptr) {
+                       float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream, const int32_t* rag = nullptr,
+                       const uint64_t* seeds = nullptr) {
   const Codec& cc = c->codec[LDC_MODEL_COND];
   const Codec& mc = c->codec[LDC_MODEL_MAIN];
   if (T % cc.hop || T % mc.hop) return fail(LDC_E_INVALID, "T must be a multiple of %d and %d (sample.py:87 trims to 640)", cc.hop, mc.hop);
@@ -1699,6 +1703,7 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
     for (int b = 0; b < B; ++b) { rag_lat.push_back(rag[b] / mc.hop); rag_fr.push_back(rag[b] / cc.hop); }
     LDCCHK(write_plan_lens(c, h, rag_lat, s));
   }
+  if (seeds) LDCCHK(write_item_keys(c, h, seeds, s));   // (on s, in front of the parts' forks and of the loop)
   // The codec front end (cond encoder -> RVQ -> upsampler -> start image) and back end (decoder) are chains of ~40 latency-bound
   // launches each (fp32 convs on a fraction of the CUs, LSTM recurrences): with per-utterance normalisation nothing couples the
   // items, so every batch part runs its own front / back end on its own stream, like its denoise steps, and the parts' chains fill
@@ -1782,10 +1787,11 @@ static int decode_body(ldc_ctx* c, const FrontSrc& src, int B, int T, int n_step
       // (the cooperative LSTMs), and one part's latency-bound back end then runs under the other's last denoise steps.
       // (c->ends_join / LDC_ENDS_JOIN: both joins as before, for A/B runs)
       if (split_ends && c->ends_join) { parts_open = false; LDCCHK(join_parts(c, h, s)); }
-      next_noise_key(c, noise == nullptr && draws);
+      if (!seeds) next_noise_key(c, noise == nullptr && draws);
       bool forked = false;
       StepSampler sm;
       sm.kind = sampler;
+      sm.item_seeds = seeds != nullptr;
       sm.ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
       sm.dpm = sampler == SAMPLER_DPM ? c->dpm_table : nullptr;
       const int dr = denoise_loop(c, h, B, x, noise, n_steps, s, (split_ends && !c->ends_join) ? &forked : nullptr, sm);
@@ -1847,8 +1853,9 @@ extern "C" int ldc_decode_ddim(ldc_ctx* c, const float* wav, int B, int T, int t
 }
 
 // ldc_decode / ldc_decode_ddim on a batch of items of different lengths (right-padded to Tmax): one call, every item as if alone
-extern "C" int ldc_decode_ragged(ldc_ctx* c, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps, float eta,
-                                 const float* noise, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+static int decode_ragged_impl(ldc_ctx* c, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps, float eta,
+                              const float* noise, const uint64_t* seeds, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out,
+                              void* stream) {
   LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
   if (!wav || !wav_out || B <= 0 || Tmax <= 0) return fail(LDC_E_INVALID, "bad arguments");
   if (t_start < 0) return fail(LDC_E_INVALID, "t_start must be >= 0 (0: DDPM halfway sampling)");
@@ -1861,7 +1868,11 @@ extern "C" int ldc_decode_ragged(ldc_ctx* c, const float* wav, const int32_t* le
   FrontSrc src;
   src.wav = wav;
   return decode_body(c, src, B, Tmax, n_steps, t_start > 0 ? SAMPLER_DDIM : SAMPLER_DDPM, draws, noise, 1, wav_out, latents_out, cond_out, codes_out,
-                     stream, lengths_host);
+                     stream, lengths_host, seeds);
+}
+extern "C" int ldc_decode_ragged(ldc_ctx* c, const float* wav, const int32_t* lengths_host, int B, int Tmax, int t_start, int n_steps, float eta,
+                                 const float* noise, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out, void* stream) {
+  return decode_ragged_impl(c, wav, lengths_host, B, Tmax, t_start, n_steps, eta, noise, nullptr, wav_out, latents_out, cond_out, codes_out, stream);
 }
 
 // ldc_get_cond on a right-padded batch (the sender side of ragged batches): every item's rows and codes as if encoded alone, 0 behind
@@ -1956,9 +1967,9 @@ extern "C" int ldc_decode_codes_ddim(ldc_ctx* c, const int64_t* codes, const uin
 // ldc_decode_codes / ldc_decode_codes_ddim with the length semantics of ldc_decode_ragged: frames_host[b] frames of item b are its own
 // (multiples of the ragged quantum / 320), the codes behind them are never read, a packed item's stream is ldc_packed_bytes(n_q,
 // frames_host[b], bits) long; t_start 0: DDPM halfway sampling, > 0: DDIM; per-item normalisation; outputs 0 beyond an item's length.
-extern "C" int ldc_decode_codes_ragged(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
-                                       int Fmax, const int32_t* frames_host, int t_start, int n_steps, float eta, const float* noise,
-                                       float* wav_out, float* latents_out, float* cond_out, void* stream) {
+static int decode_codes_ragged_impl(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                                    int Fmax, const int32_t* frames_host, int t_start, int n_steps, float eta, const float* noise,
+                                    const uint64_t* seeds, float* wav_out, float* latents_out, float* cond_out, void* stream) {
   if ((codes == nullptr) == (packed == nullptr)) return fail(LDC_E_INVALID, "exactly one of codes / packed must be given");
   if (!wav_out || B <= 0 || Fmax <= 0) return fail(LDC_E_INVALID, "bad arguments");
   if (!frames_host) return fail(LDC_E_INVALID, "null lengths");
@@ -1985,7 +1996,64 @@ extern "C" int ldc_decode_codes_ragged(ldc_ctx* c, const int64_t* codes, const u
   std::vector<int32_t> lens(B);
   for (int b = 0; b < B; ++b) lens[b] = frames_host[b] * cc.hop;
   return decode_body(c, src, B, T, n_steps, t_start > 0 ? SAMPLER_DDIM : SAMPLER_DDPM, draws, noise, 1, wav_out, latents_out, cond_out, nullptr, stream,
-                     lens.data());
+                     lens.data(), seeds);
+}
+extern "C" int ldc_decode_codes_ragged(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                                       int Fmax, const int32_t* frames_host, int t_start, int n_steps, float eta, const float* noise,
+                                       float* wav_out, float* latents_out, float* cond_out, void* stream) {
+  return decode_codes_ragged_impl(c, codes, packed, packed_stride, bits, n_q, B, Fmax, frames_host, t_start, n_steps, eta, noise, nullptr, wav_out,
+                                  latents_out, cond_out, stream);
+}
+
+// ---- item seeds ("Item seeds"): the decodes above with one Philox seed per item; item b draws what reseed(seeds[b])
+// followed by the unseeded entry at B = 1 on the item's own length draws.  Per-item normalisation at both ends, always.  The two
+// context-free refusals of every seeded entry come first (a NULL context sees them too).
+int seeded_args(int sampler, const uint64_t* seeds) {
+  if (sampler != SAMPLER_DDPM && sampler != SAMPLER_DDIM)
+    return fail(LDC_E_INVALID, "sampler %d: a seeded call takes 0 (DDPM) or 1 (DDIM) (DPM-Solver++ draws nothing: there is nothing to seed)", sampler);
+  if (!seeds) return fail(LDC_E_INVALID, "seeds NULL: a seeded call takes one seed per item");
+  return LDC_OK;
+}
+
+extern "C" int ldc_decode_seeded(ldc_ctx* c, const float* wav, const int32_t* lengths_host, int B, int Tmax, int sampler, int t_start, int n_steps,
+                                 float eta, const uint64_t* seeds, float* wav_out, float* latents_out, float* cond_out, int64_t* codes_out,
+                                 void* stream) {
+  LDCCHK(seeded_args(sampler, seeds));
+  if (sampler == SAMPLER_DDIM && t_start < 1) return fail(LDC_E_INVALID, "t_start %d: must be >= 1 with sampler 1 (DDIM)", t_start);
+  if (lengths_host)   // (t_start 0 is the ragged entries' word for DDPM)
+    return decode_ragged_impl(c, wav, lengths_host, B, Tmax, sampler == SAMPLER_DDIM ? t_start : 0, n_steps, eta, nullptr, seeds, wav_out, latents_out,
+                              cond_out, codes_out, stream);
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (!wav || !wav_out || B <= 0 || Tmax <= 0) return fail(LDC_E_INVALID, "bad arguments");
+  bool draws = true;
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  else if (n_steps < 1 || n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
+  FrontSrc src;
+  src.wav = wav;
+  return decode_body(c, src, B, Tmax, n_steps, sampler, draws, nullptr, 1, wav_out, latents_out, cond_out, codes_out, stream, nullptr, seeds);
+}
+
+extern "C" int ldc_decode_codes_seeded(ldc_ctx* c, const int64_t* codes, const uint8_t* packed, int64_t packed_stride, int bits, int n_q, int B,
+                                       int Fmax, const int32_t* frames_host, int sampler, int t_start, int n_steps, float eta, const uint64_t* seeds,
+                                       float* wav_out, float* latents_out, float* cond_out, void* stream) {
+  LDCCHK(seeded_args(sampler, seeds));
+  if (sampler == SAMPLER_DDIM && t_start < 1) return fail(LDC_E_INVALID, "t_start %d: must be >= 1 with sampler 1 (DDIM)", t_start);
+  if (frames_host)
+    return decode_codes_ragged_impl(c, codes, packed, packed_stride, bits, n_q, B, Fmax, frames_host, sampler == SAMPLER_DDIM ? t_start : 0, n_steps,
+                                    eta, nullptr, seeds, wav_out, latents_out, cond_out, stream);
+  LDCCHK(codes_args(codes, packed, packed_stride, bits, n_q, B, Fmax, wav_out));
+  if (sampler == SAMPLER_DDIM) {   // (the context-free refusals of ldc_decode_codes_ddim)
+    if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "eta must be a finite value in [0, 1]");
+    if (n_steps < 1 || n_steps > t_start) return fail(LDC_E_INVALID, "n_steps must be in [1, t_start = %d] (more would repeat timesteps)", t_start);
+  } else if (n_steps < 1) return fail(LDC_E_INVALID, "n_steps must be >= 1");
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN, true));
+  if (sampler == SAMPLER_DDPM && n_steps > c->unet.timesteps) return fail(LDC_E_INVALID, "n_steps must be in [1,%d]", c->unet.timesteps);
+  FrontSrc src;
+  int T = 0;
+  LDCCHK(codes_src(c, codes, packed, packed_stride, bits, n_q, Fmax, &src, &T));
+  bool draws = true;
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  return decode_body(c, src, B, T, n_steps, sampler, draws, nullptr, 1, wav_out, latents_out, cond_out, nullptr, stream, nullptr, seeds);
 }
 
 // ---- the decodes with DPM-Solver++(2M) sampling from t_start: ldc_decode_ddim / ldc_decode_ragged / ldc_decode_codes_ddim without eta

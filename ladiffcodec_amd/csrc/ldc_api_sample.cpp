@@ -22,6 +22,11 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
                              sm.kind == SAMPLER_DDIM ? sm.ddim : nullptr));
   }
   LDCCHK(run_ops(c, pl, true, s));
+  const uint64_t* keys = nullptr;   // the item-seeded update (never a windows plan, never DPM: the entries refuse)
+  if (sm.item_seeds) {
+    if (!pl->item_keys || pl->win_id || sm.kind == SAMPLER_DPM) return fail(LDC_E_STATE, "internal: an item-seeded step without its key table");
+    keys = pl->item_keys;
+  }
   if (pl->win_id) {   // coupled windows: x is the recordings' packed state, the blend and the update are one launch (the tape and the DPM history are packed like x, the keys are in the recording table)
     if (h.n != 1) return fail(LDC_E_STATE, "internal: a windows plan steps as one part");
     if (sm.kind == SAMPLER_DPM)
@@ -34,10 +39,10 @@ static int half_step(ldc_ctx* c, const Halves& h, int k, float* x, const float* 
                              pl->step_state, s, pl->ragged ? pl->lens : nullptr));
   else if (sm.kind == SAMPLER_DDIM)
     HIPCHK(launch_ddim_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
-                              c->unet.channels, pl->L, c->sched, sm.ddim, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr));
+                              c->unet.channels, pl->L, c->sched, sm.ddim, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr, keys));
   else
     HIPCHK(launch_p_sample_update(c->dt, x + off, pl->eps_cl, noise ? noise + off : nullptr, noise_stride, pl->x_cl, pl->B,
-                                  c->unet.channels, pl->L, c->sched, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr));
+                                  c->unet.channels, pl->L, c->sched, pl->step_state, (uint64_t)off, s, pl->ragged ? pl->lens : nullptr, keys));
   if (!c->merge_advance) HIPCHK(launch_step_advance(pl->step_state, tl, s));   // (LDC_STEP_ADVANCE_LAUNCH: the round-4 structure, for A/B runs)
   return LDC_OK;
 }
@@ -121,6 +126,7 @@ int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const float* nois
   // DDIM, DPM): all stay cached side by side
   StepGraphKey key;
   key.B = B; key.L = L; key.F = F; key.sampler = sm.kind; key.ragged = h.p[0]->ragged ? 1 : 0; key.win_id = wid;
+  key.seeded = sm.item_seeds ? 1 : 0;
   StepGraph* sg = nullptr;
   LDCCHK(step_graph_for(c, key, &sg));
   const bool par = parts_parallel(c, h);
@@ -455,6 +461,56 @@ extern "C" int ldc_dpm_sample(ldc_ctx* c, float* img, const float* cond, int t_s
   StepSampler sm;
   sm.kind = SAMPLER_DPM;
   sm.dpm = c->dpm_table;
+  LDCCHK(denoise_loop(c, h, B, c->state_buf, nullptr, n_steps, s, nullptr, sm));
+  HIPCHK(hipMemcpyAsync(img, c->state_buf, nbytes, hipMemcpyDeviceToDevice, s));
+  return finish_stream(c, stream);
+}
+
+// ---- item seeds ("Item seeds") ----------------------------------------------------------------------------------
+// The key tables of the parts' plans: allocated by the first seeded call on a plan, outside of any capture, and kept until the plan goes
+// (as ensure_history's buffers), so every captured seeded graph of the plan keeps a valid address.  The keys of THIS call go in on s in
+// front of the loop (the parts' streams fork from s behind them): seeds are data, a graph captured under one set serves any other.
+int write_item_keys(ldc_ctx* c, const Halves& h, const uint64_t* seeds, hipStream_t s) {
+  for (int k = 0; k < h.n; ++k) {
+    Plan* pl = h.p[k];
+    if (!pl->item_keys) {
+      void* p = nullptr;
+      const size_t bytes = (size_t)pl->B * sizeof(uint64_t);
+      hipError_t e = hipMalloc(&p, bytes);
+      if (e != hipSuccess) return fail(LDC_E_NOMEM, "hipMalloc(%zu) for the item keys failed: %s", bytes, hipGetErrorString(e));
+      pl->item_keys = (uint64_t*)p;
+    }
+    HIPCHK(launch_item_keys_write(pl->item_keys, seeds + h.b0[k], pl->B, s));
+  }
+  return LDC_OK;
+}
+
+// ldc_denoise (sampler 0: n_steps DDPM steps from t = n_steps - 1, t_start and eta are not read) / ldc_ddim_sample (sampler 1) on a given
+// start image, item b drawing under seeds[b] as if alone; the context's noise epoch is neither read nor advanced
+extern "C" int ldc_sample_seeded(ldc_ctx* c, float* img, const float* cond, int sampler, int t_start, int n_steps, float eta, const uint64_t* seeds,
+                                 int B, int L, int F, void* stream) {
+  LDCCHK(seeded_args(sampler, seeds));
+  LDCCHK(check_ready(c, LDC_MODEL_MAIN));
+  if (!img || !cond) return fail(LDC_E_INVALID, "null tensor");
+  if (sampler == SAMPLER_DDPM && (n_steps < 1 || n_steps > c->unet.timesteps))
+    return fail(LDC_E_INVALID, "n_steps %d: must be in [1,%d]", n_steps, c->unet.timesteps);
+  LDCCHK(check_unet_args(c, B, L, F));
+  bool draws = true;
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_schedule(c, t_start, n_steps, eta, &draws));
+  hipStream_t s = pick_stream(c, stream);
+  if (sampler == SAMPLER_DDIM) LDCCHK(ddim_upload(c, s));
+  Halves h;
+  LDCCHK(get_halves(c, B, L, F, s, &h));
+  LDCCHK(write_item_keys(c, h, seeds, s));
+  LDCCHK(load_cond(c, h, cond, s));
+  const size_t nbytes = (size_t)B * c->unet.channels * L * 4;
+  LDCCHK(ensure_state(c, nbytes));
+  HIPCHK(hipMemcpyAsync(c->state_buf, img, nbytes, hipMemcpyDeviceToDevice, s));
+  LDCCHK(load_x(c, h, c->state_buf, s));
+  StepSampler sm;
+  sm.kind = sampler;
+  sm.ddim = sampler == SAMPLER_DDIM ? c->ddim_table : nullptr;
+  sm.item_seeds = true;
   LDCCHK(denoise_loop(c, h, B, c->state_buf, nullptr, n_steps, s, nullptr, sm));
   HIPCHK(hipMemcpyAsync(img, c->state_buf, nbytes, hipMemcpyDeviceToDevice, s));
   return finish_stream(c, stream);

@@ -199,6 +199,9 @@ struct Plan {   // one UNet step for a fixed (sub-batch B, L, F); `slot` tells t
                                 // its own, made by the first DPM call on the plan (before any capture) and freed with the plan: captured DPM
                                 // graphs keep its address.  On a coupled-windows plan (below) it is the recordings' history instead,
                                 // one [channels][Ltot_r] fp32 block per recording in win_x's layout (ensure_windows_history), with the same lifetime
+  uint64_t* item_keys = nullptr;   // item-seeded calls (ldc_*_seeded): the Philox keys of this part's B items, written on the stream
+                                // in front of every seeded loop.  An allocation of its own, made by the first seeded call on the plan (before any
+                                // capture) and freed with the plan: captured seeded graphs keep its address
   // Coupled-windows plan (ldc_*_windows, ldc_*_windows_group): the ordinary equal-length plan at (B = W_sum windows,
   // L = Lw, F = Lw / up) of R recordings cut with overlap win_O; a single-recording call is R = 1 (and L its effective window: Ltot where
   // the recording is shorter than Lw).  The ORDERED list of the recordings' lengths (win_group.Ltot) and win_O are part of the cache key
@@ -249,6 +252,7 @@ enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_DPM = 2 };
 struct StepSampler {
   int kind = SAMPLER_DDPM;
   const DdimStep* ddim = nullptr;   // SAMPLER_DDIM: c->ddim_table (step_begin takes t from it, ddim_update the coefficients)
+  bool item_seeds = false;          // DDPM / DDIM: the update draws under the plans' item keys at the items' own block indices (Plan::item_keys)
   const DpmStep* dpm = nullptr;     // SAMPLER_DPM: c->dpm_table (likewise; dpm_update / windows_group_dpm_update also read and write the plan's x0_prev)
 };
 
@@ -538,6 +542,7 @@ int ragged_latent_quantum(const ldc_ctx* c);
 int get_halves(ldc_ctx* c, int B, int L, int F, hipStream_t s, Halves* h, bool ragged = false, bool items = false, int pool_id = 0);
 int load_cond(ldc_ctx* c, const Halves& h, const float* cond, hipStream_t s);
 int load_x(ldc_ctx* c, const Halves& h, const float* x, hipStream_t s);
+int seeded_args(int sampler, const uint64_t* seeds);   // the context-free refusals of every item-seeded entry (ldc_*_seeded)
 // ldc_api_sample.cpp: the denoise loop and the schedules, for ldc_decode, the windows front ends and the decode pools
 int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const float* noise, int n_steps, hipStream_t s, bool* left_forked = nullptr,
                  const StepSampler& sm = StepSampler());
@@ -547,6 +552,8 @@ int ddim_upload(ldc_ctx* c, hipStream_t s);
 int dpm_schedule(ldc_ctx* c, int t_start, int n_steps);
 int dpm_upload(ldc_ctx* c, hipStream_t s);
 int ensure_history(ldc_ctx* c, const Halves& h);
+// the parts' key tables exist (allocated outside of any capture) and hold seeds[0..B) of this call, ordered on s in front of the loop
+int write_item_keys(ldc_ctx* c, const Halves& h, const uint64_t* seeds, hipStream_t s);
 
 // runs `body` twice: once against a measuring arena, then (after sizing the scratch) for real
 template <typename F>

@@ -233,7 +233,13 @@ hipError_t launch_random_fill(float* x, int64_t n, int uniform, uint64_t seed, u
 hipError_t launch_axpby(float* x, const float* y, float a, float b, int64_t n, hipStream_t s);
 hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                                   void* x_cl, int B, int C, int L, StepTables tb, const int* st,
-                                  uint64_t elem_base, hipStream_t s, const int* lens = nullptr);   // lens [B] (positions): x and x_cl stay zero behind them
+                                  uint64_t elem_base, hipStream_t s, const int* lens = nullptr,   // lens [B] (positions): x and x_cl stay zero behind them
+                                  const uint64_t* item_keys = nullptr);
+// item_keys [B] (device; launch_p_sample_update and launch_ddim_update): the item-seeded form ("Item seeds") -- item b
+// draws under key item_keys[b] at the block index of the item alone, c_first * len_b + l (len_b = lens[b], L without lens): exactly
+// launch_p_sample_update_items' draw; elem_base and the step state's key are not read.  Written by launch_item_keys_write, stream-ordered
+// (the keys travel as kernel arguments).
+hipError_t launch_item_keys_write(uint64_t* dst, const uint64_t* keys_host, int n, hipStream_t s);
 // Per-item step state (per-item plans: ldc_unet_forward_items, decode pools): one record per item / pool slot in
 // device memory.  Nothing about an item's progress or its sampler is a kernel argument, so one captured step graph replays for any mix
 // of states, DDPM and DDIM items side by side.
@@ -281,7 +287,7 @@ struct DdimStep {
 hipError_t launch_ddim_table_write(DdimStep* dst, const DdimStep* src_host, int n, hipStream_t s);   // dst[0..n) = src_host[0..n), stream-ordered
 hipError_t launch_ddim_update(int dt, float* x, const void* eps_cl, const float* noise, int64_t noise_step_stride,
                               void* x_cl, int B, int C, int L, StepTables tb, const DdimStep* sched, const int* st,
-                              uint64_t elem_base, hipStream_t s, const int* lens = nullptr);
+                              uint64_t elem_base, hipStream_t s, const int* lens = nullptr, const uint64_t* item_keys = nullptr);
 // One iteration of DPM-Solver++(2M) in its data-prediction form: the host fills one entry per iteration j
 // (ldc_api.cpp: ldc_dpm_schedule, double arithmetic rounded once to float) into a device table that the step state indexes.
 struct DpmStep {

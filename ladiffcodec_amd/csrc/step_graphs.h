@@ -12,8 +12,10 @@ struct StepGraphKey {   // what a cache entry is found by
   int ragged = 0;    // the steps of ragged plans
   int pool_id = 0;   // != 0: the step graphs of that decode pool's plans
   int win_id = 0;    // != 0: the steps of that coupled-windows plan (Plan::win_id)
+  int seeded = 0;    // the item-seeded update launches (another kernel with another argument list: never replayed for an unseeded loop, nor the reverse)
   bool operator==(const StepGraphKey& o) const {
-    return B == o.B && L == o.L && F == o.F && sampler == o.sampler && ragged == o.ragged && pool_id == o.pool_id && win_id == o.win_id;
+    return B == o.B && L == o.L && F == o.F && sampler == o.sampler && ragged == o.ragged && pool_id == o.pool_id && win_id == o.win_id &&
+           seeded == o.seeded;
   }
 };
 

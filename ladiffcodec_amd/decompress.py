@@ -15,6 +15,10 @@ a whole-file encode, so that output is not `srcs.sample --chunk_sec` of the wave
 (Engine.decode_codes_windows, with `--dpm_steps` Engine.decode_codes_dpm_windows: one shared latent, no seams); a stream that needs
 more than 32 windows is cut into segments of codes at whole condition frames, decoded one after another and hard-joined.
 
+`--item_seeds` (as in `srcs.sample`): container i of the run's file list draws under seed (`--seed` + i) mod 2^64 as if decoded alone
+(Engine.decode_codes_seeded), in equal-length batches and with `--ragged`; its audio depends neither on `--batch_size`, the packing,
+`--in_flight` nor the number of ranks.  Not with `--chunk_sec` > 0, `--dpm_steps` or multi-channel containers.
+
 `--ragged [--ragged_waste W]` decodes mono containers of DIFFERENT lengths in shared batches (plan_container_batches,
 Engine.decode_codes_ragged): containers are grouped by (nc, bits, mode) and those whose frame count -- from the header -- is a
 multiple of chunk_quantum / 320 are packed within the waste bound; the others (a sender trims to 640 samples, not to the receiver's
@@ -196,8 +200,10 @@ def decompress(inp_args) -> List[str]:
         # a batch shares its number of codebooks: one pass per nc (a run written by one compress call has one)
         for nc in sorted({source.n_q(i) for i in range(len(files))}):
             idx = [i for i in range(len(files)) if source.n_q(i) == nc]
+            # (--item_seeds: a container is seeded by its index in the run's file list, not in its pass)
+            kw = dict(run_index=idx) if getattr(inp_args, "item_seeds", False) else {}
             written += decode_files(engines if len(engines) > 1 else engines[0], [files[i] for i in idx], inp_args, rank, world,
-                                    local_rank, sampler=sampler, source=source.subset(idx))
+                                    local_rank, sampler=sampler, source=source.subset(idx), **kw)
     finally:
         for eng in engines:
             eng.close()

@@ -28,6 +28,7 @@ EXPORTS = [
     "ldc_dpm_sample_windows", "ldc_decode_dpm_windows", "ldc_decode_codes_windows", "ldc_decode_codes_dpm_windows",
     "ldc_window_group_layout", "ldc_unet_forward_windows_group", "ldc_sample_windows_group", "ldc_decode_windows_group",
     "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
+    "ldc_sample_seeded", "ldc_decode_seeded", "ldc_decode_codes_seeded",
     "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
     "ldc_stream_min_first", "ldc_stream_create", "ldc_stream_reset", "ldc_stream_destroy", "ldc_seanet_encode_stream", "ldc_seanet_decode_stream", "ldc_get_cond_stream",
     "ldc_sconv1d", "ldc_sconvtr1d", "ldc_slstm", "ldc_unet_debug_tap", "ldc_unet_step_cost", "ldc_profile_enable",
@@ -139,6 +140,10 @@ def load() -> C.CDLL:
     lib.ldc_unet_forward_windows_group.argtypes = [vp, fp, i32, fp, i32, ip, ip, i32, i32, fp, vp]
     lib.ldc_sample_windows_group.argtypes = [vp, fp, fp, i32, i32, i32, C.c_float, fp, u64p, i32, ip, ip, i32, i32, vp]
     lib.ldc_decode_windows_group.argtypes = [vp, fp, i32, ip, i32, i32, i32, C.c_float, fp, u64p, i32, i32, fp, fp, fp, vp, vp]
+    lib.ldc_sample_seeded.argtypes = [vp, fp, fp, i32, i32, i32, C.c_float, u64p, i32, i32, i32, vp]
+    lib.ldc_decode_seeded.argtypes = [vp, fp, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, C.c_float, u64p, fp, fp, fp, vp, vp]
+    lib.ldc_decode_codes_seeded.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, C.c_float, u64p, fp, fp,
+                                            fp, vp]
     lib.ldc_ac_encode_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
     lib.ldc_ac_decode_ragged.argtypes = [vp, vp, C.c_int64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldc_unet_forward_ragged.argtypes = [vp, fp, i32, fp, C.POINTER(C.c_int32), i32, i32, i32, fp, vp]

@@ -1089,6 +1089,88 @@ class Engine:
             return {"wav": out, "latents": lat, "cond": cond}
         return out
 
+    # ---- item seeds: every item of a batch draws its noise as if alone ----------
+    SEEDED_SAMPLERS = {"ddpm": 0, "ddim": 1}
+
+    @staticmethod
+    def _seeds(seeds, B: int):
+        if seeds is None:
+            return None   # (the library refuses, with the value named)
+        seeds = [int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds]
+        if len(seeds) != B:
+            raise ValueError(f"{len(seeds)} seeds for a batch of {B}")
+        return (C.c_uint64 * B)(*seeds)
+
+    def _seeded_sampler(self, sampler):
+        return self.SEEDED_SAMPLERS.get(sampler, sampler) if isinstance(sampler, str) else int(sampler)
+
+    def sample_seeded(self, img, cond, seeds, n_steps: int, sampler="ddpm", t_start: int = 0, eta: float = 0.0):
+        """`denoise` (sampler "ddpm") / `ddim_sample` (sampler "ddim", from t_start) on the start image `img` with one seed per item:
+        item b draws what `reseed(seeds[b])` followed by the same call at B = 1 on the item alone draws, wherever it sits in the
+        batch.  The engine's noise epoch is neither read nor advanced."""
+        img = self._f32(img).clone()
+        cond = self._f32(cond)
+        B, _, Lx = img.shape
+        sd = self._seeds(seeds, B)
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_sample_seeded(self._ctx, img.data_ptr(), cond.data_ptr(), self._seeded_sampler(sampler), int(t_start),
+                                               int(n_steps), float(eta), sd, B, Lx, cond.shape[2], s))
+        finally:
+            self._exit()
+        return img
+
+    def decode_seeded(self, wav, seeds, n_steps: int, lengths=None, sampler="ddpm", t_start: int = 0, eta: float = 0.0,
+                      want_stages: bool = False):
+        """`decode` / `decode_ddim` (lengths None) or `decode_ragged` (lengths[b] samples of item b) with one seed per item and
+        per-item normalisation at both ends: item b comes out as `reseed(seeds[b])` followed by the decode of the item alone gives
+        it, whatever the batch size, the packing and the item's position."""
+        wav = self._f32(wav)
+        B, _, T = wav.shape
+        F, Lz = T // self.cond_codec.hop_length, T // self.main_codec.hop_length
+        lens = self._lengths(list(lengths), B) if lengths is not None else None
+        sd = self._seeds(seeds, B)
+        out = self._empty(B, 1, T)
+        lat = self._empty(B, self.main_codec.rep_dims, Lz) if want_stages else None
+        cond = self._empty(B, self.main_codec.rep_dims, F) if want_stages else None
+        n_q = self.cond_codec.n_q_for_bandwidth(None)
+        codes = self._empty(n_q, B, F, dtype=self.torch.int64) if want_stages else None
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        try:
+            L.check(self.lib.ldc_decode_seeded(self._ctx, wav.data_ptr(), lens, B, T, self._seeded_sampler(sampler), int(t_start), int(n_steps),
+                                               float(eta), sd, out.data_ptr(), p(lat), p(cond), p(codes), s))
+        finally:
+            self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond, "codes": codes}
+        return out
+
+    def decode_codes_seeded(self, seeds, codes=None, packed=None, lengths=None, bits: int = 10, n_steps: Optional[int] = None,
+                            sampler="ddpm", t_start: int = 0, eta: float = 0.0, want_stages: bool = False, n_q: Optional[int] = None,
+                            F: Optional[int] = None):
+        """`decode_codes` / `decode_codes_ddim` (lengths None) or `decode_codes_ragged` (lengths[b] condition frames of item b) with one
+        seed per item and per-item normalisation: the contract of `decode_seeded`; the code arguments as decode_codes_ragged."""
+        if n_steps is None:
+            raise ValueError("n_steps is required")
+        frames = [int(v) for v in lengths] if lengths is not None else None
+        if packed is not None and F is None and frames is not None:
+            F = max(frames)
+        cp, pp, stride, n_q, B, F, keep = self._codes_args(codes, packed, bits, n_q, F)
+        fr = self._lengths(frames, B) if frames is not None else None
+        sd = self._seeds(seeds, B)
+        out, lat, cond = self._codes_outputs(B, F, want_stages)
+        s = self._enter()
+        p = lambda t: t.data_ptr() if t is not None else None
+        try:
+            L.check(self.lib.ldc_decode_codes_seeded(self._ctx, cp, pp, stride, int(bits), n_q, B, F, fr, self._seeded_sampler(sampler),
+                                                     int(t_start), int(n_steps), float(eta), sd, out.data_ptr(), p(lat), p(cond), s))
+        finally:
+            self._exit()
+        if want_stages:
+            return {"wav": out, "latents": lat, "cond": cond}
+        return out
+
     # ---- accounting ------------------------------------------------------------------------------
     def unet_step_cost(self, B: int, Lz: int):
         fl, by = C.c_double(), C.c_double()

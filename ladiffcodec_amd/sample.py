@@ -17,6 +17,10 @@ Same flags, defaults and output naming as the reference.  What differs, by desig
   * `--window_group` (with `--chunk_overlap_sec`; `sample`, `sample_ddim`, `sample_dpm`) decodes SEVERAL such recordings per call
     (Engine.decode_windows_group: the windows of a group, at most 32 in all, share one batch; file order, first fit).  Recording i of
     the run's file list draws under seed (`--seed` + i) mod 2^64, whatever group or rank it lands in;
+  * `--item_seeds` (`sample`, `sample_ddim`, `decompress`; equal-length batches and `--ragged`) seeds every mono file on its own
+    (Engine.decode_seeded / decode_codes_seeded): file i of the run's file list draws under seed (`--seed` + i) mod 2^64 exactly as
+    if it were decoded alone, so its audio depends neither on `--batch_size`, the `--ragged` packing, `--in_flight` nor the number
+    of ranks.  Refused with `--chunk_sec` > 0 and on multi-channel files;
   * under `torch.distributed.run` the FILE list is sharded over the ranks (one process per GPU; all channels of a
     file stay on one rank, every output file has exactly one writer).
 Flags that are inert in the reference stay accepted and inert (`--sampling_timesteps`,
@@ -100,6 +104,10 @@ _EXTRA: List[Tuple[str, dict]] = [
                             help="--chunk_overlap_sec: decode SEVERAL long mono recordings per call (Engine.decode_windows_group): their "
                                  "windows, at most 32 in all, share one batch; recording i of the run is seeded (--seed + i) mod 2^64, so its "
                                  "audio depends neither on the grouping nor on the number of ranks")),
+    ("--item_seeds", dict(dest="item_seeds", action="store_true", default=argparse.SUPPRESS,
+                          help="seed every mono file on its own (Engine.decode_seeded): file i of the run is seeded (--seed + i) mod 2^64 and "
+                               "draws as if decoded alone, so its audio depends neither on --batch_size, --ragged packing, --in_flight nor "
+                               "the number of ranks; not with --chunk_sec > 0, not on multi-channel files")),
 ]
 
 
@@ -135,6 +143,22 @@ def window_group_option(a) -> bool:
     if not hasattr(a, "chunk_overlap_sec"):
         raise SystemExit("--window_group needs --chunk_overlap_sec (it groups the recordings that are decoded on coupled windows)")
     return True
+
+
+def item_seeds_option(a) -> bool:
+    """--item_seeds of a parsed namespace (off without the flag); refused with --chunk_sec > 0: independent chunks have no single item
+    length, and coupled windows have their own seeds (--window_group)."""
+    if not getattr(a, "item_seeds", False):
+        return False
+    if float(getattr(a, "chunk_sec", 0.0) or 0.0) > 0:
+        raise SystemExit("--item_seeds is not available with --chunk_sec > 0 (independent chunks have no single item length; coupled "
+                         "windows are seeded per recording by --window_group)")
+    return True
+
+
+def item_seeds_for(seed: int, run_index: List[int]) -> List[int]:
+    """--item_seeds: the seeds of a batch whose items are files run_index[k] of the run's file list: (seed + index) mod 2^64."""
+    return [(int(seed) + int(i)) % (1 << 64) for i in run_index]
 
 
 def _unsupported(a) -> None:
@@ -319,7 +343,11 @@ class DdpmSampler:
     def __init__(self, n_steps: int):
         self.n_steps = self.draws = int(n_steps)
 
-    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False, seeds=None):
+        if seeds is not None:   # --item_seeds: every item draws as if alone (no tape, per-item normalisation)
+            rag = isinstance(batch, RaggedBatch)
+            return eng.decode_seeded(batch.wav if rag else batch, seeds, self.n_steps, lengths=batch.lengths if rag else None,
+                                     want_stages=want_stages)
         if isinstance(batch, RaggedBatch):
             return eng.decode_ragged(batch.wav, batch.lengths, self.n_steps, noise=noise, want_stages=want_stages)
         if want_stages:
@@ -334,7 +362,11 @@ class DdimSampler:
         self.t_start, self.n_steps, self.eta = int(t_start), int(n_steps), float(eta)
         self.draws = self.n_steps
 
-    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False, seeds=None):
+        if seeds is not None:   # --item_seeds, as DdpmSampler's
+            rag = isinstance(batch, RaggedBatch)
+            return eng.decode_seeded(batch.wav if rag else batch, seeds, self.n_steps, lengths=batch.lengths if rag else None,
+                                     sampler="ddim", t_start=self.t_start, eta=self.eta, want_stages=want_stages)
         if isinstance(batch, RaggedBatch):
             return eng.decode_ragged(batch.wav, batch.lengths, self.n_steps, t_start=self.t_start, eta=self.eta, noise=noise,
                                      want_stages=want_stages)
@@ -350,7 +382,9 @@ class DpmSampler:
     def __init__(self, t_start: int, n_steps: int):
         self.t_start, self.n_steps = int(t_start), int(n_steps)
 
-    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False, seeds=None):
+        if seeds is not None:
+            raise SystemExit("--item_seeds: DPM-Solver++ draws nothing, there is nothing to seed; drop the flag")
         if isinstance(batch, RaggedBatch):
             return eng.decode_ragged_dpm(batch.wav, batch.lengths, self.t_start, self.n_steps, want_stages=want_stages)
         return eng.decode_dpm(batch, self.t_start, self.n_steps, per_item=per_item, want_stages=want_stages)
@@ -389,8 +423,17 @@ class CodesSampler:
         self.inner = inner
         self.n_steps = self.draws = inner.draws
 
-    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False):
+    def __call__(self, eng, batch, noise, per_item: bool, want_stages: bool = False, seeds=None):
         dpm = isinstance(self.inner, DpmSampler)
+        if seeds is not None:   # --item_seeds: Engine.decode_codes_seeded, DDPM and DDIM only
+            if dpm:
+                raise SystemExit("--item_seeds: DPM-Solver++ draws nothing, there is nothing to seed; drop the flag")
+            ddim = isinstance(self.inner, DdimSampler)
+            rag = isinstance(batch, RaggedCodesBatch)
+            return eng.decode_codes_seeded(seeds, codes=None if rag else batch.codes, packed=batch.packed, lengths=batch.frames if rag else None,
+                                           bits=batch.bits, n_q=batch.n_q, F=None if rag else batch.F, n_steps=self.inner.n_steps,
+                                           sampler="ddim" if ddim else "ddpm", t_start=self.inner.t_start if ddim else 0,
+                                           eta=self.inner.eta if ddim else 0.0, want_stages=want_stages)
         if isinstance(batch, RaggedCodesBatch):
             if dpm:
                 raise ValueError("DPM-Solver++ sampling has no ragged decode from codes (Engine.decode_codes_ragged takes DDPM and DDIM "
@@ -407,6 +450,10 @@ class CodesSampler:
         if isinstance(self.inner, DdimSampler):
             return eng.decode_codes_ddim(t_start=self.inner.t_start, n_steps=self.inner.n_steps, eta=self.inner.eta, **kw)
         return eng.decode_codes(n_steps=self.inner.n_steps, **kw)
+
+
+def _sampler_of(n_steps: int, sampler):
+    return sampler if sampler is not None else DdpmSampler(n_steps)
 
 
 def _sampler(inp_args, sampler):
@@ -478,13 +525,15 @@ def apply_device_fallback(eng, err) -> bool:
     return True
 
 
-def decode_with_retry(eng, batch, n_steps: int, noise, per_item: bool, sampler=None):
+def decode_with_retry(eng, batch, n_steps: int, noise, per_item: bool, sampler=None, seeds=None):
     """One engine call; a batch hit by a device-side failure (or by the report of an earlier call's) is decoded again after
     the matching fallback (apply_device_fallback), twice at most: the LSTM and the GroupNorm exchange can each give up once.
-    `sampler` (optional) replaces the DDPM decode of n_steps."""
+    `sampler` (optional) replaces the DDPM decode of n_steps; `seeds` (--item_seeds): one seed per item, through the sampler."""
     from . import lib as L
     for attempt in range(3):
         try:
+            if seeds is not None:
+                return _sampler_of(n_steps, sampler)(eng, batch, None, per_item, seeds=seeds)
             if sampler is not None:
                 return sampler(eng, batch, noise, per_item)
             return eng.decode(batch, n_steps, noise=noise, per_item=per_item)
@@ -789,9 +838,13 @@ def decode_window_files(eng, files: List[str], wavs, inp_args, overlap_sec: floa
     return written
 
 
-def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_rank: int, sampler=None, source=None) -> List[str]:
+def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_rank: int, sampler=None, source=None,
+                 run_index: Optional[List[int]] = None) -> List[str]:
     """`eng`: one engine, or a list of engines (one batch in flight per engine, each on its own stream); `sampler`: as synthesis;
-    `source`: the batch source over `files` (default LazyWavs; see there)."""
+    `source`: the batch source over `files` (default LazyWavs; see there).
+    --item_seeds: file i draws under (--seed + run_index[i]) mod 2^64 -- run_index[i]: its index in the run's file list (default: i) --
+    as if decoded alone (item_seeds_for; Engine.decode_seeded / decode_codes_seeded through the sampler), whatever batch, engine or rank
+    it lands on; a noise provider is not asked."""
     import torch
     from scipy.io import wavfile
     engines = list(eng) if isinstance(eng, (list, tuple)) else [eng]
@@ -801,6 +854,13 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
     wavs = source if source is not None else LazyWavs(files, eng)   # headers only: (channels, samples at 16 kHz); data is loaded per shard
     keep = [i for i, sh in enumerate(wavs.shapes) if sh[1] // 640 * 640 > 0]                  # sample.py:87-88
     files, wavs = [files[i] for i in keep], wavs.subset(keep)
+    item_seeds = item_seeds_option(inp_args)   # (refused with --chunk_sec > 0 before anything is decoded)
+    if item_seeds:
+        multi = [f for f, sh in zip(files, wavs.shapes) if sh[0] > 1]
+        if multi:
+            raise SystemExit(f"--item_seeds: {multi[0]} has more than one channel (a multi-channel file keeps the joint normalisation "
+                             f"over its channels, so its channels are not items that decode as if alone)")
+        run_of = [run_index[i] if run_index is not None else i for i in keep]
     chunk_sec = float(getattr(inp_args, "chunk_sec", 0.0) or 0.0)
     overlap_sec = windows_options(inp_args)
     window_group_option(inp_args)   # (--window_group without --chunk_overlap_sec is refused before anything is decoded)
@@ -840,12 +900,13 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
             # the engine's NEXT call; decode the batch again on the streamed LSTM instead of losing the run
             # (that report -- LDC_E_HIP with the failure's tag -- may well arrive in the redo itself: decode_with_retry applies the
             # matching fallback and decodes again; without a report the cooperative LSTM is the one that poisons silently)
-            eng_k, batch_k, per_item_k, noise_k = redo
-            out = decode_with_retry(eng_k, batch_k.to(dev), steps, noise_k, per_item_k, sampler).cpu()
+            eng_k, batch_k, per_item_k, noise_k = redo[:4]
+            kw_k = dict(seeds=redo[4]) if len(redo) > 4 else {}   # (--item_seeds: the same seeds, so the same audio)
+            out = decode_with_retry(eng_k, batch_k.to(dev), steps, noise_k, per_item_k, sampler, **kw_k).cpu()
             if not bool(torch.isfinite(out).all()):
                 eng_k.set_option("lstm_stream", 1)
                 eng_k.set_option("fuse_gn_epi", 0)
-                out = decode_with_retry(eng_k, batch_k.to(dev), steps, noise_k, per_item_k, sampler).cpu()
+                out = decode_with_retry(eng_k, batch_k.to(dev), steps, noise_k, per_item_k, sampler, **kw_k).cpu()
             if not bool(torch.isfinite(out).all()):
                 raise RuntimeError(f"non-finite audio decoded for {[files[i] for i in idxs]}")
         out = out.numpy()
@@ -875,13 +936,15 @@ def decode_files(eng, files: List[str], inp_args, rank: int, world: int, local_r
             retire(pending.pop(0))             # the batch this engine decoded last: its output is read before the slot is reused
         # test seam: a callable (file indices, steps, latent length) -> noise [steps, B, 128, L] replaces the device-drawn noise
         provider = getattr(inp_args, "noise_provider", None)
-        noise = provider(idxs, steps, n // hop).to(dev) if provider is not None and steps > 0 else None
+        noise = provider(idxs, steps, n // hop).to(dev) if provider is not None and steps > 0 and not item_seeds else None
+        kw = dict(seeds=item_seeds_for(inp_args.seed, [run_of[i] for i in idxs])) if item_seeds else {}
         if streams[slot] is not None:
             with torch.cuda.stream(streams[slot]):
-                out = decode_with_retry(engines[slot], batch.to(dev, non_blocking=True), steps, noise, not joint, sampler)
+                out = decode_with_retry(engines[slot], batch.to(dev, non_blocking=True), steps, noise, not joint, sampler, **kw)
         else:
-            out = decode_with_retry(engines[slot], batch.to(dev), steps, noise, not joint, sampler)
-        pending.append((out, idxs, joint, streams[slot], (engines[slot], batch, not joint, noise), lens))
+            out = decode_with_retry(engines[slot], batch.to(dev), steps, noise, not joint, sampler, **kw)
+        redo = (engines[slot], batch, not joint, noise) + ((kw["seeds"],) if item_seeds else ())
+        pending.append((out, idxs, joint, streams[slot], redo, lens))
     while pending:
         retire(pending.pop(0))
     return written_long + written

@@ -3,8 +3,8 @@
 Every flag of `srcs.sample` plus `--ddim_steps` (default 10) and `--ddim_eta` (default 0.0).  The decode starts at
 `--midway_t` from the upsampled, normalised condition, as the DDPM decode does, and runs `--ddim_steps` iterations of
 the reference's ddim_sample (ddpm_loss.py:268-303) over the timesteps reversed(linspace(-1, midway_t - 1, steps + 1)).
-Output naming, batching, `--in_flight`, `--chunk_sec` and rank sharding are those of `srcs.sample`; `--sampling_timesteps`
-stays inert, as it is there.
+Output naming, batching, `--in_flight`, `--chunk_sec`, `--item_seeds` and rank sharding are those of `srcs.sample`;
+`--sampling_timesteps` stays inert, as it is there.
 """
 from __future__ import annotations
 
