@@ -725,17 +725,24 @@ static hipError_t launch_fast_cfg(const ConvKArgs& a_in, const FastGeom& gm_in, 
   return hipGetLastError();
 }
 
-// A deeper ring (S = 4, three units in flight, one workgroup per CU) was measured and is slower at every grid
-// size: the loop is bound by LDS-DMA ISSUE (~9 copies per wave per unit next to 24 MFMAs), not by copy latency.
+// Ring depth of THIS kernel stays 2.  A deeper ring was tried on it three times in rounds 2 - 5 (S = 4, three units in flight, one
+// workgroup per CU: slower at every grid size) and lost each time, with three things against it that are this kernel's, not the idea's:
+// a copy cost ~40 instructions here (save M0 / set / copy / restore + address rebuild), so the loop was bound by copy ISSUE; the
+// deeper ring kept s_waitcnt vmcnt(0) + __syncthreads() in front of every unit, which drains the extra unit again; and it was applied
+// to every grid, so the dense launches lost a co-resident workgroup.  conv_lean_kernel (one instruction per copy) has a three-stage
+// ring with a counted copy wait and a bare barrier for the sparse grids on 64-row tiles (conv_lean.inc, round 9): 20 - 25 % off those
+// launches, 3.3 % off a decode -- and still a loss on the 128-row tiles, for the third reason (profiles/r09_ring3.md).
 template <typename T, int TG, int KC, int NA, bool RF = false>
 static hipError_t launch_fast_bn(int bn, const ConvKArgs& a, const FastGeom& gm, int M, hipStream_t s) {
   // Weights straight into VGPRs (each wave loading its own B fragments with global_load_dwordx4, only the activation
   // window staged by LDS-DMA) was built and measured: parity-clean but 10-50 % slower on every k=1/3/4 layer (k3
   // 256->256 @1200: 14.5 -> 16.7 us, k3 1024->1024 @75: 19.2 -> 28.7 us, end to end 173.6 -> 194.8 ms): a fragment
   // load touches 32 rows x 16 B of 64-byte rows and the two waves of a tile column fetch the same fragments.
-  // Deeper rings were measured twice for the 64-wide tiles (before and after the MFMA chain was made branch-free):
+  // Deeper rings of conv_fast_kernel, measured twice for the 64-wide tiles (before and after the MFMA chain was made branch-free):
   // S = 3 is 5-30 % slower, S = 4 ~85 % slower (k3 1024->1024 at L = 75: 19.8 / 22.0 / 37.3 us; end to end 167.8 ->
-  // 177.5 ms with S = 3 on the 128 x 64 tiles): the extra stage costs a co-resident workgroup per CU.
+  // 177.5 ms with S = 3 on the 128 x 64 tiles): the extra stage costs a co-resident workgroup per CU -- see above for what else
+  // those tries had against them, and profiles/r09_ring3.md for the lean kernel's three-stage ring, which the launches of these
+  // tiles now take where it costs no workgroup (ConvTune::ring3_tiles, ring3_wgs).
   if (bn == 3) return hipErrorInvalidValue;
   if (bn == 0) return launch_fast_cfg<T, 2, 2, 1, 1, TG, KC, 2, NA, RF>(a, gm, M, s);   // 64 x 64 tile for small grids
   if (bn == 1) return launch_fast_cfg<T, 2, 2, 2, 1, TG, KC, 2, NA, RF>(a, gm, M, s);   // 128 x 64 tile for medium grids

@@ -523,9 +523,15 @@ __device__ __forceinline__ uint4 lean_lds16(unsigned addr) {   // ds_read_b128 f
   return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
-template <typename T, int TM, int KIND, bool RF, int EPI, bool SK>
-__global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, const LeanGeom g) {
+// S = ring depth.  2: one unit in flight under the unit being multiplied, every trip drains the copy counter (vmcnt(0)) in front of its
+// barrier -- right where three workgroups share a CU and cover each other's waits.  3 (round 9, the launches that put one or two
+// workgroups on a CU and lose no co-resident one to the third stage: launch_lean, ConvTune::ring3_tiles / ring3_wgs): two units in flight, the wait in front of the barrier leaves the younger
+// one's copies outstanding (a counted vmcnt), the barrier is a bare s_barrier, and the copies of unit u + 2 go out in runs between the
+// MFMA groups of unit u.  Same MFMA order per accumulator, same epilogues: bit-identical to S = 2.
+template <typename T, int TM, int KIND, bool RF, int EPI, bool SK, int S = 2>
+__global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const ConvKArgs a, const LeanGeom g) {
   using SH = LeanShape<TM, KIND, RF>;
+  static_assert(S == 2 || (S == 3 && !SH::K4 && !SH::K7 && SH::NAW1 == 0), "three stages: the k = 3 and 1x1 kinds (one window run per plane)");
   constexpr int TN = 1, WM = 2, WN = 2, NW = 4, TG = SH::TG, KC = SH::KC, NS = SH::NS, NSB = SH::NSB, NAW = SH::NAW;
   constexpr int BM = SH::BM, BN = SH::BN, STAGE = SH::STAGE_BYTES, PLANE = SH::PLANE_BYTES;
   constexpr int BKE = kRowBytes / (int)sizeof(T);
@@ -626,6 +632,9 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
     }
   };
   issue(0);
+  if constexpr (S == 3) {   // two units in flight from the start
+    if (tl.u_begin + 1 < tl.u_end && !(g.debug & 16)) issue(1);
+  }
   if (g.stamps) t_dma = __builtin_amdgcn_s_memtime();
   // per-column constants of the epilogue, requested now (used behind the K loop: a bias fetched there cost the epilogue 2 k cycles of load latency)
   // (not with the folded second conv: its 32 extra accumulators leave no room -- five more live registers across the K loop tipped hipcc
@@ -723,8 +732,8 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
   }
 
   // ---- everything below runs under the first copies' latency ----
-  // zero rows (one behind every plane of both stages): 2 x KC x 16 dwords
-  if (tid < 2 * KC * 16) {
+  // zero rows (one behind every plane of every stage): S x KC x 16 dwords
+  if (tid < S * KC * 16) {
     const int st = tid / (KC * 16), rem = tid - st * (KC * 16);
     reinterpret_cast<unsigned*>(smem + st * STAGE + (rem >> 4) * PLANE + SH::ZERO_OFF)[rem & 15] = 0u;
   }
@@ -812,6 +821,104 @@ __global__ __launch_bounds__(256, 3) void conv_lean_kernel(const ConvKArgs a, co
   // (`if (u + 1 >= u_end) break;`) hipcc gives the accumulators different registers on the two paths and copies all of them -- 32 to 64
   // v_mov plus s_nop per unit -- whenever registers get tight (the folded second conv's variant: 168 VGPRs and spills).
   int u = tl.u_begin;
+  if constexpr (S == 3) {
+    // ---- three stages (unit u in stage (u - u_begin) % 3): units u and u + 1 are in flight at the top of every step ----
+    constexpr int NG = NS + (RF ? 1 : 0);   // MFMA groups of a unit (a tap or a chunk each; the folded second conv's last)
+    constexpr int NP = KC + 1;              // copy runs of a unit: one window run per plane, then the slabs
+    auto frag = [&](const int st, const int q, uint4 (&af)[2][TM], uint4 (&bf)[2]) {   // fragments of group q (q = NS: centre tap x fourth slab)
+      const int kc = q < NS ? q / TG : 0, t = q < NS ? q % TG : 1;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) af[ks][i] = lean_lds16(a_ad[i][t][ks] + (unsigned)(st * STAGE + kc * PLANE));
+        bf[ks] = lean_lds16(b_ad[ks] + (unsigned)(st * STAGE + q * 1024));
+      }
+    };
+    auto piece = [&](const int st, const int p) {   // run p of the next unit to copy into stage st (issue(), in pieces)
+      if (p < KC) {
+        lean_dma_run<SH::NAW0>(xb + p * kRowBytes, m0_win + (unsigned)(st * STAGE + p * PLANE), wcnt, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
+      } else {
+        lean_dma_all<NSB>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3]);
+        pc += KC;
+        xb += KC * kRowBytes;
+        wb += (size_t)KC * chunk_w;
+        if (pc == csw) {
+          xb = a.x2 - kBias;
+          window_offsets(ldb2);
+        }
+      }
+    };
+    // the MFMA chain of the unit in stage st, group by group; the fragments of group q + 1 are requested in front of the MFMAs of group q
+    // (the copies are a compiler-level memory barrier: what is to overlap them has to stand in front of them), and behind the MFMAs of
+    // group q goes run q of the unit that is copied into stage sti (pf; what is left of the runs behind the last group)
+    auto step = [&](const int st, const int sti, const bool pf) {
+      uint4 af[2][2][TM], bf[2][2];
+      frag(st, 0, af[0], bf[0]);
+#pragma unroll
+      for (int q = 0; q < NG; ++q) {
+        if (q + 1 < NG) frag(st, q + 1, af[(q + 1) & 1], bf[(q + 1) & 1]);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            if constexpr (RF) {
+              if (q == NS) { mfma_step<T>(acc2[i][0], af[q & 1][ks][i], bf[q & 1][ks]); continue; }
+            }
+            mfma_step<T>(acc[i][0], af[q & 1][ks][i], bf[q & 1][ks]);
+          }
+        if (pf) {
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int p = 0; p < NP; ++p)
+            if (p == q || (q == NG - 1 && p > q)) piece(sti, p);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    };
+    // "unit u has landed" with unit u + 1 left in flight: at most the copies this wave issued for ONE unit outstanding (KC wcnt + NSB: an
+    // immediate, chosen by a scalar switch; loads return in order, so anything else outstanding only makes the wait stricter)
+    auto wait_keep_one = [&]() {
+      if (NAW >= 3 && wcnt == 3u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * KC + NSB) : "memory");
+      else if (NAW >= 2 && wcnt == 2u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * KC + NSB) : "memory");
+      else if (wcnt == 1u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KC + NSB) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSB) : "memory");
+    };
+    // the barrier that hands a stage over: my fragment reads of the stage about to be overwritten are complete (lgkmcnt), nothing about
+    // the copy counter (a __syncthreads() fence would drain it again)
+    auto handover = [&]() {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");   // (nothing of the next phase moves in front of the barrier)
+    };
+    // Three units per trip and ONE loop exit (see below); every wait inside the loop has a younger unit to leave in flight
+    while (u + 3 < u_end) {
+      wait_keep_one(); handover();
+      step(0, 2, copies);
+      wait_keep_one(); handover();
+      step(1, 0, copies);
+      wait_keep_one(); handover();
+      step(2, 1, copies && u + 4 < u_end);
+      u += 3;
+    }
+    // the last one to three units (workgroup-uniform: every wave meets the same barriers); the very last wait drains the counter
+    const int left = u_end - u;
+    if (left >= 1) {
+      if (left >= 2) wait_keep_one(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      handover();
+      step(0, 2, copies && left >= 3);
+    }
+    if (left >= 2) {
+      if (left >= 3) wait_keep_one(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      handover();
+      step(1, 0, false);
+    }
+    if (left >= 3) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      handover();
+      step(2, 1, false);
+    }
+    u = u_end;
+  }
   while (u + 1 < u_end) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // my copies of unit u have landed
     __syncthreads();                                   // everybody's have; everybody is done with unit u - 1: its stage is free
@@ -1120,9 +1227,9 @@ static const LeanTile* lean_tile_table(const ConvKArgs& a, const FastGeom& gm, i
   return (LeanTile*)d;
 }
 
-template <typename T, int TM, int KIND, bool RF, int EPI, bool SK>
+template <typename T, int TM, int KIND, bool RF, int EPI, bool SK, int S = 2>
 static hipError_t launch_lean_kernel(const ConvKArgs& a, const LeanGeom& g, size_t lds, hipStream_t s) {
-  auto kern = conv_lean_kernel<T, TM, KIND, RF, EPI, SK>;
+  auto kern = conv_lean_kernel<T, TM, KIND, RF, EPI, SK, S>;
   static bool lds_opt_in = false;
   if (!lds_opt_in) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1131,7 +1238,38 @@ static hipError_t launch_lean_kernel(const ConvKArgs& a, const LeanGeom& g, size
   }
   hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), lds, s, a, g);
   __atomic_fetch_add(&g_lean_launches[KIND], 1ll, __ATOMIC_RELAXED);
+  if (S == 3) __atomic_fetch_add(&g_lean_launches[5], 1ll, __ATOMIC_RELAXED);   // (slot 5: launches on the three-stage ring, of any kind)
   return hipGetLastError();
+}
+
+// Workgroups of the three-stage fused GroupNorm kernels of this tile that fit one CU (occupancy query with their dynamic LDS; the worst
+// of the epilogues), asked once.  0 when the query fails: no fused GroupNorm launch takes the three-stage ring then.
+template <typename T, int TM, bool RF>
+static int lean_ring3_wgs_per_cu() {
+  static int cached = -1;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  if (cached >= 0) return cached;
+  using SH = LeanShape<TM, LEAN_K3, RF>;
+  int worst = 1 << 30;
+  auto ask = [&](const void* fn, bool res32) {
+    const size_t lds = std::max((size_t)3 * SH::STAGE_BYTES, (size_t)4 * TM * 32 * (32 * (res32 ? 4 : sizeof(T)) + 16));
+    int n = 0;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds) != hipSuccess) {
+      (void)hipGetLastError();
+      n = 0;
+    }
+    worst = std::min(worst, n);
+  };
+  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, RF, LEAN_EPI_GN, false, 3>), false);
+  if constexpr (!RF) {
+    ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN, true, 3>), false);
+    ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, false, 3>), true);
+    ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, true, 3>), true);
+  }
+  cached = worst;
+  return cached;
 }
 
 // The lean kernel for the launch launch_fast_cfg<T, 2, 2, TM, 1, TG, KC, 2, NA, RF> has decided (a, gm: its final arguments).
@@ -1197,13 +1335,31 @@ static hipError_t launch_lean(const ConvKArgs& a, const FastGeom& gm, int M, hip
     LeanGeom g;
     g.tiles = tiles; g.stamps = gm.stamps; g.debug = gm.debug; g.grid = gm.grid; g.ln_off = 0;
     const size_t epi_bytes = (size_t)4 * TM * 32 * (32 * ((epi == LEAN_EPI_RES || epi == LEAN_EPI_GN_RES) ? 4 : sizeof(T)) + 16);
-    size_t lds = std::max((size_t)2 * SH0::STAGE_BYTES, epi_bytes);
+    // round 9: the three-stage ring for the launches that put one or two workgroups on a CU (ConvTune::ring3_tiles; 0 = never), where
+    // ConvTune::ring3_wgs workgroups of three stages still fit a CU's LDS: the third stage must not cost a co-resident workgroup.  With
+    // two batch parts in flight the 128-row tiles (64.5 - 77 KB of ring: two per CU instead of three) lose more there than the loop
+    // gains -- +1.1 % per decode -- while the 64-row tiles (52.5 KB: still three) gain 2.3 % (profiles/r09_ring3.md).  A fused GroupNorm
+    // launch spins on its peers: it takes the ring only if unet_plan.cpp's residency rule (few_tiles) also holds with the slots of
+    // THIS kernel -- the launch as a whole, or an item's tiles plus two dispatch groups, within the share of the chip a batch part
+    // can count on.
+    const size_t lds3 = std::max((size_t)3 * SH0::STAGE_BYTES, epi_bytes) + (ln ? (size_t)SH0::BM * 8 + 16 : 0);
+    bool ring3 = tn && tn->ring3_tiles > 0 && gm.grid <= tn->ring3_tiles && (size_t)std::max(1, tn->ring3_wgs) * lds3 <= (size_t)160 * 1024 && !(gm.debug & 1);
+    if (ring3 && gn) {
+      const long slots = (long)lean_ring3_wgs_per_cu<T, TM, RF>() * tn->ring3_cu_share;
+      const long item_tiles = (long)((a.L_rows + SH0::BM - 1) / SH0::BM + 1) * gm.ntn;
+      ring3 = gm.grid <= slots || item_tiles + 16 * gm.ntn <= slots;
+    }
+    size_t lds = std::max((size_t)(ring3 ? 3 : 2) * SH0::STAGE_BYTES, epi_bytes);
     if (ln) {
       g.ln_off = (int)((lds + 15) / 16 * 16);
       lds = (size_t)g.ln_off + (size_t)SH0::BM * 8;
     }
     *launched = true;
-#define LDC_LEAN_GO(KIND_, EPI_, SK_) return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_>(a, g, lds, s)
+#define LDC_LEAN_GO(KIND_, EPI_, SK_)                                                         \
+  do {                                                                                        \
+    if (ring3) return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, 3>(a, g, lds, s);       \
+    return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, 2>(a, g, lds, s);                  \
+  } while (0)
     if constexpr (K3) {
       if constexpr (RF) {
         LDC_LEAN_GO(LEAN_K3, LEAN_EPI_GN, false);

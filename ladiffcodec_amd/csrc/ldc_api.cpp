@@ -873,6 +873,8 @@ static bool find_option(ldc_ctx* c, const std::string& n, OptRef* r) {
   // conv launchers (ConvTune)
   LDC_OPT("conv_lean", c->tune.lean, true, 0, 1)                  // conv_lean_kernel where its shapes allow; 0 = conv_fast_kernel (A/B)
   LDC_OPT("lean_all", c->tune.lean_all, true, 0, 1)               // ... also for k = 4 stride 2 and k = 7 (bf16); 0 = conv_fast_kernel for those (A/B)
+  LDC_OPT("ring3_tiles", c->tune.ring3_tiles, true, 0, 1 << 30)   // three-stage ring of conv_lean_kernel for launches of at most this many workgroups; 0 = off (A/B)
+  LDC_OPT("ring3_wgs", c->tune.ring3_wgs, true, 1, 3)             // ... where this many three-stage workgroups still fit a CU's LDS (1 = every tile)
   LDC_OPT("conv_generic", c->tune.force_generic, true, 0, 1)      // every conv on the generic kernel
   LDC_OPT("conv_small_tiles", c->tune.small_max, true, 0, 1 << 30)
   LDC_OPT("conv_splitk", c->tune.splitk, true, 0, 4)

@@ -145,6 +145,7 @@ void* PlanBuilder::resnet(const ResnetW& r, const void* x1, const void* x2, int 
     // fails (ii) and takes the conv + gn_apply pair instead of stalling every fused launch for its time-out.
     // The slots come from the occupancy query of the kernels these convs land on x the device's CUs (round 6; before: a constant 3 x 256).
     const int concurrent = std::max(2, c->split_batch);
+    c->tune.ring3_cu_share = c->num_cus / concurrent * 8 / 10;   // (the launcher applies the same rule to the three-stage kernels' own slots: conv_lean.inc)
     const long resident_slots = (long)(c->w8 ? std::min(conv_fused_gn_wgs_per_cu(DT_BF16, true), conv_fused_gn_wgs_per_cu(DT_FP8, false)) : conv_fused_gn_wgs_per_cu(dt, false)) *
                                 c->num_cus / concurrent * 8 / 10;
     auto few_tiles = [&](const int* t) {
