@@ -745,7 +745,8 @@ int ldc_debug_raise_failure(ldc_ctx* ctx, int code);
  * stage calls issue none: the count does not move across warm ldc_decode calls. */
 long long ldc_debug_sync_count(void);
 /* Test hook: conv_lean_kernel launches of this process by unit kind (0 k = 3, 1 k = 1, 2 k = 1 with the folded LayerNorm, 3 k = 4 stride 2,
- * 4 k = 7; 5 = launches of any kind on the three-stage ring, option "ring3_tiles"); -1 for an unknown kind.  A test that compares the lean kernel with conv_fast_kernel proves with it that the lean kernel ran. */
+ * 4 k = 7; 5 = launches of any kind on the full three-stage ring, option "ring3_tiles"; 6 = k = 3 launches on the window ring -- three window
+ * planes, two slab sets --, option "ring3_window"; a launch counts in 5 or in 6, never in both); -1 for an unknown kind.  A test that compares the lean kernel with conv_fast_kernel proves with it that the lean kernel ran. */
 long long ldc_debug_lean_launches(int kind);
 
 /* Host-side cost of the step-graph replays since the last reset: milliseconds spent inside hipGraphLaunch, milliseconds spent

@@ -732,6 +732,8 @@ static hipError_t launch_fast_cfg(const ConvKArgs& a_in, const FastGeom& gm_in, 
 // to every grid, so the dense launches lost a co-resident workgroup.  conv_lean_kernel (one instruction per copy) has a three-stage
 // ring with a counted copy wait and a bare barrier for the sparse grids on 64-row tiles (conv_lean.inc, round 9): 20 - 25 % off those
 // launches, 3.3 % off a decode -- and still a loss on the 128-row tiles, for the third reason (profiles/r09_ring3.md).
+// Round 10: those tiles keep their third workgroup with a third stage for the WINDOW alone (conv_lean.inc, LEAN_RING_W: three window
+// planes, two slab sets, 51.2 KB on the k = 3 128 x 64 tile): 1.0 - 1.5 % off a decode (profiles/r10_ring_window.md).
 template <typename T, int TG, int KC, int NA, bool RF = false>
 static hipError_t launch_fast_bn(int bn, const ConvKArgs& a, const FastGeom& gm, int M, hipStream_t s) {
   // Weights straight into VGPRs (each wave loading its own B fragments with global_load_dwordx4, only the activation

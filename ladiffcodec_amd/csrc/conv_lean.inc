@@ -50,7 +50,9 @@ struct LeanShape {
   static constexpr int PLANE_BYTES = PLANE_ROWS * kRowBytes + kRowBytes;   // + the zero row behind the plane
   static constexpr int ZERO_OFF = PLANE_ROWS * kRowBytes;
   static constexpr int B_OFF = KC * PLANE_BYTES;
-  static constexpr int STAGE_BYTES = B_OFF + NSB * BN * kRowBytes;
+  static constexpr int SLAB_BYTES = NSB * BN * kRowBytes;                  // the slabs of one unit
+  static constexpr int STAGE_BYTES = B_OFF + SLAB_BYTES;
+  static constexpr int RINGW_BYTES = 3 * KC * PLANE_BYTES + 2 * SLAB_BYTES;   // window ring (LEAN_RING_W): three planes, then two slab sets
   static_assert(NAW >= 1 && NAW <= 5 && NAW1 <= 2 && NSB >= 2 && NSB <= 4, "runs of at most four copies per M0 write (13-bit immediate)");
 };
 
@@ -528,10 +530,22 @@ __device__ __forceinline__ uint4 lean_lds16(unsigned addr) {   // ds_read_b128 f
 // workgroups on a CU and lose no co-resident one to the third stage: launch_lean, ConvTune::ring3_tiles / ring3_wgs): two units in flight, the wait in front of the barrier leaves the younger
 // one's copies outstanding (a counted vmcnt), the barrier is a bare s_barrier, and the copies of unit u + 2 go out in runs between the
 // MFMA groups of unit u.  Same MFMA order per accumulator, same epilogues: bit-identical to S = 2.
+// LEAN_RING_W (round 10, the k = 3 128-row tile without the folded second conv, whose three full stages would cost the CU its third
+// workgroup; ConvTune::ring3_window, ring3_window_tiles): a third stage for the WINDOW alone, 51.2 KB.  LDS holds three window
+// planes (each with its zero row) and behind them two slab sets; unit j of a tile (j = u - u_begin) uses window slot j % 3 and slab set
+// j % 2.  During unit j the slabs of unit j + 1 and then the window of unit j + 2 are issued; at the top of unit j + 1 the wave waits
+// with vmcnt(this wave's copies of ONE window run) -- loads return in order, so the slabs have landed and only the younger window stays
+// outstanding: the copy a unit waits for shrinks from window + slabs to the slabs.  Three units per trip (window slots are immediates);
+// the slab set alternates per unit, so the two sets' fragment addresses and M0 values are two register sets swapped once per trip.
+enum { LEAN_RING_W = 5 };   // (a value of S: three window planes + two slab sets)
 template <typename T, int TM, int KIND, bool RF, int EPI, bool SK, int S = 2>
 __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const ConvKArgs a, const LeanGeom g) {
   using SH = LeanShape<TM, KIND, RF>;
-  static_assert(S == 2 || (S == 3 && !SH::K4 && !SH::K7 && SH::NAW1 == 0), "three stages: the k = 3 and 1x1 kinds (one window run per plane)");
+  constexpr bool RW = S == LEAN_RING_W;
+  static_assert(S == 2 || RW || (S == 3 && !SH::K4 && !SH::K7 && SH::NAW1 == 0), "three stages: the k = 3 and 1x1 kinds (one window run per plane)");
+  static_assert(!RW || (SH::K3 && SH::NAW1 == 0 && !RF), "window ring: k = 3 units (one plane, one window run), no folded second conv");
+  static_assert(!RW || 3 * std::max(SH::RINGW_BYTES, 4 * TM * 32 * (32 * ((EPI == LEAN_EPI_RES || EPI == LEAN_EPI_GN_RES) ? 4 : (int)sizeof(T)) + 16)) <= 160 * 1024,
+                "window ring: three workgroups of it (ring or epilogue staging, whichever is larger) fit a CU's 160 KB of LDS");
   constexpr int TN = 1, WM = 2, WN = 2, NW = 4, TG = SH::TG, KC = SH::KC, NS = SH::NS, NSB = SH::NSB, NAW = SH::NAW;
   constexpr int BM = SH::BM, BN = SH::BN, STAGE = SH::STAGE_BYTES, PLANE = SH::PLANE_BYTES;
   constexpr int BKE = kRowBytes / (int)sizeof(T);
@@ -631,9 +645,31 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
       window_offsets(ldb2);
     }
   };
-  issue(0);
-  if constexpr (S == 3) {   // two units in flight from the start
-    if (tl.u_begin + 1 < tl.u_end && !(g.debug & 16)) issue(1);
+  // window ring: the two halves of issue(), with cursors of their own -- the window runs one unit ahead of the slabs, so the switch to the
+  // second input tensor follows the window that is being issued (pc counts windows), the weight pointer the slabs
+  constexpr unsigned kSlabs0 = (unsigned)(3 * PLANE - SH::B_OFF);   // slab set 0 behind the three planes, relative to m0_b / b_ad
+  auto issue_window = [&](const int slot) {   // (slot is a literal at every call site)
+    lean_dma_run<SH::NAW0>(xb, m0_win + (unsigned)(slot * PLANE), wcnt, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
+    pc += 1;
+    xb += kRowBytes;
+    if (pc == csw) {
+      xb = a.x2 - kBias;
+      window_offsets(ldb2);
+    }
+  };
+  auto issue_slabs = [&](const unsigned m0v) {
+    lean_dma_all<NSB>(wb, m0v, vb[0], vb[1], vb[2], vb[3]);
+    wb += (size_t)chunk_w;
+  };
+  if constexpr (RW) {       // window(u0), slabs(u0), window(u0 + 1)
+    issue_window(0);
+    issue_slabs(m0_b + kSlabs0);
+    if (tl.u_begin + 1 < tl.u_end && !(g.debug & 16)) issue_window(1);
+  } else {
+    issue(0);
+    if constexpr (S == 3) {   // two units in flight from the start
+      if (tl.u_begin + 1 < tl.u_end && !(g.debug & 16)) issue(1);
+    }
   }
   if (g.stamps) t_dma = __builtin_amdgcn_s_memtime();
   // per-column constants of the epilogue, requested now (used behind the K loop: a bias fetched there cost the epilogue 2 k cycles of load latency)
@@ -733,7 +769,9 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
 
   // ---- everything below runs under the first copies' latency ----
   // zero rows (one behind every plane of every stage): S x KC x 16 dwords
-  if (tid < S * KC * 16) {
+  if constexpr (RW) {   // (three planes back to back)
+    if (tid < 3 * 16) reinterpret_cast<unsigned*>(smem + (tid >> 4) * PLANE + SH::ZERO_OFF)[tid & 15] = 0u;
+  } else if (tid < S * KC * 16) {
     const int st = tid / (KC * 16), rem = tid - st * (KC * 16);
     reinterpret_cast<unsigned*>(smem + st * STAGE + (rem >> 4) * PLANE + SH::ZERO_OFF)[rem & 15] = 0u;
   }
@@ -916,6 +954,83 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       handover();
       step(2, 1, false);
+    }
+    u = u_end;
+  }
+  if constexpr (RW) {
+    // ---- window ring: at the top of unit j the copies in flight are, oldest first, ... slabs(j), window(j + 1) ----
+    constexpr int NG = NS;                  // MFMA groups of a unit: a tap each
+    // slab sets: A holds the units at positions 0 and 2 of a trip, B the one at position 1; a trip is three units, so they swap per trip
+    unsigned bA[2] = {b_ad[0] + kSlabs0, b_ad[1] + kSlabs0}, bB[2] = {bA[0] + (unsigned)SH::SLAB_BYTES, bA[1] + (unsigned)SH::SLAB_BYTES};
+    unsigned mA = m0_b + kSlabs0, mB = mA + (unsigned)SH::SLAB_BYTES;
+    auto frag = [&](const int ws, const unsigned (&bx)[2], const int q, uint4 (&af)[2][TM], uint4 (&bf)[2]) {   // window slot ws (a literal), slab set bx
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) af[ks][i] = lean_lds16(a_ad[i][q][ks] + (unsigned)(ws * PLANE));
+        bf[ks] = lean_lds16(bx[ks] + (unsigned)(q * 1024));
+      }
+    };
+    // the MFMA chain of the unit in window slot ws and slab set bx (the three-stage step, group by group); behind group 0 go the slabs
+    // of the next unit (into the other slab set, M0 value m0n), behind group 1 the window of the unit after it (into slot ws + 2):
+    // slabs first, so that the counted wait below may leave exactly the window outstanding
+    auto step = [&](const int ws, const unsigned (&bx)[2], const unsigned m0n, const bool slabs, const bool window) {
+      uint4 af[2][2][TM], bf[2][2];
+      frag(ws, bx, 0, af[0], bf[0]);
+#pragma unroll
+      for (int q = 0; q < NG; ++q) {
+        if (q + 1 < NG) frag(ws, bx, q + 1, af[(q + 1) & 1], bf[(q + 1) & 1]);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int i = 0; i < TM; ++i) mfma_step<T>(acc[i][0], af[q & 1][ks][i], bf[q & 1][ks]);
+        if ((q == 0 && slabs) || (q == 1 && window)) {
+          __builtin_amdgcn_sched_barrier(0);
+          if (q == 0) issue_slabs(m0n);
+          else issue_window((ws + 2) % 3);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    };
+    // "unit j has landed" with window(j + 1) left in flight: at most this wave's copies of ONE window run outstanding
+    auto wait_keep_window = [&]() {
+      if (NAW >= 3 && wcnt == 3u) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+      else if (NAW >= 2 && wcnt == 2u) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      else if (wcnt == 1u) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    auto handover = [&]() {   // (the three-stage ring's: fragment reads complete, bare barrier, nothing about the copy counter)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    };
+    // Three units per trip and ONE loop exit; inside the loop every unit has a younger window to leave in flight
+    while (u + 3 < u_end) {
+      wait_keep_window(); handover();
+      step(0, bA, mB, copies, copies);
+      wait_keep_window(); handover();
+      step(1, bB, mA, copies, copies);
+      wait_keep_window(); handover();
+      step(2, bA, mB, copies, copies && u + 4 < u_end);
+      u += 3;
+      { const unsigned t0 = bA[0], t1 = bA[1], tm = mA; bA[0] = bB[0]; bA[1] = bB[1]; mA = mB; bB[0] = t0; bB[1] = t1; mB = tm; }
+    }
+    // the last one to three units (workgroup-uniform); the very last wait drains the counter
+    const int left = u_end - u;
+    if (left >= 1) {
+      if (left >= 2) wait_keep_window(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      handover();
+      step(0, bA, mB, copies && left >= 2, copies && left >= 3);
+    }
+    if (left >= 2) {
+      if (left >= 3) wait_keep_window(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      handover();
+      step(1, bB, mA, copies && left >= 3, false);
+    }
+    if (left >= 3) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      handover();
+      step(2, bA, mB, false, false);
     }
     u = u_end;
   }
@@ -1239,7 +1354,42 @@ static hipError_t launch_lean_kernel(const ConvKArgs& a, const LeanGeom& g, size
   hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), lds, s, a, g);
   __atomic_fetch_add(&g_lean_launches[KIND], 1ll, __ATOMIC_RELAXED);
   if (S == 3) __atomic_fetch_add(&g_lean_launches[5], 1ll, __ATOMIC_RELAXED);   // (slot 5: launches on the three-stage ring, of any kind)
+  if (S == LEAN_RING_W) __atomic_fetch_add(&g_lean_launches[6], 1ll, __ATOMIC_RELAXED);   // (slot 6: launches on the window ring)
   return hipGetLastError();
+}
+
+// The tile the window ring is built for: k = 3 on 128 x 64 without the folded second conv.  (The 64 x 64 tile takes the full three-stage
+// ring; with the fold it would fit the window ring -- 47.2 KB -- but measured 0.3 % slower per decode on it and was taken out again; with the
+// fold on 128 x 64, and for 1x1 convs, three workgroups of the window ring do not fit a CU: profiles/r10_ring_window.md.)
+template <int TM, int KIND, bool RF>
+struct LeanRingW { static constexpr bool ok = KIND == LEAN_K3 && TM == 2 && !RF; };
+
+// lean_ring3_wgs_per_cu for the window-ring kernels: 0 when the query fails (no fused GroupNorm launch takes the window ring then)
+template <typename T>
+static int lean_ringw_wgs_per_cu() {
+  constexpr int TM = 2;
+  static int cached = -1;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  if (cached >= 0) return cached;
+  using SH = LeanShape<TM, LEAN_K3, false>;
+  int worst = 1 << 30;
+  auto ask = [&](const void* fn, bool res32) {
+    const size_t lds = std::max((size_t)SH::RINGW_BYTES, (size_t)4 * TM * 32 * (32 * (res32 ? 4 : sizeof(T)) + 16));
+    int n = 0;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds) != hipSuccess) {
+      (void)hipGetLastError();
+      n = 0;
+    }
+    worst = std::min(worst, n);
+  };
+  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN, false, LEAN_RING_W>), false);
+  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN, true, LEAN_RING_W>), false);
+  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, false, LEAN_RING_W>), true);
+  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, true, LEAN_RING_W>), true);
+  cached = worst;
+  return cached;
 }
 
 // Workgroups of the three-stage fused GroupNorm kernels of this tile that fit one CU (occupancy query with their dynamic LDS; the worst
@@ -1349,7 +1499,23 @@ static hipError_t launch_lean(const ConvKArgs& a, const FastGeom& gm, int M, hip
       const long item_tiles = (long)((a.L_rows + SH0::BM - 1) / SH0::BM + 1) * gm.ntn;
       ring3 = gm.grid <= slots || item_tiles + 16 * gm.ntn <= slots;
     }
-    size_t lds = std::max((size_t)(ring3 ? 3 : 2) * SH0::STAGE_BYTES, epi_bytes);
+    // round 10: where ring3_wgs workgroups of the full ring do NOT fit, the window ring (LEAN_RING_W: a third stage for the window
+    // alone) where ring3_wgs workgroups of IT fit -- the k = 3 128 x 64 tile (51.2 KB); ConvTune::ring3_window.  It costs no co-resident
+    // workgroup, so its grid threshold is its own (ConvTune::ring3_window_tiles, 608: the 600-tile launches gain more from it than the
+    // 304-tile ones, profiles/r10_ring_window.md); a fused GroupNorm launch under the same residency rule, with the occupancy of the
+    // window-ring kernels themselves.
+    bool ringw = false;
+    if constexpr (LeanRingW<TM, K3 ? LEAN_K3 : LEAN_K1, RF>::ok) {
+      const size_t ldsw = std::max((size_t)SH0::RINGW_BYTES, epi_bytes);
+      ringw = !ring3 && tn && tn->ring3_window && gm.grid <= tn->ring3_window_tiles &&
+              (size_t)std::max(1, tn->ring3_wgs) * lds3 > (size_t)160 * 1024 && (size_t)std::max(1, tn->ring3_wgs) * ldsw <= (size_t)160 * 1024 && !(gm.debug & 1);
+      if (ringw && gn) {
+        const long slots = (long)lean_ringw_wgs_per_cu<T>() * tn->ring3_cu_share;
+        const long item_tiles = (long)((a.L_rows + SH0::BM - 1) / SH0::BM + 1) * gm.ntn;
+        ringw = gm.grid <= slots || item_tiles + 16 * gm.ntn <= slots;
+      }
+    }
+    size_t lds = std::max(ringw ? (size_t)SH0::RINGW_BYTES : (size_t)(ring3 ? 3 : 2) * SH0::STAGE_BYTES, epi_bytes);
     if (ln) {
       g.ln_off = (int)((lds + 15) / 16 * 16);
       lds = (size_t)g.ln_off + (size_t)SH0::BM * 8;
@@ -1357,6 +1523,9 @@ static hipError_t launch_lean(const ConvKArgs& a, const FastGeom& gm, int M, hip
     *launched = true;
 #define LDC_LEAN_GO(KIND_, EPI_, SK_)                                                         \
   do {                                                                                        \
+    if constexpr (LeanRingW<TM, KIND_, RF>::ok) {                                             \
+      if (ringw) return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, LEAN_RING_W>(a, g, lds, s); \
+    }                                                                                         \
     if (ring3) return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, 3>(a, g, lds, s);       \
     return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, 2>(a, g, lds, s);                  \
   } while (0)

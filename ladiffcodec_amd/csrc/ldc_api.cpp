@@ -875,6 +875,8 @@ static bool find_option(ldc_ctx* c, const std::string& n, OptRef* r) {
   LDC_OPT("lean_all", c->tune.lean_all, true, 0, 1)               // ... also for k = 4 stride 2 and k = 7 (bf16); 0 = conv_fast_kernel for those (A/B)
   LDC_OPT("ring3_tiles", c->tune.ring3_tiles, true, 0, 1 << 30)   // three-stage ring of conv_lean_kernel for launches of at most this many workgroups; 0 = off (A/B)
   LDC_OPT("ring3_wgs", c->tune.ring3_wgs, true, 1, 3)             // ... where this many three-stage workgroups still fit a CU's LDS (1 = every tile)
+  LDC_OPT("ring3_window", c->tune.ring3_window, true, 0, 1)       // ... and where they do not but as many window rings do (k = 3, 128-row tile), the window ring; 0 = two stages (A/B)
+  LDC_OPT("ring3_window_tiles", c->tune.ring3_window_tiles, true, 0, 1 << 30)   // ... for launches of at most this many workgroups
   LDC_OPT("conv_generic", c->tune.force_generic, true, 0, 1)      // every conv on the generic kernel
   LDC_OPT("conv_small_tiles", c->tune.small_max, true, 0, 1 << 30)
   LDC_OPT("conv_splitk", c->tune.splitk, true, 0, 4)

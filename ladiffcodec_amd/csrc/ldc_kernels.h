@@ -71,7 +71,9 @@ struct ConvTune {
   int lean = 1;                 // round 6: the instruction-diet kernel (conv_lean.inc) where its shapes allow; 0 = conv_fast_kernel everywhere (LDC_CONV_LEAN)
   int ring3_tiles = 304;        // round 9: conv_lean_kernel's three-stage ring (two units in flight, counted copy waits) for k = 3 / 1x1 launches of at most this many workgroups, split-K slices included; 0 = never (profiles/r09_ring3.md)
   int ring3_wgs = 3;            // ... and only where this many three-stage workgroups still fit a CU's 160 KB of LDS (3: the 64-row tiles; 2: the 128-row tiles too; 1: every tile)
-  int ring3_cu_share = 102;     // (not an option: the CUs a batch part's fused GroupNorm launch can count on, set by the planner next to its own residency rule -- unet_plan.cpp: few_tiles)
+  int ring3_window = 1;         // round 10: where ring3_wgs full rings do not fit a CU but as many window rings do (three window planes, two slab sets, 51.2 KB: conv_lean.inc, LEAN_RING_W) -- the k = 3 128-row tile without the folded second conv -- the window ring; 0 = two stages there (A/B) (profiles/r10_ring_window.md)
+  int ring3_window_tiles = 608; // ... for launches of at most this many workgroups, split-K slices included (the window ring costs no co-resident workgroup: the 600-tile launches take it too)
+  int ring3_cu_share = 102;    // (not an option: the CUs a batch part's fused GroupNorm launch can count on, set by the planner next to its own residency rule -- unet_plan.cpp: few_tiles)
   int lean_all = 1;             // round 7: also the stride-2 downsamples (k = 4) and init_conv (k = 7) of the bf16 engine on it; 0 = conv_fast_kernel for those (A/B)
 };
 
