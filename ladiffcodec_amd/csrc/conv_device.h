@@ -833,6 +833,194 @@ __device__ __forceinline__ void epilogue_rows_dispatch(const KA& a, f32x16 (&acc
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Pieces that conv_fast_body and conv_lean_kernel share: one text, so that a fix reaches both kernels.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Timed-mode stamps, head: earliest start of the launch (every workgroup, also the split-K slices that leave early).  Returns the
+// launch's slot, nullptr when timed mode is off.
+template <typename KA>
+__device__ __forceinline__ unsigned long long* kst_begin(const KA& a, const int tid, const unsigned bid) {
+  if (!a.kst) return nullptr;
+  unsigned long long* slot = a.kst + (size_t)(a.kst_step[1] & 2047) * a.kst_stride;
+  if (tid == 0 && bid == 0) slot[0] = (unsigned long long)wall_clock64();   // workgroups are dispatched in index order
+  return slot;
+}
+// ... tail: latest end of the launch (stores drained), kept as the minimum of ~t
+__device__ __forceinline__ void kst_end(unsigned long long* slot, const int tid, const unsigned bid, const int grid) {
+  if (!slot) return;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // (every eighth workgroup and the last eight: 600 same-address atomics per launch cost the decode 8 %)
+  if (tid == 0 && ((bid & 7) == 0 || bid + 8 >= (unsigned)grid)) atomicMin(slot + 1, ~(unsigned long long)wall_clock64());
+}
+
+// Phase stamps of a workgroup (tuning aid, LDC_CONV_STAMPS): {start, prologue done, loop done, end, tables, first copies} s_memtime and
+// the XCD.  Returns the workgroup's eight words to the thread that wrote them (word 7 is the caller's), nullptr to the others.
+__device__ __forceinline__ unsigned long long* stamp_phases(unsigned long long* stamps, const int tid, const unsigned bid, unsigned long long t_start,
+                                                            unsigned long long t_pro, unsigned long long t_loop, unsigned long long t_tab,
+                                                            unsigned long long t_dma) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned long long t_end = __builtin_amdgcn_s_memtime();
+  if (tid != 0) return nullptr;
+  unsigned long long* o = stamps + (size_t)bid * 8;
+  o[0] = t_start; o[1] = t_pro; o[2] = t_loop; o[3] = t_end; o[4] = t_tab; o[5] = t_dma;
+  o[6] = (unsigned long long)(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | ((4 - 1) << 11)) & 0xf);   // HW_REG_XCC_ID[3:0]
+  return o;
+}
+
+// Folded PreNorm LayerNorm (ConvLayer::ln_s), prologue half: channel mean and rstd of this tile's BM rows (1x1 conv: input row = output
+// row) into the table st[BM][2], NT / BM threads per row over the row's 16-byte pieces -- under the latency of the first unit's copies.
+// Variance about the mean, as nn.LayerNorm / launch_ln_rows compute it (the single-pass E[x^2] - mean^2 of round 4 loses
+// digits to cancellation where |mean| >> std): the producer's partials are (sum, centred M2) per 32-column block and are merged
+// Chan-style -- mean first, then M2 + 32 (block mean - mean)^2 --; rows read here are passed over twice.
+template <typename T, int BM, int NT, typename KA>
+__device__ __forceinline__ void ln_row_stats(const KA& a, float* st, const int m0, const int M, const int tid) {
+  constexpr int TPR = NT / BM;                            // threads per row (2 or 4)
+  constexpr int EPV = 16 / (int)sizeof(T);
+  const int row = tid / TPR, part = tid - row * TPR;
+  const int C = a.C1, nvec = C / EPV;
+  const char* src = a.x1 + (size_t)min(m0 + row, M - 1) * C * sizeof(T);
+  float sm = 0.f, sq = 0.f;
+  const float2* rs = a.ln_rowstat ? reinterpret_cast<const float2*>(a.ln_rowstat) + (size_t)min(m0 + row, M - 1) * (C >> 5) : nullptr;
+  auto reduce_tpr = [&](float v) {
+#pragma unroll
+    for (int o = 1; o < TPR; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+  };
+  if (rs) {
+    // the producer of these rows (the fused block2 conv in front) left (sum, M2 about the block's own mean) per 32-column block
+    const int nblk = C >> 5;
+    for (int k0 = part; k0 < nblk; k0 += TPR * 4) {
+      float2 pr[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) pr[u] = rs[min(k0 + u * TPR, nblk - 1)];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (k0 + u * TPR < nblk) sm += pr[u].x;
+    }
+    const float mean = reduce_tpr(sm) / (float)C;
+    for (int k0 = part; k0 < nblk; k0 += TPR * 4) {
+      float2 pr[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) pr[u] = rs[min(k0 + u * TPR, nblk - 1)];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (k0 + u * TPR < nblk) {
+          const float d = pr[u].x * (1.0f / 32.0f) - mean;
+          sq += fmaf(32.0f * d, d, pr[u].y);
+        }
+    }
+    sm = mean;
+  } else {
+    // eight 16-byte pieces in flight per thread (a one-piece-at-a-time loop is a chain of dependent load latencies: it made the
+    // L = 1200 to_qkv launch 10 us longer, more than the LayerNorm launch it replaces)
+    float mean = 0.f;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+      for (int v0 = part; v0 < nvec; v0 += TPR * 8) {
+        uint4 q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int v = v0 + u * TPR;
+          q[u] = *reinterpret_cast<const uint4*>(src + (size_t)min(v, nvec - 1) * 16);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          if (v0 + u * TPR >= nvec) continue;
+          const unsigned w4[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (sizeof(T) == 4) {
+              const float f = __uint_as_float(w4[e]);
+              if (pass == 0) sm += f;
+              else sq = fmaf(f - mean, f - mean, sq);
+            } else {
+              const float f0 = __uint_as_float(w4[e] << 16), f1 = __uint_as_float(w4[e] & 0xffff0000u);
+              if (pass == 0) sm += f0 + f1;
+              else sq = fmaf(f0 - mean, f0 - mean, fmaf(f1 - mean, f1 - mean, sq));
+            }
+          }
+        }
+      }
+      if (pass == 0) mean = reduce_tpr(sm) / (float)C;
+    }
+    sm = mean;
+  }
+  sq = reduce_tpr(sq);
+  if (part == 0) {
+    st[2 * row] = sm;
+    st[2 * row + 1] = rsqrtf(sq / (float)C + 1e-5f);
+  }
+}
+
+// ... epilogue half, on a wave's accumulators: conv(LN(x)) = rstd_r * (acc - mean_r * s_n); the table was written in the prologue
+// (barriers of the K loop in between).  row_wave0 / col_wave0: the wave's first row of the tile / first column of the layer.
+template <int TM, int TN, typename KA>
+__device__ __forceinline__ void ln_apply(const KA& a, f32x16 (&acc)[TM][TN], const float* st, const int row_wave0, const int col_wave0, const int lane) {
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int col = col_wave0 + j * 32 + (lane & 31);
+    const float sn = col < a.n ? a.ln_s[col] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = row_wave0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const float2 ms = *reinterpret_cast<const float2*>(st + 2 * row);
+        acc[i][j][r] = ms.y * fmaf(-ms.x, sn, acc[i][j][r]);
+      }
+  }
+}
+
+// Split-K behind the K loop (NW waves, the ring drained): park the partial tile; the last slice to arrive adds the others and carries on
+// into the epilogue (true), the others are done (false).  Visibility: write-through (agent-scope) stores, drained, then the relaxed
+// arrival counter; the finisher reads with agent-scope loads.  (Release/acquire FENCES here write back and invalidate the whole L2: 3x
+// slower kernel.)
+template <int TM, int TN, int NW = 4, typename KA>
+__device__ __forceinline__ bool splitk_park_and_sum(const KA& a, f32x16 (&acc)[TM][TN], char* smem, const int sk_tile, const int sk_k, const int wave,
+                                                    const int lane, const int tid) {
+  int* s_last_p = reinterpret_cast<int*>(smem);   // the ring is drained: its first word carries the verdict
+  constexpr int TILE = NW * TM * TN * 1024;       // BM x BN
+  float* mine = a.sk_part + ((size_t)sk_tile * a.ksplit + sk_k) * TILE;
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        __hip_atomic_store(&mine[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane], acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // write-through stores have reached memory
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned old = atomicAdd(a.sk_count + sk_tile, 1u);
+    const int last = old == (unsigned)(a.ksplit - 1);
+    *s_last_p = last;
+    if (last) a.sk_count[sk_tile] = 0u;   // ready for the next launch that uses the counters
+  }
+  __syncthreads();
+  const int is_last = *s_last_p;
+  __syncthreads();   // the epilogue reuses this LDS
+  if (!is_last) return false;
+  // fixed summation order (slice 0, 1, .. ksplit-1, whichever arrived last): bit-reproducible from run to run.
+  // The finisher re-reads its own parked slice too.
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  for (int o = 0; o < a.ksplit; ++o) {
+    const float* other = a.sk_part + ((size_t)sk_tile * a.ksplit + o) * TILE;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          acc[i][j][r] += __hip_atomic_load(&other[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return true;
+}
+
 // conv_fast_{bf16,f32}.hip
 extern long long g_lean_launches[8];        // test hook (ldc_debug_lean_launches): conv_lean_kernel launches of this process by unit kind
 extern unsigned long long* g_conv_stamps;   // tuning aid, set by ldc_conv_microbench when LDC_CONV_STAMPS is on

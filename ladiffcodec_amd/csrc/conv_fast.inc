@@ -120,11 +120,7 @@ __device__ __forceinline__ void conv_fast_body(const ConvKArgs& a, const FastGeo
   const int M = a.B * a.L_rows;
   unsigned long long t_start = 0, t_pro = 0, t_loop = 0, t_tab = 0, t_dma = 0;
   if (gm.stamps) t_start = __builtin_amdgcn_s_memtime();
-  unsigned long long* kst_slot = nullptr;
-  if (a.kst) {   // timed-mode stamps: earliest start of the launch (every workgroup, also the split-K slices that leave early)
-    kst_slot = a.kst + (size_t)(a.kst_step[1] & 2047) * a.kst_stride;
-    if (tid == 0 && bid == 0) kst_slot[0] = (unsigned long long)wall_clock64();   // workgroups are dispatched in index order
-  }
+  unsigned long long* const kst_slot = kst_begin(a, tid, bid);   // timed-mode stamps
   if (gm.debug & 8) return;   // tuning aid: launch + boundary cost of this grid
   // XCD-aware tile order: workgroup h runs on XCD h % 8 (observed dispatch rule, used for speed only), so give
   // every XCD a contiguous run of tiles, N-tile fastest: workgroups sharing an input window hit the same L2.
@@ -296,91 +292,7 @@ __device__ __forceinline__ void conv_fast_body(const ConvKArgs& a, const FastGeo
     if (u_begin + p < nunits) load_unit(p);
   if (gm.stamps) t_dma = __builtin_amdgcn_s_memtime();
   if constexpr (!kFp8) {
-    if (a.ln_s) {
-      // folded PreNorm LayerNorm (ConvLayer::ln_s): channel mean and rstd of this tile's rows (1x1 conv: input row = output row),
-      // a few threads per row over the row's 16-byte pieces, under the latency of the first unit's copies
-      constexpr int TPR = NW * 64 / BM;                       // threads per row (2 or 4)
-      constexpr int EPV = 16 / (int)sizeof(T);
-      const int row = tid / TPR, part = tid - row * TPR;
-      const int C = a.C1, nvec = C / EPV;
-      const char* src = a.x1 + (size_t)min(m0 + row, M - 1) * C * sizeof(T);
-      // Variance about the mean, as nn.LayerNorm / launch_ln_rows compute it (ADVICE r4: the single-pass E[x^2] - mean^2 of round 4 loses
-      // digits to cancellation where |mean| >> std): the producer's partials are (sum, centred M2) per 32-column block and are merged
-      // Chan-style -- mean first, then M2 + 32 (block mean - mean)^2 --; rows read here are passed over twice.
-      float sm = 0.f, sq = 0.f;
-      const float2* rs = a.ln_rowstat ? reinterpret_cast<const float2*>(a.ln_rowstat) + (size_t)min(m0 + row, M - 1) * (C >> 5) : nullptr;
-      auto load_pair = [&](int k) -> float2 { return rs[k]; };
-      auto reduce_tpr = [&](float v) {
-#pragma unroll
-        for (int o = 1; o < TPR; o <<= 1) v += __shfl_xor(v, o);
-        return v;
-      };
-      if (rs) {
-        // the producer of these rows (the fused block2 conv in front) left (sum, M2 about the block's own mean) per 32-column block
-        const int nblk = C >> 5;
-        for (int k0 = part; k0 < nblk; k0 += TPR * 4) {
-          float2 pr[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) pr[u] = load_pair(min(k0 + u * TPR, nblk - 1));
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (k0 + u * TPR < nblk) sm += pr[u].x;
-        }
-        const float mean = reduce_tpr(sm) / (float)C;
-        for (int k0 = part; k0 < nblk; k0 += TPR * 4) {
-          float2 pr[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) pr[u] = load_pair(min(k0 + u * TPR, nblk - 1));
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (k0 + u * TPR < nblk) {
-              const float d = pr[u].x * (1.0f / 32.0f) - mean;
-              sq += fmaf(32.0f * d, d, pr[u].y);
-            }
-        }
-        sm = mean;
-      } else {
-        // eight 16-byte pieces in flight per thread (a one-piece-at-a-time loop is a chain of dependent load latencies: it made the
-        // L = 1200 to_qkv launch 10 us longer, more than the LayerNorm launch it replaces)
-        float mean = 0.f;
-#pragma unroll 1
-        for (int pass = 0; pass < 2; ++pass) {
-          for (int v0 = part; v0 < nvec; v0 += TPR * 8) {
-            uint4 q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-              const int v = v0 + u * TPR;
-              q[u] = *reinterpret_cast<const uint4*>(src + (size_t)min(v, nvec - 1) * 16);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-              if (v0 + u * TPR >= nvec) continue;
-              const unsigned w4[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                if (sizeof(T) == 4) {
-                  const float f = __uint_as_float(w4[e]);
-                  if (pass == 0) sm += f;
-                  else sq = fmaf(f - mean, f - mean, sq);
-                } else {
-                  const float f0 = __uint_as_float(w4[e] << 16), f1 = __uint_as_float(w4[e] & 0xffff0000u);
-                  if (pass == 0) sm += f0 + f1;
-                  else sq = fmaf(f0 - mean, f0 - mean, fmaf(f1 - mean, f1 - mean, sq));
-                }
-              }
-            }
-          }
-          if (pass == 0) mean = reduce_tpr(sm) / (float)C;
-        }
-        sm = mean;
-      }
-      sq = reduce_tpr(sq);
-      if (part == 0) {
-        float* st = reinterpret_cast<float*>(smem + gm.ln_off);
-        st[2 * row] = sm;
-        st[2 * row + 1] = rsqrtf(sq / (float)C + 1e-5f);
-      }
-    }
+    if (a.ln_s) ln_row_stats<T, BM, NW * 64>(a, reinterpret_cast<float*>(smem + gm.ln_off), m0, M, tid);   // folded PreNorm LayerNorm (conv_device.h)
   }
   // everything below is independent of the copies just issued: it runs under their latency
   // zero rows (one behind every plane of every stage)
@@ -543,68 +455,11 @@ __device__ __forceinline__ void conv_fast_body(const ConvKArgs& a, const FastGeo
 
   if (gm.stamps) t_loop = __builtin_amdgcn_s_memtime();
   __syncthreads();   // every wave has consumed the last ring stage: LDS is free for the output transpose
-  if (a.ksplit > 1) {
-    // park the partial tile; the last slice to arrive adds the others and carries on into the epilogue.  Visibility:
-    // write-through (agent-scope) stores, drained, then the relaxed arrival counter; the finisher reads with
-    // agent-scope loads.  (Release/acquire FENCES here write back and invalidate the whole L2: 3x slower kernel.)
-    int* s_last_p = reinterpret_cast<int*>(smem);   // the ring is drained: its first word carries the verdict
-    constexpr int TILE = BM * BN;
-    float* mine = a.sk_part + ((size_t)sk_tile * a.ksplit + sk_k) * TILE;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          __hip_atomic_store(&mine[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane], acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // write-through stores have reached memory
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned old = atomicAdd(a.sk_count + sk_tile, 1u);
-      const int last = old == (unsigned)(a.ksplit - 1);
-      *s_last_p = last;
-      if (last) a.sk_count[sk_tile] = 0u;   // ready for the next launch that uses the counters
-    }
-    __syncthreads();
-    const int is_last = *s_last_p;
-    __syncthreads();   // the epilogue reuses this LDS
-    if (!is_last) return;
-    // fixed summation order (slice 0, 1, .. ksplit-1, whichever arrived last): bit-reproducible from run to run.
-    // The finisher re-reads its own parked slice too.
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    for (int o = 0; o < a.ksplit; ++o) {
-      const float* other = a.sk_part + ((size_t)sk_tile * a.ksplit + o) * TILE;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            acc[i][j][r] += __hip_atomic_load(&other[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+  if (a.ksplit > 1) {   // park the partial tile; the last slice to arrive sums all slices and carries on into the epilogue
+    if (!splitk_park_and_sum<TM, TN, NW>(a, acc, smem, sk_tile, sk_k, wave, lane, tid)) return;
   }
   if constexpr (!kFp8) {
-    if (a.ln_s) {   // conv(LN(x)) = rstd_r * (acc - mean_r * s_n); the table was written in the prologue (barriers of the K loop in between)
-      const float* st = reinterpret_cast<const float*>(smem + gm.ln_off);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * TN * 32 + j * 32 + (lane & 31);
-        const float sn = col < a.n ? a.ln_s[col] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const float2 ms = *reinterpret_cast<const float2*>(st + 2 * row);
-            acc[i][j][r] = ms.y * fmaf(-ms.x, sn, acc[i][j][r]);
-          }
-      }
-    }
+    if (a.ln_s) ln_apply<TM, TN>(a, acc, reinterpret_cast<const float*>(smem + gm.ln_off), wm * TM * 32, n0 + wn * TN * 32, lane);
   }
   {
     constexpr int WREG = TM * 32 * (TN * 32 * (int)sizeof(TO) + 16);
@@ -616,20 +471,8 @@ __device__ __forceinline__ void conv_fast_body(const ConvKArgs& a, const FastGeo
     if (!(gm.debug & 4)) epilogue_rows_dispatch<TO, TM, TN>(a, acc, smem + (size_t)wave * wreg, m0 + wm * TM * 32, n0 + wn * TN * 32, M, m0, BM, WM, wm, 0);
     else if (acc[0][0][0] == 12345.678f) a.y[0] = 1;   // tuning aid: keep the accumulators live, store nothing
   }
-  if (kst_slot) {   // latest end of the launch (stores drained), kept as the minimum of ~t
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // (every eighth workgroup and the last eight: 600 same-address atomics per launch cost the decode 8 %)
-    if (tid == 0 && ((bid & 7) == 0 || bid + 8 >= (unsigned)gm.grid)) atomicMin(kst_slot + 1, ~(unsigned long long)wall_clock64());
-  }
-  if (gm.stamps) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-    if (tid == 0) {
-      unsigned long long* o = gm.stamps + (size_t)bid * 8;
-      o[0] = t_start; o[1] = t_pro; o[2] = t_loop; o[3] = t_end; o[4] = t_tab; o[5] = t_dma;
-      o[6] = (unsigned long long)(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | ((4 - 1) << 11)) & 0xf);   // HW_REG_XCC_ID[3:0]
-    }
-  }
+  kst_end(kst_slot, tid, bid, gm.grid);
+  if (gm.stamps) stamp_phases(gm.stamps, tid, bid, t_start, t_pro, t_loop, t_tab, t_dma);
 }
 
 
@@ -850,27 +693,14 @@ hipError_t LDC_FAST_ENTRY(const ConvLayer& ly, const ConvKArgs& a_in, int M, int
 int LDC_FAST_RESIDENCY() {
   using namespace LDC_FAST_NS;
   int worst = 1 << 30;
-  auto ask = [&](const void* fn, size_t lds) {
-    int n = 0;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds) != hipSuccess) {
-      (void)hipGetLastError();
-      n = 0;
-    }
-    worst = std::min(worst, n);
-  };
 #if !LDC_FAST_W8 && !LDC_FAST_FP8
-  auto lean_lds = [](size_t stage, int tm, bool res32) { return std::max((size_t)2 * stage, (size_t)4 * tm * 32 * (32 * (res32 ? 4 : sizeof(LDC_FAST_T)) + 16)); };
-#define LDC_ASK(TM_, RF_, EPI_, SK_) \
-  ask(reinterpret_cast<const void*>(conv_lean_kernel<LDC_FAST_T, TM_, LEAN_K3, RF_, EPI_, SK_>), lean_lds(LeanShape<TM_, LEAN_K3, RF_>::STAGE_BYTES, TM_, EPI_ == LEAN_EPI_GN_RES))
-  LDC_ASK(1, false, LEAN_EPI_GN, false); LDC_ASK(1, false, LEAN_EPI_GN, true); LDC_ASK(1, false, LEAN_EPI_GN_RES, false); LDC_ASK(1, false, LEAN_EPI_GN_RES, true);
-  LDC_ASK(2, false, LEAN_EPI_GN, false); LDC_ASK(2, false, LEAN_EPI_GN, true); LDC_ASK(2, false, LEAN_EPI_GN_RES, false); LDC_ASK(2, false, LEAN_EPI_GN_RES, true);
-  LDC_ASK(1, true, LEAN_EPI_GN, false); LDC_ASK(2, true, LEAN_EPI_GN, false);
-#undef LDC_ASK
+  for (const int n : {lean_gn_wgs_per_cu<LDC_FAST_T, 1, false, LEAN_RING_2>(), lean_gn_wgs_per_cu<LDC_FAST_T, 2, false, LEAN_RING_2>(),
+                      lean_gn_wgs_per_cu<LDC_FAST_T, 1, true, LEAN_RING_2>(), lean_gn_wgs_per_cu<LDC_FAST_T, 2, true, LEAN_RING_2>()})
+    worst = std::min(worst, n);
 #else
   const size_t b_rows = (3 * 64 * LDC_FAST_NS::kRowBytesB / kRowBytes + 63) / 64 * 64;
-  ask(reinterpret_cast<const void*>(conv_fast_kernel<LDC_FAST_T, 2, 2, 1, 1, 3, 1, 2, 2, false>), 2 * (80 + 1 + b_rows) * kRowBytes);
-  ask(reinterpret_cast<const void*>(conv_fast_kernel<LDC_FAST_T, 2, 2, 2, 1, 3, 1, 2, 3, false>), 2 * (144 + 1 + b_rows) * kRowBytes);
+  worst = std::min(worst, lean_ask_wgs(reinterpret_cast<const void*>(conv_fast_kernel<LDC_FAST_T, 2, 2, 1, 1, 3, 1, 2, 2, false>), 2 * (80 + 1 + b_rows) * kRowBytes));
+  worst = std::min(worst, lean_ask_wgs(reinterpret_cast<const void*>(conv_fast_kernel<LDC_FAST_T, 2, 2, 2, 1, 3, 1, 2, 3, false>), 2 * (144 + 1 + b_rows) * kRowBytes));
 #endif
   return worst == (1 << 30) ? 0 : worst;
 }

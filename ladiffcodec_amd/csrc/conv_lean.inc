@@ -1,27 +1,27 @@
-// conv_lean.inc -- round 6: the pipelined conv-GEMM on an instruction diet (included by conv_fast.inc for the bf16 and f32 engines).
+// conv_lean.inc -- the pipelined conv-GEMM on an instruction diet (included by conv_fast.inc; instantiated by the bf16 and f32 engines).
 //
 // Same arithmetic as conv_fast_body (same LDS window / weight slabs / XOR swizzle, same MFMA order per accumulator, same epilogues:
-// the results are bit-identical), a third of the instructions.  What changed, and why (VERDICT r5: 19 non-MFMA instructions per MFMA,
-// 103 KB of code per instantiation, every epilogue variant a run-time branch inside one kernel):
+// the results are bit-identical), a third of the instructions:
 //   * the tile of a workgroup -- (m0, n0, split-K slice, window rows, unit range), in the XCD-aware dispatch order -- is ONE 32-byte
-//     scalar load from a table the host builds per launch geometry (conv_fast_body: ~100 SALU / VALU of tile-order arithmetic and six
-//     FastDivU sequences behind a chain of kernel-argument loads);
+//     scalar load from a table the host builds per launch geometry (lean_tile_table);
 //   * an LDS-DMA copy is ONE instruction: a wave's copies of a plane are contiguous in LDS, so M0 is written once per run and the
 //     copies address their 1 KiB pieces through the instruction's immediate offset (the immediate is added to the LDS address AND to
 //     the global address: the per-lane source offsets are pre-biased once per tile; tools/glds_probe.hip); the channel-chunk advance is
-//     two scalar adds on the base pointer per unit instead of a VALU add per copy (conv_fast_body: save M0 / set / s_nop / copy /
-//     restore + address rebuild per copy, ~350 static instructions per unit);
-//   * LDS layout constants (plane, stage, slab offsets) are compile-time: fragment addresses are TM x TG x 2 registers + immediates
-//     (conv_fast_body: S x KC times as many registers, `v_add_u32 v, 0, v` in front of every read);
+//     two scalar adds on the base pointer per unit;
+//   * LDS layout constants (plane, stage, slab offsets) are compile-time: fragment addresses are TM x TG x 2 registers + immediates;
 //   * the weight slabs of a unit lie [16-column group][slab][16 rows] in LDS, so that a wave's slab copies are contiguous too;
-//   * epilogue kind, folded second conv, folded LayerNorm and split-K are template parameters chosen by the launcher: an
+//   * epilogue kind, folded second conv, folded LayerNorm, split-K and the ring are template parameters chosen by the launcher: an
 //     instantiation carries only its own path.
-// Not here (the launcher keeps conv_fast_kernel for them): fp8 weights / activations, 128 x 128 and 4 x 1-wave tiles, post-activations and
-// the unfused GroupNorm statistics; k = 4 / 7 in f32, k = 8.
-// Round 7: the bf16 step's last conv_fast_kernel launches -- the four stride-2 downsamples (k = 4) and init_conv (k = 7) -- as two more
-// unit kinds (ConvTune::lean_all).  Same window, slabs, swizzle and MFMA order again; what differs from LEAN_K3 is the plane's height
-// (LEAN_K4S2: 2 BM + 2 rows, up to five pieces per wave, copied as two runs) and, for k = 7, that a chunk makes TWO units (taps 0-3 | 4-6
-// and the zero row against a valid slab, as conv_fast_body multiplies it): the loop's two stages are the two tap groups.
+// Unit kinds (LeanShape): LEAN_K3 (3 taps x 1 chunk, optionally with the folded 1x1 conv's fourth slab), LEAN_K1 (1 tap x 2 chunks),
+// LEAN_K1_LN (the same with the folded PreNorm LayerNorm), and for the bf16 engine (ConvTune::lean_all) LEAN_K4S2 (4 taps, stride 2: a
+// plane of 2 BM + 2 rows, up to five pieces per wave, copied as two runs) and LEAN_K7 (a chunk makes TWO units, taps 0-3 | 4-6 and
+// the zero row against a valid slab, as conv_fast_body multiplies it: the two stages are the two tap groups).
+// Ring kinds (LeanRing, LeanRingTraits): two stages; three full stages; three window planes + two slab sets.  launch_lean chooses per
+// launch: the deeper rings go to the sparse grids where they cost the CU no co-resident workgroup (ConvTune::ring3_*).
+// The launcher keeps conv_fast_kernel for fp8 weights / activations, the 4 x 1-wave tiles, post-activations, the unfused GroupNorm
+// statistics, k = 4 / 7 in f32 and k = 8.
+// Measurements: profiles/r06_conv_issue.md (the diet), r07_kernel_stats.md (k = 4 / 7), r09_ring3.md, r10_ring_window.md (the rings),
+// r11_lean_one_ring.md (the one ring loop: resource table before / after).
 
 struct LeanTile { int m0, n0, sk_k, sk_tile, R_lo, nrows, u_begin, u_end; };   // one per workgroup, dispatch order
 struct LeanGeom {
@@ -36,8 +36,10 @@ struct LeanGeom {
 enum { LEAN_K3 = 0, LEAN_K1 = 1, LEAN_K1_LN = 2, LEAN_K4S2 = 3, LEAN_K7 = 4 };
 enum { LEAN_EPI_PLAIN = 0, LEAN_EPI_RES = 1, LEAN_EPI_GN = 2, LEAN_EPI_GN_RES = 3, LEAN_EPI_QKV = 4 };
 
-template <int TM, int KIND, bool RF>
+template <int TM_, int KIND_, bool RF_>
 struct LeanShape {
+  static constexpr int TM = TM_, KIND = KIND_;
+  static constexpr bool RF = RF_;
   static constexpr bool K3 = KIND == LEAN_K3, K4 = KIND == LEAN_K4S2, K7 = KIND == LEAN_K7;
   static constexpr bool TAPS = K3 || K4 || K7;                             // a unit is the tap slabs of ONE chunk
   static constexpr int TG = K3 ? 3 : (TAPS ? 4 : 1), KC = TAPS ? 1 : 2, NS = TG * KC, NSB = NS + (RF ? 1 : 0);
@@ -52,9 +54,62 @@ struct LeanShape {
   static constexpr int B_OFF = KC * PLANE_BYTES;
   static constexpr int SLAB_BYTES = NSB * BN * kRowBytes;                  // the slabs of one unit
   static constexpr int STAGE_BYTES = B_OFF + SLAB_BYTES;
-  static constexpr int RINGW_BYTES = 3 * KC * PLANE_BYTES + 2 * SLAB_BYTES;   // window ring (LEAN_RING_W): three planes, then two slab sets
   static_assert(NAW >= 1 && NAW <= 5 && NAW1 <= 2 && NSB >= 2 && NSB <= 4, "runs of at most four copies per M0 write (13-bit immediate)");
 };
+
+// The ring of a kernel: how many units are in flight under the unit being multiplied, and what the wait in front of a unit leaves out.
+//   LEAN_RING_2: two stages.  One unit in flight, every unit drains the copy counter (vmcnt(0)) in front of a __syncthreads() -- right
+//     where three workgroups share a CU and cover each other's waits.
+//   LEAN_RING_3: three stages (the launches that put one or two workgroups on a CU and lose no co-resident one to the third stage:
+//     ConvTune::ring3_tiles / ring3_wgs).  Two units in flight, the wait in front of the barrier leaves the younger one's copies
+//     outstanding (a counted vmcnt), the barrier is a bare s_barrier, and the copies of unit u + 2 go out in runs between the MFMA groups
+//     of unit u.
+//   LEAN_RING_W: a third stage for the WINDOW alone (the k = 3 128-row tile without the folded second conv, whose three full stages
+//     would cost the CU its third workgroup; ConvTune::ring3_window, ring3_window_tiles), 51.2 KB.  LDS holds three window planes (each
+//     with its zero row) and behind them two slab sets; unit j of a tile (j = u - u_begin) uses window slot j % 3 and slab set j % 2.
+//     During unit j the slabs of unit j + 1 and then the window of unit j + 2 are issued; at the top of unit j + 1 the wave waits with
+//     vmcnt(this wave's copies of ONE window run) -- loads return in order, so the slabs have landed and only the younger window stays
+//     outstanding: the copy a unit waits for shrinks from window + slabs to the slabs.
+// Same MFMA order per accumulator, same epilogues: the three are bit-identical.
+enum LeanRing { LEAN_RING_2 = 0, LEAN_RING_3 = 1, LEAN_RING_W = 2 };
+
+// What a ring is on a shape: which shapes may take it, its bytes, the workgroups per CU its kernels are compiled for, and the slot of
+// ldc_debug_lean_launches that counts its launches (0: none).  Read by the kernel and by the launcher.
+template <typename SH, LeanRing RING>
+struct LeanRingTraits {
+  // three stages: the k = 3 and 1x1 kinds (one window run per plane).  Window ring: the tile it is built for, k = 3 on 128 x 64 without
+  // the folded second conv.  (The 64 x 64 tile takes the full three-stage ring; with the fold it would fit the window ring -- 47.2 KB --
+  // but measured 0.3 % slower per decode on it and was taken out again; with the fold on 128 x 64, and for 1x1 convs, three workgroups
+  // of the window ring do not fit a CU: profiles/r10_ring_window.md.)
+  static constexpr bool ok = RING == LEAN_RING_2 || (RING == LEAN_RING_3 && !SH::K4 && !SH::K7 && SH::NAW1 == 0) ||
+                             (RING == LEAN_RING_W && SH::K3 && SH::TM == 2 && !SH::RF && SH::NAW1 == 0);
+  static constexpr int STAGES = RING == LEAN_RING_2 ? 2 : 3;                       // window planes (per chunk of a unit)
+  static constexpr int SLAB_SETS = RING == LEAN_RING_W ? 2 : STAGES;
+  static constexpr int SLABS0 = STAGES * SH::B_OFF;                                // window ring: the planes back to back, slab set 0 behind them
+  static constexpr int BYTES = RING == LEAN_RING_W ? SLABS0 + SLAB_SETS * SH::SLAB_BYTES : STAGES * SH::STAGE_BYTES;
+  static constexpr int MIN_WGS = RING == LEAN_RING_3 ? 2 : 3;                      // __launch_bounds__
+  static constexpr int COUNT_SLOT = RING == LEAN_RING_3 ? 5 : (RING == LEAN_RING_W ? 6 : 0);
+};
+
+// THE dynamic LDS of an instantiation.  The ring and the epilogue's staging share the front -- four waves' TM x 32 rows of 32 columns
+// (fp32 where a residual is added: res32) + 16 bytes of padding per row --, whichever is larger; the folded LayerNorm's (mean, rstd)
+// table of BM rows lies behind that, 16-aligned, at lean_ln_off.
+constexpr bool lean_epi_res32(int epi) { return epi == LEAN_EPI_RES || epi == LEAN_EPI_GN_RES; }
+template <typename T, int TM>
+constexpr int lean_wave_staging(bool res32) { return TM * 32 * (32 * (res32 ? 4 : (int)sizeof(T)) + 16); }   // one wave's rows
+template <typename T, typename SH, LeanRing RING>
+constexpr int lean_front_bytes(bool res32) { return std::max(LeanRingTraits<SH, RING>::BYTES, 4 * lean_wave_staging<T, SH::TM>(res32)); }
+template <typename T, typename SH, LeanRing RING>
+constexpr int lean_ln_off(bool res32) { return (lean_front_bytes<T, SH, RING>(res32) + 15) / 16 * 16; }
+template <typename T, typename SH, LeanRing RING>
+constexpr size_t lean_lds_bytes(bool res32, bool ln = false) {
+  return ln ? (size_t)lean_ln_off<T, SH, RING>(res32) + (size_t)SH::BM * 8 : (size_t)lean_front_bytes<T, SH, RING>(res32);
+}
+// (the layout in numbers: the window ring of the bf16 k = 3 128-row tile, two stages of it over its fp32 staging, the three stages of a
+// 64-row 1x1 tile with the LayerNorm table behind them)
+static_assert(lean_lds_bytes<__bf16, LeanShape<2, LEAN_K3, false>, LEAN_RING_W>(false) == 3 * 145 * 64 + 2 * 3 * 64 * 64, "window ring");
+static_assert(lean_lds_bytes<__bf16, LeanShape<2, LEAN_K3, false>, LEAN_RING_2>(true) == 2 * (145 + 3 * 64) * 64, "ring over fp32 staging");
+static_assert(lean_lds_bytes<float, LeanShape<1, LEAN_K1_LN, false>, LEAN_RING_3>(false, true) == 3 * (2 * 65 + 2 * 64) * 64 + 64 * 8, "LayerNorm table");
 
 // a run of up to N copies of 1 KiB behind ONE M0 write: copy i lands at m0v + 1024 i and reads (base + voff_i + 1024 i); only the first
 // `cnt` are issued (wave-uniform count: scalar branches, no exec masking).  The M0 write and its reader sit in one statement.
@@ -525,26 +580,31 @@ __device__ __forceinline__ uint4 lean_lds16(unsigned addr) {   // ds_read_b128 f
   return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
-// S = ring depth.  2: one unit in flight under the unit being multiplied, every trip drains the copy counter (vmcnt(0)) in front of its
-// barrier -- right where three workgroups share a CU and cover each other's waits.  3 (round 9, the launches that put one or two
-// workgroups on a CU and lose no co-resident one to the third stage: launch_lean, ConvTune::ring3_tiles / ring3_wgs): two units in flight, the wait in front of the barrier leaves the younger
-// one's copies outstanding (a counted vmcnt), the barrier is a bare s_barrier, and the copies of unit u + 2 go out in runs between the
-// MFMA groups of unit u.  Same MFMA order per accumulator, same epilogues: bit-identical to S = 2.
-// LEAN_RING_W (round 10, the k = 3 128-row tile without the folded second conv, whose three full stages would cost the CU its third
-// workgroup; ConvTune::ring3_window, ring3_window_tiles): a third stage for the WINDOW alone, 51.2 KB.  LDS holds three window
-// planes (each with its zero row) and behind them two slab sets; unit j of a tile (j = u - u_begin) uses window slot j % 3 and slab set
-// j % 2.  During unit j the slabs of unit j + 1 and then the window of unit j + 2 are issued; at the top of unit j + 1 the wave waits
-// with vmcnt(this wave's copies of ONE window run) -- loads return in order, so the slabs have landed and only the younger window stays
-// outstanding: the copy a unit waits for shrinks from window + slabs to the slabs.  Three units per trip (window slots are immediates);
-// the slab set alternates per unit, so the two sets' fragment addresses and M0 values are two register sets swapped once per trip.
-enum { LEAN_RING_W = 5 };   // (a value of S: three window planes + two slab sets)
-template <typename T, int TM, int KIND, bool RF, int EPI, bool SK, int S = 2>
-__global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const ConvKArgs a, const LeanGeom g) {
+// "the unit at the top of the ring has landed" with the younger copies left in flight: at most MUL x (this wave's window copies per
+// run) + FIX copies outstanding -- an immediate, chosen by a scalar switch; loads return in order, so anything else outstanding only
+// makes the wait stricter
+template <int NAW, int MUL, int FIX>
+__device__ __forceinline__ void lean_wait_keep(const unsigned wcnt) {
+  if (NAW >= 3 && wcnt == 3u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * MUL + FIX) : "memory");
+  else if (NAW >= 2 && wcnt == 2u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * MUL + FIX) : "memory");
+  else if (wcnt == 1u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MUL + FIX) : "memory");
+  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FIX) : "memory");
+}
+// the barrier that hands a stage over: my fragment reads of the stage about to be overwritten are complete (lgkmcnt), nothing about
+// the copy counter (a __syncthreads() fence would drain it again)
+__device__ __forceinline__ void lean_handover() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");   // (nothing of the next phase moves in front of the barrier)
+}
+
+template <typename T, int TM, int KIND, bool RF, int EPI, bool SK, LeanRing RING = LEAN_RING_2>
+__global__ __launch_bounds__(256, (LeanRingTraits<LeanShape<TM, KIND, RF>, RING>::MIN_WGS)) void conv_lean_kernel(const ConvKArgs a, const LeanGeom g) {
   using SH = LeanShape<TM, KIND, RF>;
-  constexpr bool RW = S == LEAN_RING_W;
-  static_assert(S == 2 || RW || (S == 3 && !SH::K4 && !SH::K7 && SH::NAW1 == 0), "three stages: the k = 3 and 1x1 kinds (one window run per plane)");
-  static_assert(!RW || (SH::K3 && SH::NAW1 == 0 && !RF), "window ring: k = 3 units (one plane, one window run), no folded second conv");
-  static_assert(!RW || 3 * std::max(SH::RINGW_BYTES, 4 * TM * 32 * (32 * ((EPI == LEAN_EPI_RES || EPI == LEAN_EPI_GN_RES) ? 4 : (int)sizeof(T)) + 16)) <= 160 * 1024,
+  using RT = LeanRingTraits<SH, RING>;
+  constexpr bool R3 = RING == LEAN_RING_3, RW = RING == LEAN_RING_W;
+  static_assert(RT::ok, "this ring is not for this shape (LeanRingTraits)");
+  static_assert(!RW || 3 * lean_lds_bytes<T, SH, RING>(lean_epi_res32(EPI)) <= 160 * 1024,
                 "window ring: three workgroups of it (ring or epilogue staging, whichever is larger) fit a CU's 160 KB of LDS");
   constexpr int TN = 1, WM = 2, WN = 2, NW = 4, TG = SH::TG, KC = SH::KC, NS = SH::NS, NSB = SH::NSB, NAW = SH::NAW;
   constexpr int BM = SH::BM, BN = SH::BN, STAGE = SH::STAGE_BYTES, PLANE = SH::PLANE_BYTES;
@@ -564,11 +624,7 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
   unsigned long long t_start = 0, t_pro = 0, t_loop = 0, t_tab = 0, t_dma = 0;
   GnStamp gst = {0ull, 0ull, 0ull, 0u};
   if (g.stamps) t_start = __builtin_amdgcn_s_memtime();
-  unsigned long long* kst_slot = nullptr;
-  if (a.kst) {   // timed-mode stamps (conv_fast_body)
-    kst_slot = a.kst + (size_t)(a.kst_step[1] & 2047) * a.kst_stride;
-    if (tid == 0 && bid == 0) kst_slot[0] = (unsigned long long)wall_clock64();
-  }
+  unsigned long long* const kst_slot = kst_begin(a, tid, bid);   // timed-mode stamps
   if (g.debug & 8) return;
   // (through the constant address space: a uniform, invariant address -- ONE s_load_dwordx8; as a plain global pointer it is a vector load + readfirstlane)
   typedef const __attribute__((address_space(4))) LeanTile* tile_cptr;
@@ -617,58 +673,57 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
   const unsigned m0_b = lds_base + (unsigned)(SH::B_OFF + wave * NSB * 1024);
   if (g.stamps) t_tab = __builtin_amdgcn_s_memtime();
 
+  // ---- the producer: four primitives, composed by every loop below (LDS offsets are literals at every call site) ----
   const unsigned wcnt0 = SH::NAW1 ? min(wcnt, (unsigned)SH::NAW0) : wcnt, wcnt1 = wcnt - wcnt0;
-  auto issue = [&](const int st) {   // (st is a literal at every call site)
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc) {
-      lean_dma_run<SH::NAW0>(xb + kc * kRowBytes, m0_win + (unsigned)(st * STAGE + kc * PLANE), wcnt0, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
-      if constexpr (SH::NAW1 > 0)
-        lean_dma_run<SH::NAW1>(xb + kc * kRowBytes, m0_win + (unsigned)(st * STAGE + kc * PLANE + SH::NAW0 * 1024), wcnt1, vw[NAW > 3 ? 3 : 0], vw[NAW > 4 ? 4 : 0], 0u);
-    }
-    if constexpr (SH::K7) {
-      // taps 0-3 of the chunk into stage 0, taps 4-6 into stage 1 with the chunk's window once more; the fourth slab of the second group
-      // is tap 4 again (conv_fast_body: "pointed at a valid one"): it meets the zero row
-      if (st == 0) {
-        lean_dma_all<4>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3]);
-        wb += (size_t)4 * slab_bytes;
-        return;
-      }
-      lean_dma_all<4>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3] - 3u * slab_bytes);
-    } else {
-      lean_dma_all<NSB>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3]);
-    }
-    pc += KC;
-    xb += KC * kRowBytes;
-    wb += SH::K7 ? (size_t)3 * slab_bytes : (size_t)KC * chunk_w;
+  auto copy_window = [&](const int kc, const unsigned off) {   // this wave's run(s) of the window of chunk pc + kc into the plane at LDS offset off
+    lean_dma_run<SH::NAW0>(xb + kc * kRowBytes, m0_win + off, wcnt0, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
+    if constexpr (SH::NAW1 > 0) lean_dma_run<SH::NAW1>(xb + kc * kRowBytes, m0_win + off + (unsigned)(SH::NAW0 * 1024), wcnt1, vw[NAW > 3 ? 3 : 0], vw[NAW > 4 ? 4 : 0], 0u);
+  };
+  auto copy_slabs = [&](const unsigned m0v, const unsigned v3) {   // this wave's pieces of the slabs at the weight cursor to the M0 value m0v
+    lean_dma_all<NSB>(wb, m0v, vb[0], vb[1], vb[2], v3);
+  };
+  auto next_window = [&](const int n) {   // the window cursor, n chunks on
+    pc += n;
+    xb += n * kRowBytes;
     if (pc == csw) {   // the concatenated input's second tensor from here on
       xb = a.x2 - kBias;
       window_offsets(ldb2);
     }
   };
-  // window ring: the two halves of issue(), with cursors of their own -- the window runs one unit ahead of the slabs, so the switch to the
-  // second input tensor follows the window that is being issued (pc counts windows), the weight pointer the slabs
-  constexpr unsigned kSlabs0 = (unsigned)(3 * PLANE - SH::B_OFF);   // slab set 0 behind the three planes, relative to m0_b / b_ad
-  auto issue_window = [&](const int slot) {   // (slot is a literal at every call site)
-    lean_dma_run<SH::NAW0>(xb, m0_win + (unsigned)(slot * PLANE), wcnt, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
-    pc += 1;
-    xb += kRowBytes;
-    if (pc == csw) {
-      xb = a.x2 - kBias;
-      window_offsets(ldb2);
+  auto next_weights = [&](const size_t bytes) { wb += bytes; };
+  // a whole unit into stage st of the staged rings
+  auto issue = [&](const int st) {
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) copy_window(kc, (unsigned)(st * STAGE + kc * PLANE));
+    if constexpr (SH::K7) {
+      // taps 0-3 of the chunk into stage 0, taps 4-6 into stage 1 with the chunk's window once more; the fourth slab of the second group
+      // is tap 4 again (conv_fast_body: "pointed at a valid one"): it meets the zero row
+      if (st == 0) {
+        copy_slabs(m0_b, vb[3]);
+        next_weights((size_t)4 * slab_bytes);
+        return;
+      }
+      copy_slabs(m0_b + (unsigned)(st * STAGE), vb[3] - 3u * slab_bytes);
+      next_weights((size_t)3 * slab_bytes);
+    } else {
+      copy_slabs(m0_b + (unsigned)(st * STAGE), vb[3]);
+      next_weights((size_t)KC * chunk_w);
     }
+    next_window(KC);
   };
-  auto issue_slabs = [&](const unsigned m0v) {
-    lean_dma_all<NSB>(wb, m0v, vb[0], vb[1], vb[2], vb[3]);
-    wb += (size_t)chunk_w;
-  };
+  // window ring: the window runs one unit ahead of the slabs, so the switch to the second input tensor follows the window that is being
+  // issued (pc counts windows), the weight pointer the slabs
+  auto issue_window = [&](const int slot) { copy_window(0, (unsigned)(slot * PLANE)); next_window(1); };
+  auto issue_slabs = [&](const unsigned m0v) { copy_slabs(m0v, vb[3]); next_weights((size_t)chunk_w); };
+  const bool second_unit = tl.u_begin + 1 < tl.u_end && !(g.debug & 16);
   if constexpr (RW) {       // window(u0), slabs(u0), window(u0 + 1)
     issue_window(0);
-    issue_slabs(m0_b + kSlabs0);
-    if (tl.u_begin + 1 < tl.u_end && !(g.debug & 16)) issue_window(1);
+    issue_slabs(m0_b + (unsigned)(RT::SLABS0 - SH::B_OFF));
+    if (second_unit) issue_window(1);
   } else {
     issue(0);
-    if constexpr (S == 3) {   // two units in flight from the start
-      if (tl.u_begin + 1 < tl.u_end && !(g.debug & 16)) issue(1);
+    if constexpr (R3) {     // two units in flight from the start
+      if (second_unit) issue(1);
     }
   }
   if (g.stamps) t_dma = __builtin_amdgcn_s_memtime();
@@ -688,92 +743,13 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
   };
   if constexpr (!RF) fetch_cols();
 
-  if constexpr (LN) {
-    // folded PreNorm LayerNorm (ConvLayer::ln_s): channel mean and rstd of this tile's rows, under the latency of the first unit's copies
-    // (conv_fast_body's prologue block, unchanged arithmetic)
-    constexpr int TPR = NW * 64 / BM;                       // threads per row (2 or 4)
-    constexpr int EPV = 16 / (int)sizeof(T);
-    const int row = tid / TPR, part = tid - row * TPR;
-    const int C = a.C1, nvec = C / EPV;
-    const char* src = a.x1 + (size_t)min(m0 + row, M - 1) * C * sizeof(T);
-    float sm = 0.f, sq = 0.f;
-    const float2* rs = a.ln_rowstat ? reinterpret_cast<const float2*>(a.ln_rowstat) + (size_t)min(m0 + row, M - 1) * (C >> 5) : nullptr;
-    auto reduce_tpr = [&](float v) {
-#pragma unroll
-      for (int o = 1; o < TPR; o <<= 1) v += __shfl_xor(v, o);
-      return v;
-    };
-    if (rs) {
-      const int nblk = C >> 5;
-      for (int k0 = part; k0 < nblk; k0 += TPR * 4) {
-        float2 pr[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) pr[u] = rs[min(k0 + u * TPR, nblk - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (k0 + u * TPR < nblk) sm += pr[u].x;
-      }
-      const float mean = reduce_tpr(sm) / (float)C;
-      for (int k0 = part; k0 < nblk; k0 += TPR * 4) {
-        float2 pr[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) pr[u] = rs[min(k0 + u * TPR, nblk - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (k0 + u * TPR < nblk) {
-            const float d = pr[u].x * (1.0f / 32.0f) - mean;
-            sq += fmaf(32.0f * d, d, pr[u].y);
-          }
-      }
-      sm = mean;
-    } else {
-      float mean = 0.f;
-#pragma unroll 1
-      for (int pass = 0; pass < 2; ++pass) {
-        for (int v0 = part; v0 < nvec; v0 += TPR * 8) {
-          uint4 q[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int v = v0 + u * TPR;
-            q[u] = *reinterpret_cast<const uint4*>(src + (size_t)min(v, nvec - 1) * 16);
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            if (v0 + u * TPR >= nvec) continue;
-            const unsigned w4[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if (sizeof(T) == 4) {
-                const float f = __uint_as_float(w4[e]);
-                if (pass == 0) sm += f;
-                else sq = fmaf(f - mean, f - mean, sq);
-              } else {
-                const float f0 = __uint_as_float(w4[e] << 16), f1 = __uint_as_float(w4[e] & 0xffff0000u);
-                if (pass == 0) sm += f0 + f1;
-                else sq = fmaf(f0 - mean, f0 - mean, fmaf(f1 - mean, f1 - mean, sq));
-              }
-            }
-          }
-        }
-        if (pass == 0) mean = reduce_tpr(sm) / (float)C;
-      }
-      sm = mean;
-    }
-    sq = reduce_tpr(sq);
-    if (part == 0) {
-      float* st = reinterpret_cast<float*>(smem + g.ln_off);
-      st[2 * row] = sm;
-      st[2 * row + 1] = rsqrtf(sq / (float)C + 1e-5f);
-    }
-  }
+  if constexpr (LN) ln_row_stats<T, BM, NW * 64>(a, reinterpret_cast<float*>(smem + g.ln_off), m0, M, tid);   // folded PreNorm LayerNorm (conv_device.h)
 
   // ---- everything below runs under the first copies' latency ----
-  // zero rows (one behind every plane of every stage): S x KC x 16 dwords
-  if constexpr (RW) {   // (three planes back to back)
-    if (tid < 3 * 16) reinterpret_cast<unsigned*>(smem + (tid >> 4) * PLANE + SH::ZERO_OFF)[tid & 15] = 0u;
-  } else if (tid < S * KC * 16) {
+  // zero rows (one behind every plane of every stage; the window ring's planes lie back to back): STAGES x KC x 16 dwords
+  if (tid < RT::STAGES * KC * 16) {
     const int st = tid / (KC * 16), rem = tid - st * (KC * 16);
-    reinterpret_cast<unsigned*>(smem + st * STAGE + (rem >> 4) * PLANE + SH::ZERO_OFF)[rem & 15] = 0u;
+    reinterpret_cast<unsigned*>(smem + st * (RW ? SH::B_OFF : STAGE) + (rem >> 4) * PLANE + SH::ZERO_OFF)[rem & 15] = 0u;
   }
   // fragment addresses of this lane (stage 0, plane 0): A[i][tap][k-half], B[k-half]; stage / plane / slab offsets are immediates
   const int kh = lane >> 5;
@@ -859,42 +835,27 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
   // (`if (u + 1 >= u_end) break;`) hipcc gives the accumulators different registers on the two paths and copies all of them -- 32 to 64
   // v_mov plus s_nop per unit -- whenever registers get tight (the folded second conv's variant: 168 VGPRs and spills).
   int u = tl.u_begin;
-  if constexpr (S == 3) {
-    // ---- three stages (unit u in stage (u - u_begin) % 3): units u and u + 1 are in flight at the top of every step ----
+  if constexpr (R3 || RW) {
+    // ---- the three-unit rings: ONE loop, two policies (what lies where, what is copied behind which MFMA group, what a wait keeps) ----
     constexpr int NG = NS + (RF ? 1 : 0);   // MFMA groups of a unit (a tap or a chunk each; the folded second conv's last)
-    constexpr int NP = KC + 1;              // copy runs of a unit: one window run per plane, then the slabs
-    auto frag = [&](const int st, const int q, uint4 (&af)[2][TM], uint4 (&bf)[2]) {   // fragments of group q (q = NS: centre tap x fourth slab)
-      const int kc = q < NS ? q / TG : 0, t = q < NS ? q % TG : 1;
+    // the MFMA chain of one unit, group by group: window fragments at LDS offset woff, slab fragments at bx + boff (q = NS: centre tap x
+    // fourth slab).  The fragments of group q + 1 are requested in front of the MFMAs of group q (the copies are a compiler-level memory
+    // barrier: what is to overlap them has to stand in front of them); behind the MFMAs of group q, where on(q), goes copy(q).
+    auto step = [&](const unsigned woff, const unsigned (&bx)[2], const unsigned boff, auto&& on, auto&& copy) {
+      auto frag = [&](const int q, uint4 (&af)[2][TM], uint4 (&bf)[2]) {
+        const int kc = q < NS ? q / TG : 0, t = q < NS ? q % TG : 1;
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
+        for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) af[ks][i] = lean_lds16(a_ad[i][t][ks] + (unsigned)(st * STAGE + kc * PLANE));
-        bf[ks] = lean_lds16(b_ad[ks] + (unsigned)(st * STAGE + q * 1024));
-      }
-    };
-    auto piece = [&](const int st, const int p) {   // run p of the next unit to copy into stage st (issue(), in pieces)
-      if (p < KC) {
-        lean_dma_run<SH::NAW0>(xb + p * kRowBytes, m0_win + (unsigned)(st * STAGE + p * PLANE), wcnt, vw[0], vw[NAW > 1 ? 1 : 0], vw[NAW > 2 ? 2 : 0]);
-      } else {
-        lean_dma_all<NSB>(wb, m0_b + (unsigned)(st * STAGE), vb[0], vb[1], vb[2], vb[3]);
-        pc += KC;
-        xb += KC * kRowBytes;
-        wb += (size_t)KC * chunk_w;
-        if (pc == csw) {
-          xb = a.x2 - kBias;
-          window_offsets(ldb2);
+          for (int i = 0; i < TM; ++i) af[ks][i] = lean_lds16(a_ad[i][t][ks] + woff + (unsigned)(kc * PLANE));
+          bf[ks] = lean_lds16(bx[ks] + boff + (unsigned)(q * 1024));
         }
-      }
-    };
-    // the MFMA chain of the unit in stage st, group by group; the fragments of group q + 1 are requested in front of the MFMAs of group q
-    // (the copies are a compiler-level memory barrier: what is to overlap them has to stand in front of them), and behind the MFMAs of
-    // group q goes run q of the unit that is copied into stage sti (pf; what is left of the runs behind the last group)
-    auto step = [&](const int st, const int sti, const bool pf) {
+      };
       uint4 af[2][2][TM], bf[2][2];
-      frag(st, 0, af[0], bf[0]);
+      frag(0, af[0], bf[0]);
 #pragma unroll
       for (int q = 0; q < NG; ++q) {
-        if (q + 1 < NG) frag(st, q + 1, af[(q + 1) & 1], bf[(q + 1) & 1]);
+        if (q + 1 < NG) frag(q + 1, af[(q + 1) & 1], bf[(q + 1) & 1]);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -904,136 +865,81 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
             }
             mfma_step<T>(acc[i][0], af[q & 1][ks][i], bf[q & 1][ks]);
           }
-        if (pf) {
+        if (on(q)) {
           __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int p = 0; p < NP; ++p)
-            if (p == q || (q == NG - 1 && p > q)) piece(sti, p);
+          copy(q);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     };
-    // "unit u has landed" with unit u + 1 left in flight: at most the copies this wave issued for ONE unit outstanding (KC wcnt + NSB: an
-    // immediate, chosen by a scalar switch; loads return in order, so anything else outstanding only makes the wait stricter)
-    auto wait_keep_one = [&]() {
-      if (NAW >= 3 && wcnt == 3u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * KC + NSB) : "memory");
-      else if (NAW >= 2 && wcnt == 2u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * KC + NSB) : "memory");
-      else if (wcnt == 1u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KC + NSB) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSB) : "memory");
+    // Window ring: the two slab sets.  A holds the units at positions 0 and 2 of a trip, B the one at position 1; a trip is three units
+    // and the set alternates per unit, so the sets' fragment addresses and M0 values are two register sets swapped once per trip.
+    constexpr unsigned kSlabs0 = (unsigned)(RT::SLABS0 - SH::B_OFF);   // slab set 0, relative to m0_b / b_ad
+    unsigned bA[2] = {b_ad[0] + kSlabs0, b_ad[1] + kSlabs0}, bB[2] = {bA[0] + (unsigned)SH::SLAB_BYTES, bA[1] + (unsigned)SH::SLAB_BYTES};
+    unsigned mA = m0_b + kSlabs0, mB = mA + (unsigned)SH::SLAB_BYTES;
+    // The unit at position pos of a trip (a literal); n1 / n2: the next unit / the one after it exists and is to be copied.
+    //   full ring: unit j in stage j % 3; behind group q goes run q of the unit after the next (one window run per plane, then the
+    //     slabs; what is left of the runs behind the last group); the wait keeps one whole unit: KC wcnt + NSB copies.
+    //   window ring: at the top of unit j the copies in flight are, oldest first, ... slabs(j), window(j + 1); behind group 0 go the
+    //     slabs of the next unit (into the other set), behind group 1 the window of the unit after it (into slot pos + 2) -- slabs
+    //     first, so that the wait may keep exactly the window: wcnt copies.
+    auto unit = [&](const int pos, const bool n1, const bool n2) {
+      if constexpr (R3) {
+        step((unsigned)(pos * STAGE), b_ad, (unsigned)(pos * STAGE), [&](const int) { return n2; }, [&](const int q) {
+          constexpr int NP = KC + 1;   // copy runs of a unit
+          const int st = (pos + 2) % 3;
+#pragma unroll
+          for (int p = 0; p < NP; ++p)
+            if (p == q || (q == NG - 1 && p > q)) {
+              if (p < KC) {
+                copy_window(p, (unsigned)(st * STAGE + p * PLANE));
+              } else {
+                copy_slabs(m0_b + (unsigned)(st * STAGE), vb[3]);
+                next_weights((size_t)KC * chunk_w);
+                next_window(KC);
+              }
+            }
+        });
+      } else {
+        step((unsigned)(pos * PLANE), pos == 1 ? bB : bA, 0u, [&](const int q) { return (q == 0 && n1) || (q == 1 && n2); }, [&](const int q) {
+          if (q == 0) issue_slabs(pos == 1 ? mA : mB);
+          else issue_window((pos + 2) % 3);
+        });
+      }
     };
-    // the barrier that hands a stage over: my fragment reads of the stage about to be overwritten are complete (lgkmcnt), nothing about
-    // the copy counter (a __syncthreads() fence would drain it again)
-    auto handover = [&]() {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");   // (nothing of the next phase moves in front of the barrier)
-    };
-    // Three units per trip and ONE loop exit (see below); every wait inside the loop has a younger unit to leave in flight
+    auto wait_keep = [&]() { lean_wait_keep<NAW, R3 ? KC : 1, R3 ? NSB : 0>(wcnt); };
+    // Three units per trip (stages and window slots are immediates) and ONE loop exit (see above); inside the loop every unit has a
+    // younger one to leave in flight
     while (u + 3 < u_end) {
-      wait_keep_one(); handover();
-      step(0, 2, copies);
-      wait_keep_one(); handover();
-      step(1, 0, copies);
-      wait_keep_one(); handover();
-      step(2, 1, copies && u + 4 < u_end);
+      wait_keep(); lean_handover();
+      unit(0, copies, copies);
+      wait_keep(); lean_handover();
+      unit(1, copies, copies);
+      wait_keep(); lean_handover();
+      unit(2, copies, copies && u + 4 < u_end);
       u += 3;
+      if constexpr (RW) { const unsigned t0 = bA[0], t1 = bA[1], tm = mA; bA[0] = bB[0]; bA[1] = bB[1]; mA = mB; bB[0] = t0; bB[1] = t1; mB = tm; }
     }
     // the last one to three units (workgroup-uniform: every wave meets the same barriers); the very last wait drains the counter
     const int left = u_end - u;
     if (left >= 1) {
-      if (left >= 2) wait_keep_one(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      handover();
-      step(0, 2, copies && left >= 3);
+      if (left >= 2) wait_keep(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      lean_handover();
+      unit(0, copies && left >= 2, copies && left >= 3);
     }
     if (left >= 2) {
-      if (left >= 3) wait_keep_one(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      handover();
-      step(1, 0, false);
+      if (left >= 3) wait_keep(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      lean_handover();
+      unit(1, copies && left >= 3, false);
     }
     if (left >= 3) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      handover();
-      step(2, 1, false);
+      lean_handover();
+      unit(2, false, false);
     }
     u = u_end;
   }
-  if constexpr (RW) {
-    // ---- window ring: at the top of unit j the copies in flight are, oldest first, ... slabs(j), window(j + 1) ----
-    constexpr int NG = NS;                  // MFMA groups of a unit: a tap each
-    // slab sets: A holds the units at positions 0 and 2 of a trip, B the one at position 1; a trip is three units, so they swap per trip
-    unsigned bA[2] = {b_ad[0] + kSlabs0, b_ad[1] + kSlabs0}, bB[2] = {bA[0] + (unsigned)SH::SLAB_BYTES, bA[1] + (unsigned)SH::SLAB_BYTES};
-    unsigned mA = m0_b + kSlabs0, mB = mA + (unsigned)SH::SLAB_BYTES;
-    auto frag = [&](const int ws, const unsigned (&bx)[2], const int q, uint4 (&af)[2][TM], uint4 (&bf)[2]) {   // window slot ws (a literal), slab set bx
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[ks][i] = lean_lds16(a_ad[i][q][ks] + (unsigned)(ws * PLANE));
-        bf[ks] = lean_lds16(bx[ks] + (unsigned)(q * 1024));
-      }
-    };
-    // the MFMA chain of the unit in window slot ws and slab set bx (the three-stage step, group by group); behind group 0 go the slabs
-    // of the next unit (into the other slab set, M0 value m0n), behind group 1 the window of the unit after it (into slot ws + 2):
-    // slabs first, so that the counted wait below may leave exactly the window outstanding
-    auto step = [&](const int ws, const unsigned (&bx)[2], const unsigned m0n, const bool slabs, const bool window) {
-      uint4 af[2][2][TM], bf[2][2];
-      frag(ws, bx, 0, af[0], bf[0]);
-#pragma unroll
-      for (int q = 0; q < NG; ++q) {
-        if (q + 1 < NG) frag(ws, bx, q + 1, af[(q + 1) & 1], bf[(q + 1) & 1]);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int i = 0; i < TM; ++i) mfma_step<T>(acc[i][0], af[q & 1][ks][i], bf[q & 1][ks]);
-        if ((q == 0 && slabs) || (q == 1 && window)) {
-          __builtin_amdgcn_sched_barrier(0);
-          if (q == 0) issue_slabs(m0n);
-          else issue_window((ws + 2) % 3);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    };
-    // "unit j has landed" with window(j + 1) left in flight: at most this wave's copies of ONE window run outstanding
-    auto wait_keep_window = [&]() {
-      if (NAW >= 3 && wcnt == 3u) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else if (NAW >= 2 && wcnt == 2u) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else if (wcnt == 1u) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    auto handover = [&]() {   // (the three-stage ring's: fragment reads complete, bare barrier, nothing about the copy counter)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    };
-    // Three units per trip and ONE loop exit; inside the loop every unit has a younger window to leave in flight
-    while (u + 3 < u_end) {
-      wait_keep_window(); handover();
-      step(0, bA, mB, copies, copies);
-      wait_keep_window(); handover();
-      step(1, bB, mA, copies, copies);
-      wait_keep_window(); handover();
-      step(2, bA, mB, copies, copies && u + 4 < u_end);
-      u += 3;
-      { const unsigned t0 = bA[0], t1 = bA[1], tm = mA; bA[0] = bB[0]; bA[1] = bB[1]; mA = mB; bB[0] = t0; bB[1] = t1; mB = tm; }
-    }
-    // the last one to three units (workgroup-uniform); the very last wait drains the counter
-    const int left = u_end - u;
-    if (left >= 1) {
-      if (left >= 2) wait_keep_window(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      handover();
-      step(0, bA, mB, copies && left >= 2, copies && left >= 3);
-    }
-    if (left >= 2) {
-      if (left >= 3) wait_keep_window(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      handover();
-      step(1, bB, mA, copies && left >= 3, false);
-    }
-    if (left >= 3) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      handover();
-      step(2, bA, mB, false, false);
-    }
-    u = u_end;
-  }
+  // ---- two stages: two units per trip, no fragment look-ahead, every unit drains the copy counter in front of a __syncthreads() ----
   while (u + 1 < u_end) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // my copies of unit u have landed
     __syncthreads();                                   // everybody's have; everybody is done with unit u - 1: its stage is free
@@ -1053,59 +959,12 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
   if (g.stamps) t_loop = __builtin_amdgcn_s_memtime();
   __syncthreads();   // every wave has consumed the last ring stage: LDS is free for the output transpose
 
-  if constexpr (SK) {
-    // split-K (conv_fast_body): park the partial tile write-through, count in, the last slice sums all slices in slice order
-    int* s_last_p = reinterpret_cast<int*>(smem);
-    constexpr int TILE = BM * BN;
-    const int sk_tile = tl.sk_tile, sk_k = tl.sk_k;
-    float* mine = a.sk_part + ((size_t)sk_tile * a.ksplit + sk_k) * TILE;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        __hip_atomic_store(&mine[((wave * TM + i) * 16 + r) * 64 + lane], acc[i][0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned old = atomicAdd(a.sk_count + sk_tile, 1u);
-      const int last = old == (unsigned)(a.ksplit - 1);
-      *s_last_p = last;
-      if (last) a.sk_count[sk_tile] = 0u;
-    }
-    __syncthreads();
-    const int is_last = *s_last_p;
-    __syncthreads();
-    if (!is_last) return;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.0f;
-    for (int o = 0; o < a.ksplit; ++o) {
-      const float* other = a.sk_part + ((size_t)sk_tile * a.ksplit + o) * TILE;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          acc[i][0][r] += __hip_atomic_load(&other[((wave * TM + i) * 16 + r) * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+  if constexpr (SK) {   // park the partial tile; the last slice to arrive sums all slices and carries on into the epilogue
+    if (!splitk_park_and_sum<TM, TN, NW>(a, acc, smem, tl.sk_tile, tl.sk_k, wave, lane, tid)) return;
   }
-  if constexpr (LN) {   // conv(LN(x)) = rstd_r * (acc - mean_r * s_n)
-    const float* st = reinterpret_cast<const float*>(smem + g.ln_off);
-    const int col = n0 + wn * 32 + (lane & 31);
-    const float sn = col < a.n ? a.ln_s[col] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const float2 ms = *reinterpret_cast<const float2*>(st + 2 * row);
-        acc[i][0][r] = ms.y * fmaf(-ms.x, sn, acc[i][0][r]);
-      }
-  }
+  if constexpr (LN) ln_apply<TM, TN>(a, acc, reinterpret_cast<const float*>(smem + g.ln_off), wm * TM * 32, n0 + wn * 32, lane);
   {
-    constexpr int WREG = TM * 32 * (32 * (int)sizeof(T) + 16);
-    constexpr int WREG32 = TM * 32 * (32 * 4 + 16);
-    constexpr int wreg = (EPI == LEAN_EPI_RES || EPI == LEAN_EPI_GN_RES) ? WREG32 : WREG;
+    constexpr int wreg = lean_wave_staging<T, TM>(lean_epi_res32(EPI));
     char* wl = smem + (size_t)wave * wreg;
     const int mw = m0 + wm * TM * 32, cw = n0 + wn * 32;
     if (!(g.debug & 4)) {
@@ -1132,17 +991,9 @@ __global__ __launch_bounds__(256, S == 3 ? 2 : 3) void conv_lean_kernel(const Co
       a.y[0] = 1;   // tuning aid: keep the accumulators live, store nothing
     }
   }
-  if (kst_slot) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0 && ((bid & 7) == 0 || bid + 8 >= (unsigned)g.grid)) atomicMin(kst_slot + 1, ~(unsigned long long)wall_clock64());
-  }
+  kst_end(kst_slot, tid, bid, g.grid);
   if (g.stamps) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-    if (tid == 0) {
-      unsigned long long* o = g.stamps + (size_t)bid * 8;
-      o[0] = t_start; o[1] = t_pro; o[2] = t_loop; o[3] = t_end; o[4] = t_tab; o[5] = t_dma;
-      o[6] = (unsigned long long)(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | ((4 - 1) << 11)) & 0xf);   // HW_REG_XCC_ID[3:0]
+    if (unsigned long long* o = stamp_phases(g.stamps, tid, bid, t_start, t_pro, t_loop, t_tab, t_dma)) {
       // fused GroupNorm apply (wave 0): ticks from the loop's end to statistics published / first poll back / all gathered (16 bits each, x 4), polls
       const auto d4 = [&](unsigned long long t) { return t > t_loop ? (unsigned long long)min((unsigned long long)0xffff, (t - t_loop) >> 2) : 0ull; };
       o[7] = d4(gst.t_pub) | (d4(gst.t_first) << 16) | (d4(gst.t_done) << 32) | ((unsigned long long)min(gst.polls, 0xffffu) << 48);
@@ -1342,90 +1193,88 @@ static const LeanTile* lean_tile_table(const ConvKArgs& a, const FastGeom& gm, i
   return (LeanTile*)d;
 }
 
-template <typename T, int TM, int KIND, bool RF, int EPI, bool SK, int S = 2>
-static hipError_t launch_lean_kernel(const ConvKArgs& a, const LeanGeom& g, size_t lds, hipStream_t s) {
-  auto kern = conv_lean_kernel<T, TM, KIND, RF, EPI, SK, S>;
+// one instantiation: its dynamic LDS (lean_lds_bytes) and the place of its LayerNorm table are its own
+template <typename T, int TM, int KIND, bool RF, int EPI, bool SK, LeanRing RING>
+static hipError_t launch_lean_kernel(const ConvKArgs& a, LeanGeom g, hipStream_t s) {
+  using SH = LeanShape<TM, KIND, RF>;
+  constexpr bool LN = KIND == LEAN_K1_LN;
+  auto kern = conv_lean_kernel<T, TM, KIND, RF, EPI, SK, RING>;
   static bool lds_opt_in = false;
   if (!lds_opt_in) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     lds_opt_in = true;
   }
+  g.ln_off = LN ? lean_ln_off<T, SH, RING>(lean_epi_res32(EPI)) : 0;
+  constexpr size_t lds = lean_lds_bytes<T, SH, RING>(lean_epi_res32(EPI), LN);
   hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), lds, s, a, g);
   __atomic_fetch_add(&g_lean_launches[KIND], 1ll, __ATOMIC_RELAXED);
-  if (S == 3) __atomic_fetch_add(&g_lean_launches[5], 1ll, __ATOMIC_RELAXED);   // (slot 5: launches on the three-stage ring, of any kind)
-  if (S == LEAN_RING_W) __atomic_fetch_add(&g_lean_launches[6], 1ll, __ATOMIC_RELAXED);   // (slot 6: launches on the window ring)
+  // (slot 5: launches on the three-stage ring, of any kind; slot 6: launches on the window ring)
+  if (LeanRingTraits<SH, RING>::COUNT_SLOT) __atomic_fetch_add(&g_lean_launches[LeanRingTraits<SH, RING>::COUNT_SLOT], 1ll, __ATOMIC_RELAXED);
   return hipGetLastError();
 }
-
-// The tile the window ring is built for: k = 3 on 128 x 64 without the folded second conv.  (The 64 x 64 tile takes the full three-stage
-// ring; with the fold it would fit the window ring -- 47.2 KB -- but measured 0.3 % slower per decode on it and was taken out again; with the
-// fold on 128 x 64, and for 1x1 convs, three workgroups of the window ring do not fit a CU: profiles/r10_ring_window.md.)
-template <int TM, int KIND, bool RF>
-struct LeanRingW { static constexpr bool ok = KIND == LEAN_K3 && TM == 2 && !RF; };
-
-// lean_ring3_wgs_per_cu for the window-ring kernels: 0 when the query fails (no fused GroupNorm launch takes the window ring then)
-template <typename T>
-static int lean_ringw_wgs_per_cu() {
-  constexpr int TM = 2;
-  static int cached = -1;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  if (cached >= 0) return cached;
-  using SH = LeanShape<TM, LEAN_K3, false>;
-  int worst = 1 << 30;
-  auto ask = [&](const void* fn, bool res32) {
-    const size_t lds = std::max((size_t)SH::RINGW_BYTES, (size_t)4 * TM * 32 * (32 * (res32 ? 4 : sizeof(T)) + 16));
-    int n = 0;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds) != hipSuccess) {
-      (void)hipGetLastError();
-      n = 0;
-    }
-    worst = std::min(worst, n);
-  };
-  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN, false, LEAN_RING_W>), false);
-  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN, true, LEAN_RING_W>), false);
-  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, false, LEAN_RING_W>), true);
-  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, true, LEAN_RING_W>), true);
-  cached = worst;
-  return cached;
+// ... on the ring the launcher chose, where the shape may take it (LeanRingTraits::ok; the launcher asks for no other)
+template <typename T, int TM, int KIND, bool RF, int EPI, bool SK>
+static hipError_t launch_lean_ring(LeanRing ring, const ConvKArgs& a, const LeanGeom& g, hipStream_t s) {
+  using SH = LeanShape<TM, KIND, RF>;
+  if constexpr (LeanRingTraits<SH, LEAN_RING_W>::ok) {
+    if (ring == LEAN_RING_W) return launch_lean_kernel<T, TM, KIND, RF, EPI, SK, LEAN_RING_W>(a, g, s);
+  }
+  if constexpr (LeanRingTraits<SH, LEAN_RING_3>::ok) {
+    if (ring == LEAN_RING_3) return launch_lean_kernel<T, TM, KIND, RF, EPI, SK, LEAN_RING_3>(a, g, s);
+  }
+  return launch_lean_kernel<T, TM, KIND, RF, EPI, SK, LEAN_RING_2>(a, g, s);
 }
 
-// Workgroups of the three-stage fused GroupNorm kernels of this tile that fit one CU (occupancy query with their dynamic LDS; the worst
-// of the epilogues), asked once.  0 when the query fails: no fused GroupNorm launch takes the three-stage ring then.
-template <typename T, int TM, bool RF>
-static int lean_ring3_wgs_per_cu() {
+// workgroups of a kernel that fit one CU with this much dynamic LDS; 0 when the query fails
+static int lean_ask_wgs(const void* fn, size_t lds) {
+  int n = 0;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    n = 0;
+  }
+  return n;
+}
+// Workgroups of the k = 3 fused GroupNorm kernels of this tile and ring that fit one CU (occupancy query with their dynamic LDS; the
+// worst of the epilogues), asked once.  0 when the query fails: no fused GroupNorm launch takes a deeper ring then.
+template <typename T, int TM, bool RF, LeanRing RING>
+static int lean_gn_wgs_per_cu() {
   static int cached = -1;
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
   if (cached >= 0) return cached;
   using SH = LeanShape<TM, LEAN_K3, RF>;
   int worst = 1 << 30;
-  auto ask = [&](const void* fn, bool res32) {
-    const size_t lds = std::max((size_t)3 * SH::STAGE_BYTES, (size_t)4 * TM * 32 * (32 * (res32 ? 4 : sizeof(T)) + 16));
-    int n = 0;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds) != hipSuccess) {
-      (void)hipGetLastError();
-      n = 0;
-    }
-    worst = std::min(worst, n);
+  auto ask = [&](auto epi, auto sk) {
+    constexpr int EPI = decltype(epi)::value;
+    worst = std::min(worst, lean_ask_wgs(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, RF, EPI, decltype(sk)::value, RING>),
+                                         lean_lds_bytes<T, SH, RING>(lean_epi_res32(EPI))));
   };
-  ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, RF, LEAN_EPI_GN, false, 3>), false);
-  if constexpr (!RF) {
-    ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN, true, 3>), false);
-    ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, false, 3>), true);
-    ask(reinterpret_cast<const void*>(conv_lean_kernel<T, TM, LEAN_K3, false, LEAN_EPI_GN_RES, true, 3>), true);
+  using GN = std::integral_constant<int, LEAN_EPI_GN>;
+  using GN_RES = std::integral_constant<int, LEAN_EPI_GN_RES>;
+  ask(GN(), std::false_type());
+  if constexpr (!RF) {   // (the folded second conv: fused GroupNorm without residual, never split)
+    ask(GN(), std::true_type());
+    ask(GN_RES(), std::false_type());
+    ask(GN_RES(), std::true_type());
   }
   cached = worst;
   return cached;
+}
+// A fused GroupNorm launch spins on its peers: unet_plan.cpp's residency rule (few_tiles) with the slots of the kernel it is to run on --
+// the launch as a whole, or an item's tiles plus two dispatch groups, within the share of the chip a batch part can count on.
+static bool lean_gn_resident(const ConvKArgs& a, const FastGeom& gm, int BM, int wgs_per_cu) {
+  const long slots = (long)wgs_per_cu * a.tune->ring3_cu_share;
+  const long item_tiles = (long)((a.L_rows + BM - 1) / BM + 1) * gm.ntn;
+  return gm.grid <= slots || item_tiles + 16 * gm.ntn <= slots;
 }
 
 // The lean kernel for the launch launch_fast_cfg<T, 2, 2, TM, 1, TG, KC, 2, NA, RF> has decided (a, gm: its final arguments).
 // *launched stays false where this launch is outside the lean kernel's shapes (the caller launches conv_fast_kernel).
 template <typename T, int TM, int TG, int KC, bool RF>
 static hipError_t launch_lean(const ConvKArgs& a, const FastGeom& gm, int M, hipStream_t s, bool* launched) {
+#define LDC_LEAN_GO(KIND_, EPI_, SK_) return launch_lean_ring<T, TM, KIND_, RF, EPI_, SK_>(ring, a, g, s)
   *launched = false;
   if constexpr (kW8 || kFp8 || !((TG == 3 && KC == 1) || (TG == 1 && KC == 2) || (TG == 4 && KC == 1 && sizeof(T) == 2)) || (RF && TG != 3)) {
     return hipSuccess;
@@ -1448,16 +1297,15 @@ static hipError_t launch_lean(const ConvKArgs& a, const FastGeom& gm, int M, hip
     if (max_rows > (k4 ? SH4::PLANE_ROWS : SH7::PLANE_ROWS)) return hipSuccess;   // (odd input lengths: conv_fast_kernel)
     LeanGeom g;
     g.tiles = tiles; g.stamps = gm.stamps; g.debug = gm.debug; g.grid = gm.grid; g.ln_off = 0;
-    const size_t epi_bytes = (size_t)4 * TM * 32 * (32 * (res ? 4 : sizeof(T)) + 16);
-    const size_t lds = std::max((size_t)2 * (k4 ? SH4::STAGE_BYTES : SH7::STAGE_BYTES), epi_bytes);
+    const LeanRing ring = LEAN_RING_2;
     *launched = true;
     if (k4) {
-      if (res) return launch_lean_kernel<T, TM, LEAN_K4S2, false, LEAN_EPI_RES, false>(a, g, lds, s);
-      if (sk) return launch_lean_kernel<T, TM, LEAN_K4S2, false, LEAN_EPI_PLAIN, true>(a, g, lds, s);
-      return launch_lean_kernel<T, TM, LEAN_K4S2, false, LEAN_EPI_PLAIN, false>(a, g, lds, s);
+      if (res) LDC_LEAN_GO(LEAN_K4S2, LEAN_EPI_RES, false);
+      if (sk) LDC_LEAN_GO(LEAN_K4S2, LEAN_EPI_PLAIN, true);
+      LDC_LEAN_GO(LEAN_K4S2, LEAN_EPI_PLAIN, false);
     }
-    if (res) return launch_lean_kernel<T, TM, LEAN_K7, false, LEAN_EPI_RES, false>(a, g, lds, s);
-    return launch_lean_kernel<T, TM, LEAN_K7, false, LEAN_EPI_PLAIN, false>(a, g, lds, s);
+    if (res) LDC_LEAN_GO(LEAN_K7, LEAN_EPI_RES, false);
+    LDC_LEAN_GO(LEAN_K7, LEAN_EPI_PLAIN, false);
   } else {
     constexpr bool K3 = TG == 3;
     const ConvTune* tn = a.tune;
@@ -1484,51 +1332,27 @@ static hipError_t launch_lean(const ConvKArgs& a, const FastGeom& gm, int M, hip
     if (max_rows > SH0::PLANE_ROWS) return hipSuccess;   // (strided / dilated windows: conv_fast_kernel)
     LeanGeom g;
     g.tiles = tiles; g.stamps = gm.stamps; g.debug = gm.debug; g.grid = gm.grid; g.ln_off = 0;
-    const size_t epi_bytes = (size_t)4 * TM * 32 * (32 * ((epi == LEAN_EPI_RES || epi == LEAN_EPI_GN_RES) ? 4 : sizeof(T)) + 16);
-    // round 9: the three-stage ring for the launches that put one or two workgroups on a CU (ConvTune::ring3_tiles; 0 = never), where
+    // The three-stage ring for the launches that put one or two workgroups on a CU (ConvTune::ring3_tiles; 0 = never), where
     // ConvTune::ring3_wgs workgroups of three stages still fit a CU's LDS: the third stage must not cost a co-resident workgroup.  With
     // two batch parts in flight the 128-row tiles (64.5 - 77 KB of ring: two per CU instead of three) lose more there than the loop
-    // gains -- +1.1 % per decode -- while the 64-row tiles (52.5 KB: still three) gain 2.3 % (profiles/r09_ring3.md).  A fused GroupNorm
-    // launch spins on its peers: it takes the ring only if unet_plan.cpp's residency rule (few_tiles) also holds with the slots of
-    // THIS kernel -- the launch as a whole, or an item's tiles plus two dispatch groups, within the share of the chip a batch part
-    // can count on.
-    const size_t lds3 = std::max((size_t)3 * SH0::STAGE_BYTES, epi_bytes) + (ln ? (size_t)SH0::BM * 8 + 16 : 0);
-    bool ring3 = tn && tn->ring3_tiles > 0 && gm.grid <= tn->ring3_tiles && (size_t)std::max(1, tn->ring3_wgs) * lds3 <= (size_t)160 * 1024 && !(gm.debug & 1);
-    if (ring3 && gn) {
-      const long slots = (long)lean_ring3_wgs_per_cu<T, TM, RF>() * tn->ring3_cu_share;
-      const long item_tiles = (long)((a.L_rows + SH0::BM - 1) / SH0::BM + 1) * gm.ntn;
-      ring3 = gm.grid <= slots || item_tiles + 16 * gm.ntn <= slots;
-    }
-    // round 10: where ring3_wgs workgroups of the full ring do NOT fit, the window ring (LEAN_RING_W: a third stage for the window
-    // alone) where ring3_wgs workgroups of IT fit -- the k = 3 128 x 64 tile (51.2 KB); ConvTune::ring3_window.  It costs no co-resident
-    // workgroup, so its grid threshold is its own (ConvTune::ring3_window_tiles, 608: the 600-tile launches gain more from it than the
-    // 304-tile ones, profiles/r10_ring_window.md); a fused GroupNorm launch under the same residency rule, with the occupancy of the
-    // window-ring kernels themselves.
-    bool ringw = false;
-    if constexpr (LeanRingW<TM, K3 ? LEAN_K3 : LEAN_K1, RF>::ok) {
-      const size_t ldsw = std::max((size_t)SH0::RINGW_BYTES, epi_bytes);
-      ringw = !ring3 && tn && tn->ring3_window && gm.grid <= tn->ring3_window_tiles &&
-              (size_t)std::max(1, tn->ring3_wgs) * lds3 > (size_t)160 * 1024 && (size_t)std::max(1, tn->ring3_wgs) * ldsw <= (size_t)160 * 1024 && !(gm.debug & 1);
-      if (ringw && gn) {
-        const long slots = (long)lean_ringw_wgs_per_cu<T>() * tn->ring3_cu_share;
-        const long item_tiles = (long)((a.L_rows + SH0::BM - 1) / SH0::BM + 1) * gm.ntn;
-        ringw = gm.grid <= slots || item_tiles + 16 * gm.ntn <= slots;
+    // gains -- +1.1 % per decode -- while the 64-row tiles (52.5 KB: still three) gain 2.3 % (profiles/r09_ring3.md).
+    // Where ring3_wgs workgroups of the full ring do NOT fit, the window ring where ring3_wgs workgroups of IT fit -- the k = 3
+    // 128 x 64 tile (51.2 KB); ConvTune::ring3_window.  It costs no co-resident workgroup, so its grid threshold is its own
+    // (ConvTune::ring3_window_tiles, 608: the 600-tile launches gain more from it than the 304-tile ones, profiles/r10_ring_window.md).
+    // A fused GroupNorm launch takes either only if it stays resident with the occupancy of that ring's kernels (lean_gn_resident).
+    const size_t cu_lds = (size_t)160 * 1024, wgs = (size_t)std::max(1, tn ? tn->ring3_wgs : 1);
+    const bool fits3 = wgs * lean_lds_bytes<T, SH0, LEAN_RING_3>(res32, ln) <= cu_lds;
+    LeanRing ring = LEAN_RING_2;
+    if (tn && !(gm.debug & 1)) {
+      if (tn->ring3_tiles > 0 && gm.grid <= tn->ring3_tiles && fits3 && (!gn || lean_gn_resident(a, gm, SH0::BM, lean_gn_wgs_per_cu<T, TM, RF, LEAN_RING_3>())))
+        ring = LEAN_RING_3;
+      if constexpr (LeanRingTraits<SH0, LEAN_RING_W>::ok) {
+        if (ring == LEAN_RING_2 && tn->ring3_window && gm.grid <= tn->ring3_window_tiles && !fits3 && wgs * lean_lds_bytes<T, SH0, LEAN_RING_W>(res32) <= cu_lds &&
+            (!gn || lean_gn_resident(a, gm, SH0::BM, lean_gn_wgs_per_cu<T, TM, false, LEAN_RING_W>())))
+          ring = LEAN_RING_W;
       }
     }
-    size_t lds = std::max(ringw ? (size_t)SH0::RINGW_BYTES : (size_t)(ring3 ? 3 : 2) * SH0::STAGE_BYTES, epi_bytes);
-    if (ln) {
-      g.ln_off = (int)((lds + 15) / 16 * 16);
-      lds = (size_t)g.ln_off + (size_t)SH0::BM * 8;
-    }
     *launched = true;
-#define LDC_LEAN_GO(KIND_, EPI_, SK_)                                                         \
-  do {                                                                                        \
-    if constexpr (LeanRingW<TM, KIND_, RF>::ok) {                                             \
-      if (ringw) return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, LEAN_RING_W>(a, g, lds, s); \
-    }                                                                                         \
-    if (ring3) return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, 3>(a, g, lds, s);       \
-    return launch_lean_kernel<T, TM, KIND_, RF, EPI_, SK_, 2>(a, g, lds, s);                  \
-  } while (0)
     if constexpr (K3) {
       if constexpr (RF) {
         LDC_LEAN_GO(LEAN_K3, LEAN_EPI_GN, false);

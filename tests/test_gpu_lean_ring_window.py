@@ -1,4 +1,4 @@
-"""Round 10: the window ring of the lean conv kernel (conv_lean.inc, S = LEAN_RING_W; options ring3_window, ring3_window_tiles).
+"""Round 10: the window ring of the lean conv kernel (conv_lean.inc, ring kind LEAN_RING_W; options ring3_window, ring3_window_tiles).
 
 Where three workgroups of the full three-stage ring do not fit a CU's LDS but three of the window ring do -- the k = 3 128 x 64 tile
 without the folded res_conv -- a launch of at most ring3_window_tiles workgroups keeps three WINDOW planes and two slab sets: the slabs of

@@ -589,13 +589,42 @@ def test_folded_layernorm_on_rows_with_a_large_mean():
     over rows read by the conv itself, Chan-merged (sum, M2) partials per 32-column block from the producing conv): rows with
     mean / std ~ 170 through the folded conv, against launch_ln_rows + a plain conv.  The fold's own rearrangement
     rstd * (W x - mean * s_n) loses log10(mean / std) digits of an fp32 accumulator, hence 2e-3 rather than 2e-5 at dc = 100
-    (the single-pass variance was off by 10 % there)."""
+    (the single-pass variance was off by 10 % there).
+    Both pipelined kernels take the row statistics, the LayerNorm apply and the split-K sum from the same functions (conv_device.h),
+    so the tests that hold one kernel against the other cannot see a mistake there: the fold runs on conv_fast_kernel (option
+    conv_lean 0) and on conv_lean_kernel (1), each against launch_ln_rows + a plain conv, and so does one split-K conv (B = 1,
+    L = 75, 1024 -> 1024, k = 3 on the 128 x 64 tile, both dtypes) against the generic kernel, with the bounds of
+    test_conv_fast_every_tile_shape_against_generic_kernel.  ldc_debug_lean_launches says which kernel ran."""
     import ctypes as C
     e = engine("r84", "f32")
     lib = L.load()
-    for dtype, dc, tol in ((L.LDC_F32, 0.0, 2e-5), (L.LDC_F32, 100.0, 2e-3), (L.LDC_BF16, 2.0, 3e-2)):
-        for C_, n_out in ((256, 384), (1024, 384)):
-            d = (C.c_double * 2)()
-            m = C.c_double()
-            L.check(lib.ldc_ln_fold_compare(e._ctx, dtype, 300, C_, n_out, dc, d, C.byref(m)))
-            assert m.value > 0.1 and d[0] < tol * m.value and d[1] < tol * m.value, (dtype, dc, C_, d[0], d[1], m.value)
+    K3, K1_LN = 0, 2                                     # ldc_debug_lean_launches: unit kinds (conv_lean.inc)
+
+    def lean_counts():
+        return [lib.ldc_debug_lean_launches(i) for i in range(7)]
+
+    try:
+        for lean in (0, 1):
+            e.set_option("conv_lean", lean)
+            for dtype, dc, tol in ((L.LDC_F32, 0.0, 2e-5), (L.LDC_F32, 100.0, 2e-3), (L.LDC_BF16, 2.0, 3e-2)):
+                for C_, n_out in ((256, 384), (1024, 384)):
+                    d = (C.c_double * 2)()
+                    m = C.c_double()
+                    before = lean_counts()
+                    L.check(lib.ldc_ln_fold_compare(e._ctx, dtype, 300, C_, n_out, dc, d, C.byref(m)))
+                    ran = [a - b for a, b in zip(lean_counts(), before)]
+                    print("ln fold", lean, dtype, dc, C_, d[0], d[1], m.value, ran)
+                    # (conv_lean 1: both folded convs on the lean kernel; 0: no lean launch at all)
+                    assert ran[K1_LN] == 2 if lean else sum(ran) == 0, (lean, dtype, C_, ran)
+                    assert m.value > 0.1 and d[0] < tol * m.value and d[1] < tol * m.value, (lean, dtype, dc, C_, d[0], d[1], m.value)
+            for dt, tol_out in ((L.LDC_F32, 1e-5), (L.LDC_BF16, 1.0 / 128)):
+                d, m, r = C.c_double(), C.c_double(), C.c_double()
+                before = lean_counts()
+                L.check(lib.ldc_conv_compare(e._ctx, dt, 1, 75, 1024, 0, 1024, 3, 1, 0, 1, 0, 0, 0, C.byref(d), C.byref(m), C.byref(r)))
+                ran = [a - b for a, b in zip(lean_counts(), before)]
+                print("split-K conv", lean, dt, d.value, m.value, r.value, ran)
+                assert (ran[K3] == 1 and sum(ran[:5]) == 1) if lean else sum(ran) == 0, (lean, dt, ran)
+                assert m.value > 0.1 and d.value <= tol_out * m.value, (lean, dt, d.value, m.value)
+                assert r.value < 1e-4, (lean, dt, r.value)
+    finally:
+        e.set_option("conv_lean", 1)
