@@ -312,11 +312,14 @@ int ldc_unet_forward_items(ldc_ctx* ctx, const float* x, const int32_t* t_host /
  * sampler, timestep, iteration, noise (tape or Philox key), length and "is running" flag in device memory.  Items are admitted into
  * free slots and taken out of finished ones while the others keep stepping.
  * The sampler is a property of an item, not of the pool: ldc_pool_admit admits a halfway-DDPM item, ldc_pool_admit_ddim a DDIM item
- * with a schedule (t_start, n_steps, eta) of its own, into the same pool, in any mix; an 8-iteration DDIM item leaves its slot while a
- * 50-step DDPM neighbour keeps going.  The pool owns one schedule row per slot (timesteps entries, 32 KB), allocated with the pool.
+ * with a schedule (t_start, n_steps, eta) of its own, ldc_pool_admit_dpm a DPM-Solver++(2M) item with a schedule (t_start, n_steps),
+ * into the same pool, in any mix; an 8-iteration DDIM or DPM item leaves its slot while a 50-step DDPM neighbour keeps going.  The
+ * pool owns one schedule row per slot (timesteps entries, 32 KB) and one x0 history block per slot (the size of its latents), both
+ * allocated with the pool; the history is never cleared, an item's first iteration does not read it.
  * Contract: a DDPM item's latents are those of ldc_denoise(img, cond, noise, n_steps, B = 1, L, F) on the item alone, a DDIM item's
- * those of ldc_ddim_sample(img, cond, noise, fill_start = 0, t_start, n_steps, eta, B = 1, L, F) -- whatever the other slots hold
- * (either sampler, any schedule), whenever it was admitted, whichever slot it sits in -- within rounding (the unfused GroupNorm
+ * those of ldc_ddim_sample(img, cond, noise, fill_start = 0, t_start, n_steps, eta, B = 1, L, F), a DPM item's those of
+ * ldc_dpm_sample(img, cond, t_start, n_steps, B = 1, L, F) -- whatever the other slots hold
+ * (any sampler, any schedule), whenever it was admitted, whichever slot it sits in -- within rounding (the unfused GroupNorm
  * statistics are summed with atomics: the contract of ldc_decode_ragged, not bit identity).
  * What stays out of a pool: the fp8 engine, the fused GroupNorm and attention launch forms (a per-item plan takes the unfused ones),
  * and fill_start (a start image drawn on the device: the caller passes img).
@@ -329,8 +332,8 @@ int ldc_unet_forward_items(ldc_ctx* ctx, const float* x, const int32_t* t_host /
  * makes a call synchronous on the context's own stream.  Destroy a context's pools before the context.
  * Refused with LDC_E_INVALID before any GPU work, ldc_last_error() naming the value: a slot outside [0, slots); admit into a slot
  * that is not free; L off the ragged latent quantum or above Lmax; n_steps outside [1, timesteps]; n <= 0; slots <= 0; a pool of
- * another context; a null pointer; an fp8 engine; for a DDIM item t_start outside [1, timesteps], n_steps outside [1, t_start], eta
- * outside [0, 1] or not finite.  ldc_pool_take of a slot that is not finished: LDC_E_STATE.  After a refusal the
+ * another context; a null pointer; an fp8 engine; for a DDIM or DPM item t_start outside [1, timesteps], n_steps outside
+ * [1, t_start]; for a DDIM item eta outside [0, 1] or not finite.  ldc_pool_take of a slot that is not finished: LDC_E_STATE.  After a refusal the
  * pool goes on as if the call had not been made.  A call that fails AFTER its GPU work began (LDC_E_HIP, LDC_E_NOMEM) marks the
  * pool: it then refuses with LDC_E_STATE until every slot has been evicted. */
 typedef struct ldc_pool ldc_pool;
@@ -346,6 +349,11 @@ int ldc_pool_admit(ldc_ctx* ctx, ldc_pool* pool, int slot, const float* img, con
  * what ldc_reseed(ctx, seed) gives the first ldc_ddim_sample at B = 1.  ldc_pool_remaining counts its iterations. */
 int ldc_pool_admit_ddim(ldc_ctx* ctx, ldc_pool* pool, int slot, const float* img, const float* cond, int L, int t_start, int n_steps,
                         float eta, const float* noise, uint64_t seed, void* stream);
+/* A DPM-Solver++(2M) item: n_steps iterations on the timesteps ldc_ddim_times(t_start, n_steps) with the coefficients of
+ * ldc_dpm_schedule, i.e. ldc_dpm_sample at B = 1.  Deterministic: no noise, seed or eta, nothing is drawn.  The item's x0 history is its
+ * slot's; what an earlier item left there is never read.  ldc_pool_remaining counts its iterations. */
+int ldc_pool_admit_dpm(ldc_ctx* ctx, ldc_pool* pool, int slot, const float* img, const float* cond, int L, int t_start, int n_steps,
+                       void* stream);
 int ldc_pool_step(ldc_ctx* ctx, ldc_pool* pool, int n, void* stream);         /* n steps of every running slot; a slot stops behind its last step */
 int ldc_pool_remaining(const ldc_pool* pool, int32_t* remaining_host /*[slots]*/);   /* host mirror, no GPU work: -1 free, 0 finished, k > 0 running */
 int ldc_pool_take(ldc_ctx* ctx, ldc_pool* pool, int slot, float* latents_out /*[1,C,L]*/, void* stream);   /* finished slots only; frees the slot */
@@ -503,8 +511,8 @@ int ldc_decode_codes_ragged(ldc_ctx* ctx, const int64_t* codes, const uint8_t* p
  * context-free ones): t_start outside [1, timesteps], n_steps outside [1, t_start], null pointers, and the shape refusals of the
  * DDIM call each one mirrors.  The steps replay captured graphs keyed by (B, L, F) and the sampler kind: every n_steps reuses them,
  * and no call replays a DDPM or DDIM graph.  The x0 history lives with the cached plan of each batch part.
- * On coupled windows: ldc_dpm_sample_windows and its decodes, above.
- * Not available: decode pools, ldc_decode_codes_ragged, the SDE and third-order variants. */
+ * On coupled windows: ldc_dpm_sample_windows and its decodes, above.  In decode pools: ldc_pool_admit_dpm, above.
+ * Not available: ldc_decode_codes_ragged, the SDE and third-order variants. */
 int ldc_dpm_schedule(const float* sqrt_recip, const float* sqrt_recipm1, int timesteps, int t_start, int n_steps, int* t_out,
                      float* coef_out);
 /* ldc_ddim_sample's arguments without noise, fill_start and eta: img holds the start image. */

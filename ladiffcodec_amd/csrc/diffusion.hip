@@ -1136,9 +1136,9 @@ __global__ __launch_bounds__(1024) void step_begin_items_kernel(ItemState* items
       ItemState* it = items + b;
       const int run = it->remaining > 0;
       if (run && advance) {
-        const DdimStep* sc = it->sched;
+        const SchedEntry* sc = it->sched;
         const int j = it->j + 1;
-        it->t = sc ? sc[max(j, 0)].t : it->t - 1;   // DDIM: the timestep of iteration j of the item's own strided schedule
+        it->t = sc ? sc[max(j, 0)].t : it->t - 1;   // DDIM, DPM: the timestep of iteration j of the item's own strided schedule
         it->j = j;
         it->remaining -= 1;
       }
@@ -1161,20 +1161,32 @@ hipError_t launch_step_begin_items(ItemState* items, int B, int* st, void* zero,
 
 // p_sample_update_kernel with everything about the step read from the item's record.  Same 32 x 32 tiling; the item's state is [C][len]
 // on its own length, so a tile behind the item's end (and every tile of an idle item) leaves before it touches memory.  The sampler is
-// the item's too: a record with a schedule takes ddim_update_kernel's arithmetic with the coefficients of sched[j], a record without
-// one p_sample's.  The branch is uniform over the workgroup (one item per blockIdx.z), so one launch serves any mix of the two.
+// the item's too: a record without a schedule takes p_sample's arithmetic, one with a schedule ddim_update_kernel's (ITEM_DDIM) or
+// dpm_update_kernel's (ITEM_DPM) with the coefficients of sched[j].  The branch is uniform over the workgroup (one item per
+// blockIdx.z), so one launch serves any mix of the three.  x0_prev is the DPM items' history, item b's [C][len] block at the stride
+// of x: only a DPM item touches it, and it loads it only on an iteration that has a predecessor and is not the last.
 template <typename T>
 __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int C,
-                                                                    int Lmax, StepTables tb, const ItemState* items, int n_t) {
+                                                                    int Lmax, StepTables tb, const ItemState* items, int n_t,
+                                                                    float* x0_prev) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, c0 = blockIdx.y * 32, l0 = blockIdx.x * 32;
   const ItemState it = items[b];
   const int L = min(it.len, Lmax);
-  if (!it.active || l0 >= L) return;   // (uniform over the workgroup) idle: neither x nor x_cl is stored, neither the tape nor the schedule is dereferenced
+  const bool sched = it.sched != nullptr;
+  const bool dpm = sched && it.kind == ITEM_DPM, ddim = sched && !dpm;
+  // (uniform over the workgroup) idle: neither x, x_cl nor the history is stored, neither the tape nor the schedule is dereferenced.
+  // A DPM record in a launch without a history is not run either
+  if (!it.active || l0 >= L || (dpm && !x0_prev)) return;
   float* xb = x + (size_t)b * x_item_stride;
+  float* hb = x0_prev + (dpm ? (size_t)b * x_item_stride : 0);
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  // the tensor loads need the record only: issue them before the dependent chain schedule entry -> coefficient tables
-  float ev[4], xin[4];
+  // the tensor loads need the record only: issue them before the dependent chain schedule entry -> coefficient tables.  So does the
+  // history's: behind step_begin_items_kernel, "has a predecessor" is j >= 1 and "last" is remaining == 0 (what the table's has_prev and
+  // last say).  Iteration 0 and the last iteration do not load it: whatever an earlier item left in the slot reaches no value
+  const int j = it.j;
+  const bool hist = dpm && j >= 1 && it.remaining > 0;
+  float ev[4], xin[4], pv[4];
 #pragma unroll
   for (int ii = 0; ii < 4; ++ii) {
     const int i = ty + ii * 8;
@@ -1182,22 +1194,25 @@ __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, in
     ev[ii] = (l < L && c < C) ? dld<T>(eps_cl, ((size_t)b * Lmax + l) * C + c) : 0.f;
     const int cc = c0 + i, ll = l0 + tx;
     xin[ii] = (cc < C && ll < L) ? xb[(size_t)cc * L + ll] : 0.f;
+    pv[ii] = (hist && cc < C && ll < L) ? hb[(size_t)cc * L + ll] : 0.f;
   }
-  const int j = it.j;
-  const uint64_t seed = ((uint64_t)it.key_hi << 32) | (uint64_t)it.key_lo;
-  const bool ddim = it.sched != nullptr;
-  DdimStep sp{};
-  if (ddim) sp = it.sched[min(max(j, 0), n_t - 1)];   // (the pool's arena row holds n_t entries)
-  const int t = min(max(ddim ? sp.t : it.t, 0), n_t - 1);
+  SchedEntry se;
+  se.ddim = DdimStep{};
+  if (sched) se = it.sched[min(max(j, 0), n_t - 1)];   // (the pool's arena row holds n_t entries)
+  const DdimStep& sp = se.ddim;   // (read only under ddim)
+  const DpmStep& dp = se.dpm;     // (read only under dpm)
+  const int t = min(max(sched ? se.t : it.t, 0), n_t - 1);
   const float recip = tb.sqrt_recip_alphas_cumprod[t], recipm1 = tb.sqrt_recipm1_alphas_cumprod[t];
-  float c1 = 0.f, c2 = 0.f, sigma = sp.sigma;
-  if (!ddim) {
+  float c1 = 0.f, c2 = 0.f, sigma = ddim ? sp.sigma : 0.f;
+  if (!sched) {
     c1 = tb.posterior_mean_coef1[t];
     c2 = tb.posterior_mean_coef2[t];
     sigma = expf(0.5f * tb.posterior_log_variance_clipped[t]);
   }
-  // noise is read or drawn only here: DDPM at t > 0, DDIM on an iteration that is not the last and has sigma > 0
-  const bool draw = ddim ? (!sp.last && sp.sigma > 0.f) : t > 0;
+  // noise is read or drawn only here: DDPM at t > 0, DDIM on an iteration that is not the last and has sigma > 0, DPM never (neither
+  // its tape pointer nor its key is used)
+  const bool draw = dpm ? false : ddim ? (!sp.last && sp.sigma > 0.f) : t > 0;
+  const uint64_t seed = ((uint64_t)it.key_hi << 32) | (uint64_t)it.key_lo;
 #pragma unroll
   for (int ii = 0; ii < 4; ++ii) tile[ty + ii * 8][tx] = ev[ii];
   __syncthreads();
@@ -1218,7 +1233,14 @@ __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, in
       float x0 = recip * xv - recipm1 * e;
       x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
       float v;
-      if (ddim) {
+      if (dpm) {   // dpm_update_kernel: the table's last / has_prev choose the coefficients, pv was loaded where the record agrees
+        v = x0;
+        if (!dp.last) {
+          v = dp.a * xv + dp.b0 * x0;
+          if (dp.has_prev) v += dp.b1 * pv[ii];
+          hb[idx] = x0;
+        }
+      } else if (ddim) {
         v = x0;
         if (!sp.last) {
           v = x0 * sp.sqrt_an + sp.c * e;
@@ -1242,12 +1264,14 @@ __global__ __launch_bounds__(256) void p_sample_update_items_kernel(float* x, in
   }
 }
 hipError_t launch_p_sample_update_items(int dt, float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int B, int C, int Lmax,
-                                        StepTables tb, const ItemState* items, int T, hipStream_t s) {
+                                        StepTables tb, const ItemState* items, int T, float* x0_prev, hipStream_t s) {
   dim3 grid((Lmax + 31) / 32, (C + 31) / 32, B);
   if (dt == DT_F32)
-    hipLaunchKernelGGL(p_sample_update_items_kernel<float>, grid, dim3(256), 0, s, x, x_item_stride, eps_cl, x_cl, C, Lmax, tb, items, T);
+    hipLaunchKernelGGL(p_sample_update_items_kernel<float>, grid, dim3(256), 0, s, x, x_item_stride, eps_cl, x_cl, C, Lmax, tb, items, T,
+                       x0_prev);
   else
-    hipLaunchKernelGGL(p_sample_update_items_kernel<__bf16>, grid, dim3(256), 0, s, x, x_item_stride, eps_cl, x_cl, C, Lmax, tb, items, T);
+    hipLaunchKernelGGL(p_sample_update_items_kernel<__bf16>, grid, dim3(256), 0, s, x, x_item_stride, eps_cl, x_cl, C, Lmax, tb, items, T,
+                       x0_prev);
   return hipGetLastError();
 }
 

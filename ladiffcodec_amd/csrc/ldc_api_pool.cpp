@@ -1,8 +1,9 @@
 // ldc_api_pool.cpp -- a timestep per item: ldc_unet_forward_items and the decode pools (include/ladiffcodec.h, "decode pools";
 // DESIGN.md section 5d).  Host-side C++ only.  The per-item plan is the ragged plan of unet_plan.cpp (PlanBuilder under Plan::items) whose
 // item-state table (ItemState, ldc_kernels.h) replaces the part's step_state {t, j, key} and cur_ss row; the kernels that read the table
-// are step_begin_items, gn_apply (t_stride) and p_sample_update_items.  The sampler is part of the record too: a DDIM item's record points
-// to its schedule, a row of the pool's schedule arena (ldc_pool_admit_ddim).
+// are step_begin_items, gn_apply (t_stride) and p_sample_update_items.  The sampler is part of the record too: a DDIM or DPM-Solver++
+// item's record names its kind and points to its schedule, a row of the pool's schedule arena (ldc_pool_admit_ddim, ldc_pool_admit_dpm);
+// a DPM item's x0 history is its slot's block of the pool's history buffer.
 #include "ldc_internal.h"
 
 namespace {
@@ -67,7 +68,7 @@ int pool_half_step(ldc_ctx* c, ldc_pool* p, int k, hipStream_t sk) {
   HIPCHK(launch_step_begin_items(pl->item_state, pl->B, pl->step_state, pl->zero_ptr, pl->zero_bytes, 1, sk));
   LDCCHK(run_ops(c, pl, true, sk));
   HIPCHK(launch_p_sample_update_items(c->dt, p->x + (size_t)p->h.b0[k] * item, item, pl->eps_cl, pl->x_cl, pl->B, C, p->Lmax, c->sched,
-                                      pl->item_state, c->unet.timesteps, sk));
+                                      pl->item_state, c->unet.timesteps, p->x0_prev + (size_t)p->h.b0[k] * item, sk));
   return LDC_OK;
 }
 
@@ -189,12 +190,18 @@ extern "C" int ldc_pool_create(ldc_ctx* c, int slots, int Lmax, ldc_pool** out) 
     void* x = nullptr;
     LDCCHK(p->mem.alloc(&x, (size_t)slots * C * Lmax * 4));
     p->x = (float*)x;
-    // the schedule arena: a row of `timesteps` entries per slot (a DDIM item runs at most that many iterations), zero = DDPM-free rows
+    // the DPM items' x0 history, the layout of x: always allocated, so its address is in every captured graph of the pool, also one
+    // captured before the first DPM item.  Not cleared: a DPM item's iteration 0 does not load it
+    void* hist = nullptr;
+    LDCCHK(p->mem.alloc(&hist, (size_t)slots * C * Lmax * 4));
+    p->x0_prev = (float*)hist;
+    // the schedule arena: a row of `timesteps` entries per slot (a DDIM or DPM item runs at most that many iterations), zero = DDPM-free rows
     void* sc = nullptr;
-    const size_t sched_bytes = (size_t)slots * c->unet.timesteps * sizeof(DdimStep);
+    const size_t sched_bytes = (size_t)slots * c->unet.timesteps * sizeof(SchedEntry);
     LDCCHK(p->mem.alloc(&sc, sched_bytes));
-    p->sched = (DdimStep*)sc;
+    p->sched = (SchedEntry*)sc;
     p->sched_host.reserve(c->unet.timesteps);
+    p->dpm_host.reserve(c->unet.timesteps);
     HIPCHK(hipMemsetAsync(p->sched, 0, sched_bytes, s));
     // every slot idle on finite state: zero latents and condition, the shortest length, t = 0
     HIPCHK(hipMemsetAsync(p->x, 0, (size_t)slots * C * Lmax * 4, s));
@@ -233,22 +240,23 @@ extern "C" int ldc_pool_destroy(ldc_pool* p) {
   return LDC_OK;
 }
 
-// ldc_pool_admit (t_start == 0: DDPM, n_steps steps from t = n_steps - 1) and ldc_pool_admit_ddim (t_start > 0: n_steps DDIM iterations
-// on the schedule (t_start, n_steps, eta), written into the slot's row of the pool's arena)
-static int pool_admit(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const float* cond, int L, int t_start, int n_steps, float eta,
-                      const float* noise, uint64_t seed, void* stream, const char* entry) {
-  const bool ddim = t_start != 0;
+// ldc_pool_admit (kind ITEM_DDPM: n_steps steps from t = n_steps - 1, t_start not read), ldc_pool_admit_ddim (ITEM_DDIM: n_steps DDIM
+// iterations on the schedule (t_start, n_steps, eta), written into the slot's row of the pool's arena) and ldc_pool_admit_dpm (ITEM_DPM:
+// n_steps DPM-Solver++ iterations on the schedule (t_start, n_steps) in the same row; no noise, seed or eta)
+static int pool_admit(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const float* cond, int L, int kind, int t_start, int n_steps,
+                      float eta, const float* noise, uint64_t seed, void* stream, const char* entry) {
+  const bool ddim = kind == ITEM_DDIM, dpm = kind == ITEM_DPM;
   LDCCHK(check_pool(c, p, entry));
   if (!img || !cond) return fail(LDC_E_INVALID, "%s: null pointer: %s", entry, !img ? "img" : "cond");
   LDCCHK(check_slot(p, slot, entry));
   if (p->remaining[slot] >= 0)
     return fail(LDC_E_INVALID, "%s: slot %d is not free (%s, %d steps remaining)", entry, slot, p->remaining[slot] ? "running" : "finished", p->remaining[slot]);
   LDCCHK(check_item_length(L, p->Lmax, ragged_latent_quantum(c), entry, slot));
-  if (ddim) {
+  if (ddim || dpm) {
     if (t_start < 1 || t_start > c->unet.timesteps) return fail(LDC_E_INVALID, "%s: t_start = %d must be in [1, %d]", entry, t_start, c->unet.timesteps);
     if (n_steps < 1 || n_steps > t_start)
       return fail(LDC_E_INVALID, "%s: n_steps = %d must be in [1, t_start = %d] (more would repeat timesteps)", entry, n_steps, t_start);
-    if (!(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "%s: eta = %g must be a finite value in [0, 1]", entry, (double)eta);
+    if (ddim && !(eta >= 0.0f && eta <= 1.0f)) return fail(LDC_E_INVALID, "%s: eta = %g must be a finite value in [0, 1]", entry, (double)eta);
   } else if (n_steps < 1 || n_steps > c->unet.timesteps) {
     return fail(LDC_E_INVALID, "%s: n_steps = %d must be in [1, %d]", entry, n_steps, c->unet.timesteps);
   }
@@ -256,6 +264,8 @@ static int pool_admit(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const
   if (ddim) {   // (host only: nothing of the pool has moved if this fails)
     bool draws = false;
     LDCCHK(ddim_schedule_fill(c, t_start, n_steps, eta, &p->sched_host, &draws));
+  } else if (dpm) {
+    LDCCHK(dpm_schedule_fill(c, t_start, n_steps, &p->dpm_host));
   }
   hipStream_t s = pick_stream(c, stream);
   const int up = upsample_factor(c), F = L / up, C = c->unet.channels, Cc = c->unet.cond_channels, Lmax = p->Lmax;
@@ -281,15 +291,17 @@ static int pool_admit(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const
     HIPCHK(hipMemcpyAsync(p->x + (size_t)slot * C * Lmax, img, (size_t)C * L * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemsetAsync((char*)pk->x_cl + sb * xrow, 0, xrow, s));
     HIPCHK(launch_to_cl(c->dt, img, (char*)pk->x_cl + sb * xrow, 1, C, L, nullptr, 0, 0.f, s));
-    // a DDIM item's schedule into the slot's row of the arena, in front of the record that points to it (the slot is free: no step
-    // issued before this call reads the row)
-    DdimStep* row = p->sched + (size_t)slot * c->unet.timesteps;
-    if (ddim) HIPCHK(launch_ddim_table_write(row, p->sched_host.data(), n_steps, s));
+    // a DDIM or DPM item's schedule into the slot's row of the arena, in front of the record that points to it (the slot is free: no
+    // step issued before this call reads the row).  The slot's history is NOT cleared: a DPM item's iteration 0 does not load it
+    SchedEntry* row = p->sched + (size_t)slot * c->unet.timesteps;
+    if (ddim) HIPCHK(launch_ddim_table_write(&row->ddim, p->sched_host.data(), n_steps, s));
+    if (dpm) HIPCHK(launch_dpm_table_write(&row->dpm, p->dpm_host.data(), n_steps, s));
     // the record last: the state BEFORE the first step (the step's first kernel advances to iteration 0: t = n_steps - 1, or the
     // first timestep of the schedule)
     ItemState r = idle_record(L);
-    r.t = ddim ? t_start : n_steps; r.j = -1; r.key_lo = (unsigned)seed; r.key_hi = (unsigned)(seed >> 32); r.remaining = n_steps; r.noise = noise;
-    r.sched = ddim ? row : nullptr;
+    r.t = ddim || dpm ? t_start : n_steps; r.j = -1; r.key_lo = (unsigned)seed; r.key_hi = (unsigned)(seed >> 32); r.remaining = n_steps; r.noise = noise;
+    r.kind = kind;
+    r.sched = ddim || dpm ? row : nullptr;
     HIPCHK(launch_items_write(pk->item_state + sb, &r, 1, pk->lens + sb, pk->flens + sb, up, s));
     p->remaining[slot] = n_steps;
     p->len[slot] = L;
@@ -301,16 +313,17 @@ static int pool_admit(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const
 
 extern "C" int ldc_pool_admit(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const float* cond, int L, int n_steps, const float* noise,
                               uint64_t seed, void* stream) {
-  return pool_admit(c, p, slot, img, cond, L, 0, n_steps, 0.0f, noise, seed, stream, "ldc_pool_admit");
+  return pool_admit(c, p, slot, img, cond, L, ITEM_DDPM, 0, n_steps, 0.0f, noise, seed, stream, "ldc_pool_admit");
 }
 
 extern "C" int ldc_pool_admit_ddim(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const float* cond, int L, int t_start, int n_steps,
                                    float eta, const float* noise, uint64_t seed, void* stream) {
-  const char* entry = "ldc_pool_admit_ddim";
-  LDCCHK(check_pool(c, p, entry));
-  // (t_start 0 is ldc_pool_admit's convention inside pool_admit, not a schedule)
-  if (t_start < 1) return fail(LDC_E_INVALID, "%s: t_start = %d must be in [1, %d]", entry, t_start, c->unet.timesteps);
-  return pool_admit(c, p, slot, img, cond, L, t_start, n_steps, eta, noise, seed, stream, entry);
+  return pool_admit(c, p, slot, img, cond, L, ITEM_DDIM, t_start, n_steps, eta, noise, seed, stream, "ldc_pool_admit_ddim");
+}
+
+extern "C" int ldc_pool_admit_dpm(ldc_ctx* c, ldc_pool* p, int slot, const float* img, const float* cond, int L, int t_start, int n_steps,
+                                  void* stream) {
+  return pool_admit(c, p, slot, img, cond, L, ITEM_DPM, t_start, n_steps, 0.0f, nullptr, 0, stream, "ldc_pool_admit_dpm");
 }
 
 extern "C" int ldc_pool_step(ldc_ctx* c, ldc_pool* p, int n, void* stream) {

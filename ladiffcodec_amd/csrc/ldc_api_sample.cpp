@@ -393,17 +393,18 @@ extern "C" int ldc_dpm_schedule(const float* sqrt_recip, const float* sqrt_recip
   return LDC_OK;
 }
 
-// the schedule of a DPM call into c->dpm_host (the context's host copies of the two tables)
-int dpm_schedule(ldc_ctx* c, int t_start, int n_steps) {
+// the schedule of a DPM call into `out` (n_steps entries), from the context's host copies of the two tables.  The context's samplers
+// fill c->dpm_host (dpm_schedule below), a decode pool the row of one slot.
+int dpm_schedule_fill(ldc_ctx* c, int t_start, int n_steps, std::vector<DpmStep>* out) {
   const int T = c->unet.timesteps;
   LDCCHK(dpm_args(T, t_start, n_steps));
   if ((int)c->sqrt_recip_ac.size() != T || (int)c->sqrt_recipm1_ac.size() != T) return fail(LDC_E_STATE, "no sqrt_recip / sqrt_recipm1 schedule loaded");
   std::vector<int> ts(n_steps);
   std::vector<float> coef((size_t)n_steps * 3);
   LDCCHK(ldc_dpm_schedule(c->sqrt_recip_ac.data(), c->sqrt_recipm1_ac.data(), T, t_start, n_steps, ts.data(), coef.data()));
-  c->dpm_host.assign(n_steps, DpmStep{});
+  out->assign(n_steps, DpmStep{});
   for (int j = 0; j < n_steps; ++j) {
-    DpmStep& e = c->dpm_host[j];
+    DpmStep& e = (*out)[j];
     e.t = ts[j];
     e.last = j == n_steps - 1;   // (the timestep list ends in -1: the final iteration, and only it)
     e.has_prev = j >= 1 && !e.last;
@@ -411,6 +412,7 @@ int dpm_schedule(ldc_ctx* c, int t_start, int n_steps) {
   }
   return LDC_OK;
 }
+int dpm_schedule(ldc_ctx* c, int t_start, int n_steps) { return dpm_schedule_fill(c, t_start, n_steps, &c->dpm_host); }
 
 // c->dpm_host -> the context's device table, ordered on s behind everything queued there before (as ddim_upload)
 int dpm_upload(ldc_ctx* c, hipStream_t s) {

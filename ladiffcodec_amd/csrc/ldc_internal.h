@@ -485,15 +485,18 @@ struct ldc_stream {
 // A decode pool (ldc_pool_create): `slots` items that step together on one captured graph per batch part while each
 // keeps its own timestep, iteration, noise and length.  The state of record is on the device: the items' records, x_cl, the processed
 // condition (in the pool's pinned per-item plans), the fp32 latents x [slots][C * Lmax] (item b: [C][len_b] at b * C * Lmax) and the
-// schedule arena (one row of DdimStep per slot: the record of a DDIM item points into its slot's row).  The host keeps a mirror of the
-// step counts only.
+// schedule arena (one row of SchedEntry per slot: the record of a DDIM or DPM item points into its slot's row) and the DPM items' x0
+// history x0_prev, laid out exactly like x.  The host keeps a mirror of the step counts only.
 struct ldc_pool {
   ldc_ctx* ctx = nullptr;
   int id = 0, slots = 0, Lmax = 0, Fmax = 0;
   Halves h;                          // the pool's plans (pinned: Plan::pool_id)
   float* x = nullptr;                // [slots][C * Lmax] fp32
-  DdimStep* sched = nullptr;         // [slots][timesteps]: allocated with the pool, so a warm DDIM admit allocates nothing
-  std::vector<DdimStep> sched_host;  // the row being written by an admit (kept: no allocation on a warm call)
+  float* x0_prev = nullptr;          // [slots][C * Lmax] fp32: the DPM items' history.  Allocated with the pool (its address is in every
+                                     // captured graph), never cleared: iteration 0 of an item does not load it
+  SchedEntry* sched = nullptr;       // [slots][timesteps]: allocated with the pool, so a warm DDIM / DPM admit allocates nothing
+  std::vector<DdimStep> sched_host;  // the row being written by a DDIM admit (kept: no allocation on a warm call)
+  std::vector<DpmStep> dpm_host;     // likewise by a DPM admit
   std::vector<int> remaining;        // -1 free, 0 finished, k > 0 running
   std::vector<int> len;              // latent frames of the slot's item (the minimum length while free)
   hipStream_t last_stream = nullptr;
@@ -549,6 +552,7 @@ int denoise_loop(ldc_ctx* c, const Halves& h, int B, float* x, const float* nois
 int ddim_schedule_fill(ldc_ctx* c, int t_start, int n_steps, float eta, std::vector<DdimStep>* out, bool* draws);
 int ddim_schedule(ldc_ctx* c, int t_start, int n_steps, float eta, bool* draws);
 int ddim_upload(ldc_ctx* c, hipStream_t s);
+int dpm_schedule_fill(ldc_ctx* c, int t_start, int n_steps, std::vector<DpmStep>* out);
 int dpm_schedule(ldc_ctx* c, int t_start, int n_steps);
 int dpm_upload(ldc_ctx* c, hipStream_t s);
 int ensure_history(ldc_ctx* c, const Halves& h);

@@ -7,6 +7,7 @@
 // nearest-upsampling / striding / causal reflect padding into row-index arithmetic.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "ldc_windows.h"   // WinGroupRec, WinGroupTile: what the window-group kernels read, as the host builder writes it
@@ -247,8 +248,9 @@ hipError_t launch_p_sample_update(int dt, float* x, const void* eps_cl, const fl
 hipError_t launch_item_keys_write(uint64_t* dst, const uint64_t* keys_host, int n, hipStream_t s);
 // Per-item step state (per-item plans: ldc_unet_forward_items, decode pools): one record per item / pool slot in
 // device memory.  Nothing about an item's progress or its sampler is a kernel argument, so one captured step graph replays for any mix
-// of states, DDPM and DDIM items side by side.
-struct DdimStep;
+// of states, DDPM, DDIM and DPM-Solver++ items side by side.
+union SchedEntry;
+enum { ITEM_DDPM = 0, ITEM_DDIM = 1, ITEM_DPM = 2 };   // ItemState::kind (zero: what every record without a schedule is)
 struct ItemState {
   int t;                // timestep of the step being executed (unet.py:422-437: one per item)
   int j;                // iteration: which entry of the noise tape / Philox step the update uses
@@ -256,15 +258,16 @@ struct ItemState {
   int remaining;        // steps not yet begun (0 = idle: finished, evicted or never admitted)
   int len;              // the item's own latent frames (the ragged plan's lens[] holds the same value)
   int active;           // set by the step's first kernel: this step runs for the item (an idle item is computed on and discarded)
-  int pad_;
-  const float* noise;   // the item's tape [n_steps][C][len] (contiguous for its OWN length) or null: Philox draws
-  const DdimStep* sched;   // the item's DDIM schedule, entry j for iteration j (the pool's arena row of its slot), or null: DDPM p_sample
+  int kind;             // the item's sampler: ITEM_DDPM, ITEM_DDIM or ITEM_DPM; a record with sched == null is DDPM whatever this says
+  const float* noise;   // the item's tape [n_steps][C][len] (contiguous for its OWN length) or null: Philox draws; never read for a DPM item
+  const SchedEntry* sched;   // the item's schedule, entry j for iteration j (the pool's arena row of its slot), or null: DDPM p_sample
 };
 constexpr int kItemStateInts = (int)(sizeof(ItemState) / sizeof(int));
+static_assert(sizeof(ItemState) == 48, "the record's size is part of the per-item plans (gn_apply's t_stride): the sampler kind took the pad word");
 // dst[0..n) = src_host[0..n), stream-ordered (kernel arguments carry the records); lens / flens (optional): lens[i] = len, flens[i] = len / up
 hipError_t launch_items_write(ItemState* dst, const ItemState* src_host, int n, int* lens, int* flens, int up, hipStream_t s);
 // First kernel of a step of a per-item plan: for every item, active = remaining > 0 and, with `advance`, a running item moves on
-// (j + 1, remaining - 1; t - 1 for a DDPM item, t = sched[j].t for an item with a schedule); counts the part's epoch word st[4] up once;
+// (j + 1, remaining - 1; t - 1 for a DDPM item, t = sched[j].t for an item with a schedule, of either kind); counts the part's epoch word st[4] up once;
 // clears the step's accumulator region as launch_step_begin does.
 // The timestep's (scale | shift) row is NOT copied: gn_apply selects it from the table by the item's t (launch_gn_apply, t_stride).
 hipError_t launch_step_begin_items(ItemState* items, int B, int* st, void* zero, size_t zero_bytes, int advance, hipStream_t s);
@@ -274,8 +277,12 @@ hipError_t launch_step_begin_items(ItemState* items, int B, int* st, void* zero,
 // schedule is dereferenced; rows >= len are never touched (x_cl stays zero there from the admission).  T = timesteps (t is clamped to the
 // tables).  An item with a schedule (ItemState::sched) takes launch_ddim_update's arithmetic instead, in the same launch (the branch is
 // uniform over a workgroup): coefficients of sched[j], noise read or drawn only where !last && sigma > 0, same tape layout and Philox group.
+// An item of kind ITEM_DPM takes launch_dpm_update's: coefficients of sched[j].dpm, nothing drawn, neither the tape pointer nor the key
+// read.  x0_prev: the items' x0 history, laid out exactly like x (item b's [C][len] block at x0_prev + b * x_item_stride), loaded only
+// where the advanced record says j >= 1 && remaining > 0 (what the table's has_prev && !last say), written on every iteration but the
+// last, never cleared; rows >= len and idle items never touch it.  Null where no DPM item can exist: a DPM record is then not stored.
 hipError_t launch_p_sample_update_items(int dt, float* x, int64_t x_item_stride, const void* eps_cl, void* x_cl, int B, int C, int Lmax,
-                                        StepTables tb, const ItemState* items, int T, hipStream_t s);
+                                        StepTables tb, const ItemState* items, int T, float* x0_prev, hipStream_t s);
 // One iteration of DDIM sampling (reference ddpm_loss.py ddim_sample, clip_denoised): the host fills one entry per
 // iteration j (ldc_api.cpp: ddim_schedule) into a device table that the step state indexes.
 struct DdimStep {
@@ -304,6 +311,16 @@ struct DpmStep {
   float b1;        // -phi / (2 r); 0 on the first iteration
   float pad_[2];
 };
+// One entry of an item's schedule (a decode pool's arena, ItemState::sched): a DdimStep for an ITEM_DDIM record, a DpmStep for an
+// ITEM_DPM one.  Both are 32 bytes with `t` as their first word, so step_begin_items_kernel advances t = sched[j + 1].t without knowing
+// the kind; the update kernel reads the member the record's kind names.
+union SchedEntry {
+  int t;
+  DdimStep ddim;
+  DpmStep dpm;
+};
+static_assert(sizeof(DdimStep) == 32 && sizeof(DpmStep) == 32 && sizeof(SchedEntry) == 32, "schedule entries of every kind share one arena row");
+static_assert(offsetof(DdimStep, t) == 0 && offsetof(DpmStep, t) == 0, "t is the first word of a schedule entry of every kind");
 // x0 = clamp(sqrt_recip_ac[t] x - sqrt_recipm1_ac[t] eps, -1, 1); x <- last ? x0 : a x + b0 x0 + (has_prev ? b1 x0_prev : 0), in fp32;
 // then x0_prev <- x0 on every iteration but the last.  Same layouts and `lens` rule as launch_ddim_update (x, x_cl and x0_prev are
 // zero behind an item's length); x0_prev [B][C][L] fp32, the layout of x.  No noise: nothing is drawn.

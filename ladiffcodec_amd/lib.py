@@ -29,7 +29,7 @@ EXPORTS = [
     "ldc_window_group_layout", "ldc_unet_forward_windows_group", "ldc_sample_windows_group", "ldc_decode_windows_group",
     "ldc_decode_ragged", "ldc_unet_forward_ragged", "ldc_get_cond_ragged", "ldc_decode_codes_ragged", "ldc_ac_encode_ragged", "ldc_ac_decode_ragged",
     "ldc_sample_seeded", "ldc_decode_seeded", "ldc_decode_codes_seeded",
-    "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
+    "ldc_unet_forward_items", "ldc_pool_create", "ldc_pool_destroy", "ldc_pool_admit", "ldc_pool_admit_ddim", "ldc_pool_admit_dpm", "ldc_pool_step", "ldc_pool_remaining", "ldc_pool_take", "ldc_pool_peek", "ldc_pool_evict",
     "ldc_stream_min_first", "ldc_stream_create", "ldc_stream_reset", "ldc_stream_destroy", "ldc_seanet_encode_stream", "ldc_seanet_decode_stream", "ldc_get_cond_stream",
     "ldc_sconv1d", "ldc_sconvtr1d", "ldc_slstm", "ldc_unet_debug_tap", "ldc_unet_step_cost", "ldc_profile_enable",
     "ldc_profile_read", "ldc_profile_read_classes", "ldc_conv_microbench", "ldc_conv_compare", "ldc_conv_compare_fp8", "ldc_ln_fold_compare", "ldc_gn_microbench", "ldc_host_stats", "ldc_graph_schedule", "ldc_stream_info", "ldc_clock_sample", "ldc_debug_raise_failure", "ldc_debug_attn_core", "ldc_debug_attention_block", "ldc_debug_resnet_block", "ldc_debug_sea_conv", "ldc_debug_sea_op", "ldc_debug_sync_count", "ldc_debug_lean_launches", "ldc_xcc_census", "ldc_timeline_enable", "ldc_timeline_read", "ldc_kstamps_enable", "ldc_kstamps_reset", "ldc_kstamps_read", "ldc_packed_bytes", "ldc_pack_codes", "ldc_unpack_codes",
@@ -152,6 +152,7 @@ def load() -> C.CDLL:
     lib.ldc_pool_destroy.argtypes = [vp]
     lib.ldc_pool_admit.argtypes = [vp, vp, i32, fp, fp, i32, i32, fp, C.c_uint64, vp]
     lib.ldc_pool_admit_ddim.argtypes = [vp, vp, i32, fp, fp, i32, i32, i32, C.c_float, fp, C.c_uint64, vp]
+    lib.ldc_pool_admit_dpm.argtypes = [vp, vp, i32, fp, fp, i32, i32, i32, vp]
     lib.ldc_pool_step.argtypes = [vp, vp, i32, vp]
     lib.ldc_pool_remaining.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.ldc_pool_take.argtypes = [vp, vp, i32, fp, vp]

@@ -911,11 +911,13 @@ class Engine:
     def open_pool(self, slots: int, max_samples: int, sampler: str = "ddpm") -> "DecodePool":
         """A decode pool (ldc_pool_create): `slots` items of up to max_samples samples step together on one captured step graph while each
         keeps its own sampler, timestep, step count, noise and length; items are submitted and popped while the others keep stepping.
-        The sampler is a property of an item, not of the pool: `DecodePool.submit(..., t_start=..., eta=...)` admits a DDIM item beside
-        DDPM ones.  `sampler` is kept for callers that pass "ddpm"; nothing else is a sampler of a pool."""
+        The sampler is a property of an item, not of the pool: `DecodePool.submit(..., t_start=..., eta=...)` admits a DDIM item and
+        `DecodePool.submit(..., t_start=..., sampler="dpm")` a DPM-Solver++(2M) item beside DDPM ones.  `sampler` is kept for callers
+        that pass "ddpm"; nothing else is a sampler of a pool."""
         if sampler != "ddpm":
             raise ValueError(f"sampler {sampler!r}: a pool has no sampler of its own, every item brings one: "
-                             "open the pool without it and pass submit(t_start=..., eta=...) for a DDIM item")
+                             "open the pool without it and pass submit(t_start=..., eta=...) for a DDIM item, "
+                             "submit(t_start=..., sampler=\"dpm\") for a DPM-Solver++ item")
         return DecodePool(self, slots, max_samples)
 
     # ---- the calls a DecodePool makes (a stub engine without a GPU provides these) ------------
@@ -962,6 +964,16 @@ class Engine:
         finally:
             self._exit()
         return noise                       # (as pool_admit)
+
+    def pool_admit_dpm(self, h, slot: int, img, cond, t_start: int, n_steps: int) -> None:
+        """ldc_pool_admit_dpm: n_steps DPM-Solver++(2M) iterations from t_start; nothing is drawn, so there is no noise and no seed"""
+        img, cond = self._f32(img), self._f32(cond)
+        s = self._enter()
+        try:
+            L.check(self.lib.ldc_pool_admit_dpm(self._ctx, h, int(slot), img.data_ptr(), cond.data_ptr(), int(img.shape[-1]), int(t_start),
+                                                int(n_steps), s))
+        finally:
+            self._exit()
 
     def pool_step(self, h, n: int) -> None:
         s = self._enter()
@@ -1348,8 +1360,9 @@ class CodecStream:
 class DecodePool:
     """A fixed set of slots that step together (Engine.open_pool, ldc_pool_*): `submit` admits an item into a free slot, `step`
     advances every running item, `finished` lists the tickets whose items are done, `pop` takes one out and decodes its waveform.
-    An item comes out as `Engine.denoise` (a DDPM item) or `Engine.ddim_sample` (a DDIM item, `submit(t_start=...)`) gives it alone
-    at B = 1, whatever the other slots hold -- either sampler, any schedule -- within rounding.  The bookkeeping
+    An item comes out as `Engine.denoise` (a DDPM item), `Engine.ddim_sample` (a DDIM item, `submit(t_start=...)`) or
+    `Engine.dpm_sample` (a DPM-Solver++(2M) item, `submit(t_start=..., sampler="dpm")`) gives it alone
+    at B = 1, whatever the other slots hold -- any sampler, any schedule -- within rounding.  The bookkeeping
     here is plain Python over the library's host mirror (`pool_remaining`); the engine may be any object with the `pool_*` methods."""
 
     def __init__(self, eng, slots: int, max_samples: int):
@@ -1372,17 +1385,32 @@ class DecodePool:
     def free_slots(self):
         return [i for i, r in enumerate(self.remaining()) if r < 0]
 
-    def submit(self, wav=None, codes=None, n_steps: int = 50, noise=None, seed=None, t_start: int = 0, eta: float = 0.0) -> int:
+    def submit(self, wav=None, codes=None, n_steps: int = 50, noise=None, seed=None, t_start: int = 0, eta: float = 0.0,
+               sampler: Optional[str] = None) -> int:
         """wav [1, 1, T] or codes [n_q, 1, F] of ONE item; noise [n_steps, 1, C, L] or None (Philox with key `seed`, the ticket number when
-        None).  t_start 0 (the convention of `Engine.decode_ragged`): halfway DDPM sampling, n_steps steps; t_start > 0: n_steps DDIM
-        iterations from t_start with `eta`, and `remaining` counts iterations.  -> ticket.  Raises when no slot is free."""
+        None).  sampler None: t_start 0 (the convention of `Engine.decode_ragged`) is halfway DDPM sampling, n_steps steps; t_start > 0 is
+        n_steps DDIM iterations from t_start with `eta`, and `remaining` counts iterations.  sampler "dpm": n_steps DPM-Solver++(2M)
+        iterations from t_start >= 1; nothing is drawn, so a `noise`, a `seed` or a non-zero `eta` is a ValueError.  "ddpm" (t_start 0)
+        and "ddim" (t_start >= 1) name the two routes of None.  -> ticket.  Raises when no slot is free."""
+        if sampler not in (None, "ddpm", "ddim", "dpm"):
+            raise ValueError(f"sampler {sampler!r}: an item's sampler is \"ddpm\", \"ddim\" or \"dpm\" (None: by t_start)")
+        if sampler == "dpm":
+            given = [n for n, bad in (("noise", noise is not None), ("seed", seed is not None), ("eta", float(eta) != 0.0)) if bad]
+            if given:
+                raise ValueError(f"sampler \"dpm\" draws nothing: {', '.join(given)} would be ignored, leave it out")
+        if sampler in ("ddim", "dpm") and int(t_start) < 1:
+            raise ValueError(f"sampler {sampler!r} needs t_start >= 1, not {t_start}")
+        if sampler == "ddpm" and t_start:
+            raise ValueError(f"sampler \"ddpm\" runs n_steps steps from t = n_steps - 1: t_start = {t_start} must be 0")
         free = self.free_slots()
         if not free:
             raise RuntimeError(f"no free slot in a pool of {self.slots}: step until an item has finished and pop it")
         img, cond = self.eng.pool_front(wav=wav, codes=codes)
         ticket = self._next
         key = ticket if seed is None else int(seed)
-        if t_start:
+        if sampler == "dpm":
+            kept = self.eng.pool_admit_dpm(self._h, free[0], img, cond, int(t_start), int(n_steps))
+        elif t_start:
             kept = self.eng.pool_admit_ddim(self._h, free[0], img, cond, int(t_start), int(n_steps), float(eta), noise, key)
         else:
             kept = self.eng.pool_admit(self._h, free[0], img, cond, int(n_steps), noise, key)
